@@ -3,8 +3,13 @@
 per GPU (BASELINE.json metric; workload = configs[3]: radon --dataset=PA --method=i, interleaved
 CP/NCP, 4 + 4 = "8 leapfrog steps" per step, main.py:493), on the fused HIP kernels.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     (N > 1: python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...)
+
+A plain run sets up, runs W warm-up and K timed steps, and prints the line; `--dump-outputs DIR` also writes what the last
+timed step computed (the chain state and a seeded sample of its trace rows, DIR/<name>.npy).  `--full` adds everything
+else, each figure timed in runs of its own -- the live clock probe, the second scaling leg of an N > 1 job, the secondary
+kernels and models, the ESS/sec flow, the CPU baselines -- and writes the extras file.
 
 A "step" is one launch of the hot path over the rank's whole chain batch: `--transitions`
 (default 1 024) sampler steps for every chain -- 13 ms per step, so that a handful of warm-up steps cover
@@ -124,6 +129,31 @@ def election_issue_bound(form, L, clock_ghz=2.4):
     cyc = lambda b: sum(ISSUE_CYCLES[k] * v for k, v in b.items())
     per_transition = (L - 1) * cyc(m["interior"]) + cyc(m["closing"]) + cyc(m["start"])      # one wave = 16 chains
     return 256 * 4 * clock_ghz * 1e9 * 16 * L / per_transition, per_transition
+
+
+DUMP_BUDGET_BYTES = 60 * 10 ** 6      # all arrays of --dump-outputs together, under 64 MB with the .npy headers
+
+
+def dump_outputs(out_dir, arrays, seed=0):
+    """Write every tensor of `arrays` as out_dir/<name>.npy: floating point as float32, integer counts as float64.  The
+    smallest go first and each takes at most an even share of what is left of DUMP_BUDGET_BYTES; an array larger than its
+    share is written as out_dir/<name>_sample.npy, the flattened elements at sorted indices drawn by
+    RandomState(seed) -- the same shape gives the same indices, so two builds' dumps compare element for element."""
+    os.makedirs(out_dir, exist_ok=True)
+    esize = lambda t: 4 if t.is_floating_point() else 8
+    items = sorted(arrays.items(), key=lambda kv: kv[1].numel() * esize(kv[1]))
+    left = DUMP_BUDGET_BYTES
+    for i, (name, t) in enumerate(items):
+        share = left // (len(items) - i)
+        flat = t.detach().reshape(-1)
+        if flat.numel() * esize(t) > share:
+            idx = np.unique(np.random.RandomState(seed).randint(0, flat.numel(), size=share // esize(t), dtype=np.int64))
+            flat, name = flat[torch.as_tensor(idx, device=flat.device)], name + "_sample"
+        else:
+            flat = flat.reshape(t.shape)
+        a = flat.to(torch.float32 if t.is_floating_point() else torch.float64).cpu().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        left -= a.nbytes
 
 
 def _time_launches(fn, n, warm=2):
@@ -359,14 +389,17 @@ def main():
     ap.add_argument("--thin", type=int, default=2, help="a trace row every THIN-th sampler step (reference: 2)")
     ap.add_argument("--dataset", default="PA")
     ap.add_argument("--lanes", type=int, default=0, help="lanes per chain (0 = library default)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline figure (see the module docstring); off by default")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's outputs as DIR/<name>.npy (rank 0's chains)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
     ap.add_argument("--headline-only", action="store_true",
-                    help="skip the secondary figures: profiler runs, so that every launch of the headline kernel in "
-                         "the trace is a timed or warm-up step")
-    ap.add_argument("--no-ess", action="store_true", help="skip the reference-flow ESS/sec run")
+                    help="with --full: skip the secondary figures")
+    ap.add_argument("--no-ess", action="store_true", help="with --full: skip the reference-flow ESS/sec run")
     ap.add_argument("--verbose", action="store_true", help="let the CLI flows' progress through (to stderr)")
     ap.add_argument("--extras", default=os.path.join(ROOT, "bench_extras.json"),
-                    help="where the secondary figures go (the stdout line stays short and names this path)")
+                    help="with --full: where the secondary figures go (the stdout line stays short and names this path)")
     ap.add_argument("--no-trace", action="store_true", help="diagnostic: do not record trace rows")
     ap.add_argument("--stats", action="store_true", help="diagnostic: accumulate the in-kernel streaming statistics "
                                                          "(arp_hmc_io.stats) instead of writing trace rows")
@@ -455,6 +488,7 @@ def main():
                 eng.hmc_run(st, eps0, L, Tn, seed=7, chain_offset=off, adapt_kind=_lib.ADAPT_DUAL,
                             n_adapt=10 ** 9, n_burnin=st.step if not stats else 0, thin=thin_n, trace=trace,
                             trace_centered=True, lanes=lanes, **skw)
+        launch.trace, launch.stats = trace, stats_t           # what a caller receives besides the chain state
         return launch, st
 
     rec = not args.no_trace
@@ -484,16 +518,22 @@ def main():
     launch, st = make_launcher(T, thin, record=rec, stats=args.stats)
     elapsed, per_launch_ms = timed_leg(launch)
     kern_ms = float(np.mean(per_launch_ms))
+    if args.dump_outputs and rank == 0:
+        outs = {k: getattr(st, k) for k in ("q", "grad", "logp", "adapt", "adapt1", "accept_count", "accept_count1")}
+        outs.update((k, v) for k, v in (("trace", launch.trace), ("stats", launch.stats)) if v is not None)
+        dump_outputs(args.dump_outputs, outs)
     try:
         relay_segments = eng.relay_geometry()["segments"]     # of the last timed launch (arp_relay_geometry)
     except Exception:
         relay_segments = None
     # the shader clock this box holds under a vector-bound load, measured now, while the chip is at the temperature and power
     # state of the timed region (arp_clock_probe: s_memtime / s_memrealtime around 10 ms of packed FMAs on every SIMD)
-    try:
-        clock_live = engine.clock_probe(dev, 10.0)
-    except Exception:
-        clock_live = None
+    clock_live = None
+    if args.full:
+        try:
+            clock_live = engine.clock_probe(dev, 10.0)
+        except Exception:
+            pass
 
     # end-of-run statistics exchange (the only collectives of the path, parallel.py): all-gather of a per-chain
     # statistic (here the acceptance rate; a sampling run gathers the per-chain minimum ESS the same way) and the
@@ -519,14 +559,14 @@ def main():
 
     LL = 2 * num_ls if inter else L
     extras = {}
-    secondary = world == 1 and not args.headline_only
+    secondary = args.full and world == 1 and not args.headline_only
 
     # N > 1: the OTHER reading of the job, timed in the same run (same W and K, same barriers).  The headline leg is
     # `--scaling` (default weak: --chains per GPU); the second leg is strong (--chains in total, C/N per rank: BASELINE
     # configs[3] read literally) or, under --scaling strong, weak.  In the weak leg every GPU runs exactly the 1-GPU job,
     # so weak_rate / N is this node's own 1-GPU rate and the strong leg's speed-up over it needs no second run.
     other_leg = None
-    if world > 1:
+    if world > 1 and args.full:
         if args.scaling == "weak":
             lo2, hi2 = parallel.shard_bounds(args.chains, rank, world)
             C2, off2, C2_total = hi2 - lo2, lo2, args.chains
@@ -913,7 +953,7 @@ def main():
                      "dual-averaging adaptation, centred trace row every %d transition(s)" % (
                          args.dataset, args.chains, "/GPU" if args.scaling == "weak" else " total", L, T, thin)))
         cpu, cpu_shaped = None, None
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             try:
                 cpu = cpu_baseline(spec, num_ls if inter else L, 8192, 64, eps_i if inter else eps0, 8, inter)
             except Exception as e:  # the oracle is a checker; its absence must not hide the GPU number
@@ -955,21 +995,22 @@ def main():
         if cpu is not None:
             line["cpu_baseline"] = {k: cpu.get(k) for k in ("value", "unit", "cores", "kind", "sample", "error") if k in cpu}
         # ---- everything else: bench_extras.json ----
-        full = dict(line)
-        full["roofline"] = roof
-        full["ess"] = ess_info
-        full.update(extras)
-        if cpu is not None:
-            full["cpu_baseline"] = cpu
-        if cpu_shaped is not None:
-            full["cpu_baseline_reference_shaped"] = cpu_shaped
-        try:
-            with open(args.extras, "w") as f:
-                json.dump(full, f, indent=1)
-            line["extras"] = os.path.relpath(args.extras, ROOT) if args.extras.startswith(ROOT) else args.extras
-        except OSError as e:
-            line["extras"] = None
-            line["extras_error"] = repr(e)
+        if args.full:
+            full = dict(line)
+            full["roofline"] = roof
+            full["ess"] = ess_info
+            full.update(extras)
+            if cpu is not None:
+                full["cpu_baseline"] = cpu
+            if cpu_shaped is not None:
+                full["cpu_baseline_reference_shaped"] = cpu_shaped
+            try:
+                with open(args.extras, "w") as f:
+                    json.dump(full, f, indent=1)
+                line["extras"] = os.path.relpath(args.extras, ROOT) if args.extras.startswith(ROOT) else args.extras
+            except OSError as e:
+                line["extras"] = None
+                line["extras_error"] = repr(e)
         text = json.dumps(line)
         assert len(text) < 4096 and "\n" not in text, len(text)
         sys.stderr.flush()

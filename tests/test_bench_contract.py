@@ -75,11 +75,51 @@ def test_stdout_line_is_short_and_the_rest_goes_to_the_extras_file():
     assert len(re.findall(r"file=json_out", s)) == 1
 
 
-def test_issue_mix_comes_from_the_newest_ledger():
+def _bench_module():
     import importlib.util
     spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
     b = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(b)
+    return b
+
+
+def test_dump_outputs_fits_the_budget_and_samples_reproducibly(tmp_path, monkeypatch):
+    """--dump-outputs: small arrays whole (float32 / counts as float64), an array over its share of the budget as a
+    seeded sample of its flattened elements, everything together within the budget, the same files on a second call."""
+    import numpy as np
+    import torch
+    b = _bench_module()
+    monkeypatch.setattr(b, "DUMP_BUDGET_BYTES", 100000)
+    g = torch.Generator().manual_seed(0)
+    arrays = {"q": torch.randn(64, 71, generator=g), "logp": torch.randn(64, generator=g),
+              "accept_count": torch.randint(0, 1000, (64,), dtype=torch.int32, generator=g),
+              "trace": torch.randn(16, 64, 71, generator=g)}
+    for d in ("a", "b"):
+        b.dump_outputs(str(tmp_path / d), arrays, seed=3)
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["accept_count.npy", "logp.npy", "q.npy", "trace_sample.npy"]
+    for n in names:
+        assert np.array_equal(np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)), n
+    q, acc = np.load(tmp_path / "a" / "q.npy"), np.load(tmp_path / "a" / "accept_count.npy")
+    assert q.dtype == np.float32 and np.array_equal(q, arrays["q"].numpy())
+    assert acc.dtype == np.float64 and np.array_equal(acc, arrays["accept_count"].numpy())
+    flat = arrays["trace"].numpy().reshape(-1)
+    total = sum(np.load(tmp_path / "a" / n).nbytes for n in names)
+    assert total <= 100000
+    share = (100000 - (q.nbytes + acc.nbytes + 64 * 4)) // 4
+    idx = np.unique(np.random.RandomState(3).randint(0, flat.size, size=share, dtype=np.int64))
+    assert np.array_equal(np.load(tmp_path / "a" / "trace_sample.npy"), flat[idx])
+
+
+def test_plain_run_leaves_the_secondary_figures_to_full():
+    s = _src()
+    assert 'add_argument("--full", action="store_true"' in s and 'add_argument("--dump-outputs"' in s
+    assert "secondary = args.full and" in s and "if world > 1 and args.full:" in s
+    assert "if args.full and world == 1 and not args.no_cpu_baseline:" in s
+
+
+def test_issue_mix_comes_from_the_newest_ledger():
+    b = _bench_module()
     mix, src = b.headline_mix()
     assert src.startswith("profiles/r") and src.endswith("_headline_ledger.txt")
     assert set(mix) == set(b.HEADLINE_COST) and 1400 < sum(mix.values()) < 1700

@@ -144,6 +144,9 @@ def _cli_sequence(results_dir, chains=7, ess_small=3, ess_mid=5):
 
 def _cli_worker(rank, ws, port, results_dir, chains=7, ess_small=3, ess_mid=5):
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), WORLD_SIZE=str(ws), RANK=str(rank), LOCAL_RANK=str(rank))
+    if torch.cuda.is_available() and torch.cuda.device_count() < ws:
+        # main.py selects the GPU of LOCAL_RANK when it sees one: on a box with fewer GPUs than ranks they share them
+        os.environ.update(ARP_DEBUG="1", ARP_SHARE_GPU="1")
     _fake_engine(None)
     # VI first, BEFORE any process group exists: ranks != 0 must leave on RANK alone, rank 0 runs without one
     from autoreparam_amd import main as cli

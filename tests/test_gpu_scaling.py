@@ -119,7 +119,7 @@ def test_two_rank_bench_line(scaling):
     env = _two_rank_env()
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr=127.0.0.1",
            "--master-port=%d" % _free_port(), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-           "--chains", "4096", "--transitions", "32", "--scaling", scaling]
+           "--chains", "4096", "--transitions", "32", "--scaling", scaling, "--full"]
     r = subprocess.run(cmd, env=env, cwd=ROOT, timeout=900, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -238,7 +238,7 @@ def check_driver_line(stdout, combined=None):
 
 
 def test_bench_stdout_is_one_json_line(tmp_path):
-    """`python bench.py` the way the driver runs the N = 1 bench: stdout holds the one short JSON line and nothing else; the
+    """`python bench.py --full` the way the driver runs the N = 1 bench: stdout holds the one short JSON line and nothing else; the
     CLI flows it drives (VI fits, tuning runs, the ESS run) are silent, so the line is also the last line of the combined
     stream; the long secondary figures are in the extras file the line names."""
     env = dict(os.environ, PYTHONPATH=ROOT)
@@ -246,7 +246,7 @@ def test_bench_stdout_is_one_json_line(tmp_path):
         env.pop(k, None)
     ex = str(tmp_path / "extras.json")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--chains", "4096", "--transitions", "32",
-           "--extras", ex]
+           "--extras", ex, "--full"]
     r = subprocess.run(cmd, env=env, cwd=ROOT, timeout=900, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
     assert r.returncode == 0, r.stderr[-3000:]
     j = check_driver_line(r.stdout)
@@ -265,3 +265,32 @@ def test_bench_stdout_is_one_json_line(tmp_path):
     assert r2.returncode == 0
     last = [l for l in r2.stdout.splitlines() if l.strip()][-1]
     assert json.loads(last)["n_gpus"] == 1 and len(last) < 4096
+
+
+def test_plain_bench_is_lean_and_dumps_the_same_outputs_twice(tmp_path):
+    """`python bench.py` without --full: the line with the contract's keys and nothing measured beyond the timed steps (no
+    CPU baseline, no ESS run, no clock probe, no extras file); --dump-outputs writes the last timed step's chain state and
+    trace, and a second run with the same arguments writes the same arrays."""
+    env = dict(os.environ, PYTHONPATH=ROOT)
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT"):
+        env.pop(k, None)
+    ex = tmp_path / "extras.json"
+    dumps = []
+    for d in ("a", "b"):
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--chains", "4096",
+               "--transitions", "32", "--extras", str(ex), "--dump-outputs", str(tmp_path / d)]
+        r = subprocess.run(cmd, env=env, cwd=ROOT, timeout=900, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
+        assert r.returncode == 0, r.stderr[-3000:]
+        j = check_driver_line(r.stdout)
+        assert j["steps"] == 3 and j["ms_per_step"] > 0 and j["value"] > 0
+        assert "cpu_baseline" not in j and j["ess_per_sec"] is None and j["roofline"]["clock_ghz_live"] is None
+        assert "extras" not in j and not ex.exists()
+        dumps.append({f: np.load(tmp_path / d / f) for f in sorted(os.listdir(tmp_path / d))})
+    a, b = dumps
+    assert sorted(a) == ["accept_count.npy", "accept_count1.npy", "adapt.npy", "adapt1.npy", "grad.npy", "logp.npy", "q.npy",
+                         "trace.npy"]
+    assert a["q.npy"].shape == (4096, 71) and a["trace.npy"].shape == (16, 4096, 71) and a["q.npy"].dtype == np.float32
+    assert a["accept_count.npy"].dtype == np.float64 and a["accept_count.npy"].max() <= 4 * 32
+    assert sum(v.nbytes for v in a.values()) <= 64 * 10 ** 6 and np.isfinite(a["trace.npy"]).all()
+    for f in a:
+        assert np.array_equal(a[f], b[f]), f

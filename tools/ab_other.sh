@@ -3,7 +3,7 @@
 PAT=$1; shift
 for rep in 1 2; do for v in "$@"; do
   if [ -z "$v" ]; then L=""; else L="ARP_DEBUG=1 ARP_LIB_PATH=$PWD/autoreparam_amd/libautoreparam_hip$v.so"; fi
-  env $L python bench.py --no-cpu-baseline --no-ess --steps 10 --warmup 3 2>/dev/null | python -c "
+  env $L python bench.py --full --no-cpu-baseline --no-ess --steps 10 --warmup 3 2>/dev/null | python -c "
 import sys, json
 b=json.loads([l for l in sys.stdin if l.startswith('{')][-1])
 for k,v in b['other_models'].items():

@@ -19,5 +19,5 @@ if len(sys.argv) > 1 and sys.argv[1] == "standalone":
     r = bench.reference_flow_ess("PA", 65536, 0)
     print({k: r[k] for k in ("mcmc_time_sec", "ess_per_sec", "mean_min_ess_per_chain", "num_ls_chosen")})
 else:
-    sys.argv = ["bench.py", "--steps", "20", "--warmup", "5", "--no-cpu-baseline"]
+    sys.argv = ["bench.py", "--full", "--steps", "20", "--warmup", "5", "--no-cpu-baseline"]
     bench.main()
