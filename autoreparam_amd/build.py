@@ -16,7 +16,8 @@ FLAGS += os.environ.get("ARP_HIPCC_FLAGS", "").split()   # experiments only (e.g
 # per-file flags.  German credit's matrix-core likelihood: let the MFMAs write VGPRs (the forward product's result is
 # consumed by VALU instructions at once; from AGPRs every element costs a v_accvgpr_read first: 601 -> 460 instructions
 # per 128-row tile)
-FILE_FLAGS = {"inst_german.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"]}
+FILE_FLAGS = {"inst_german.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],
+              "inst_german_gamma.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"]}
 
 
 def _sources():

@@ -85,7 +85,7 @@ static const std::vector<LaneOps>* family(const arp_model* m) {
     case ARP_MODEL_RADON: return &radon_ops();
     case ARP_MODEL_EIGHT_SCHOOLS: return &schools_ops();
     case ARP_MODEL_ELECTION: return &election_ops();
-    case ARP_MODEL_GERMAN_CREDIT: return &german_ops();
+    case ARP_MODEL_GERMAN_CREDIT: return m->german_prior ? &german_gamma_ops() : &german_ops();
     case ARP_MODEL_RADON_STDDVS: return &radon_sd_ops();
     case ARP_MODEL_NEALS_FUNNEL: return &funnel_ops();
     case ARP_MODEL_ELECTRIC: return &electric_ops();
@@ -527,6 +527,14 @@ int arp_model_set_option(arp_model* m, const char* key, const char* value) {
     } else { set_error("arp_model_set_option: german_math is one of auto, f32, bf16x3"); return 1; }
     return 0;
   }
+  if (!strcmp(key, "german_prior")) {
+    // prior of the feature scales: log-normal centred (german_credit_lognormalcentered) or Gamma (german_credit_gammascale)
+    if (m->model != ARP_MODEL_GERMAN_CREDIT) { set_error("arp_model_set_option: german_prior applies to german credit only"); return 1; }
+    if (!strcmp(value, "lognormal")) m->german_prior = 0;
+    else if (!strcmp(value, "gamma")) m->german_prior = 1;
+    else { set_error("arp_model_set_option: german_prior is one of lognormal, gamma"); return 1; }
+    return 0;
+  }
   if (!strcmp(key, "vi_launch")) {
     // how arp_vi_run starts a kernel whose workgroups wait for each other: "cooperative" (hipLaunchCooperativeKernel),
     // "plain" (ordinary launch, one at a time per process) or "auto" (cooperative where the device supports it)
@@ -585,7 +593,8 @@ static const LaneOps* select_ops(arp_model* m, int K_req, int C) {
   const long long fill = (m->model == ARP_MODEL_RADON || m->model == ARP_MODEL_TIME_SERIES) ? 65536 : 131072;
   // German credit at 4 lanes per chain: the likelihood on bf16 matrix cores with three-piece operands where the data
   // allow it (model_german.h), unless the caller asked for the f32 matrix-core form (arp_model_set_option)
-  if (m->model == ARP_MODEL_GERMAN_CREDIT && K_req == 4 && m->german.Xb && m->german_math != 1) return &german_bf3_ops();
+  if (m->model == ARP_MODEL_GERMAN_CREDIT && K_req == 4 && m->german.Xb && m->german_math != 1)
+    return m->german_prior ? &german_gamma_bf3_ops() : &german_bf3_ops();
   const LaneOps* o = pick(*fam, m->n_groups, K_req, C, m->model != ARP_MODEL_GERMAN_CREDIT, fill,
                           m->model == ARP_MODEL_TIME_SERIES ? 2 : 1);
   if (!o) set_error("no kernel instantiation for this (lanes_per_chain, group count): add <Model>Lane<K, ceil(groups/K)> to the model's inst_*.hip");
@@ -803,7 +812,7 @@ int arp_vi_run(arp_model* m, int which, const arp_vi_config* cfg, const arp_vi_i
   // German credit: the row-part lane on bf16 matrix cores with three-piece operands where the data allow it (64-observation
   // tiles), else on f32 matrix cores (128-observation tiles) -- the same choice as the chain kernels make (select_ops)
   const bool german_bf3 = m->model == ARP_MODEL_GERMAN_CREDIT && m->german.Xb && m->german_math != 1;
-  if (german_bf3) o = &german_bf3_ops();
+  if (german_bf3) o = m->german_prior ? &german_gamma_bf3_ops() : &german_bf3_ops();
   if (m->D > o->vi_dmax) { set_error("arp_vi_run: model dimension exceeds this model's VI kernel instantiation"); return 1; }
   ViParams P;
   P.n_steps = cfg->n_steps; P.n_mc = cfg->n_mc; P.learn_a = cfg->learn_a; P.tied_b = cfg->tied_b; P.a_prior = cfg->a_prior; P.D = m->D;

@@ -310,6 +310,8 @@ const std::vector<LaneOps>& schools_ops();
 const std::vector<LaneOps>& election_ops();
 const std::vector<LaneOps>& german_ops();
 const LaneOps& german_bf3_ops();   // 4 lanes per chain, likelihood on bf16 matrix cores with three-piece operands
+const std::vector<LaneOps>& german_gamma_ops();   // the same two with Gamma-prior scales (german_credit_gammascale)
+const LaneOps& german_gamma_bf3_ops();
 const std::vector<LaneOps>& radon_sd_ops();
 const std::vector<LaneOps>& funnel_ops();
 const std::vector<LaneOps>& electric_ops();
@@ -322,7 +324,8 @@ struct arp_model {
   int D = 0;
   int device = 0;
   bool host_only = false;
-  int german_math = 0;       // 0 auto (bf16 x 3 where the data allow), 1 f32 matrix cores, 2 bf16 x 3 (arp_model_set_option)    // test hook (arp_api.hip: host_only): no device behind this handle
+  int german_math = 0;       // 0 auto (bf16 x 3 where the data allow), 1 f32 matrix cores, 2 bf16 x 3 (arp_model_set_option)
+  int german_prior = 0;      // prior of German credit's feature scales: 0 log-normal centred, 1 Gamma (arp_model_set_option)    // test hook (arp_api.hip: host_only): no device behind this handle
   int n_groups = 0;          // slice axis length (radon J, election 52, schools 8)
   float* dev_tables = nullptr;   // one allocation holding all frozen tables
   float* dev_ab[2] = {nullptr, nullptr};  // [2][D]: a then b, per parameterisation

@@ -15,6 +15,15 @@
 //   d/dbt_d  = -bt_d e_d^2 + v_d exp((1-b_d) bls_d),   e_d = exp(-b_d bls_d)
 //   hb_d     = b_d (bt_d e_d)^2 - b_d + v_d (1-b_d) beta_d
 //   d/dblt_d = hb_d - r_d,  r_d = blt_d - a_d ols;   d/dols = sum a_d r_d + (1-a_d) hb_d
+//
+// The same lane with PRIOR_ = kGermanGamma is german_credit_gammascale (reference models.py:926-964): the same data and
+// likelihood, Gamma-prior scales.
+//   bls_d = log g_d, g_d ~ Gamma(1/2, 1/2)   log density 0.5 bls_d - 0.5 exp(bls_d) (Jacobian included, constant
+//                                            -0.5 log 2 pi: the one N(ols, 1) drops above); never reparameterised
+//   beta_d ~ N(0, exp(ols + bls_d))          s_d = ols + bls_d: bt_d ~ N(0, exp(b_d s_d)), beta_d = exp((1-b_d) s_d) bt_d
+// ols and beta have loc 0, so a[] plays no part.  With e_d = exp(-b_d s_d), zb_d = bt_d e_d:
+//   h_d      = b_d (zb_d^2 - 1) + v_d (1-b_d) beta_d
+//   d/dbt_d  = v_d exp((1-b_d) s_d) - zb_d e_d,   d/dbls_d = h_d + 0.5 - 0.5 exp(bls_d),   d/dols = sum h_d
 #pragma once
 #include "arp_device.h"
 
@@ -71,6 +80,8 @@ __host__ __device__ inline void bf3_split(float x, uint32_t& h, uint32_t& m, uin
   c_.u = m; c_.f = b_.f - c_.f; l = c_.u;
 }
 
+enum GermanPrior { kGermanLogNormal = 0, kGermanGamma = 1 };   // prior of the feature scales (see the top of the file)
+
 struct GermanArgs {
   const float* X;   // [N][64] row-major, columns >= F are zero
   const float* y;   // [N]
@@ -87,7 +98,9 @@ struct GermanArgs {
 // the gradient with weight `pw` (1 in the workgroup that owns row part 0, 0 elsewhere), so that the SUM over the row
 // parts of everything grad() and dparam() return is the whole model's -- they are affine in the likelihood's v.
 // BF3_: the likelihood on bf16 matrix cores with three-piece operands (above) instead of f32 matrix cores; K = 4 only.
-template <int K_, int NLS_, int W_ = kBlock / 64, bool PART_ = false, bool BF3_ = false>
+// PRIOR_: the prior of the scales, log-normal centred (german_credit_lognormalcentered) or Gamma
+// (german_credit_gammascale); the likelihood routines are shared.
+template <int K_, int NLS_, int W_ = kBlock / 64, bool PART_ = false, bool BF3_ = false, int PRIOR_ = kGermanLogNormal>
 struct GermanLane {
   static_assert(!BF3_ || K_ == 4, "the bf16 x 3 likelihood serves the 4-lane kernels");
   static constexpr int kTileObs = BF3_ ? kBf3Rows : kGermanTileRows;   // observations per tile of this lane's image
@@ -105,7 +118,8 @@ struct GermanLane {
   static constexpr int MINW = K_ >= 8 ? 2 : 1;   // waves per SIMD the register allocator must leave room for
   using Args = GermanArgs;
 
-  float a[NLS], b[NLS];     // a of bls_d, b of beta_d (the only ones that matter)
+  static constexpr bool GAMMA = PRIOR_ == kGermanGamma;
+  float a[GAMMA ? 1 : NLS], b[NLS];   // a of bls_d (log-normal only), b of beta_d: the only ones that matter
   float s0i, c0;            // 1/10^b0, 10^(1-b0)
   const float* X; const float* y; const float* Xt; const float* Xb;
   int N, F, slot, nown;
@@ -166,7 +180,7 @@ struct GermanLane {
 #pragma unroll
     for (int i = 0; i < NLS; ++i) {
       bool ok = i < nown;
-      a[i] = ok ? av[1 + slot * NLS + i] : 0.0f;
+      if constexpr (!GAMMA) a[i] = ok ? av[1 + slot * NLS + i] : 0.0f;
       b[i] = ok ? bv[1 + F + slot * NLS + i] : 0.0f;
     }
   }
@@ -1065,6 +1079,11 @@ struct GermanLane {
 
   template <bool LOGP>
   ARP_DEV float grad(const float (&q)[ND], float (&g)[ND]) const {
+    if constexpr (GAMMA) return grad_gamma<LOGP>(q, g);
+    else return grad_lognormal<LOGP>(q, g);
+  }
+  template <bool LOGP>
+  ARP_DEV float grad_lognormal(const float (&q)[ND], float (&g)[ND]) const {
     ARP_T0(tg);
     if constexpr (K == 4) first_tile();
     const float ols = c0 * q[0];
@@ -1123,39 +1142,111 @@ struct GermanLane {
     return lp;
   }
 
-  ARP_DEV void dparam(const float (&q)[ND], const float (&g)[ND], float (&da)[ND], float (&db)[ND]) const {
+  template <bool LOGP>
+  ARP_DEV float likelihood(const float (&beta)[NLS], float (&v)[NLS]) const {
+    if constexpr (K == 8) return likelihood_k8<LOGP>(beta, v);
+    else if constexpr (K == 4 && BF3_) return likelihood_bf3<LOGP>(beta, v);
+    else if constexpr (K == 4) return likelihood_mfma<LOGP>(beta, v);
+    else return likelihood_generic<LOGP>(beta, v);
+  }
+
+  // Gamma scales (see the top of the file).  Row-part form: every prior term weighted by pw, as in grad() above.
+  template <bool LOGP>
+  ARP_DEV float grad_gamma(const float (&q)[ND], float (&g)[ND]) const {
+    if constexpr (K == 4) first_tile();
     const float ols = c0 * q[0];
-#pragma unroll
-    for (int i = 0; i < ND; ++i) { da[i] = 0.0f; db[i] = 0.0f; }
-    // (PART_: g is this row part's share of the gradient; the constant 1 of the two affine forms counts once)
-    db[0] = -2.302585092994046f * fmaf(q[0], g[0], pw());
+    float beta[NLS], v[NLS], s[NLS];
 #pragma unroll
     for (int i = 0; i < NLS; ++i) {
-      bool ok = i < nown;
-      float bls = fmaf(-a[i], ols, q[NG + i]) + ols;
-      da[NG + i] = ok ? -ols * g[NG + i] : 0.0f;
-      db[NG + NLS + i] = ok ? -bls * fmaf(q[NG + NLS + i], g[NG + NLS + i], pw()) : 0.0f;
+      s[i] = q[NG + i] + ols;
+      beta[i] = fast_exp((1.0f - b[i]) * s[i]) * q[NG + NLS + i];   // padding: q = 0 -> beta = 0
+      v[i] = 0.0f;
+    }
+    float lp = likelihood<LOGP>(beta, v);
+    const float w_ = pw();
+    float lq = 0.0f, g_ols = 0.0f;
+#pragma unroll
+    for (int i = 0; i < NLS; ++i) {
+      const float e = fast_exp(-b[i] * s[i]);
+      const float zb = q[NG + NLS + i] * e;
+      const float eb = fast_exp(q[NG + i]);
+      const float hb = fmaf(w_ * b[i], fmaf(zb, zb, -1.0f), v[i] * (1.0f - b[i]) * beta[i]);
+      const bool ok = i < nown;
+      g[NG + NLS + i] = ok ? fmaf(v[i], fast_exp((1.0f - b[i]) * s[i]), -w_ * zb * e) : 0.0f;
+      g[NG + i] = ok ? fmaf(w_, fmaf(-0.5f, eb, 0.5f), hb) : 0.0f;
+      g_ols += ok ? hb : 0.0f;
+      if (LOGP) lq += ok ? fmaf(-0.5f * zb, zb, fmaf(-b[i], s[i], fmaf(0.5f, q[NG + i], -0.5f * eb))) : 0.0f;
+    }
+    g_ols = group_sum<K>(g_ols);
+    const float u0 = q[0] * s0i;
+    g[0] = fmaf(c0, g_ols, -w_ * u0 * s0i);
+    if (LOGP) lp += w_ * (group_sum<K>(lq) - 0.5f * u0 * u0);
+    return lp;
+  }
+
+  ARP_DEV void dparam(const float (&q)[ND], const float (&g)[ND], float (&da)[ND], float (&db)[ND]) const {
+    if constexpr (GAMMA) {
+      // a is inert; bls is not reparameterised; beta: -s_d (bt_d g_bt_d + 1) with s_d = ols + bls_d
+      const float ols = c0 * q[0];
+#pragma unroll
+      for (int i = 0; i < ND; ++i) { da[i] = 0.0f; db[i] = 0.0f; }
+      db[0] = -2.302585092994046f * fmaf(q[0], g[0], pw());
+#pragma unroll
+      for (int i = 0; i < NLS; ++i) {
+        const bool ok = i < nown;
+        db[NG + NLS + i] = ok ? -(q[NG + i] + ols) * fmaf(q[NG + NLS + i], g[NG + NLS + i], pw()) : 0.0f;
+      }
+    } else {
+      const float ols = c0 * q[0];
+#pragma unroll
+      for (int i = 0; i < ND; ++i) { da[i] = 0.0f; db[i] = 0.0f; }
+      // (PART_: g is this row part's share of the gradient; the constant 1 of the two affine forms counts once)
+      db[0] = -2.302585092994046f * fmaf(q[0], g[0], pw());
+#pragma unroll
+      for (int i = 0; i < NLS; ++i) {
+        bool ok = i < nown;
+        float bls = fmaf(-a[i], ols, q[NG + i]) + ols;
+        da[NG + i] = ok ? -ols * g[NG + i] : 0.0f;
+        db[NG + NLS + i] = ok ? -bls * fmaf(q[NG + NLS + i], g[NG + NLS + i], pw()) : 0.0f;
+      }
     }
   }
 
   ARP_DEV void to_centered(const float (&q)[ND], float (&x)[ND]) const {
     const float ols = c0 * q[0];
     x[0] = ols;
+    if constexpr (GAMMA) {   // bls maps to itself, beta's scale is exp(ols + bls)
 #pragma unroll
-    for (int i = 0; i < NLS; ++i) {
-      float bls = q[NG + i] + (1.0f - a[i]) * ols;
-      x[NG + i] = bls;
-      x[NG + NLS + i] = fast_exp((1.0f - b[i]) * bls) * q[NG + NLS + i];
+      for (int i = 0; i < NLS; ++i) {
+        x[NG + i] = q[NG + i];
+        x[NG + NLS + i] = fast_exp((1.0f - b[i]) * (q[NG + i] + ols)) * q[NG + NLS + i];
+      }
+    } else {
+#pragma unroll
+      for (int i = 0; i < NLS; ++i) {
+        float bls = q[NG + i] + (1.0f - a[i]) * ols;
+        x[NG + i] = bls;
+        x[NG + NLS + i] = fast_exp((1.0f - b[i]) * bls) * q[NG + NLS + i];
+      }
     }
   }
   ARP_DEV void from_centered(const float (&x)[ND], float (&q)[ND]) const {
     const float ols = x[0];
     q[0] = ols / c0;
+    if constexpr (GAMMA) {
 #pragma unroll
-    for (int i = 0; i < NLS; ++i) {
-      bool ok = i < nown;
-      q[NG + i] = ok ? x[NG + i] - (1.0f - a[i]) * ols : 0.0f;
-      q[NG + NLS + i] = ok ? x[NG + NLS + i] * fast_exp(-(1.0f - b[i]) * x[NG + i]) : 0.0f;
+      for (int i = 0; i < NLS; ++i) {
+        const bool ok = i < nown;
+        q[NG + i] = ok ? x[NG + i] : 0.0f;
+        q[NG + NLS + i] = ok ? x[NG + NLS + i] * fast_exp(-(1.0f - b[i]) * (x[NG + i] + ols)) : 0.0f;
+      }
+    } else {
+#pragma unroll
+      for (int i = 0; i < NLS; ++i) {
+        bool ok = i < nown;
+        q[NG + i] = ok ? x[NG + i] - (1.0f - a[i]) * ols : 0.0f;
+        q[NG + NLS + i] = ok ? x[NG + NLS + i] * fast_exp(-(1.0f - b[i]) * x[NG + i]) : 0.0f;
+      }
     }
   }
 };

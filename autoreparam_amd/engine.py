@@ -49,6 +49,8 @@ class Engine(object):
         with torch.cuda.device(self.device):
             _lib.check(self._L.arp_model_create(C.byref(ds), C.byref(self._h)))
         del keep
+        for key, value in getattr(spec, "options", ()):
+            self.set_option(key, value)
         self.D = self._L.arp_model_dim(self._h)
         assert self.D == spec.D, (self.D, spec.D)
         self._ab = [None, None]

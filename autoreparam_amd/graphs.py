@@ -81,6 +81,8 @@ def make_cvip_graph(model_config, parameterisation_type="exp", tied_pparams=Fals
     spec = model_config.model
     init = collections.OrderedDict()
     for name, shp in zip(spec.part_names, spec.part_shapes):
+        if name in spec.fixed_parts:   # not reparameterised: the reference creates no variable for it
+            continue
         if tied_pparams:
             init[name + "_a"] = np.full(shp, 0.5, np.float32)      # broadcast shape of loc and scale
         else:

@@ -106,6 +106,8 @@ def find_best_learning_rate(elbo, variational_parameters, learnable_parameters_p
         learned_reparam = collections.OrderedDict()
         for k, name in enumerate(spec.part_names):
             lo, hi = spec.offsets[k], spec.offsets[k + 1]
+            if name in spec.fixed_parts:   # not reparameterised: no variable in the reference's learned dict
+                continue
             if bv is None:
                 learned_reparam[name + "_a"] = av[lo:hi].reshape(spec.part_shapes[k]).astype(np.float32)
             else:   # untied: the reference's variable shapes (a shared value is a scalar)

@@ -1,6 +1,6 @@
 """Model definitions for the hot path: the four hierarchical models named by
-BASELINE.json plus radon_stddvs, neals_funnel, electric and time_series, as frozen
-data + a model id the HIP engine understands.
+BASELINE.json plus radon_stddvs, neals_funnel, electric, time_series and
+german_credit_gammascale, as frozen data + a model id the HIP engine understands.
 
 Mirrors the reference's ``models.get_model_by_name(name, dataset) -> ModelConfig``
 (models.py:51-54, 1144-1175).  In the reference ``ModelConfig.model`` is an
@@ -25,12 +25,18 @@ ModelConfig = collections.namedtuple(
 class ModelSpec(object):
     """Joint density of one model: id, latent parts in trace order, raw inputs."""
 
-    def __init__(self, name, model_id, part_names, part_shapes, raw, observed, scalar_loc=(), scalar_scale=()):
+    def __init__(self, name, model_id, part_names, part_shapes, raw, observed, scalar_loc=(), scalar_scale=(),
+                 fixed_parts=(), options=()):
         # vector parts whose reference random variable has a SCALAR loc / scale: with --notied_pparams the
         # reference gives `<rv>_a` the loc's shape and `<rv>_b` the scale's (program_transformations.py:486-533),
         # i.e. one shared value for the part
         self.scalar_loc = set(scalar_loc)
         self.scalar_scale = set(scalar_scale)
+        # parts the reference's interceptors never reparameterise (not Normal random variables): they have no
+        # `<rv>_a` / `<rv>_b`, and the kernels ignore whatever (a, b) they are given
+        self.fixed_parts = set(fixed_parts)
+        # (key, value) pairs for arp_model_set_option, applied when an Engine is created
+        self.options = tuple(options)
         self.name = name
         self.model_id = model_id
         self.part_names = list(part_names)
@@ -63,6 +69,8 @@ class ModelSpec(object):
         optionally ``<rv>_b`` (missing ``_b`` means 1, exactly as the reference's
         get_or_init falls back at program_transformations.py:495-500; other keys
         such as ``*_prior_mean`` are ignored).
+        Parts in ``fixed_parts`` need no entry; they take the value of the rest ('NCP': 0, else 1), which keeps the
+        engine's CP / NCP classification of the whole vector.
         """
         a = np.ones(self.D, np.float32)
         b = np.ones(self.D, np.float32)
@@ -74,6 +82,8 @@ class ModelSpec(object):
             raise ValueError("unknown parameterisation %r" % (reparam,))
         for k, name in enumerate(self.part_names):
             lo, hi = self.offsets[k], self.offsets[k + 1]
+            if name in self.fixed_parts:
+                continue
             if name + "_a" not in reparam:
                 raise KeyError("parameterisation has no entry for %s_a" % name)
             a[lo:hi] = np.broadcast_to(np.asarray(reparam[name + "_a"], np.float32).reshape(-1), (hi - lo,))
@@ -203,6 +213,18 @@ def _spec_german():
                      r, {"y": r["y"][np.newaxis, ...]}, scalar_loc=("beta_log_scales",))
 
 
+def _spec_german_gammascale():
+    """German credit with Gamma(1/2, 1/2) priors on the feature scales (reference models.py:926-964): the same data,
+    parts and likelihood as the log-normal model; beta_log_scales is the log of a Gamma variable, which the reference's
+    interceptors do not reparameterise."""
+    r = _load("german_credit.npz")
+    F = r["X"].shape[1]
+    return ModelSpec("german_credit_gammascale", _lib.MODEL_GERMAN_CREDIT,
+                     ["overall_log_scale", "beta_log_scales", "beta"], [(), (F,), (F,)],
+                     r, {"y": r["y"][np.newaxis, ...]}, fixed_parts=("beta_log_scales",),
+                     options=(("german_prior", "gamma"),))
+
+
 def _spec_election():
     r = _load("election88.npz")
     S = int(r["n_state"])
@@ -227,11 +249,14 @@ def get_model_by_name(model_name, dataset=None):
         spec = _spec_time_series()
     elif model_name == "german_credit_lognormalcentered":
         spec = _spec_german()
+    elif model_name == "german_credit_gammascale":
+        spec = _spec_german_gammascale()
     elif model_name in ("election", "election88"):
         spec = _spec_election()
     else:
         raise Exception("unknown model {} (this build covers 8schools, radon, radon_stddvs, "
-                        "neals_funnel, electric, time_series, german_credit_lognormalcentered, election)".format(model_name))
+                        "neals_funnel, electric, time_series, german_credit_lognormalcentered, "
+                        "german_credit_gammascale, election)".format(model_name))
     from . import engine  # deferred: converters run on the device
 
     varnames = spec.part_names

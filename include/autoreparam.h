@@ -40,7 +40,7 @@ extern "C" {
 enum {
   ARP_MODEL_EIGHT_SCHOOLS = 0,
   ARP_MODEL_RADON = 1,
-  ARP_MODEL_GERMAN_CREDIT = 2, /* german_credit_lognormalcentered */
+  ARP_MODEL_GERMAN_CREDIT = 2, /* german_credit_lognormalcentered; german_credit_gammascale with option "german_prior" */
   ARP_MODEL_ELECTION = 3,
   ARP_MODEL_NEALS_FUNNEL = 5, /* models.py:671-696; no dataset fields are read */
   ARP_MODEL_RADON_STDDVS = 4, /* radon with per-county observation scales, models.py:763-806 */
@@ -136,7 +136,11 @@ int arp_model_dim(const arp_model* m);                 /* D */
  * per chain -- "f32" = f32 matrix cores (v_mfma_f32_16x16x4_f32, exact f32 products), "bf16x3" = bf16 matrix cores with every
  * operand as three bf16 pieces (six leading cross products: f32-equivalent, error ~ 2^-23 per product; needs a design matrix
  * with at most 8 columns that are not exact in one bf16 piece -- the reference's data have 7), "auto" (default) = bf16x3 where
- * the data allow it.  "vi_launch": how arp_vi_run starts a launch whose workgroups wait for each other inside the launch --
+ * the data allow it.  "german_prior": the prior of german credit's feature scales -- "lognormal" (default) =
+ * german_credit_lognormalcentered, beta_log_scales ~ N(overall_log_scale, 1), beta ~ N(0, exp(beta_log_scales)); "gamma" =
+ * german_credit_gammascale, beta_log_scales = log g, g ~ Gamma(1/2, 1/2), beta ~ N(0, exp(overall_log_scale +
+ * beta_log_scales)), where beta_log_scales is never reparameterised (its a, b are ignored) and no a has any effect.  Same
+ * data, dimension, state layout, random streams and dropped constant; takes effect from the next launch.  "vi_launch": how arp_vi_run starts a launch whose workgroups wait for each other inside the launch --
  * "cooperative" = hipLaunchCooperativeKernel (the runtime checks the grid against the device's capacity and serialises such
  * launches of the process), "plain" = an ordinary launch sized by an occupancy query, one such launch at a time per process,
  * "auto" (default) = cooperative where the device supports it, plain if the runtime refuses the grid.  (Kernels of other
