@@ -12,8 +12,6 @@ namespace arp {
 static thread_local std::string g_err;
 void set_error(const std::string& msg) { g_err = msg; }
 
-static const double kHalfLog2Pi = 0.9189385332046727;
-
 // geometry of the last arp_vi_run of this thread (arp_vi_geometry: a measurement hook)
 struct ViGeometry { int v[6]; };
 static thread_local ViGeometry g_vi_geometry = {{0, 0, 0, 0, 0, 0}};
@@ -55,7 +53,7 @@ static bool debug_int(const char* name, int* out) {
 // `exact`: the family needs NL == ceil(groups / K), rounded up to a multiple of `unit` (only a lane's last slice may be
 // padding; time_series: a lane owns whole time steps, unit = 2) -- the random-stream partition depends on it.
 static const LaneOps* pick(const std::vector<LaneOps>& ops, int groups, int K_req, int C, bool exact,
-                           long long fill_lanes = 131072, int unit = 1) {
+                           long long fill_lanes, int unit) {
   auto best_for = [&](int K) -> const LaneOps* {
     const LaneOps* best = nullptr;
     const int need = ((groups + K - 1) / K + unit - 1) / unit * unit;
@@ -65,8 +63,7 @@ static const LaneOps* pick(const std::vector<LaneOps>& ops, int groups, int K_re
     return best;
   };
   if (K_req > 0) return best_for(K_req);
-  // default: the fewest lanes per chain that still put `fill_lanes` lanes on the device -- two waves on every
-  // SIMD of the 256 CUs (256 x 4 x 2 x 64 = 131072) unless the family measured better with one
+  // default: the fewest lanes per chain that still put `fill_lanes` lanes on the device (arp_build.hip: kFamilies)
   std::vector<int> Ks;
   for (const auto& o : ops) if (std::find(Ks.begin(), Ks.end(), o.K) == Ks.end()) Ks.push_back(o.K);
   std::sort(Ks.begin(), Ks.end());
@@ -78,335 +75,6 @@ static const LaneOps* pick(const std::vector<LaneOps>& ops, int groups, int K_re
     if ((long long)C * K >= fill_lanes) return o;
   }
   return last;
-}
-
-static const std::vector<LaneOps>* family(const arp_model* m) {
-  switch (m->model) {
-    case ARP_MODEL_RADON: return &radon_ops();
-    case ARP_MODEL_EIGHT_SCHOOLS: return &schools_ops();
-    case ARP_MODEL_ELECTION: return &election_ops();
-    case ARP_MODEL_GERMAN_CREDIT: return m->german_prior ? &german_gamma_ops() : &german_ops();
-    case ARP_MODEL_RADON_STDDVS: return &radon_sd_ops();
-    case ARP_MODEL_NEALS_FUNNEL: return &funnel_ops();
-    case ARP_MODEL_ELECTRIC: return &electric_ops();
-    case ARP_MODEL_TIME_SERIES: return &time_series_ops();
-    default: return nullptr;
-  }
-}
-static const void* family_args(const arp_model* m) {
-  switch (m->model) {
-    case ARP_MODEL_RADON: return &m->radon;
-    case ARP_MODEL_EIGHT_SCHOOLS: return &m->schools;
-    case ARP_MODEL_ELECTION: return &m->election;
-    case ARP_MODEL_GERMAN_CREDIT: return &m->german;
-    case ARP_MODEL_RADON_STDDVS: return &m->radon_sd;
-    case ARP_MODEL_NEALS_FUNNEL: return &m->funnel;
-    case ARP_MODEL_ELECTRIC: return &m->electric;
-    case ARP_MODEL_TIME_SERIES: return &m->time_series;
-    default: return nullptr;
-  }
-}
-
-static int upload_tables(arp_model* m);
-
-static int build_radon(arp_model* m, const arp_dataset* d) {
-  const int J = d->n_groups, N = d->n_obs;
-  if (!d->group_host || !d->u_host || !d->x_host || !d->y_host || J <= 0 || N <= 0) {
-    set_error("radon: group/u/x/y and n_groups/n_obs are required");
-    return 1;
-  }
-  std::vector<double> n(J, 0.0), sx(J, 0.0), sy(J, 0.0);
-  double sxy = 0, sxx = 0, syy = 0;
-  for (int i = 0; i < N; ++i) {
-    int j = d->group_host[i];
-    double x = d->x_host[i], y = d->y_host[i];
-    sxy += x * y; sxx += x * x; syy += y * y;
-    // tf.one_hot gives an all-zero row for an out-of-range county: such an
-    // observation sees no county effect and only informs b2 (models.py:834-836)
-    if (j < 0 || j >= J) continue;
-    n[j] += 1; sx[j] += x; sy[j] += y;
-  }
-  m->D = 3 + J;
-  m->n_groups = J;
-  m->host_tables.resize(4 * (size_t)J);
-  for (int j = 0; j < J; ++j) {
-    m->host_tables[j] = (float)n[j];
-    m->host_tables[J + j] = (float)sx[j];
-    m->host_tables[2 * J + j] = (float)sy[j];
-    m->host_tables[3 * J + j] = d->u_host[j];
-  }
-  if (upload_tables(m)) return 1;
-  m->radon.n = m->dev_tables;
-  m->radon.sx = m->dev_tables + J;
-  m->radon.sy = m->dev_tables + 2 * J;
-  m->radon.u = m->dev_tables + 3 * J;
-  m->radon.sxy = (float)sxy;
-  m->radon.sxx = (float)sxx;
-  double sy_tot = 0, suy_tot = 0;
-  for (int j = 0; j < J; ++j) { sy_tot += sy[j]; suy_tot += (double)d->u_host[j] * sy[j]; }
-  m->radon.sy_tot = (float)sy_tot;
-  m->radon.suy_tot = (float)suy_tot;
-  m->radon.J = J;
-  // every Normal has unit scale under every (a,b): const = -(3+J+N) 0.5 log 2pi - 0.5 Syy
-  m->const_base = -(3.0 + J + N) * kHalfLog2Pi - 0.5 * syy;
-  return 0;
-}
-
-static int upload_tables(arp_model* m) {
-  if (m->host_only) {
-    m->dev_tables = (float*)malloc(std::max<size_t>(1, m->host_tables.size()) * sizeof(float));
-    if (!m->dev_tables) { set_error("upload_tables: out of memory"); return 1; }
-    memcpy(m->dev_tables, m->host_tables.data(), m->host_tables.size() * sizeof(float));
-    return 0;
-  }
-  ARP_HIP_OK(hipMalloc(&m->dev_tables, m->host_tables.size() * sizeof(float)));
-  ARP_HIP_OK(hipMemcpy(m->dev_tables, m->host_tables.data(), m->host_tables.size() * sizeof(float),
-                       hipMemcpyHostToDevice));
-  return 0;
-}
-
-// reference models.py:131-147: y_host = effects, u_host = stddevs
-static int build_schools(arp_model* m, const arp_dataset* d) {
-  if (!d->y_host || !d->u_host) { set_error("8schools: y (effects) and u (stddevs) are required"); return 1; }
-  m->D = 10; m->n_groups = 8;
-  m->host_tables.assign(d->y_host, d->y_host + 8);
-  m->host_tables.insert(m->host_tables.end(), d->u_host, d->u_host + 8);
-  if (upload_tables(m)) return 1;
-  m->schools.y = m->dev_tables;
-  m->schools.sigma = m->dev_tables + 8;
-  double c = -18.0 * kHalfLog2Pi;
-  for (int k = 0; k < 8; ++k) c -= log((double)d->u_host[k]);
-  m->const_base = c;
-  m->top_scale = {{0, log(5.0)}, {1, log(5.0)}};
-  return 0;
-}
-
-// reference models.py:967-989: group = 1-based state fed to tf.one_hot(., S); x = female, x2 = black
-static int build_election(arp_model* m, const arp_dataset* d) {
-  const int S = d->n_groups, N = d->n_obs;
-  if (!d->group_host || !d->x_host || !d->x2_host || !d->y_host || S <= 0 || N <= 0) {
-    set_error("election: group/x(female)/x2(black)/y and n_groups/n_obs are required");
-    return 1;
-  }
-  m->D = S + 4; m->n_groups = S + 1;
-  std::vector<double> cn((size_t)(S + 1) * 4, 0.0), cy((size_t)(S + 1) * 4, 0.0);
-  for (int i = 0; i < N; ++i) {
-    int t = d->group_host[i];
-    if (t < 0 || t >= S) t = S;  // all-zero one-hot row: no state effect
-    int c = (d->x_host[i] != 0.0f ? 1 : 0) + (d->x2_host[i] != 0.0f ? 2 : 0);
-    if ((d->x_host[i] != 0.0f && d->x_host[i] != 1.0f) || (d->x2_host[i] != 0.0f && d->x2_host[i] != 1.0f)) {
-      set_error("election: female/black must be 0/1 indicators for the cell collapse");
-      return 1;
-    }
-    cn[(size_t)t * 4 + c] += 1.0;
-    cy[(size_t)t * 4 + c] += d->y_host[i];
-  }
-  m->host_tables.resize(cn.size() * 2);
-  for (size_t i = 0; i < cn.size(); ++i) { m->host_tables[i] = (float)cn[i]; m->host_tables[cn.size() + i] = (float)cy[i]; }
-  if (upload_tables(m)) return 1;
-  m->election.cell_n = m->dev_tables;
-  m->election.cell_y = m->dev_tables + cn.size();
-  m->election.S = S;
-  m->const_base = -(4.0 + S) * kHalfLog2Pi;
-  m->top_scale = {{0, log(100.0)}, {1, log(10.0)}, {2 + S, log(100.0)}, {3 + S, log(100.0)}};
-  return 0;
-}
-
-// reference models.py:763-806 (radon_stddvs): same inputs as radon; every county keeps all six
-// second-order sufficient statistics because its observation scale is a latent
-static int build_radon_sd(arp_model* m, const arp_dataset* d) {
-  const int J = d->n_groups, N = d->n_obs;
-  if (!d->group_host || !d->u_host || !d->x_host || !d->y_host || J <= 0 || N <= 0) {
-    set_error("radon_stddvs: group/u/x/y and n_groups/n_obs are required");
-    return 1;
-  }
-  std::vector<double> st(6 * (size_t)J, 0.0);
-  for (int i = 0; i < N; ++i) {
-    int j = d->group_host[i];
-    if (j < 0 || j >= J) {   // a zero one-hot row would give the observation a zero scale (models.py:785-786)
-      set_error("radon_stddvs: county index out of range");
-      return 1;
-    }
-    double x = d->x_host[i], y = d->y_host[i];
-    st[j] += 1; st[J + j] += x; st[2 * J + j] += y; st[3 * J + j] += x * x; st[4 * J + j] += x * y; st[5 * J + j] += y * y;
-  }
-  m->D = 3 + 2 * J; m->n_groups = J;
-  m->host_tables.resize(7 * (size_t)J);
-  for (size_t k = 0; k < 6 * (size_t)J; ++k) m->host_tables[k] = (float)st[k];
-  for (int j = 0; j < J; ++j) m->host_tables[6 * (size_t)J + j] = d->u_host[j];
-  if (upload_tables(m)) return 1;
-  float* t = m->dev_tables;
-  m->radon_sd.n = t; m->radon_sd.sx = t + J; m->radon_sd.sy = t + 2 * J; m->radon_sd.sxx = t + 3 * J;
-  m->radon_sd.sxy = t + 4 * J; m->radon_sd.syy = t + 5 * J; m->radon_sd.u = t + 6 * J;
-  m->radon_sd.J = J;
-  m->const_base = -(3.0 + 2.0 * J + N) * kHalfLog2Pi;
-  return 0;
-}
-
-// reference models.py:860-904: X = [N][F] design matrix (intercept, standardised
-// numerics, one-hot blocks), y = 0/1 outcomes
-static int build_german(arp_model* m, const arp_dataset* d) {
-  const int N = d->n_obs, F = d->n_features;
-  if (!d->X_host || !d->y_host || N <= 0 || F <= 0 || F > kGermanCols) {
-    set_error("german_credit: X, y, n_obs and 0 < n_features <= 64 are required");
-    return 1;
-  }
-  m->D = 1 + 2 * F; m->n_groups = F;
-  // [N][64] rows + outcomes (the 8- and 16-lane likelihoods), then the image the matrix-core likelihood copies
-  // into LDS with LDS-DMA (model_german.h, "tile image"): per 128 observations the rows with their 16-byte chunks
-  // XOR-permuted, and one piece of outcomes
-  const size_t plain = ((size_t)N * kGermanCols + N + 255) & ~(size_t)255;
-  const int nt = (N + kGermanTileRows - 1) / kGermanTileRows;
-  m->host_tables.assign(plain + (size_t)nt * kGermanImgTile, 0.0f);
-  for (int n = 0; n < N; ++n)
-    for (int f = 0; f < F; ++f) m->host_tables[(size_t)n * kGermanCols + f] = d->X_host[(size_t)n * F + f];
-  for (int n = 0; n < N; ++n) m->host_tables[(size_t)N * kGermanCols + n] = d->y_host[n];
-  for (int t = 0; t < nt; ++t) {
-    float* img = m->host_tables.data() + plain + (size_t)t * kGermanImgTile;
-    for (int r = 0; r < kGermanTileRows; ++r) {
-      const int n = t * kGermanTileRows + r;
-      if (n >= N) break;
-      float* rowp = img + r * kGermanCols;   // chunk c of row r at chunk position c ^ (r & 11)
-      for (int f = 0; f < F; ++f) rowp[((((f >> 2) ^ (r & 11)) & 15) << 2) + (f & 3)] = d->X_host[(size_t)n * F + f];
-      img[32 * 256 + r] = d->y_host[n];
-    }
-  }
-  // the bf16 x 3 image (model_german.h): usable when at most 8 columns are not exact in ONE bf16 piece
-  const size_t f32_floats = m->host_tables.size();
-  std::vector<int> split;
-  for (int f = 0; f < F; ++f) {
-    bool exact = true;
-    for (int n = 0; n < N && exact; ++n) {
-      uint32_t h, mm_, l;
-      bf3_split(d->X_host[(size_t)n * F + f], h, mm_, l);
-      exact = mm_ == 0u && l == 0u;
-    }
-    if (!exact) split.push_back(f);
-  }
-  const bool bf3 = (int)split.size() <= kBf3MaxSplit;
-  const int ntb = (N + kBf3Rows - 1) / kBf3Rows;
-  for (int q = 0; q < kBf3MaxSplit; ++q) m->german.sidx[q] = bf3 && q < (int)split.size() ? split[q] : -1;
-  if (bf3) {
-    m->host_tables.resize(f32_floats + (size_t)ntb * kBf3ImgTile, 0.0f);
-    auto put = [](unsigned char* img, size_t byte_off, uint32_t bits) {      // the bf16 = high half of the f32 pattern
-      img[byte_off] = (unsigned char)(bits >> 16); img[byte_off + 1] = (unsigned char)(bits >> 24);
-    };
-    for (int t = 0; t < ntb; ++t) {
-      unsigned char* img = reinterpret_cast<unsigned char*>(m->host_tables.data() + f32_floats + (size_t)t * kBf3ImgTile);
-      for (int r = 0; r < kBf3Rows; ++r) {
-        const int n = t * kBf3Rows + r;
-        if (n >= N) break;
-        // where observation r sits in a backward fragment: k-step s, lane group g, element jj
-        const int s_ = r >> 5, rr = r & 31;
-        const int g = rr < 16 ? rr >> 2 : (rr - 16) >> 2, jj = rr < 16 ? rr & 3 : 4 + ((rr - 16) & 3);
-        for (int f = 0; f < F; ++f) {
-          uint32_t h, mm_, l;
-          bf3_split(d->X_host[(size_t)n * F + f], h, mm_, l);
-          put(img, kBf3XhF + (size_t)r * 128 + ((((size_t)f >> 3) ^ (((size_t)r >> 1) & 7)) << 4) + (f & 7) * 2, h);
-          put(img, kBf3XhB + (size_t)s_ * 4096 + (size_t)f * 64 + (((size_t)g ^ (((size_t)f >> 2) & 3)) << 4) + jj * 2, h);
-        }
-        for (int q = 0; q < (int)split.size(); ++q) {
-          uint32_t h, mm_, l;
-          bf3_split(d->X_host[(size_t)n * F + split[q]], h, mm_, l);
-          const size_t rowb = kBf3XaF + (size_t)r * 64, sw = ((size_t)r >> 2) & 3;
-          put(img, rowb + ((0 ^ sw) << 4) + q * 2, mm_);       // [xm | xm | xl | 0]
-          put(img, rowb + ((1 ^ sw) << 4) + q * 2, mm_);
-          put(img, rowb + ((2 ^ sw) << 4) + q * 2, l);
-          for (int part = 0; part < 2; ++part) {                // output rows q (xm) and 8 + q (xl)
-            const size_t o = (size_t)part * 8 + q;
-            put(img, kBf3XaB + (size_t)s_ * 1024 + o * 64 + (((size_t)g ^ ((o >> 2) & 3)) << 4) + jj * 2, part ? l : mm_);
-          }
-        }
-        reinterpret_cast<float*>(img + kBf3Y)[r] = d->y_host[n];
-      }
-    }
-  }
-  if (upload_tables(m)) return 1;
-  m->german.X = m->dev_tables;
-  m->german.y = m->dev_tables + (size_t)N * kGermanCols;
-  m->german.Xt = m->dev_tables + plain;
-  m->german.Xb = bf3 ? m->dev_tables + f32_floats : nullptr;
-  m->german.N = N; m->german.F = F;
-  m->const_base = -(1.0 + 2.0 * F) * kHalfLog2Pi;
-  m->top_scale = {{0, log(10.0)}};
-  return 0;
-}
-
-// reference models.py:1011-1046: group = pair, group2 = grade, group3 = grade_pair (all 1-based, fed to
-// tf.one_hot as they are), x = treatment, y = scores.  Observations collapse to (pair, treatment) cells.
-static int build_electric(arp_model* m, const arp_dataset* d) {
-  const int P = d->n_groups, N = d->n_obs, G = d->n_features;
-  if (!d->group_host || !d->group2_host || !d->group3_host || !d->x_host || !d->y_host || P <= 0 || N <= 0) {
-    set_error("electric: group(pair)/group2(grade)/group3(grade_pair)/x(treatment)/y and n_groups/n_obs are required");
-    return 1;
-  }
-  if (G != kElG) { set_error("electric: n_features (n_grade = n_grade_pair) must be 4"); return 1; }
-  const int R = P + 1;   // group P: observations whose pair index falls on the all-zero one-hot row
-  std::vector<double> n(2 * (size_t)R, 0.0), sy(2 * (size_t)R, 0.0), syy(2 * (size_t)R, 0.0);
-  std::vector<int> grade(R, -1);
-  for (int i = 0; i < N; ++i) {
-    int j = d->group_host[i];
-    if (j < 0 || j >= P) j = P;
-    int g = d->group2_host[i];
-    if (g < 0 || g >= G) g = G;   // zero row: b = 0, scale exp(0)
-    const float t = d->x_host[i];
-    if (t != 0.0f && t != 1.0f) { set_error("electric: treatment must be a 0/1 indicator for the cell collapse"); return 1; }
-    if (grade[j] >= 0 && grade[j] != g) {
-      set_error("electric: the observations of one pair must share a grade for the cell collapse");
-      return 1;
-    }
-    grade[j] = g;
-    const size_t c = (size_t)(t != 0.0f) * R + j;
-    const double y = d->y_host[i];
-    n[c] += 1; sy[c] += y; syy[c] += y * y;
-  }
-  m->D = 3 * G + P; m->n_groups = R;
-  m->host_tables.assign(13 * (size_t)R, 0.0f);
-  float* T = m->host_tables.data();
-  for (int j = 0; j < R; ++j) {
-    if (j < P) {
-      const int k = d->group3_host[j];
-      if (k >= 0 && k < G) T[(size_t)k * R + j] = 100.0f;
-    }
-    if (grade[j] >= 0 && grade[j] < G) T[(size_t)(4 + grade[j]) * R + j] = 1.0f;
-    double ss = 0;
-    for (int t = 0; t < 2; ++t) {
-      const size_t c = (size_t)t * R + j;
-      const double mean = n[c] > 0 ? sy[c] / n[c] : 0.0;
-      T[(size_t)(8 + 2 * t) * R + j] = (float)n[c];
-      T[(size_t)(9 + 2 * t) * R + j] = (float)mean;
-      ss += syy[c] - n[c] * mean * mean;
-    }
-    T[(size_t)12 * R + j] = (float)(ss > 0 ? ss : 0.0);
-  }
-  if (upload_tables(m)) return 1;
-  float* t = m->dev_tables;
-  m->electric.wm = t; m->electric.og = t + 4 * (size_t)R;
-  m->electric.n0 = t + 8 * (size_t)R; m->electric.y0 = t + 9 * (size_t)R;
-  m->electric.n1 = t + 10 * (size_t)R; m->electric.y1 = t + 11 * (size_t)R;
-  m->electric.ss = t + 12 * (size_t)R;
-  m->electric.P = P;
-  m->const_base = -(double)(m->D + N) * kHalfLog2Pi;
-  for (int k = 0; k < G; ++k) m->top_scale.push_back({2 * G + P + k, log(100.0)});
-  return 0;
-}
-
-// reference models.py:1069-1141: x = regressor (years), y = series, n_obs = T
-static int build_time_series(arp_model* m, const arp_dataset* d) {
-  const int T = d->n_obs;
-  if (!d->x_host || !d->y_host || T <= 0) { set_error("time_series: x, y and n_obs are required"); return 1; }
-  // the block scan splits the T steps over the lanes of a chain in blocks of ceil(T / K) (the last lanes padded); the
-  // instantiations of inst_time_series.hip are those of the reference's T = 60
-  if (T != kTsSteps) { set_error("time_series: n_obs must be 60 (add TimeSeriesLane<K, 2 ceil(T / K)> to inst_time_series.hip for another length)"); return 1; }
-  m->D = 3 + 2 * T; m->n_groups = 2 * T;
-  m->host_tables.assign(d->x_host, d->x_host + T);
-  m->host_tables.insert(m->host_tables.end(), d->y_host, d->y_host + T);
-  if (upload_tables(m)) return 1;
-  m->time_series.x = m->dev_tables;
-  m->time_series.y = m->dev_tables + T;
-  m->time_series.T = T;
-  m->const_base = -(double)(m->D + T) * kHalfLog2Pi - T * log(0.12);
-  return 0;
 }
 
 namespace {
@@ -436,8 +104,12 @@ const char* arp_last_error(void) { return g_err.c_str(); }
 
 int arp_model_create(const arp_dataset* data, arp_model** out) {
   if (!data || !out) { set_error("arp_model_create: null argument"); return 1; }
+  // (before anything is allocated: an unknown id has nothing to release)
+  const Family* family = family_of(data->model);
+  if (!family) { set_error("arp_model_create: unknown model id"); return 1; }
   std::unique_ptr<arp_model> m(new arp_model());
   m->model = data->model;
+  m->family = family;
   m->host_only = host_only();
   if (m->host_only) m->device = -1;
   else {
@@ -456,20 +128,7 @@ int arp_model_create(const arp_dataset* data, arp_model** out) {
       ARP_HIP_OK(mapped);
     }
   }
-  int rc;
-  switch (data->model) {
-    case ARP_MODEL_RADON: rc = build_radon(m.get(), data); break;
-    case ARP_MODEL_EIGHT_SCHOOLS: rc = build_schools(m.get(), data); break;
-    case ARP_MODEL_ELECTION: rc = build_election(m.get(), data); break;
-    case ARP_MODEL_GERMAN_CREDIT: rc = build_german(m.get(), data); break;
-    case ARP_MODEL_RADON_STDDVS: rc = build_radon_sd(m.get(), data); break;
-    case ARP_MODEL_ELECTRIC: rc = build_electric(m.get(), data); break;
-    case ARP_MODEL_TIME_SERIES: rc = build_time_series(m.get(), data); break;
-    case ARP_MODEL_NEALS_FUNNEL:   // models.py:671-696: no data
-      m->D = 2; m->n_groups = 1; m->const_base = -2.0 * kHalfLog2Pi; m->top_scale = {{0, log(3.0)}};
-      rc = 0; break;
-    default: set_error("arp_model_create: unknown model id"); return 1;
-  }
+  const int rc = family->build(m.get(), data);
   if (rc) { arp_model_destroy(m.release()); return rc; }
   for (int w = 0; w < 2; ++w) {
     if (m->host_only) {
@@ -576,27 +235,28 @@ int arp_model_set_param(arp_model* m, int which, const float* a_host, const floa
   return 0;
 }
 
+// The instantiation that serves K lanes per chain (0: by chain count, pick).  German credit's variant choice is made here and
+// nowhere else: the prior of the scales names the table (indexed by GermanPrior: a third prior is one more entry), and at
+// 4 lanes per chain the likelihood runs on bf16 matrix cores with three-piece operands where the data allow it
+// (model_german.h), unless the caller asked for the f32 matrix-core form (arp_model_set_option).
+static const LaneOps* lane_ops(const arp_model* m, int K, int C) {
+  const Family& f = *m->family;
+  const std::vector<LaneOps>* table = &f.ops();
+  if (m->model == ARP_MODEL_GERMAN_CREDIT) {
+    static const struct { const std::vector<LaneOps>& (*table)(); const LaneOps& (*bf3)(); } by_prior[] = {
+        {german_ops, german_bf3_ops}, {german_gamma_ops, german_gamma_bf3_ops}};
+    if (K == 4 && m->german.Xb && m->german_math != 1) return &by_prior[m->german_prior].bf3();
+    table = &by_prior[m->german_prior].table();
+  }
+  return pick(*table, m->n_groups, K, C, f.exact, f.fill_lanes, f.unit);
+}
+
 static const LaneOps* select_ops(arp_model* m, int K_req, int C) {
-  const auto* fam = family(m);
-  if (!fam) { set_error("model family has no kernels"); return nullptr; }
   if (K_req != 0 && K_req != 1 && K_req != 2 && K_req != 4 && K_req != 8 && K_req != 16) {
     set_error("lanes_per_chain must be 0,1,2,4,8 or 16");
     return nullptr;
   }
-  // german credit: the 4-lane instantiation runs its likelihood on the matrix cores and beats the
-  // wider ones at every chain count (per workgroup 4x the 8-lane and 17x the 16-lane rate)
-  if (K_req == 0 && m->model == ARP_MODEL_GERMAN_CREDIT) K_req = 4;
-  // radon: a wider split costs more replicated work than a second wave per SIMD returns (bench.py --chains 8192:
-  // 1.21e10 leapfrog-steps/s at 8 lanes per chain, 1.07e10 at 16), so one wave per SIMD is enough
-  // time_series likewise: 4 lanes per chain (one wave per SIMD at 16 384 chains) beat 8 and 16 in every form wherever
-  // they fill the SIMDs once (round 3 sweep, profiles/r03_time_series_sweep.txt)
-  const long long fill = (m->model == ARP_MODEL_RADON || m->model == ARP_MODEL_TIME_SERIES) ? 65536 : 131072;
-  // German credit at 4 lanes per chain: the likelihood on bf16 matrix cores with three-piece operands where the data
-  // allow it (model_german.h), unless the caller asked for the f32 matrix-core form (arp_model_set_option)
-  if (m->model == ARP_MODEL_GERMAN_CREDIT && K_req == 4 && m->german.Xb && m->german_math != 1)
-    return m->german_prior ? &german_gamma_bf3_ops() : &german_bf3_ops();
-  const LaneOps* o = pick(*fam, m->n_groups, K_req, C, m->model != ARP_MODEL_GERMAN_CREDIT, fill,
-                          m->model == ARP_MODEL_TIME_SERIES ? 2 : 1);
+  const LaneOps* o = lane_ops(m, K_req ? K_req : m->family->default_lanes, C);
   if (!o) set_error("no kernel instantiation for this (lanes_per_chain, group count): add <Model>Lane<K, ceil(groups/K)> to the model's inst_*.hip");
   return o;
 }
@@ -606,7 +266,7 @@ int arp_logp_grad(arp_model* m, int which, const float* x, int n_chains, float* 
   if (!m || which < 0 || which > 1 || !x || !logp || !grad || n_chains <= 0) { set_error("arp_logp_grad: bad argument"); return 1; }
   const LaneOps* o = select_ops(m, lanes_per_chain, n_chains);
   if (!o) return 1;
-  o->logp_grad(family_args(m), m->dev_ab[which], m->dev_ab[which] + m->D, x, n_chains, m->D, logp, grad,
+  o->logp_grad(m->args, m->dev_ab[which], m->dev_ab[which] + m->D, x, n_chains, m->D, logp, grad,
                (hipStream_t)stream);
   ARP_HIP_OK(hipGetLastError());
   return 0;
@@ -616,7 +276,7 @@ int arp_transform(arp_model* m, int which, int dir, const float* in, int n_chain
   if (!m || which < 0 || which > 1 || !in || !out || n_chains <= 0 || (dir != 0 && dir != 1)) { set_error("arp_transform: bad argument"); return 1; }
   const LaneOps* o = select_ops(m, 0, n_chains);
   if (!o) return 1;
-  o->transform(family_args(m), m->dev_ab[which], m->dev_ab[which] + m->D, dir, in, n_chains, m->D, out,
+  o->transform(m->args, m->dev_ab[which], m->dev_ab[which] + m->D, dir, in, n_chains, m->D, out,
                (hipStream_t)stream);
   ARP_HIP_OK(hipGetLastError());
   return 0;
@@ -630,6 +290,13 @@ static int check_adapt(const arp_hmc_config* cfg) {
   if (cfg->adapt_kind == ARP_ADAPT_SIMPLE && !(cfg->adapt_rate > 0.0f)) { set_error("adapt_rate must be positive"); return 1; }
   return 0;
 }
+// the adaptation schedule as the kernels read it (kernels.h: adapt_update)
+static void fill_adapt(HmcParams& P, const arp_hmc_config* cfg) {
+  P.adapt_kind = cfg->adapt_kind; P.n_adapt = cfg->n_adapt;
+  P.adapt_target = cfg->adapt_target; P.adapt_rate = cfg->adapt_rate;
+  P.adapt_log_target = logf(cfg->adapt_target > 0.f ? cfg->adapt_target : 1e-30f);
+  P.adapt_inv_opr = 1.0f / (1.0f + cfg->adapt_rate);
+}
 
 // Relay segments (kernels.h: relay_begin; host_common.h: relay_plan): a launch's steps cut into segments that are handed
 // from workgroup to workgroup inside the launch, so that a CU that is free takes the next (segment, chain block) in line
@@ -637,9 +304,13 @@ static int check_adapt(const arp_hmc_config* cfg) {
 // zeroed flag word per chain block that belongs to THIS launch alone -- a stream-ordered allocation, given back behind the
 // launch (relay_release), so launches of one handle that overlap on different streams never share a word -- and `segs` =
 // -1 (the launcher decides with its kernel's occupancy), a forced count (ARP_DEBUG=1 ARP_SEGMENTS=n) or 1 (`allowed` false).
+// no relay: the launch's steps in one segment (P.n_steps is set)
+static void relay_off(HmcParams& P) {
+  P.segs = 1; P.seg_len = P.n_steps; P.seg_blocks = 0; P.seg_epoch = 0; P.seg_flags = nullptr;
+  P.seg_ctrl = nullptr; P.seg_err_host = nullptr; P.seg_timeout = 6000000000ull; P.seg_fault = 0;
+}
 static int relay_prepare(arp_model* m, const arp_hmc_config* cfg, int K, bool allowed, hipStream_t stream, HmcParams* P) {
-  P->segs = 1; P->seg_len = cfg->n_steps; P->seg_blocks = 0; P->seg_epoch = 0; P->seg_flags = nullptr;
-  P->seg_ctrl = nullptr; P->seg_err_host = nullptr; P->seg_timeout = 6000000000ull; P->seg_fault = 0;
+  relay_off(*P);
   arp::relay_device_cus() = m->cus;
   if (!allowed || cfg->n_steps < 256) return 0;
   int segs = -1, dbg = 0;
@@ -695,10 +366,7 @@ static int fill_params(arp_model* m, const arp_hmc_config* cfg, const arp_hmc_io
   HmcParams& P = *Pp;
   P.C = cfg->n_chains; P.L = cfg->n_leapfrog; P.n_steps = cfg->n_steps;
   P.step_base = cfg->step_base; P.chain_offset = cfg->chain_offset; P.seed = cfg->seed;
-  P.adapt_kind = cfg->adapt_kind; P.n_adapt = cfg->n_adapt;
-  P.adapt_target = cfg->adapt_target; P.adapt_rate = cfg->adapt_rate;
-  P.adapt_log_target = logf(cfg->adapt_target > 0.f ? cfg->adapt_target : 1e-30f);
-  P.adapt_inv_opr = 1.0f / (1.0f + cfg->adapt_rate);
+  fill_adapt(P, cfg);
   P.n_burnin = cfg->n_burnin; P.thin = cfg->thin;
   P.n_samples = (io->trace || io->trace_accept || io->stats || io->rec_accept_count) ? cfg->n_samples : 0;
   if (io->stats && cfg->stats_batch < 1) { set_error("stats_batch must be >= 1 when stats is given"); return 1; }
@@ -725,8 +393,7 @@ static int fill_params(arp_model* m, const arp_hmc_config* cfg, const arp_hmc_io
   P.trace_chains = (cfg->trace_chains > 0 && cfg->trace_chains < cfg->n_chains) ? cfg->trace_chains : cfg->n_chains;
   P.L1 = 0; P.adapt1 = nullptr; P.accept_count1 = nullptr; P.eps0_1 = nullptr; P.trace_accept1 = nullptr;
   P.rec_accept1 = nullptr;
-  P.segs = 1; P.seg_len = cfg->n_steps; P.seg_blocks = 0; P.seg_epoch = 0; P.seg_flags = nullptr;
-  P.seg_ctrl = nullptr; P.seg_err_host = nullptr; P.seg_timeout = 6000000000ull; P.seg_fault = 0;
+  relay_off(P);
   return 0;
 }
 
@@ -743,13 +410,9 @@ int arp_hmc_run(arp_model* m, int which, const arp_hmc_config* cfg, const arp_hm
   if (cfg->n_steps == 0) return 0;
   const LaneOps* o = select_ops(m, cfg->lanes_per_chain, cfg->n_chains);
   if (!o) return 1;
-  auto fn = o->hmc;
-  if (m->param_kind[which] == kModeCP && o->hmc_cp) fn = o->hmc_cp;
-  if (m->param_kind[which] == kModeNCP && o->hmc_ncp) fn = o->hmc_ncp;
-  if (m->param_kind[which] == kModeB1 && o->hmc_b1) fn = o->hmc_b1;
-  if (m->param_kind[which] == kModeVIP && o->hmc_vip_pk) fn = o->hmc_vip_pk;
   if (relay_prepare(m, cfg, o->K, true, (hipStream_t)stream, &P)) return 1;
-  fn(family_args(m), m->dev_ab[which], m->dev_ab[which] + m->D, P, (hipStream_t)stream);
+  // (kModeVIP too: where a family has the general form on the packed layer, "hmc_vip_pk", it sits in that slot -- host_common.h)
+  o->hmc[m->param_kind[which]](m->args, m->dev_ab[which], m->dev_ab[which] + m->D, P, (hipStream_t)stream);
   const hipError_t launched = hipGetLastError();
   if (relay_release(P, (hipStream_t)stream)) return 1;
   ARP_HIP_OK(launched);
@@ -777,11 +440,10 @@ int arp_interleaved_run(arp_model* m, const arp_hmc_config* cfg, int n_leapfrog_
   if (cfg->n_steps == 0) return 0;
   const LaneOps* o = select_ops(m, cfg->lanes_per_chain, cfg->n_chains);
   if (!o) return 1;
-  auto fn = o->interleaved;
-  if (m->param_kind[0] == kModeCP && m->param_kind[1] == kModeNCP && o->interleaved_cp_ncp) fn = o->interleaved_cp_ncp;
+  const auto fn = o->interleaved[m->param_kind[0] == kModeCP && m->param_kind[1] == kModeNCP];
   // (kernels that carry the gradient from step to step need it to travel with the state, as it does between launches)
   if (relay_prepare(m, cfg, o->K, io->k0.grad != nullptr, (hipStream_t)stream, &P)) return 1;
-  fn(family_args(m), m->dev_ab[0], m->dev_ab[0] + m->D, m->dev_ab[1], m->dev_ab[1] + m->D, P, (hipStream_t)stream);
+  fn(m->args, m->dev_ab[0], m->dev_ab[0] + m->D, m->dev_ab[1], m->dev_ab[1] + m->D, P, (hipStream_t)stream);
   const hipError_t launched = hipGetLastError();
   if (relay_release(P, (hipStream_t)stream)) return 1;
   ARP_HIP_OK(launched);
@@ -799,20 +461,12 @@ int arp_vi_run(arp_model* m, int which, const arp_vi_config* cfg, const arp_vi_i
     return 1;
   }
   if (m->D > kViDmax) { set_error("arp_vi_run: model dimension exceeds the VI kernel's limit"); return 1; }
-  const auto* fam = family(m);
-  if (!fam) { set_error("model family has no kernels"); return 1; }
-  // the VI kernel wants the smallest per-lane slice: the widest lanes-per-chain instantiation that has one
-  // (german credit: its matrix-core instantiation)
-  int Kmax = 0;
-  for (const auto& o : *fam) if (o.vi) Kmax = std::max(Kmax, o.K);
-  if (m->model == ARP_MODEL_GERMAN_CREDIT) Kmax = 4;
-  const LaneOps* o = pick(*fam, m->n_groups, Kmax, 1 << 30, m->model != ARP_MODEL_GERMAN_CREDIT, 131072,
-                          m->model == ARP_MODEL_TIME_SERIES ? 2 : 1);
+  // the VI kernel wants the smallest per-lane slice: the widest lanes-per-chain instantiation that has one, unless the
+  // family names its own (german credit: its matrix-core instantiation, in the variant the chain kernels take too)
+  int K_vi = m->family->vi_lanes;
+  if (!K_vi) for (const auto& t : m->family->ops()) if (t.vi) K_vi = std::max(K_vi, t.K);
+  const LaneOps* o = lane_ops(m, K_vi, 1 << 30);
   if (!o || !o->vi) { set_error("no VI kernel instantiation covers this group count"); return 1; }
-  // German credit: the row-part lane on bf16 matrix cores with three-piece operands where the data allow it (64-observation
-  // tiles), else on f32 matrix cores (128-observation tiles) -- the same choice as the chain kernels make (select_ops)
-  const bool german_bf3 = m->model == ARP_MODEL_GERMAN_CREDIT && m->german.Xb && m->german_math != 1;
-  if (german_bf3) o = m->german_prior ? &german_gamma_bf3_ops() : &german_bf3_ops();
   if (m->D > o->vi_dmax) { set_error("arp_vi_run: model dimension exceeds this model's VI kernel instantiation"); return 1; }
   ViParams P;
   P.n_steps = cfg->n_steps; P.n_mc = cfg->n_mc; P.learn_a = cfg->learn_a; P.tied_b = cfg->tied_b; P.a_prior = cfg->a_prior; P.D = m->D;
@@ -850,10 +504,9 @@ int arp_vi_run(arp_model* m, int which, const arp_vi_config* cfg, const arp_vi_i
   int G = (cfg->n_mc + CPW - 1) / CPW;                   // one pass
   int R = 1;
   if (o->vi_parts) {
-    // German credit: the observations' 128-row tiles are split too, so that a learning rate's group has about 32
-    // workgroups (five learning rates: 160 CUs) and a gradient is two tiles of matrix-core work per wave
-    const int tile_obs = german_bf3 ? kBf3Rows : kGermanTileRows;
-    const int nt = (m->german.N + tile_obs - 1) / tile_obs;
+    // German credit: the observations' tiles (128 rows on f32 matrix cores, 64 on bf16 x 3) are split too, so that a learning
+    // rate's group has about 32 workgroups (five learning rates: 160 CUs) and a gradient is two tiles of matrix-core work per wave
+    const int nt = (m->german.N + o->vi_tile_obs - 1) / o->vi_tile_obs;
     R = std::min(nt, std::max(1, 32 / G));
   }
   int dbg = 0;
@@ -929,13 +582,13 @@ int arp_vi_run(arp_model* m, int which, const arp_vi_config* cfg, const arp_vi_i
       }
       // every polled word starts at zero (epochs start at 1): the flag and this launch's granules
       ARP_HIP_OK(hipMemsetAsync(m->vi_ws, 0, need, (hipStream_t)stream));
-      hipError_t launched = o->vi(family_args(m), m->dev_ab[which], m->dev_ab[which] + m->D, P, ng, coop, (hipStream_t)stream);
+      hipError_t launched = o->vi(m->args, m->dev_ab[which], m->dev_ab[which] + m->D, P, ng, coop, (hipStream_t)stream);
       if (coop && m->vi_launch == 0 && (launched == hipErrorCooperativeLaunchTooLarge || launched == hipErrorNotSupported)) {
         // "auto" only: the runtime counts co-residency more strictly than the occupancy query above (or lacks the feature
         // after all) -- take the plain launch, one at a time per process, as round 5 did
         (void)hipGetLastError();
         if (!one_at_a_time.owns_lock()) one_at_a_time.lock();
-        launched = o->vi(family_args(m), m->dev_ab[which], m->dev_ab[which] + m->D, P, ng, false, (hipStream_t)stream);
+        launched = o->vi(m->args, m->dev_ab[which], m->dev_ab[which] + m->D, P, ng, false, (hipStream_t)stream);
       }
       ARP_HIP_OK(launched);
       g_vi_attempts = std::max(g_vi_attempts, attempt + 1);
@@ -984,10 +637,7 @@ int arp_adapt_probe(const arp_hmc_config* cfg, const float* log_accept, int n, f
   if (check_adapt(cfg)) return 1;
   HmcParams P{};
   P.n_steps = cfg->n_steps; P.step_base = cfg->step_base;
-  P.adapt_kind = cfg->adapt_kind; P.n_adapt = cfg->n_adapt;
-  P.adapt_target = cfg->adapt_target; P.adapt_rate = cfg->adapt_rate;
-  P.adapt_log_target = logf(cfg->adapt_target > 0.f ? cfg->adapt_target : 1e-30f);
-  P.adapt_inv_opr = 1.0f / (1.0f + cfg->adapt_rate);
+  fill_adapt(P, cfg);
   hipLaunchKernelGGL(adapt_probe_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, P, log_accept, n, adapt,
                      kappa_out);
   ARP_HIP_OK(hipGetLastError());

@@ -37,35 +37,33 @@ void set_error(const std::string& msg);
     }                                                                             \
   } while (0)
 
+using HmcFn = void (*)(const void* args, const float* a, const float* b, const HmcParams& P, hipStream_t s);
+using InterleavedFn = void (*)(const void* args, const float* a0, const float* b0, const float* a1, const float* b1,
+                              const HmcParams& P, hipStream_t s);
+
 // Launchers a model family exports for one (lanes-per-chain, slice-size) pair.
 struct LaneOps {
-  int K, NL;   // lanes per chain; groups (counties, states, features ...) owned by one lane
+  int K = 0, NL = 0;   // lanes per chain; groups (counties, states, features ...) owned by one lane
   void (*logp_grad)(const void* args, const float* a, const float* b, const float* x, int C, int D,
-                    float* logp, float* grad, hipStream_t s);
+                    float* logp, float* grad, hipStream_t s) = nullptr;
   void (*transform)(const void* args, const float* a, const float* b, int dir, const float* in,
-                    int C, int D, float* out, hipStream_t s);
-  void (*hmc)(const void* args, const float* a, const float* b, const HmcParams& P, hipStream_t s);
-  void (*interleaved)(const void* args, const float* a0, const float* b0, const float* a1, const float* b1,
-                      const HmcParams& P, hipStream_t s);
+                    int C, int D, float* out, hipStream_t s) = nullptr;
+  // chain launcher by the handle's parameterisation, indexed by kModeVIP / kModeCP / kModeNCP / kModeB1: every slot holds
+  // the generic kernel in the general (a, b) form unless the lane model or its packed family has that form at compile time
+  HmcFn hmc[4] = {};
+  // [0] any pair of parameterisations, [1] the compile-time (CP, NCP) pair (the generic kernel again where there is none)
+  InterleavedFn interleaved[2] = {};
   // mean-field VI: `n_groups` learning rates x (P.G x P.R) workgroups of vi_block threads (kernels.h: vi_kernel)
   // coop: hipLaunchCooperativeKernel -- the runtime itself guarantees that every workgroup of the grid is resident (or
   // refuses the launch), which is what the in-launch hand-offs of a learning rate's group need
-  hipError_t (*vi)(const void* args, const float* a, const float* b, const ViParams& P, int n_groups, bool coop, hipStream_t s);
-  // compile-time parameterisations (nullptr when the lane model has none): hmc for CP / NCP,
-  // interleaved for the (CP, NCP) pair
-  void (*hmc_cp)(const void* args, const float* a, const float* b, const HmcParams& P, hipStream_t s);
-  void (*hmc_ncp)(const void* args, const float* a, const float* b, const HmcParams& P, hipStream_t s);
-  void (*interleaved_cp_ncp)(const void* args, const float* a0, const float* b0, const float* a1, const float* b1,
-                             const HmcParams& P, hipStream_t s);
-  // hmc for "a free, b = 1" (nullptr when the lane model has no such form)
-  void (*hmc_b1)(const void* args, const float* a, const float* b, const HmcParams& P, hipStream_t s);
-  // the general per-element (a, b) on the packed chain layer, where a lane model has it (election); nullptr: the generic kernel
-  void (*hmc_vip_pk)(const void* args, const float* a, const float* b, const HmcParams& P, hipStream_t s);
+  hipError_t (*vi)(const void* args, const float* a, const float* b, const ViParams& P, int n_groups, bool coop, hipStream_t s) = nullptr;
   // shape of the VI kernel's workgroups: threads, whether the lane model splits a gradient's observations into row
-  // parts (German credit), and how many workgroups of it one CU holds (occupancy query)
+  // parts (German credit) and then the observations per tile of its image, and how many workgroups of it one CU holds
+  // (occupancy query)
   int vi_block = 0;
   int vi_dmax = 0;
   bool vi_parts = false;
+  int vi_tile_obs = 0;
   int (*vi_occ)() = nullptr;
 };
 
@@ -126,13 +124,6 @@ inline HmcParams relay_plan(const HmcParams& P, int blocks, F kernel) {
   return Q;
 }
 
-// launch KERNEL over NBLOCKS chain blocks (x the segments relay_plan decides), the kernel's own arguments first, P last
-#define ARP_RELAY_LAUNCH(KERNEL, NBLOCKS, STREAM, P, ...)                                                   \
-  do {                                                                                                      \
-    const HmcParams Q_ = relay_plan(P, NBLOCKS, KERNEL);                                                     \
-    hipLaunchKernelGGL(KERNEL, dim3((NBLOCKS) * Q_.segs), dim3(kBlock), 0, STREAM, __VA_ARGS__, Q_);         \
-  } while (0)
-
 template <class Lane>
 struct Launch {
   static int blocks(int C) { return (int)(((long long)C * Lane::K + kBlock - 1) / kBlock); }
@@ -146,15 +137,17 @@ struct Launch {
     hipLaunchKernelGGL(transform_kernel<Lane>, dim3(blocks(C)), dim3(kBlock), 0, s,
                        *(const typename Lane::Args*)args, a, b, dir, in, C, D, out);
   }
+  template <int MODE>
   static void hmc(const void* args, const float* a, const float* b, const HmcParams& P, hipStream_t s) {
-    const HmcParams Q = relay_plan(P, blocks(P.C), hmc_kernel<Lane>);
-    hipLaunchKernelGGL(hmc_kernel<Lane>, dim3(blocks(P.C) * Q.segs), dim3(kBlock), 0, s,
+    const HmcParams Q = relay_plan(P, blocks(P.C), hmc_kernel<Lane, MODE>);
+    hipLaunchKernelGGL((hmc_kernel<Lane, MODE>), dim3(blocks(P.C) * Q.segs), dim3(kBlock), 0, s,
                        *(const typename Lane::Args*)args, a, b, Q);
   }
+  template <int M0, int M1>
   static void interleaved(const void* args, const float* a0, const float* b0, const float* a1, const float* b1,
                           const HmcParams& P, hipStream_t s) {
-    const HmcParams Q = relay_plan(P, blocks(P.C), interleaved_kernel<Lane>);
-    hipLaunchKernelGGL(interleaved_kernel<Lane>, dim3(blocks(P.C) * Q.segs), dim3(kBlock), 0, s,
+    const HmcParams Q = relay_plan(P, blocks(P.C), interleaved_kernel<Lane, M0, M1>);
+    hipLaunchKernelGGL((interleaved_kernel<Lane, M0, M1>), dim3(blocks(P.C) * Q.segs), dim3(kBlock), 0, s,
                        *(const typename Lane::Args*)args, a0, b0, a1, b1, Q);
   }
   static constexpr int kViB = lane_vi_block<Lane>::value;
@@ -175,40 +168,29 @@ struct Launch {
       if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, vi_kernel<Lane, kViB>, kViB, 0) != hipSuccess) n = 0;
     return n;
   }
+  // the VI launcher of this lane into `o` (German credit: a lane sized for the VI kernel's workgroup, in its row-part form,
+  // beside chain launchers from the lane sized for kBlock)
   static void set_vi(LaneOps& o) {
     if constexpr (Lane::HAS_VI) {
       o.vi = &vi; o.vi_block = kViB; o.vi_parts = lane_has_part<Lane>::value; o.vi_occ = &vi_occ;
       o.vi_dmax = lane_vi_dmax<Lane>::value;
+      if constexpr (lane_has_part<Lane>::value) o.vi_tile_obs = Lane::kTileObs;
     }
-  }
-  template <int MODE>
-  static void hmc_m(const void* args, const float* a, const float* b, const HmcParams& P, hipStream_t s) {
-    const HmcParams Q = relay_plan(P, blocks(P.C), hmc_kernel<Lane, MODE>);
-    hipLaunchKernelGGL((hmc_kernel<Lane, MODE>), dim3(blocks(P.C) * Q.segs), dim3(kBlock), 0, s,
-                       *(const typename Lane::Args*)args, a, b, Q);
-  }
-  static void interleaved_m(const void* args, const float* a0, const float* b0, const float* a1, const float* b1,
-                            const HmcParams& P, hipStream_t s) {
-    const HmcParams Q = relay_plan(P, blocks(P.C), interleaved_kernel<Lane, kModeCP, kModeNCP>);
-    hipLaunchKernelGGL((interleaved_kernel<Lane, kModeCP, kModeNCP>), dim3(blocks(P.C) * Q.segs), dim3(kBlock), 0, s,
-                       *(const typename Lane::Args*)args, a0, b0, a1, b1, Q);
-  }
-  // only the VI launcher (a lane sized for the VI kernel's workgroup; nothing else is instantiated)
-  static LaneOps vi_only() {
-    LaneOps o{Lane::K, Lane::NGRP, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    set_vi(o);
-    return o;
   }
   template <class L, class = void> struct has_b1 : std::false_type {};
   template <class L> struct has_b1<L, std::enable_if_t<L::HAS_MODE_B1>> : std::true_type {};
   static LaneOps ops() {
-    LaneOps o{Lane::K, Lane::NGRP, &logp_grad, &transform, &hmc, &interleaved, nullptr, nullptr, nullptr, nullptr, nullptr};
+    LaneOps o;
+    o.K = Lane::K; o.NL = Lane::NGRP;
+    o.logp_grad = &logp_grad; o.transform = &transform;
+    for (auto& f : o.hmc) f = &hmc<kModeVIP>;
+    for (auto& f : o.interleaved) f = &interleaved<kModeVIP, kModeVIP>;
     set_vi(o);
-    if constexpr (has_b1<Lane>::value) o.hmc_b1 = &hmc_m<kModeB1>;
+    if constexpr (has_b1<Lane>::value) o.hmc[kModeB1] = &hmc<kModeB1>;
     if constexpr (Lane::HAS_MODES) {
-      o.hmc_cp = &hmc_m<kModeCP>;
-      o.hmc_ncp = &hmc_m<kModeNCP>;
-      o.interleaved_cp_ncp = &interleaved_m;
+      o.hmc[kModeCP] = &hmc<kModeCP>;
+      o.hmc[kModeNCP] = &hmc<kModeNCP>;
+      o.interleaved[1] = &interleaved<kModeCP, kModeNCP>;
     }
     return o;
   }
@@ -231,6 +213,25 @@ inline bool stats_lds_enabled() {
   return on;
 }
 
+// Launch of a packed chain kernel (pk_chain.h) over the chain blocks of K lanes per chain (x the segments relay_plan decides
+// for the kernel it is given: its occupancy cache is keyed by the kernel's address), the kernel's own arguments first, P last.
+// A run that accumulates statistics takes StatsLds, the instantiation with the accumulators in LDS (the same kernel as Plain
+// where they do not fit: PkBlock::kStatsFit).  (StatsLds is named first because a translation unit emits its kernels in the
+// order they are first named: the code objects stay byte for byte what they were.)
+template <int K, auto StatsLds, auto Plain, class... Args>
+void pk_launch(const HmcParams& P, hipStream_t s, const Args&... args) {
+  const int nb = (int)(((long long)P.C * K + kBlock - 1) / kBlock);
+  const auto kernel = (StatsLds != Plain && P.stats && stats_lds_enabled()) ? StatsLds : Plain;
+  const HmcParams Q = relay_plan(P, nb, kernel);
+  hipLaunchKernelGGL(kernel, dim3(nb * Q.segs), dim3(kBlock), 0, s, args..., Q);
+}
+// pk_hmc_kernel in one compile-time parameterisation; AB: the kernel reads the handle's (a, b) arrays
+template <class T, int MODE, bool AB = true>
+void pk_hmc(const void* args, const float* a, const float* b, const HmcParams& P, hipStream_t s) {
+  pk_launch<T::K, pk_hmc_kernel<T, MODE, PkBlock<T>::kStatsFit>, pk_hmc_kernel<T, MODE>>(
+      P, s, *(const typename T::Args*)args, AB ? a : nullptr, AB ? b : nullptr);
+}
+
 // Radon: the generic lane kernels serve the general VIP form, the packed kernels of radon_fast.h the two
 // compile-time parameterisations (centred, non-centred) and their interleaving.
 template <int K, int NL>
@@ -240,68 +241,54 @@ LaneOps radon_lane_ops() {
   // on the generic kernels)
   if constexpr (K >= 4 && NL >= 4) {
     using T = RadonPk<K, NL>;
-    // a run that accumulates statistics takes the instantiation with the accumulators in LDS when they fit
-    constexpr bool SL = PkBlock<T>::kStatsFit;
-    o.hmc_cp = [](const void* args, const float*, const float*, const HmcParams& P, hipStream_t s) {
-      const int nb = Launch<RadonLane<K, NL>>::blocks(P.C);
-      if (SL && P.stats && stats_lds_enabled()) ARP_RELAY_LAUNCH((pk_hmc_kernel<T, kModeCP, SL>), nb, s, P, *(const RadonArgs*)args, nullptr, nullptr);
-      else ARP_RELAY_LAUNCH((pk_hmc_kernel<T, kModeCP>), nb, s, P, *(const RadonArgs*)args, nullptr, nullptr);
-    };
-    o.hmc_ncp = [](const void* args, const float*, const float*, const HmcParams& P, hipStream_t s) {
-      const int nb = Launch<RadonLane<K, NL>>::blocks(P.C);
-      if (SL && P.stats && stats_lds_enabled()) ARP_RELAY_LAUNCH((pk_hmc_kernel<T, kModeNCP, SL>), nb, s, P, *(const RadonArgs*)args, nullptr, nullptr);
-      else ARP_RELAY_LAUNCH((pk_hmc_kernel<T, kModeNCP>), nb, s, P, *(const RadonArgs*)args, nullptr, nullptr);
-    };
+    o.hmc[kModeCP] = &pk_hmc<T, kModeCP, false>;
+    o.hmc[kModeNCP] = &pk_hmc<T, kModeNCP, false>;
     // cVIP / dVIP runs: a free per county (m has unit scale, so b is inert: "a free, b = 1" and the untied form are the
-    // same kernel)
-    o.hmc_vip_pk = [](const void* args, const float* a, const float* b, const HmcParams& P, hipStream_t s) {
-      const int nb = Launch<RadonLane<K, NL>>::blocks(P.C);
-      if (SL && P.stats && stats_lds_enabled()) ARP_RELAY_LAUNCH((pk_hmc_kernel<T, kModeVIP, SL>), nb, s, P, *(const RadonArgs*)args, a, b);
-      else ARP_RELAY_LAUNCH((pk_hmc_kernel<T, kModeVIP>), nb, s, P, *(const RadonArgs*)args, a, b);
-    };
-    o.hmc_b1 = o.hmc_vip_pk;
-    o.interleaved_cp_ncp = [](const void* args, const float*, const float*, const float*, const float*,
-                              const HmcParams& P, hipStream_t s) {
-      const int nb = Launch<RadonLane<K, NL>>::blocks(P.C);
-      if (SL && P.stats && stats_lds_enabled()) ARP_RELAY_LAUNCH((radon_interleaved_kernel<T, SL>), nb, s, P, *(const RadonArgs*)args);
-      else ARP_RELAY_LAUNCH((radon_interleaved_kernel<T>), nb, s, P, *(const RadonArgs*)args);
+    // same kernel).  The general form on the packed layer ("hmc_vip_pk") takes the generic kernel's kModeVIP slot
+    o.hmc[kModeVIP] = o.hmc[kModeB1] = &pk_hmc<T, kModeVIP>;
+    o.interleaved[1] = [](const void* args, const float*, const float*, const float*, const float*,
+                          const HmcParams& P, hipStream_t s) {
+      pk_launch<K, radon_interleaved_kernel<T, PkBlock<T>::kStatsFit>, radon_interleaved_kernel<T>>(P, s, *(const RadonArgs*)args);
     };
   }
   return o;
 }
 
-// Election: the generic lane kernels serve the general VIP form and the interleaved sampler, the packed kernels
-// (election_fast.h on pk_chain.h) the three compile-time parameterisations of a plain HMC run.
+// Election: the generic lane kernels serve the interleaved sampler in the general form, the packed kernels
+// (election_fast.h on pk_chain.h) every plain HMC run: the three compile-time parameterisations and the general per-element
+// (a, b), with the statistics accumulators in LDS where they fit (two workgroups per CU instead of three).
 template <int K, int NL>
 LaneOps election_lane_ops() {
   LaneOps o = Launch<ElectionLane<K, NL>>::ops();
   if constexpr (K >= 4) {
     using T = ElectionPk<K, NL>;
-    constexpr bool SL = PkBlock<T>::kStatsFit;   // statistics accumulators in LDS (two workgroups per CU instead of three)
-#define ARP_EL(MODE)                                                                                              \
-    [](const void* args, const float* a, const float* b, const HmcParams& P, hipStream_t s) {                     \
-      const int nb = Launch<ElectionLane<K, NL>>::blocks(P.C);                                                      \
-      if (SL && P.stats && stats_lds_enabled())                                                                    \
-        ARP_RELAY_LAUNCH((pk_hmc_kernel<T, MODE, SL>), nb, s, P, *(const ElectionArgs*)args, a, b); \
-      else                                                                                                         \
-        ARP_RELAY_LAUNCH((pk_hmc_kernel<T, MODE>), nb, s, P, *(const ElectionArgs*)args, a, b);  \
-    }
-    o.hmc_cp = ARP_EL(kModeCP);
-    o.hmc_ncp = ARP_EL(kModeNCP);
-    o.hmc_b1 = ARP_EL(kModeB1);
-    o.hmc_vip_pk = ARP_EL(kModeVIP);
-#undef ARP_EL
+    o.hmc[kModeCP] = &pk_hmc<T, kModeCP>;
+    o.hmc[kModeNCP] = &pk_hmc<T, kModeNCP>;
+    o.hmc[kModeB1] = &pk_hmc<T, kModeB1>;
+    o.hmc[kModeVIP] = &pk_hmc<T, kModeVIP>;   // "hmc_vip_pk": the general form on the packed layer takes the generic kernel's slot
     // --method=i: centred / non-centred interleaving on the packed layer (pk_chain.h: pk_interleaved_kernel)
-    o.interleaved_cp_ncp = [](const void* args, const float* a0, const float* b0, const float*, const float*,
-                              const HmcParams& P, hipStream_t s) {
-      const int nb = Launch<ElectionLane<K, NL>>::blocks(P.C);
-      if (SL && P.stats && stats_lds_enabled())
-        ARP_RELAY_LAUNCH((pk_interleaved_kernel<T, kModeCP, kModeNCP, SL>), nb, s, P, *(const ElectionArgs*)args, a0, b0);
-      else
-        ARP_RELAY_LAUNCH((pk_interleaved_kernel<T, kModeCP, kModeNCP>), nb, s, P, *(const ElectionArgs*)args, a0, b0);
+    o.interleaved[1] = [](const void* args, const float* a0, const float* b0, const float*, const float*,
+                          const HmcParams& P, hipStream_t s) {
+      pk_launch<K, pk_interleaved_kernel<T, kModeCP, kModeNCP, PkBlock<T>::kStatsFit>, pk_interleaved_kernel<T, kModeCP, kModeNCP>>(
+          P, s, *(const ElectionArgs*)args, a0, b0);
     };
   }
   return o;
+}
+
+// German credit under one prior of the scales (model_german.h: GermanPrior).  At 4 lanes per chain the likelihood runs on the
+// matrix cores, f32 or (BF3) bf16 with three-piece operands: chain kernels from the lane sized for 4 waves per workgroup, the
+// VI kernel from the same lane in its row-part form, sized for the VI workgroup.
+template <int PRIOR, bool BF3>
+LaneOps german_lane4_ops() {
+  LaneOps o = Launch<GermanLane<4, 16, kBlock / 64, false, BF3, PRIOR>>::ops();
+  Launch<GermanLane<4, 16, kGermanViBlock / 64, true, BF3, PRIOR>>::set_vi(o);
+  return o;
+}
+template <int PRIOR>
+std::vector<LaneOps> german_lane_ops() {
+  return {german_lane4_ops<PRIOR, false>(), Launch<GermanLane<8, 8, kBlock / 64, false, false, PRIOR>>::ops(),
+          Launch<GermanLane<16, 4, kBlock / 64, false, false, PRIOR>>::ops()};
 }
 
 // per-family tables (defined in inst_*.hip)
@@ -317,15 +304,31 @@ const std::vector<LaneOps>& funnel_ops();
 const std::vector<LaneOps>& electric_ops();
 const std::vector<LaneOps>& time_series_ops();
 
+// What a model id is on the host (arp_build.hip: kFamilies, one row per ARP_MODEL_*): how its handle is built, its launcher
+// table, and how an instantiation is chosen from the table (arp_api.hip: pick).
+struct Family {
+  int model;                                         // ARP_MODEL_*: the row's own index
+  int (*build)(arp_model* m, const arp_dataset* d);  // sufficient statistics -> tables, m->args, D, n_groups, constants
+  const std::vector<LaneOps>& (*ops)();
+  bool exact;             // the family needs NL == ceil(groups / K) rounded up to `unit` (the random-stream partition)
+  int unit;
+  long long fill_lanes;   // default lanes per chain: the fewest that still put this many lanes on the device ...
+  int default_lanes;      // ... or this many whatever the chain count (0: by chain count)
+  int vi_lanes;           // lanes per chain of the VI kernel (0: the widest instantiation that has a VI launcher)
+};
+const Family* family_of(int model);   // nullptr: unknown id
+
 }  // namespace arp
 
 struct arp_model {
   int model = -1;
+  const arp::Family* family = nullptr;
+  const void* args = nullptr;   // the family's kernel arguments: the one live *Args member below (set by Family::build)
   int D = 0;
   int device = 0;
-  bool host_only = false;
+  bool host_only = false;    // test hook (arp_api.hip: host_only): no device behind this handle
   int german_math = 0;       // 0 auto (bf16 x 3 where the data allow), 1 f32 matrix cores, 2 bf16 x 3 (arp_model_set_option)
-  int german_prior = 0;      // prior of German credit's feature scales: 0 log-normal centred, 1 Gamma (arp_model_set_option)    // test hook (arp_api.hip: host_only): no device behind this handle
+  int german_prior = 0;      // prior of German credit's feature scales, a GermanPrior: 0 log-normal centred, 1 Gamma (arp_model_set_option)
   int n_groups = 0;          // slice axis length (radon J, election 52, schools 8)
   float* dev_tables = nullptr;   // one allocation holding all frozen tables
   float* dev_ab[2] = {nullptr, nullptr};  // [2][D]: a then b, per parameterisation

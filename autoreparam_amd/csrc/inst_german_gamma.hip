@@ -3,24 +3,12 @@
 #include "host_common.h"
 
 namespace arp {
-// chain kernels from the lanes sized for 4 waves per workgroup, the VI kernel from the 4-lane (matrix-core)
-// instantiation in its row-part form, sized for the VI workgroup (as inst_german.hip)
-static LaneOps with_vi(LaneOps o, const LaneOps& vi) {
-  o.vi = vi.vi; o.vi_block = vi.vi_block; o.vi_parts = vi.vi_parts; o.vi_occ = vi.vi_occ; o.vi_dmax = vi.vi_dmax;
-  return o;
-}
 const LaneOps& german_gamma_bf3_ops() {
-  static const LaneOps o = with_vi(Launch<GermanLane<4, 16, kBlock / 64, false, true, kGermanGamma>>::ops(),
-                                   Launch<GermanLane<4, 16, kGermanViBlock / 64, true, true, kGermanGamma>>::vi_only());
+  static const LaneOps o = german_lane4_ops<kGermanGamma, true>();
   return o;
 }
 const std::vector<LaneOps>& german_gamma_ops() {
-  static const std::vector<LaneOps> t = {
-      with_vi(Launch<GermanLane<4, 16, kBlock / 64, false, false, kGermanGamma>>::ops(),
-              Launch<GermanLane<4, 16, kGermanViBlock / 64, true, false, kGermanGamma>>::vi_only()),
-      Launch<GermanLane<8, 8, kBlock / 64, false, false, kGermanGamma>>::ops(),
-      Launch<GermanLane<16, 4, kBlock / 64, false, false, kGermanGamma>>::ops(),
-  };
+  static const std::vector<LaneOps> t = german_lane_ops<kGermanGamma>();
   return t;
 }
 }  // namespace arp

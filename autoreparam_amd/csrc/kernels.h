@@ -67,7 +67,8 @@ struct HmcParams {
 // relay_begin rewrites the kernel's OWN copy of the parameters to the segment's view (steps, first transition, recording
 // schedule -- the arithmetic of arp_api.hip: fill_params); relay_end raises the flag.  A wait is bounded (seg_timeout):
 // on expiry the launch is marked failed -- device word for the other waiters, pinned host word for arp_model_check -- and
-// every workgroup still waiting leaves without touching the state (seg < 0: the kernels return at once).
+// every workgroup still waiting returns at once (seg < 0).  Segments that ran before have stored their steps, so such a launch
+// leaves its chains partly advanced -- discard them.
 // ---------------------------------------------------------------------------
 struct RelayId { unsigned bid; int seg; };
 ARP_DEV RelayId relay_begin(HmcParams& P) {
