@@ -1,6 +1,6 @@
 """Pretty-printer for the result files main.py writes (reference analyze.py:30-185):
 
-    python -m autoreparam_amd.analyze --results_dir=. --model=radon_MN --elbos --ess --reparams
+    python -m autoreparam_amd.analyze --results_dir=. --model=radon_MN --elbos --ess --rhat --reparams
 
 The reference's method list is stale (`cVIP_exp_tied`, analyze.py:19-26) and it expects a
 `num_leapfrog_steps` key that main.py only writes for interleaved runs; here every
@@ -77,9 +77,36 @@ def report_ess(results, normalize_times=False, num_samples=10000):
     return lines
 
 
+def report_rhat(results, results_dir=None, model_name=None, threshold=1.01):
+    """Build-specific: the convergence diagnostics of every sampling run that recorded them (split R-hat over the chains
+    whose trace was kept; for a streaming run the un-split R-hat of all chains next to it), the last run of each file,
+    and -- where <method>_rhat.npz is at hand -- the elements above the customary threshold."""
+    lines = []
+    for m, r in results.items():
+        if "split_rhat_max" not in r:
+            continue
+        fmt = lambda v: "n/a" if v is None else "{:.4f}".format(v)
+        worst = max((v for v in (r["split_rhat_max"][-1], r["rhat_max_all_chains"][-1]) if v is not None), default=None)
+        line = "split R-hat max {} over {} chains; all chains (un-split) {}; {:.3f}s : {}{}".format(
+            fmt(r["split_rhat_max"][-1]), r["split_rhat_chains"][-1], fmt(r["rhat_max_all_chains"][-1]),
+            r["diagnostics_time_sec"][-1], m, "" if worst is None or worst <= threshold else "   <-- NOT CONVERGED")
+        lines.append(line)
+        path = os.path.join(results_dir or ".", model_name or "", m + "_rhat.npz")
+        if os.path.exists(path):
+            z = np.load(path)
+            for key in z.files:
+                if key.startswith(("split_rhat/", "rhat_all_chains/")):
+                    v = np.asarray(z[key], np.float64)
+                    bad = np.argwhere(v > threshold)
+                    if len(bad):
+                        lines.append("      {}: {} element(s) above {}, worst {:.4f} at {}".format(
+                            key, len(bad), threshold, np.nanmax(v), tuple(int(i) for i in np.unravel_index(np.nanargmax(v), v.shape))))
+    return lines
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
-    for f in ("elbos", "ess", "reparams", "normalize_times"):
+    for f in ("elbos", "ess", "reparams", "normalize_times", "rhat"):
         ap.add_argument("--" + f, action="store_true")
     ap.add_argument("--model", default="all")
     ap.add_argument("--results_dir", default="")
@@ -98,6 +125,8 @@ def main(argv=None):
             print("\n".join(report_reparams(results)) + "\n")
         if args.ess:
             print("\n".join(report_ess(results, args.normalize_times)) + "\n")
+        if args.rhat:
+            print("\n".join(report_rhat(results, root, name)) + "\n")
 
 
 if __name__ == "__main__":

@@ -1,0 +1,90 @@
+"""Convergence diagnostics across chains: the potential scale reduction factor R-hat (Gelman-Rubin; the split form of
+BDA3 / Stan / ArviZ, without rank normalisation) and the pooled posterior mean / sd of every element.
+
+Build-specific (the reference runs 100 chains and reports the within-chain ESS only).  The per-chain moments come from
+one pass over a trace that is already on the device (`arp_split_moments`) or from the in-kernel statistics of a
+streaming run (`arp_hmc_io.stats` through engine.stats_summary); `arp_moments_fold` sums them over chains into five
+[D] vectors that are additive over chains, hence over ranks; the statistic itself is a few lines of float64 numpy.
+
+With m rows (chains, or half-chains) of n draws each, W = mean of the rows' variances and B/n = variance of the rows'
+means:  rhat = sqrt(((n-1)/n W + B/n) / W),  pooled sd = sqrt((n-1)/n W + B/n),  pooled mean = mean of the rows' means.
+"""
+import collections
+import ctypes as C
+
+import numpy as np
+import torch
+
+# rhat, mean, sd: [D] float64 (NaN where W = 0 or fewer than two rows have a finite variance); rows = m, the number of
+# rows with a finite variance; constant_rows = how many of them never moved (variance exactly 0)
+Rhat = collections.namedtuple("Rhat", ["rhat", "mean", "sd", "rows", "constant_rows"])
+
+
+def split_moments(trace, split=True):
+    """(mean, var) [P, C, D] float32 device tensors of a recorded [S, C, D] float32 trace on the GPU: P = 2 halves of
+    S // 2 draws (split) or P = 1.  A leading or inner block of chains of a wider trace is taken in place, as
+    util.effective_sample_size does; the workspace of the long-trace route is owned here."""
+    from . import _lib
+    if not (trace.is_cuda and trace.dtype == torch.float32 and trace.dim() == 3):
+        raise ValueError("split_moments: a float32 [S, C, D] trace on the GPU is required (there is no CPU fallback)")
+    S, Cn, D = trace.shape
+    P = 2 if split else 1
+    mean = torch.empty(P, Cn, D, dtype=torch.float32, device=trace.device)
+    var = torch.empty(P, Cn, D, dtype=torch.float32, device=trace.device)
+    if Cn == 0 or D == 0:
+        return mean, var
+    if S == 0:
+        return mean.fill_(float("nan")), var.fill_(float("nan"))
+    in_place = trace.is_contiguous() or (trace.stride(2) == 1 and trace.stride(1) == D and S > 1)
+    x = trace if in_place else trace.contiguous()
+    row_stride = x.stride(0) if S > 1 else Cn * D
+    L = _lib.lib()
+    with torch.cuda.device(x.device):
+        need = int(L.arp_moments_workspace_bytes(S, Cn * D, int(bool(split))))
+        ws = torch.empty(need, dtype=torch.uint8, device=x.device) if need > 0 else None
+        _lib.check(L.arp_split_moments(C.c_void_p(x.data_ptr()), S, Cn * D, row_stride, int(bool(split)),
+                                       C.c_void_p(mean.data_ptr()), C.c_void_p(var.data_ptr()),
+                                       C.c_void_p(ws.data_ptr() if ws is not None else 0), need,
+                                       C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+        del ws
+    return mean, var
+
+
+def fold(mean, var):
+    """The [5, D] float64 device tensor of `arp_moments_fold` over every leading axis of `mean`, `var` ([..., D] float32
+    on the GPU): count, sum of mean, sum of mean^2, sum of var over the rows with a finite var, and how many have var == 0."""
+    from . import _lib
+    if not (mean.is_cuda and mean.shape == var.shape):
+        raise ValueError("fold: mean and var of one shape on the GPU are required (there is no CPU fallback)")
+    D = int(mean.shape[-1])
+    m = mean.reshape(-1, D).to(torch.float32).contiguous()
+    v = var.reshape(-1, D).to(torch.float32).contiguous()
+    sums = torch.empty(5, D, dtype=torch.float64, device=mean.device)
+    if D == 0:
+        return sums
+    with torch.cuda.device(mean.device):
+        _lib.check(_lib.lib().arp_moments_fold(C.c_void_p(m.data_ptr()), C.c_void_p(v.data_ptr()), m.shape[0], D,
+                                               C.c_void_p(sums.data_ptr()),
+                                               C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+    return sums
+
+
+def rhat_from_sums(sums, n):
+    """The statistic from the (all-reduced) [5, D] sums of `fold` over rows of `n` draws each -> Rhat."""
+    s = np.asarray(sums.cpu() if torch.is_tensor(sums) else sums, np.float64)
+    n = float(n)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        m = s[0]
+        nan = np.full_like(m, np.nan)
+        w = np.where(m >= 1, s[3] / m, nan)
+        b_n = np.where(m >= 2, (s[2] - s[1] * s[1] / m) / (m - 1), nan)
+        b_n = np.maximum(b_n, 0.0)                     # (propagates NaN)
+        v = (n - 1.0) / n * w + b_n if n > 0 else nan
+        rhat = np.where(w > 0, np.sqrt(v / w), nan)
+        return Rhat(rhat, np.where(m >= 1, s[1] / m, nan), np.sqrt(v), m, s[4])
+
+
+def from_stats(mean, var):
+    """The sums for the UN-split R-hat of every chain of a streaming run from the per-chain (mean, var) [C, D] that
+    engine.stats_summary returns (the statistics planes keep no half-way snapshot)."""
+    return fold(mean, var)

@@ -38,6 +38,9 @@ _DEFS = [
     ("ess_chains", int, 1024, "Streaming mode: the chains with global id below this keep their whole [S, k, D] trace on "
                               "the device, and the reported ESS is the reference's autocorrelation ESS of those chains "
                               "(the batch-means figure of all chains is written next to it)."),
+    ("convergence_diagnostics", bool, True, "Sampling runs: split R-hat across chains and the pooled posterior mean / sd of "
+                                            "every element (JSON keys, <base>_rhat.npz), computed after the mcmc clock "
+                                            "has stopped; --noconvergence_diagnostics skips all of it."),
     ("lanes_per_chain", int, 0, "Lanes of a wave64 a chain is spread over (0 = automatic)."),
 ]
 

@@ -16,11 +16,14 @@ from .flags import FLAGS
 
 HmcInnerResults = collections.namedtuple("HmcInnerResults", ["is_accepted"])
 # ess_info (EssInfo: which estimator the returned ESS is, over how many chains) and moments (per-chain mean / variance from
-# the in-kernel accumulators of a streaming run, else None) belong to the call that produced them and travel with its result
-KernelResults = collections.namedtuple("KernelResults", ["inner_results", "new_step_size", "step", "ess_info", "moments"],
-                                       defaults=(None, None))
-InterleavedKernelResults = collections.namedtuple("InterleavedKernelResults", ["cp_results", "ncp_results", "ess_info", "moments"],
-                                                  defaults=(None, None))
+# the in-kernel accumulators of a streaming run, else None) belong to the call that produced them and travel with its result;
+# so does trace: the flat [S, C, D] device trace of a whole-trace run, or the [S, k, D] kept trace of a streaming run
+# (its first ess_info.chains chains are the ESS subset) -- what the convergence diagnostics read (main.py); None when the
+# producer has none to offer
+KernelResults = collections.namedtuple("KernelResults", ["inner_results", "new_step_size", "step", "ess_info", "moments", "trace"],
+                                       defaults=(None, None, None))
+InterleavedKernelResults = collections.namedtuple("InterleavedKernelResults", ["cp_results", "ncp_results", "ess_info", "moments",
+                                                                               "trace"], defaults=(None, None, None))
 
 # transitions per launch: keeps a single launch well under a second at any size
 _MAX_STEPS_PER_LAUNCH = 4096
@@ -405,7 +408,8 @@ def hmc(target, model_config, step_size_init, initial_states, reparam, flags=FLA
     eng.check()                                   # a relay hand-over that timed out inside a launch surfaces here
     ess = spec.unpack(ess_flat.cpu().numpy())
     step_mult = st.adapt[:, 0].cpu().numpy()
-    kernel_results = KernelResults(HmcInnerResults(accs[0]), step_mult, st.step, info, moments)
+    kernel_results = KernelResults(HmcInnerResults(accs[0]), step_mult, st.step, info, moments,
+                                   trace if trace is not None else kept)
     if trace is not None:
         states_transformed = _device_parts(spec, trace)
         states_orig = _LazyOriginalStates(eng, spec, trace, 0)
@@ -455,5 +459,5 @@ def hmc_interleaved(model_config, target_cp, target_ncp, num_leapfrog_steps_cp, 
     kr = InterleavedKernelResults(
         cp_results=KernelResults(HmcInnerResults(accs[0]), st.adapt[:, 0].cpu().numpy(), st.step),
         ncp_results=KernelResults(HmcInnerResults(accs[1]), st.adapt1[:, 0].cpu().numpy(), st.step),
-        ess_info=info, moments=moments)
+        ess_info=info, moments=moments, trace=trace if trace is not None else kept)
     return states, kr, ess

@@ -19,7 +19,7 @@ from collections import OrderedDict
 
 import numpy as np
 
-from . import graphs, inference, models, parallel, util
+from . import diagnostics, graphs, inference, models, parallel, util
 from .flags import FLAGS
 
 
@@ -190,6 +190,89 @@ def _ess_report(info, model_config, flags, dev, ess_parts=None):
     return out
 
 
+RHAT_WARN = 1.01          # the customary threshold above which chains are said not to have mixed
+
+
+def _finite_or_none(x):
+    """A JSON number, or None (written as null) for NaN / inf: `nan` is not JSON and never equals itself."""
+    x = float(x)
+    return x if np.isfinite(x) else None
+
+
+def _nan_max(x):
+    """(largest finite entry, its index), or (nan, -1) when there is none."""
+    x = np.asarray(x, np.float64)
+    ok = np.flatnonzero(np.isfinite(x))
+    if not ok.size:
+        return float("nan"), -1
+    at = int(ok[x[ok].argmax()])
+    return float(x[at]), at
+
+
+def _convergence_report(kernel_results, model_config, flags, dev):
+    """Build-specific (--convergence_diagnostics): do the chains of this run agree with each other?  Split R-hat of every
+    element over the chains whose trace is on the device (all of them in a whole-trace run; the --ess_chains subset of a
+    streaming run) and, for a streaming run, the un-split R-hat of ALL chains from the in-kernel statistics next to it
+    (autoreparam_amd/diagnostics.py).  Returns (JSON keys, arrays for <base>_rhat.npz); ({}, None) when the run offers
+    no device trace or the flag is off.  Called after the mcmc clock has stopped: its own wall time is a key of its own.
+    Never raises on a short run, a rank without chains or constant series: those end in NaN (null in the JSON).
+    (A collective when ws > 1: every rank calls it.)"""
+    trace = getattr(kernel_results, "trace", None)
+    if not getattr(flags, "convergence_diagnostics", True) or trace is None:
+        return {}, None
+    clock = time.time()
+    spec = model_config.model
+    S, C_local, D = (int(v) for v in trace.shape)
+    info, moments = kernel_results.ess_info, kernel_results.moments
+    streaming = moments is not None
+    k = C_local
+    if streaming:
+        # the kept trace also holds the --num_chains_to_save chains: the ESS subset is its leading block
+        k = int(info.chains) if info is not None and info.estimator == "autocorrelation" else 0
+
+    def reduced(sums, count):
+        # the five [D] vectors and the chain count in ONE all-reduce per statistic
+        t = parallel.all_reduce_sum(np.concatenate([sums.cpu().numpy().ravel(), [float(count)]]), dev).cpu().numpy()
+        return t[:-1].reshape(5, D), int(round(t[-1]))
+
+    def by_part(arrays, rows):
+        for key, flat in rows:
+            for name, part in zip(spec.part_names, spec.unpack(flat)):
+                arrays["%s/%s" % (key, name)] = part
+
+    none = trace.new_empty(0, D)
+    local = diagnostics.fold(*diagnostics.split_moments(trace[:, :k], split=True)) if k > 0 else diagnostics.fold(none, none)
+    sums, n_split = reduced(local, k)
+    split = diagnostics.rhat_from_sums(sums, S // 2)
+    split_max, at = _nan_max(split.rhat)
+    arrays = OrderedDict()
+    by_part(arrays, (("split_rhat", split.rhat), ("posterior_mean", split.mean), ("posterior_sd", split.sd)))
+    util.print_("    split R-hat over {} chains: max {:.4f} (element {})".format(n_split, split_max, at))
+    all_max = float("nan")
+    if streaming:
+        sums_all, n_all = reduced(diagnostics.from_stats(*moments), int(moments[0].shape[0]))     # (the kept trace is narrower)
+        whole = diagnostics.rhat_from_sums(sums_all, S)
+        all_max, at_all = _nan_max(whole.rhat)
+        by_part(arrays, (("rhat_all_chains", whole.rhat), ("posterior_mean_all_chains", whole.mean),
+                         ("posterior_sd_all_chains", whole.sd)))
+        util.print_("    R-hat of all {} chains (un-split, in-kernel statistics): max {:.4f} (element {})".format(
+            n_all, all_max, at_all))
+    if max(np.nan_to_num(split_max), np.nan_to_num(all_max)) > RHAT_WARN:
+        util.print_("    WARNING: R-hat above {}: the chains have not converged to one distribution "
+                    "(the elements: <base>_rhat.npz)".format(RHAT_WARN))
+    keys = {"split_rhat_max": _finite_or_none(split_max), "split_rhat_chains": n_split,
+            "rhat_max_all_chains": _finite_or_none(all_max) if streaming else None,
+            "diagnostics_time_sec": time.time() - clock}
+    return keys, arrays
+
+
+def save_rhat(file_path_base, arrays):
+    """`<base>_rhat.npz` (build-specific): per latent part `split_rhat/<part>` and the pooled `posterior_mean/<part>`,
+    `posterior_sd/<part>` over the chains the split statistic covers, [*event] each; a streaming run adds the same three
+    over ALL chains from the in-kernel statistics (`rhat_all_chains/`, `posterior_mean_all_chains/`, `posterior_sd_all_chains/`)."""
+    np.savez(file_path_base + "_rhat.npz", **arrays)
+
+
 def _read_vi_fit(file_path):
     """The JSON a VI run of the same method left behind (step sizes, variational parameters, tuning runs so far)."""
     if not os.path.exists(file_path):
@@ -254,6 +337,10 @@ def run_hmc(model_config, results_dir, file_path, tuning=False, flags=FLAGS, out
         ess_chains_total=n_ess)
     util.print_("ESS per 1000 gradients: {} +/- {}".format(ess_min, sem_min))
     extra = _ess_report(info, model_config, flags, dev, normalized_ess_final)
+    rhat_arrays = None
+    if not tuning:
+        convergence, rhat_arrays = _convergence_report(kernel_results, model_config, flags, dev)
+        extra.update(convergence)
     if ws > 1 and not tuning:
         # _ess.npz / _ess.txt hold every chain's per-element ESS: collect the other ranks' blocks (a collective: all ranks)
         normalized_ess_final = parallel.gather_parts(normalized_ess_final, n_ess, flags.device)
@@ -274,6 +361,8 @@ def run_hmc(model_config, results_dir, file_path, tuning=False, flags=FLAGS, out
                      acceptance_rate=float(acceptance_rate), mcmc_time_sec=mcmc_time, **extra)
     save_ess(file_path_base=file_path[:-5], samples=samples, param_names=_param_names(model_config),
              normalized_ess_final=normalized_ess_final, num_chains_to_save=flags.num_chains_to_save)
+    if rhat_arrays is not None:
+        save_rhat(file_path[:-5], rhat_arrays)
     return summary
 
 
@@ -301,6 +390,9 @@ def run_interleaved_hmc_with_leapfrog_steps(model_config, results_dir, num_leapf
     ess_min, sem_min, acc_cp, _ = parallel.summarize(normalized_ess_final, is_accepted_cp, flags.num_samples,
                                                      flags.num_chains, device=dev, ess_chains_total=n_ess)
     extra = _ess_report(info, model_config, flags, dev, normalized_ess_final)
+    # (before the trace is released below)
+    convergence, rhat_arrays = _convergence_report(kernel_results, model_config, flags, dev)
+    extra.update(convergence)
     acc_ncp = float(parallel.all_reduce_sum(float(np.sum(is_accepted_ncp)), dev).item()) * 100.0 / float(
         flags.num_samples * flags.num_chains)
     util.print_("ESS: {} +/- {}".format(ess_min, sem_min))
@@ -315,7 +407,7 @@ def run_interleaved_hmc_with_leapfrog_steps(model_config, results_dir, num_leapf
     else:
         states = [np.zeros((flags.num_samples, 0), np.float32) for _ in states]
     del kernel_results, is_accepted_cp, is_accepted_ncp
-    return (ess_min, sem_min, acc_cp, acc_ncp, mcmc_time, states, normalized_ess_final, extra)
+    return (ess_min, sem_min, acc_cp, acc_ncp, mcmc_time, states, normalized_ess_final, extra, rhat_arrays)
 
 
 def _first_existing(results_dir, names):
@@ -357,7 +449,8 @@ def run_interleaved_hmc(model_config, results_dir, file_path, flags=FLAGS):
             initial_states_cp=initial_states_cp, flags=flags)
         if kept is None or float(run[0]) > float(kept[0]):
             kept, kept_ls = run, num_ls
-    ess_min, sem_min, acceptance_rate_cp, acceptance_rate_ncp, mcmc_time, samples, normalized_ess_final, extra = kept
+    (ess_min, sem_min, acceptance_rate_cp, acceptance_rate_ncp, mcmc_time, samples, normalized_ess_final, extra,
+     rhat_arrays) = kept
     flags.num_leapfrog_steps = 2 * kept_ls
     if parallel.world()[0] != 0:
         return kept
@@ -367,6 +460,8 @@ def run_interleaved_hmc(model_config, results_dir, file_path, flags=FLAGS):
                      mcmc_time_sec=mcmc_time, **extra)
     save_ess(file_path_base=file_path[:-5], samples=samples, param_names=_param_names(model_config),
              normalized_ess_final=normalized_ess_final, num_chains_to_save=flags.num_chains_to_save)
+    if rhat_arrays is not None:
+        save_rhat(file_path[:-5], rhat_arrays)
     return kept
 
 

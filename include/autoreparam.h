@@ -265,6 +265,29 @@ int64_t arp_ess_workspace_bytes(int64_t n_samples, int64_t n_series);
 int arp_ess_ws(const float* trace, int64_t n_samples, int64_t n_series, int64_t row_stride, float* ess,
                void* workspace, int64_t workspace_bytes, void* stream);
 
+/* Convergence diagnostics across chains (build-specific: the reference reports the within-chain ESS only).
+ *
+ * First and second moments of every series of a recorded trace, whole or per half.  Same trace addressing as arp_ess:
+ * n_samples rows of row_stride floats, series i is column i (i < n_series).  split = 0: one part, all rows.
+ * split = 1: two parts of h = n_samples / 2 rows each, rows [0, h) and [n_samples - h, n_samples) (an odd run drops its
+ * middle row, as Stan / ArviZ do).  mean, var: [P][n_series] (P = 1 + split), var with the n - 1 divisor.  A part of one
+ * row has var = NaN (an empty part, n_samples = 1 with split = 1, mean = NaN as well), a constant part var = 0 exactly.
+ * Never fails on a short trace.  Shifted sums per chunk of 256 rows, chunks merged pairwise in a fixed order: a result
+ * is bitwise reproducible and the same for a column however it is reached (alignment, grid, route).
+ * arp_moments_workspace_bytes is 0 where one launch over the series axis fills the device; otherwise (few series, many
+ * rows) it is the size of the per-chunk partials with which the row axis is cut over workgroups too and a second launch
+ * merges them.  Without such a workspace (NULL, or fewer bytes) the one-launch form is taken.  256-byte aligned. */
+int64_t arp_moments_workspace_bytes(int64_t n_samples, int64_t n_series, int split);
+int arp_split_moments(const float* trace, int64_t n_samples, int64_t n_series, int64_t row_stride, int split,
+                      float* mean, float* var, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* Column sums over `n_rows` rows of [n_rows][D] float32 moments (rows = chains, or half-chains: the [P][C][D] planes of
+ * arp_split_moments are [(P C)][D] rows).  Over the rows whose var is finite: sums[0][d] = their number, sums[1][d] =
+ * sum of mean, sums[2][d] = sum of mean^2, sums[3][d] = sum of var; sums[4][d] = number of rows with var == 0 (series that
+ * never moved).  float64 accumulation in a fixed order (bitwise reproducible); sums is a DEVICE [5][D] double buffer.
+ * The five vectors are additive over chains, hence over ranks.  n_rows = 0 gives zeros. */
+int arp_moments_fold(const float* mean, const float* var, int64_t n_rows, int32_t D, double* sums, void* stream);
+
 /* Test hook: the step-size adaptation recurrence of the chain kernels on SCRIPTED log acceptance ratios
  * (tfp.mcmc.DualAveragingStepSizeAdaptation / SimpleStepSizeAdaptation as wired at inference.py:224-226, 288-306;
  * SURVEY.md 8c known answer (7)).  For each of `n` independent rows, applies the update after transitions
