@@ -26,26 +26,9 @@ static std::mutex g_vi_launch_mutex;
 // under a sanitizer -- on a GPU-less machine (tests/test_api_fuzz.py).  Nothing can be computed with such a handle:
 // every call that gets past validation fails with HIP's own "no device" error at its first HIP call.
 static bool host_only() {
+  static bool said = false;             // asked at every arp_model_create, announced once
   const char* e = getenv("ARP_HOST_ONLY");
-  const char* d = getenv("ARP_DEBUG");
-  if (!(e && e[0] == '1' && d && d[0] == '1' && d[1] == 0)) return false;
-  static bool said = false;
-  if (!said) { fprintf(stderr, "libautoreparam_hip: DEBUG SWITCH ARP_HOST_ONLY=1 is in effect (handles without a device: validation only)\n"); said = true; }
-  return true;
-}
-
-// integer experiment switch, honoured under ARP_DEBUG=1 only and announced on stderr
-static bool debug_int(const char* name, int* out) {
-  const char* e = getenv(name);
-  if (!e || !e[0]) return false;
-  const char* d = getenv("ARP_DEBUG");
-  if (!(d && d[0] == '1' && d[1] == 0)) {
-    fprintf(stderr, "libautoreparam_hip: %s=%s IGNORED (experiment switch; set ARP_DEBUG=1 to enable it)\n", name, e);
-    return false;
-  }
-  fprintf(stderr, "libautoreparam_hip: DEBUG SWITCH %s=%s is in effect\n", name, e);
-  *out = atoi(e);
-  return true;
+  return e && e[0] == '1' && debug_switch("ARP_HOST_ONLY", " (handles without a device: validation only)", &said);
 }
 
 // pick the instantiation: requested lanes-per-chain (or a default from the chain
@@ -371,21 +354,8 @@ static int fill_params(arp_model* m, const arp_hmc_config* cfg, const arp_hmc_io
   P.n_samples = (io->trace || io->trace_accept || io->stats || io->rec_accept_count) ? cfg->n_samples : 0;
   if (io->stats && cfg->stats_batch < 1) { set_error("stats_batch must be >= 1 when stats is given"); return 1; }
   P.trace_centered = cfg->trace_centered;
-  {
-    // result r is taken after transition n = 1 + burnin + r*thin (1-based, global);
-    // in-launch step s completes transition step_base + s + 1
-    long long first_n = 1 + (long long)cfg->n_burnin;
-    long long r0 = 0;
-    if (cfg->step_base + 1 > first_n) {
-      r0 = (cfg->step_base + 1 - first_n + cfg->thin - 1) / cfg->thin;
-      first_n += r0 * cfg->thin;
-    }
-    long long s0 = first_n - cfg->step_base - 1;
-    P.rec_step = s0 < cfg->n_steps ? (int)s0 : -1;
-    P.rec_row = (int)(r0 < 0x7fffffff ? r0 : 0x7fffffff);
-    P.stats_batch = cfg->stats_batch > 0 ? cfg->stats_batch : 1;
-    P.stats_bpos = (int)(r0 % P.stats_batch);
-  }
+  P.stats_batch = cfg->stats_batch > 0 ? cfg->stats_batch : 1;
+  rec_schedule(P);             // rec_step, rec_row, stats_bpos (kernels.h)
   P.D = m->D;
   P.q = io->q; P.grad = io->grad; P.logp = io->logp; P.adapt = io->adapt;
   P.rng = io->rng; P.accept_count = io->accept_count; P.eps0 = io->eps0;
@@ -450,7 +420,10 @@ int arp_interleaved_run(arp_model* m, const arp_hmc_config* cfg, int n_leapfrog_
   return 0;
 }
 
-int arp_vi_run(arp_model* m, int which, const arp_vi_config* cfg, const arp_vi_io* io, void* stream) {
+// arp_vi_run's arguments, the instantiation that serves them (*op), the kernel's view of them (P: all but the geometry and the
+// workspace) and the group arrays
+static int vi_check(arp_model* m, int which, const arp_vi_config* cfg, const arp_vi_io* io, hipStream_t stream,
+                    const LaneOps** op, ViParams& P) {
   if (!m || !cfg || !io || which < 0 || which > 1) { set_error("arp_vi_run: null argument"); return 1; }
   if (cfg->n_lr <= 0 || cfg->n_steps <= 0 || cfg->n_mc <= 0 || cfg->n_mc > 4096) {
     set_error("arp_vi_run: n_lr, n_steps must be positive and 0 < n_mc <= 4096");
@@ -465,10 +438,9 @@ int arp_vi_run(arp_model* m, int which, const arp_vi_config* cfg, const arp_vi_i
   // family names its own (german credit: its matrix-core instantiation, in the variant the chain kernels take too)
   int K_vi = m->family->vi_lanes;
   if (!K_vi) for (const auto& t : m->family->ops()) if (t.vi) K_vi = std::max(K_vi, t.K);
-  const LaneOps* o = lane_ops(m, K_vi, 1 << 30);
+  const LaneOps* o = *op = lane_ops(m, K_vi, 1 << 30);
   if (!o || !o->vi) { set_error("no VI kernel instantiation covers this group count"); return 1; }
   if (m->D > o->vi_dmax) { set_error("arp_vi_run: model dimension exceeds this model's VI kernel instantiation"); return 1; }
-  ViParams P;
   P.n_steps = cfg->n_steps; P.n_mc = cfg->n_mc; P.learn_a = cfg->learn_a; P.tied_b = cfg->tied_b; P.a_prior = cfg->a_prior; P.D = m->D;
   P.seed = cfg->seed;
   P.const_base = (float)m->const_base;
@@ -485,8 +457,8 @@ int arp_vi_run(arp_model* m, int which, const arp_vi_config* cfg, const arp_vi_i
   for (const int* grp : {P.a_group, P.b_group}) {
     if (!grp) continue;
     std::vector<int> g(m->D);
-    ARP_HIP_OK(hipMemcpyAsync(g.data(), grp, m->D * sizeof(int), hipMemcpyDeviceToHost, (hipStream_t)stream));
-    ARP_HIP_OK(hipStreamSynchronize((hipStream_t)stream));
+    ARP_HIP_OK(hipMemcpyAsync(g.data(), grp, m->D * sizeof(int), hipMemcpyDeviceToHost, stream));
+    ARP_HIP_OK(hipStreamSynchronize(stream));
     for (int d = 0; d < m->D; ++d) {
       const int l = g[d];
       bool ok = l >= 0 && l <= d && g[l] == l;
@@ -497,106 +469,130 @@ int arp_vi_run(arp_model* m, int which, const arp_vi_config* cfg, const arp_vi_i
       }
     }
   }
-  // ---- geometry of the launch (kernels.h: vi_kernel): G sample groups x R row parts per learning rate
-  const int B = o->vi_block, K = o->K;
+  return 0;
+}
+
+// Geometry of arp_vi_run's launches (kernels.h: vi_kernel): G sample groups x R row parts per learning rate.  It decides
+// whether a learning rate's workgroups are resident together, that is, whether a fit finishes or runs into its bounds.
+struct ViPlan {
+  int B, K;                  // threads of a workgroup, lanes per chain
+  int G, R, GR;              // sample groups, row parts, workgroups of a learning rate (G * R)
+  int occ;                   // workgroups of the kernel one CU holds (occupancy query)
+  long long capacity;        // workgroups the plan lets be resident together
+  int groups_per_launch;     // learning rates one launch takes
+  int nq, Tp;                // quantities per latent the workgroups exchange; floats of an exchanged row, padded
+  size_t ws_bytes;           // hand-off workspace: the error flag's 256 bytes, then the granules
+  size_t snap_floats;        // the rows a launch starts from, kept for a retry (0: nothing waits, nothing is retried)
+  bool coop;                 // cooperative launch
+};
+// Arithmetic only: no HIP call, nothing of the handle.  `o`: the instantiation's shape (K, vi_block, vi_parts); occ: its
+// occupancy query; tiles: tiles of German credit's observations (vi_parts); g_max, r_forced: ARP_VI_G / ARP_VI_R (0: not
+// set); n_keep: parameter rows per learning rate a retry restores.
+static int vi_plan(const arp_vi_config* cfg, int D, const LaneOps& o, int occ, int cus, int tiles, int g_max, int r_forced,
+                   int n_keep, int vi_launch, bool coop_ok, ViPlan* plan) {
+  ViPlan& p = *plan;
+  const int B = p.B = o.vi_block, K = p.K = o.K;
   const int CPW = B / K;                                 // draws a workgroup takes per pass
   const int unit = kViBlock / B;                         // G must be a multiple of this when a lane takes several draws
   int G = (cfg->n_mc + CPW - 1) / CPW;                   // one pass
   int R = 1;
-  if (o->vi_parts) {
-    // German credit: the observations' tiles (128 rows on f32 matrix cores, 64 on bf16 x 3) are split too, so that a learning
-    // rate's group has about 32 workgroups (five learning rates: 160 CUs) and a gradient is two tiles of matrix-core work per wave
-    const int nt = (m->german.N + o->vi_tile_obs - 1) / o->vi_tile_obs;
-    R = std::min(nt, std::max(1, 32 / G));
-  }
-  int dbg = 0;
-  if (debug_int("ARP_VI_G", &dbg) && dbg > 0 && !o->vi_parts) G = std::min(G, dbg);      // experiments (ARP_DEBUG=1 only)
-  if (debug_int("ARP_VI_R", &dbg) && dbg > 0 && o->vi_parts) R = dbg;
-  int occ = o->vi_occ ? o->vi_occ() : 0;
+  // German credit: the observations' tiles (128 rows on f32 matrix cores, 64 on bf16 x 3) are split too, so that a learning
+  // rate's group has about 32 workgroups (five learning rates: 160 CUs) and a gradient is two tiles of matrix-core work per wave
+  if (o.vi_parts) R = std::min(tiles, std::max(1, 32 / G));
+  if (g_max > 0 && !o.vi_parts) G = std::min(G, g_max);      // experiments (ARP_DEBUG=1 only)
+  if (r_forced > 0 && o.vi_parts) R = r_forced;
+  p.occ = occ;
   if (occ <= 0) { set_error("arp_vi_run: the VI kernel does not fit on this device (occupancy query)"); return 1; }
   // every workgroup of a group has to be resident together (they wait for each other twice per step).  One or two per
   // CU is an LDS or register-file limit, which the query gets right; at more than that it can be one workgroup per CU
   // high (MI355X_MICROARCH.md, residency: the scalar-register edge), so one is given away
-  const long long capacity = (long long)(occ > 2 ? occ - 1 : occ) * m->cus;
+  const long long capacity = p.capacity = (long long)(occ > 2 ? occ - 1 : occ) * cus;
   while ((long long)G * R > capacity && R > 1) R = (R + 1) / 2;
-  if ((long long)G * R > capacity && o->vi_parts) {
+  if ((long long)G * R > capacity && o.vi_parts) {
     set_error("arp_vi_run: n_mc draws of this model do not fit on the device in one pass");   // 4 096 draws: 128 workgroups
     return 1;
   }
   if ((long long)G * R > capacity) G = (int)std::max<long long>(unit, capacity / R / unit * unit);
   if ((long long)G * CPW < cfg->n_mc && G % unit != 0) G = (G + unit - 1) / unit * unit;   // several draws per lane: whole turns
   if ((long long)G * R > capacity) { set_error("arp_vi_run: one learning rate's workgroups do not fit on this device"); return 1; }
-  const int GR = G * R;
-  const int groups_per_launch = (int)std::max<long long>(1, std::min<long long>(cfg->n_lr, capacity / GR));
-  const int nq = cfg->learn_a ? 4 : 2;
-  const int Tp = (nq * m->D + 1 + 15) & ~15;
-  const size_t need = GR > 1 ? 256 + groups_per_launch * vi_xch_group_granules(GR, Tp) * 8 : 256;
-  if (m->vi_ws_bytes < need) {
-    if (m->vi_ws) { ARP_HIP_OK(hipStreamSynchronize((hipStream_t)stream)); (void)hipFree(m->vi_ws); m->vi_ws = nullptr; m->vi_ws_bytes = 0; }
-    ARP_HIP_OK(hipMalloc(&m->vi_ws, need));
-    m->vi_ws_bytes = need;
-  }
-  P.G = G; P.R = R; P.xch_tp = Tp;
-  P.err = (int*)m->vi_ws;
-  P.xch = GR > 1 ? (unsigned long long*)((char*)m->vi_ws + 256) : nullptr;
-  g_vi_geometry = {B, G, R, groups_per_launch, (int)std::min<long long>((long long)cfg->n_lr * GR, capacity), occ};
+  p.G = G; p.R = R;
+  const int GR = p.GR = G * R;
+  p.groups_per_launch = (int)std::max<long long>(1, std::min<long long>(cfg->n_lr, capacity / GR));
+  p.nq = cfg->learn_a ? 4 : 2;
+  p.Tp = (p.nq * D + 1 + 15) & ~15;
+  p.ws_bytes = GR > 1 ? 256 + p.groups_per_launch * vi_xch_group_granules(GR, p.Tp) * 8 : 256;
+  p.snap_floats = GR > 1 ? (size_t)n_keep * p.groups_per_launch * D : 0;
   // A group's workgroups wait for each other, so all of them must be resident.  Cooperative launch (the default where the
   // device has it): the runtime checks the grid against the device's capacity and serialises such launches of the process.
   // Plain launch: the occupancy arithmetic above plus one such launch at a time in this process (the mutex).  Neither holds
-  // against kernels of other queues or processes: see the retry below.
-  const bool coop = GR > 1 && (m->vi_launch == 2 || (m->vi_launch == 0 && m->coop_ok));
-  if (m->vi_launch == 2 && !m->coop_ok) { set_error("arp_vi_run: vi_launch=cooperative but the device does not support cooperative launches"); return 1; }
-  std::unique_lock<std::mutex> one_at_a_time(g_vi_launch_mutex, std::defer_lock);
-  if (GR > 1 && !coop) one_at_a_time.lock();
-  // A launch whose hand-offs ran into their bound (the device was shared with kernels of other queues or processes for
-  // that long: no launch mode guarantees residency against THOSE) is not an error yet: the parameters it started from are
-  // kept, and it is taken again with four times the bound -- 2 s, 8 s, 32 s -- before the call gives up.  A fit under
-  // contention is slower, not failed; an undisturbed one never takes the second launch.
-  const size_t rowf = (size_t)m->D;
-  const int n_keep = 2 + (io->w ? 1 : 0) + (io->wb && cfg->learn_a ? 1 : 0);
-  if (GR > 1 && m->vi_snap_floats < (size_t)n_keep * groups_per_launch * rowf) {
-    if (m->vi_snap) { ARP_HIP_OK(hipStreamSynchronize((hipStream_t)stream)); (void)hipFree(m->vi_snap); m->vi_snap = nullptr; m->vi_snap_floats = 0; }
-    ARP_HIP_OK(hipMalloc((void**)&m->vi_snap, (size_t)n_keep * groups_per_launch * rowf * sizeof(float)));
-    m->vi_snap_floats = (size_t)n_keep * groups_per_launch * rowf;
+  // against kernels of other queues or processes: see the retry (vi_launch_chunks).
+  p.coop = GR > 1 && (vi_launch == 2 || (vi_launch == 0 && coop_ok));
+  if (vi_launch == 2 && !coop_ok) { set_error("arp_vi_run: vi_launch=cooperative but the device does not support cooperative launches"); return 1; }
+  return 0;
+}
+
+// A handle-owned device buffer grown to `count` elements of `elem` bytes (never shrunk).  The old one is given back only
+// once the work on `stream` that may still read it is done.
+static int grow_device(void** buf, size_t* have, size_t count, size_t elem, hipStream_t stream) {
+  if (*have >= count) return 0;
+  if (*buf) { ARP_HIP_OK(hipStreamSynchronize(stream)); (void)hipFree(*buf); *buf = nullptr; *have = 0; }
+  ARP_HIP_OK(hipMalloc(buf, count * elem));
+  *have = count;
+  return 0;
+}
+
+// the parameter rows of a chunk (`chunk` floats each, from float `first` of every row) to the snapshot, or back
+static int vi_snapshot(float* snap, float* const (&rows)[4], size_t first, size_t chunk, bool restore, hipStream_t stream) {
+  size_t k = 0;
+  for (float* r : rows) {
+    if (!r) continue;
+    float* const live = r + first;
+    float* const kept = snap + (k++) * chunk;
+    ARP_HIP_OK(hipMemcpyAsync(restore ? live : kept, restore ? kept : live, chunk * sizeof(float), hipMemcpyDeviceToDevice, stream));
   }
-  int fault_attempts = 0;               // test hook (ARP_DEBUG=1): treat the first n launches of every chunk as timed out
+  return 0;
+}
+
+// The learning rates, plan.groups_per_launch per launch.  A launch whose hand-offs ran into their bound (the device was
+// shared with kernels of other queues or processes for that long: no launch mode guarantees residency against THOSE) is not
+// an error yet: the parameters it started from are kept, and it is taken again with four times the bound -- 2 s, 8 s, 32 s
+// -- before the call gives up.  A fit under contention is slower, not failed; an undisturbed one never takes the second launch.
+static int vi_launch_chunks(arp_model* m, int which, const LaneOps* o, const arp_vi_config* cfg, const arp_vi_io* io,
+                            const ViPlan& plan, ViParams P, std::unique_lock<std::mutex>& one_at_a_time, hipStream_t stream) {
+  const int GR = plan.GR, groups_per_launch = plan.groups_per_launch;
+  const size_t rowf = (size_t)m->D;
+  int dbg = 0, fault_attempts = 0;      // test hook (ARP_DEBUG=1): treat the first n launches of every chunk as timed out
   if (debug_int("ARP_VI_FAULT_ATTEMPTS", &dbg) && dbg > 0) fault_attempts = dbg;
   g_vi_attempts = 0;
   for (int lr0 = 0; lr0 < cfg->n_lr; lr0 += groups_per_launch) {
     const int ng = std::min(groups_per_launch, cfg->n_lr - lr0);
-    float* rows[4] = {io->loc, io->rho, io->w, (io->wb && cfg->learn_a) ? io->wb : nullptr};
+    float* const rows[4] = {io->loc, io->rho, io->w, (io->wb && cfg->learn_a) ? io->wb : nullptr};
     const size_t chunk = (size_t)ng * rowf;
-    if (GR > 1) {
-      size_t k = 0;
-      for (float* r : rows)
-        if (r) ARP_HIP_OK(hipMemcpyAsync(m->vi_snap + (k++) * chunk, r + (size_t)lr0 * rowf, chunk * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
-    }
+    if (GR > 1 && vi_snapshot(m->vi_snap, rows, (size_t)lr0 * rowf, chunk, false, stream)) return 1;
     P.lr0 = lr0;
     P.spin_ticks = kViSpinTicks;
     for (int attempt = 0;; ++attempt) {
       if (attempt > 0) {
-        size_t k = 0;
-        for (float* r : rows)
-          if (r) ARP_HIP_OK(hipMemcpyAsync(r + (size_t)lr0 * rowf, m->vi_snap + (k++) * chunk, chunk * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+        if (vi_snapshot(m->vi_snap, rows, (size_t)lr0 * rowf, chunk, true, stream)) return 1;
         P.spin_ticks *= 4;
       }
       // every polled word starts at zero (epochs start at 1): the flag and this launch's granules
-      ARP_HIP_OK(hipMemsetAsync(m->vi_ws, 0, need, (hipStream_t)stream));
-      hipError_t launched = o->vi(m->args, m->dev_ab[which], m->dev_ab[which] + m->D, P, ng, coop, (hipStream_t)stream);
-      if (coop && m->vi_launch == 0 && (launched == hipErrorCooperativeLaunchTooLarge || launched == hipErrorNotSupported)) {
-        // "auto" only: the runtime counts co-residency more strictly than the occupancy query above (or lacks the feature
+      ARP_HIP_OK(hipMemsetAsync(m->vi_ws, 0, plan.ws_bytes, stream));
+      hipError_t launched = o->vi(m->args, m->dev_ab[which], m->dev_ab[which] + m->D, P, ng, plan.coop, stream);
+      if (plan.coop && m->vi_launch == 0 && (launched == hipErrorCooperativeLaunchTooLarge || launched == hipErrorNotSupported)) {
+        // "auto" only: the runtime counts co-residency more strictly than the occupancy query (vi_plan) (or lacks the feature
         // after all) -- take the plain launch, one at a time per process, as round 5 did
         (void)hipGetLastError();
         if (!one_at_a_time.owns_lock()) one_at_a_time.lock();
-        launched = o->vi(m->args, m->dev_ab[which], m->dev_ab[which] + m->D, P, ng, false, (hipStream_t)stream);
+        launched = o->vi(m->args, m->dev_ab[which], m->dev_ab[which] + m->D, P, ng, false, stream);
       }
       ARP_HIP_OK(launched);
       g_vi_attempts = std::max(g_vi_attempts, attempt + 1);
       if (GR <= 1) break;
       // the hand-offs' waits are bounded: a group that was not resident together reports it here instead of hanging
       int err = 0;
-      ARP_HIP_OK(hipMemcpyAsync(&err, m->vi_ws, sizeof(int), hipMemcpyDeviceToHost, (hipStream_t)stream));
-      ARP_HIP_OK(hipStreamSynchronize((hipStream_t)stream));
+      ARP_HIP_OK(hipMemcpyAsync(&err, m->vi_ws, sizeof(int), hipMemcpyDeviceToHost, stream));
+      ARP_HIP_OK(hipStreamSynchronize(stream));
       if (attempt < fault_attempts) err = 1;
       if (!err) break;
       if (attempt == 2) {
@@ -607,6 +603,31 @@ int arp_vi_run(arp_model* m, int which, const arp_vi_config* cfg, const arp_vi_i
     }
   }
   return 0;
+}
+
+int arp_vi_run(arp_model* m, int which, const arp_vi_config* cfg, const arp_vi_io* io, void* stream) {
+  const hipStream_t st = (hipStream_t)stream;
+  const LaneOps* o = nullptr;
+  ViParams P;
+  if (vi_check(m, which, cfg, io, st, &o, P)) return 1;
+  int g_max = 0, r_forced = 0;
+  debug_int("ARP_VI_G", &g_max);
+  debug_int("ARP_VI_R", &r_forced);
+  const int tiles = o->vi_parts ? (m->german.N + o->vi_tile_obs - 1) / o->vi_tile_obs : 0;
+  const int n_keep = 2 + (io->w ? 1 : 0) + (io->wb && cfg->learn_a ? 1 : 0);
+  ViPlan plan;
+  if (vi_plan(cfg, m->D, *o, o->vi_occ ? o->vi_occ() : 0, m->cus, tiles, g_max, r_forced, n_keep, m->vi_launch, m->coop_ok, &plan)) return 1;
+  if (grow_device(&m->vi_ws, &m->vi_ws_bytes, plan.ws_bytes, 1, st)) return 1;
+  P.G = plan.G; P.R = plan.R; P.xch_tp = plan.Tp;
+  P.err = (int*)m->vi_ws;
+  P.xch = plan.GR > 1 ? (unsigned long long*)((char*)m->vi_ws + 256) : nullptr;
+  g_vi_geometry = {plan.B, plan.G, plan.R, plan.groups_per_launch,
+                   (int)std::min<long long>((long long)cfg->n_lr * plan.GR, plan.capacity), plan.occ};
+  // plain launches of waiting workgroups: one at a time in this process, from here to the end of the call
+  std::unique_lock<std::mutex> one_at_a_time(g_vi_launch_mutex, std::defer_lock);
+  if (plan.GR > 1 && !plan.coop) one_at_a_time.lock();
+  if (grow_device((void**)&m->vi_snap, &m->vi_snap_floats, plan.snap_floats, sizeof(float), st)) return 1;
+  return vi_launch_chunks(m, which, o, cfg, io, plan, P, one_at_a_time, st);
 }
 
 int arp_vi_attempts(int32_t* out1) {

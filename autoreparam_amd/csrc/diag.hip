@@ -241,10 +241,8 @@ Parts make_parts(int64_t n_samples, int split) {
 
 // experiments and tests (ARP_DEBUG=1 only): ARP_MOMENTS_ROUTE=long | wide overrides the library's choice of route
 int forced_route() {
-  const char* e = getenv("ARP_MOMENTS_ROUTE");
-  const char* d = getenv("ARP_DEBUG");
-  if (!(e && d && d[0] == '1' && d[1] == 0)) return 0;
-  return e[0] == 'l' ? 2 : e[0] == 'w' ? 1 : 0;
+  const char* e = debug_switch("ARP_MOMENTS_ROUTE");
+  return !e ? 0 : e[0] == 'l' ? 2 : e[0] == 'w' ? 1 : 0;
 }
 
 bool long_route(const Parts& pt, int64_t n_series) {

@@ -797,11 +797,9 @@ extern "C" int arp_ess_ws(const float* trace, int64_t n_samples, int64_t n_serie
   bool tile_path = n_samples >= kTileMinS && n_samples <= kTileMaxS && n_series >= 2 && row_stride < (1ll << 29);
   {
     // which kernel takes short series: the library default below, or (experiments, ARP_DEBUG=1) ARP_ESS_TILE=0 / 1
-    const char* e = getenv("ARP_ESS_TILE");
-    const char* d = getenv("ARP_DEBUG");
-    const bool dbg = e && d && d[0] == '1' && d[1] == 0;
-    if (!kEssTileDefault) tile_path = tile_path && dbg && e[0] == '1';
-    else if (dbg && e[0] == '0') tile_path = false;
+    const char* e = debug_switch("ARP_ESS_TILE");
+    if (!kEssTileDefault) tile_path = tile_path && e && e[0] == '1';
+    else if (e && e[0] == '0') tile_path = false;
   }
   if (tile_path) {
     static thread_local int cus_of[64] = {0};

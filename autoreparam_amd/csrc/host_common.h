@@ -196,20 +196,34 @@ struct Launch {
   }
 };
 
-// experiments only: ARP_STATS_LDS=0 sends statistics runs down the plane-per-sample route of kernels.h again.  Honoured
-// under ARP_DEBUG=1 only and announced on stderr: a stray variable must not change which kernel a production run takes.
+// The one gate of the library's experiment and test switches: the value of the environment variable `name`, honoured under
+// ARP_DEBUG=1 only and announced on stderr -- a stray variable must not change which kernel a production run takes, and says
+// that it was ignored.  nullptr: unset, empty or ignored.  `note` ends the announcement; `said` (a switch that is asked for
+// on every call but announces itself once per process) holds whether it has.
+inline const char* debug_switch(const char* name, const char* note = "", bool* said = nullptr) {
+  const char* e = getenv(name);
+  if (!e || !e[0]) return nullptr;
+  const char* d = getenv("ARP_DEBUG");
+  if (!(d && d[0] == '1' && d[1] == 0)) {
+    fprintf(stderr, "libautoreparam_hip: %s=%s IGNORED (experiment switch; set ARP_DEBUG=1 to enable it)\n", name, e);
+    return nullptr;
+  }
+  if (!(said && *said)) fprintf(stderr, "libautoreparam_hip: DEBUG SWITCH %s=%s is in effect%s\n", name, e, note);
+  if (said) *said = true;
+  return e;
+}
+// integer experiment switch
+inline bool debug_int(const char* name, int* out) {
+  const char* e = debug_switch(name);
+  if (e) *out = atoi(e);
+  return e != nullptr;
+}
+
+// experiments only: ARP_STATS_LDS=0 sends statistics runs down the plane-per-sample route of kernels.h again (asked once
+// per process; any other value is the default and says nothing)
 inline bool stats_lds_enabled() {
-  static const bool on = [] {
-    const char* e = getenv("ARP_STATS_LDS");
-    if (!(e && e[0] == '0')) return true;
-    const char* d = getenv("ARP_DEBUG");
-    if (!(d && d[0] == '1' && d[1] == 0)) {
-      fprintf(stderr, "libautoreparam_hip: ARP_STATS_LDS=0 IGNORED (experiment switch; set ARP_DEBUG=1 to enable it)\n");
-      return true;
-    }
-    fprintf(stderr, "libautoreparam_hip: DEBUG SWITCH ARP_STATS_LDS=0 is in effect (statistics take the plane-per-sample route)\n");
-    return false;
-  }();
+  static const char* const e = getenv("ARP_STATS_LDS");
+  static const bool on = !(e && e[0] == '0' && debug_switch("ARP_STATS_LDS", " (statistics take the plane-per-sample route)"));
   return on;
 }
 

@@ -49,6 +49,18 @@ struct HmcParams {
   int seg_fault;                    // test hook (ARP_DEBUG=1 ARP_RELAY_FAULT=1): segments never raise their flag
 };
 
+// The recording schedule of the steps P describes -- a launch (arp_api.hip: fill_params) or one relay segment of it
+// (relay_begin) -- from step_base, n_steps, n_burnin, thin and stats_batch: result r is taken after transition
+// n = 1 + burnin + r*thin (1-based, global); in-launch step s completes transition step_base + s + 1
+__host__ __device__ __forceinline__ void rec_schedule(HmcParams& P) {
+  long long first_n = 1 + (long long)P.n_burnin, r0 = 0;
+  if (P.step_base + 1 > first_n) { r0 = (P.step_base + 1 - first_n + P.thin - 1) / P.thin; first_n += r0 * P.thin; }
+  const long long s0 = first_n - P.step_base - 1;
+  P.rec_step = s0 < P.n_steps ? (int)s0 : -1;
+  P.rec_row = (int)(r0 < 0x7fffffff ? r0 : 0x7fffffff);
+  P.stats_bpos = (int)(r0 % P.stats_batch);
+}
+
 
 // ---------------------------------------------------------------------------
 // Relay.  The workgroups of a launch that are resident together (one or two per CU) are often exactly one or two rounds,
@@ -65,7 +77,7 @@ struct HmcParams {
 // workgroups out in and whatever else shares the device.  The lowest unfinished ticket never waits on an unfinished one, so
 // the launch always advances (no reliance on in-order dispatch: round 5's form indexed with blockIdx).
 // relay_begin rewrites the kernel's OWN copy of the parameters to the segment's view (steps, first transition, recording
-// schedule -- the arithmetic of arp_api.hip: fill_params); relay_end raises the flag.  A wait is bounded (seg_timeout):
+// schedule -- rec_schedule, as arp_api.hip: fill_params calls it for the launch); relay_end raises the flag.  A wait is bounded (seg_timeout):
 // on expiry the launch is marked failed -- device word for the other waiters, pinned host word for arp_model_check -- and
 // every workgroup still waiting returns at once (seg < 0).  Segments that ran before have stored their steps, so such a launch
 // leaves its chains partly advanced -- discard them.
@@ -92,12 +104,7 @@ ARP_DEV RelayId relay_begin(HmcParams& P) {
     P.n_steps = n < 0 ? 0 : n;
     P.step_base += start;
     if (r.seg > 0) {
-      long long first_n = 1 + (long long)P.n_burnin, r0 = 0;
-      if (P.step_base + 1 > first_n) { r0 = (P.step_base + 1 - first_n + P.thin - 1) / P.thin; first_n += r0 * P.thin; }
-      const long long s0 = first_n - P.step_base - 1;
-      P.rec_step = s0 < P.n_steps ? (int)s0 : -1;
-      P.rec_row = (int)(r0 < 0x7fffffff ? r0 : 0x7fffffff);
-      P.stats_bpos = (int)(r0 % P.stats_batch);
+      rec_schedule(P);
       if (threadIdx.x == 0) {
         unsigned* const f = P.seg_flags + r.bid;
         const unsigned want = P.seg_epoch + (unsigned)r.seg;

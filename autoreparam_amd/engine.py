@@ -37,6 +37,21 @@ class ChainState(object):
         self.step = 0  # transitions done
 
 
+def _hmc_config(state, n_leapfrog, n_steps, seed, chain_offset, adapt_kind, n_adapt, adapt_target, adapt_rate, n_burnin,
+                thin, trace, trace_accept, trace_centered, lanes, stats_batch, n_samples, trace_chains):
+    """The arp_hmc_config of one launch (Engine.hmc_run, Engine.interleaved_run).  `n_samples` falls back to the rows of
+    whichever recording buffer is given."""
+    cfg = _lib.HmcConfig()
+    cfg.n_chains, cfg.n_leapfrog, cfg.n_steps, cfg.step_base = state.q.shape[0], int(n_leapfrog), int(n_steps), int(state.step)
+    cfg.chain_offset, cfg.seed, cfg.lanes_per_chain = int(chain_offset), int(seed), int(lanes)
+    cfg.adapt_kind, cfg.n_adapt, cfg.adapt_target, cfg.adapt_rate = int(adapt_kind), int(n_adapt), float(adapt_target), float(adapt_rate)
+    cfg.n_burnin, cfg.thin, cfg.stats_batch, cfg.trace_chains = int(n_burnin), int(thin), int(stats_batch), int(trace_chains)
+    cfg.n_samples = int(n_samples) if n_samples is not None else (int(trace.shape[0]) if trace is not None else (
+        int(trace_accept.shape[0]) if trace_accept is not None else 0))
+    cfg.trace_centered = 1 if trace_centered else 0
+    return cfg
+
+
 class Engine(object):
     def __init__(self, spec, device=None):
         if not torch.cuda.is_available():
@@ -124,25 +139,8 @@ class Engine(object):
         transitions; with them a run needs no trace, or only one of the first `trace_chains` chains
         (`trace` is then [S, trace_chains, D]).  `n_samples` = recorded samples of the whole run when no
         trace buffer gives it."""
-        cfg = _lib.HmcConfig()
-        cfg.n_chains = state.q.shape[0]
-        cfg.n_leapfrog = int(n_leapfrog)
-        cfg.n_steps = int(n_steps)
-        cfg.step_base = int(state.step)
-        cfg.chain_offset = int(chain_offset)
-        cfg.seed = int(seed)
-        cfg.adapt_kind = int(adapt_kind)
-        cfg.n_adapt = int(n_adapt)
-        cfg.adapt_target = float(adapt_target)
-        cfg.adapt_rate = float(adapt_rate)
-        cfg.n_burnin = int(n_burnin)
-        cfg.thin = int(thin)
-        cfg.n_samples = int(n_samples) if n_samples is not None else (int(trace.shape[0]) if trace is not None else (
-            int(trace_accept.shape[0]) if trace_accept is not None else 0))
-        cfg.trace_centered = 1 if trace_centered else 0
-        cfg.lanes_per_chain = int(lanes)
-        cfg.stats_batch = int(stats_batch)
-        cfg.trace_chains = int(trace_chains)
+        cfg = _hmc_config(state, n_leapfrog, n_steps, seed, chain_offset, adapt_kind, n_adapt, adapt_target, adapt_rate, n_burnin,
+                          thin, trace, trace_accept, trace_centered, lanes, stats_batch, n_samples, trace_chains)
         io = _lib.HmcIO()
         io.q, io.grad, io.logp = _ptr(state.q), _ptr(state.grad), _ptr(state.logp)
         io.adapt, io.rng, io.accept_count = _ptr(state.adapt), _ptr(state.rng), _ptr(state.accept_count)
@@ -163,25 +161,8 @@ class Engine(object):
                         trace_chains=0, rec_accept0=None, rec_accept1=None):
         """Advance `state` by n_steps interleaved steps (parameterisation 0 then 1 per step);
         stats / rec_accept* / trace_chains / n_samples as in hmc_run."""
-        cfg = _lib.HmcConfig()
-        cfg.n_chains = state.q.shape[0]
-        cfg.n_leapfrog = int(n_leapfrog_0)
-        cfg.n_steps = int(n_steps)
-        cfg.step_base = int(state.step)
-        cfg.chain_offset = int(chain_offset)
-        cfg.seed = int(seed)
-        cfg.adapt_kind = int(adapt_kind)
-        cfg.n_adapt = int(n_adapt)
-        cfg.adapt_target = float(adapt_target)
-        cfg.adapt_rate = float(adapt_rate)
-        cfg.n_burnin = int(n_burnin)
-        cfg.thin = int(thin)
-        cfg.n_samples = int(n_samples) if n_samples is not None else (int(trace.shape[0]) if trace is not None else (
-            int(trace_accept0.shape[0]) if trace_accept0 is not None else 0))
-        cfg.trace_centered = 1 if trace_centered else 0
-        cfg.lanes_per_chain = int(lanes)
-        cfg.stats_batch = int(stats_batch)
-        cfg.trace_chains = int(trace_chains)
+        cfg = _hmc_config(state, n_leapfrog_0, n_steps, seed, chain_offset, adapt_kind, n_adapt, adapt_target, adapt_rate, n_burnin,
+                          thin, trace, trace_accept0, trace_centered, lanes, stats_batch, n_samples, trace_chains)
         io = _lib.InterleavedIO()
         io.k0.q = _ptr(state.q)
         io.k0.grad, io.k0.logp = _ptr(state.grad), _ptr(state.logp)   # carried gradient / log density
