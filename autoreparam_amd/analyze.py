@@ -86,16 +86,22 @@ def report_rhat(results, results_dir=None, model_name=None, threshold=1.01):
         if "split_rhat_max" not in r:
             continue
         fmt = lambda v: "n/a" if v is None else "{:.4f}".format(v)
-        worst = max((v for v in (r["split_rhat_max"][-1], r["rhat_max_all_chains"][-1]) if v is not None), default=None)
-        line = "split R-hat max {} over {} chains; all chains (un-split) {}; {:.3f}s : {}{}".format(
-            fmt(r["split_rhat_max"][-1]), r["split_rhat_chains"][-1], fmt(r["rhat_max_all_chains"][-1]),
+        ranked = "rank_rhat_max" in r                      # (--rank_normalized_rhat runs only)
+        worst = max((v for v in (r["split_rhat_max"][-1], r["rhat_max_all_chains"][-1],
+                                 r["rank_rhat_max"][-1] if ranked else None) if v is not None), default=None)
+        rank_cols = "" if not ranked else " rank-normalised max {} (bulk {}, tail {}) over {} chains, {};".format(
+            fmt(r["rank_rhat_max"][-1]), fmt(r["rank_rhat_bulk_max"][-1]), fmt(r["rank_rhat_tail_max"][-1]),
+            r["rank_rhat_chains"][-1],
+            "n/a" if r["rank_rhat_time_sec"][-1] is None else "{:.3f}s".format(r["rank_rhat_time_sec"][-1]))
+        line = "split R-hat max {} over {} chains; all chains (un-split) {};{} {:.3f}s : {}{}".format(
+            fmt(r["split_rhat_max"][-1]), r["split_rhat_chains"][-1], fmt(r["rhat_max_all_chains"][-1]), rank_cols,
             r["diagnostics_time_sec"][-1], m, "" if worst is None or worst <= threshold else "   <-- NOT CONVERGED")
         lines.append(line)
         path = os.path.join(results_dir or ".", model_name or "", m + "_rhat.npz")
         if os.path.exists(path):
             z = np.load(path)
             for key in z.files:
-                if key.startswith(("split_rhat/", "rhat_all_chains/")):
+                if key.startswith(("split_rhat/", "rhat_all_chains/", "rank_rhat_bulk/", "rank_rhat_tail/")):
                     v = np.asarray(z[key], np.float64)
                     bad = np.argwhere(v > threshold)
                     if len(bad):

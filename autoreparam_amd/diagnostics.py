@@ -1,5 +1,7 @@
 """Convergence diagnostics across chains: the potential scale reduction factor R-hat (Gelman-Rubin; the split form of
-BDA3 / Stan / ArviZ, without rank normalisation) and the pooled posterior mean / sd of every element.
+BDA3 / Stan / ArviZ, without rank normalisation) and the pooled posterior mean / sd of every element; and, on request,
+the rank-normalised, folded form of Vehtari, Gelman, Simpson, Carpenter, Buerkner 2021 (`rank_rhat`: what Stan, posterior
+and ArviZ report as R-hat now) with the pooled posterior median and 5 % / 95 % quantiles.
 
 Build-specific (the reference runs 100 chains and reports the within-chain ESS only).  The per-chain moments come from
 one pass over a trace that is already on the device (`arp_split_moments`) or from the in-kernel statistics of a
@@ -18,6 +20,9 @@ import torch
 # rhat, mean, sd: [D] float64 (NaN where W = 0 or fewer than two rows have a finite variance); rows = m, the number of
 # rows with a finite variance; constant_rows = how many of them never moved (variance exactly 0)
 Rhat = collections.namedtuple("Rhat", ["rhat", "mean", "sd", "rows", "constant_rows"])
+# bulk, tail: the split R-hat of the rank-normalised and of the folded, rank-normalised trace; rhat = fmax of the two;
+# median, q05, q95: order statistics of the pooled draws; rows, constant_rows as above (of the bulk trace); [D] float64
+RankRhat = collections.namedtuple("RankRhat", ["bulk", "tail", "rhat", "median", "q05", "q95", "rows", "constant_rows"])
 
 
 def split_moments(trace, split=True):
@@ -88,3 +93,69 @@ def from_stats(mean, var):
     """The sums for the UN-split R-hat of every chain of a streaming run from the per-chain (mean, var) [C, D] that
     engine.stats_summary returns (the statistics planes keep no half-way snapshot)."""
     return fold(mean, var)
+
+
+def rank_workspace_bytes(S, Cn, D, fold=False):
+    """Bytes of device workspace `rank_normalize` takes for a [S, Cn, D] trace (next to its [S, Cn, D] float32 result)."""
+    from . import _lib
+    if S <= 0 or Cn <= 0 or D <= 0:
+        return 0
+    need = int(_lib.lib().arp_rank_workspace_bytes(S, Cn, D, int(bool(fold))))
+    if need <= 0:
+        _lib.check(1)
+    return need
+
+
+def rank_normalize(trace, fold=False, probs=None, rank2=None):
+    """(z, median, quantiles) device tensors of a recorded [S, C, D] float32 trace on the GPU (`arp_rank_normalize`):
+    z [S, C, D] float32, the normal score Phi^-1((r - 3/8) / (N + 1/4)) of every draw's average rank r among the
+    N = S C pooled draws of its element -- of the draw itself, or (fold) of its float32 distance from the element's
+    median; median [D] float32 and quantiles [len(probs), D] float32 (None without probs): order statistics of the
+    pooled draws, x_(k) with k = ceil(p N).  rank2: an optional contiguous [S, C, D] int32 device tensor that receives
+    2 r - 1 as unsigned 32-bit words.  A leading or inner block of chains of a wider trace is taken in place, as
+    split_moments takes it; the workspace is owned here."""
+    from . import _lib
+    if not (trace.is_cuda and trace.dtype == torch.float32 and trace.dim() == 3):
+        raise ValueError("rank_normalize: a float32 [S, C, D] trace on the GPU is required (there is no CPU fallback)")
+    S, Cn, D = trace.shape
+    probs = None if probs is None else [float(p) for p in probs]
+    z = torch.empty(S, Cn, D, dtype=torch.float32, device=trace.device)
+    median = torch.full((D,), float("nan"), dtype=torch.float32, device=trace.device)
+    quantiles = None if probs is None else torch.full((len(probs), D), float("nan"), dtype=torch.float32, device=trace.device)
+    if rank2 is not None and not (rank2.is_cuda and rank2.dtype == torch.int32 and rank2.is_contiguous()
+                                  and tuple(rank2.shape) == (S, Cn, D)):
+        raise ValueError("rank_normalize: rank2 must be a contiguous int32 [S, C, D] tensor on the GPU")
+    if S == 0 or Cn == 0 or D == 0:
+        return z, median, quantiles
+    in_place = trace.is_contiguous() or (trace.stride(2) == 1 and trace.stride(1) == D and S > 1)
+    x = trace if in_place else trace.contiguous()
+    row_stride = x.stride(0) if S > 1 else Cn * D
+    L = _lib.lib()
+    with torch.cuda.device(x.device):
+        need = rank_workspace_bytes(S, Cn, D, fold)
+        ws = torch.empty(need, dtype=torch.uint8, device=x.device)
+        pr = (C.c_double * len(probs))(*probs) if probs else None
+        _lib.check(L.arp_rank_normalize(C.c_void_p(x.data_ptr()), S, Cn, D, row_stride, int(bool(fold)),
+                                        C.c_void_p(z.data_ptr()), C.c_void_p(rank2.data_ptr() if rank2 is not None else 0),
+                                        C.c_void_p(median.data_ptr()), pr, len(probs) if probs else 0,
+                                        C.c_void_p(quantiles.data_ptr() if probs else 0),
+                                        C.c_void_p(ws.data_ptr()), need, C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+        del ws
+    return z, median, quantiles
+
+
+def rank_rhat(trace):
+    """The rank-normalised split R-hat of every element of a [S, C, D] float32 trace on the GPU -> RankRhat: `bulk` from
+    the normal scores of the draws, `tail` from those of their distances from the median, `rhat` the larger, each through
+    split_moments -> fold -> rhat_from_sums on the z-score trace.  The ranks are taken over all S rows: for odd S the
+    middle draw is ranked but belongs to no half; for even S this is the value of Stan and posterior::rhat."""
+    S = int(trace.shape[0])
+    z, median, q = rank_normalize(trace, fold=False, probs=(0.05, 0.95))
+    bulk = rhat_from_sums(fold(*split_moments(z, True)), S // 2)
+    del z
+    z, _, _ = rank_normalize(trace, fold=True)
+    tail = rhat_from_sums(fold(*split_moments(z, True)), S // 2)
+    del z
+    q = q.cpu().numpy().astype(np.float64)
+    return RankRhat(bulk.rhat, tail.rhat, np.fmax(bulk.rhat, tail.rhat), median.cpu().numpy().astype(np.float64), q[0], q[1],
+                    bulk.rows, bulk.constant_rows)

@@ -41,6 +41,11 @@ _DEFS = [
     ("convergence_diagnostics", bool, True, "Sampling runs: split R-hat across chains and the pooled posterior mean / sd of "
                                             "every element (JSON keys, <base>_rhat.npz), computed after the mcmc clock "
                                             "has stopped; --noconvergence_diagnostics skips all of it."),
+    ("rank_normalized_rhat", bool, False, "Sampling runs, with --convergence_diagnostics: also the rank-normalised, folded "
+                                          "split R-hat (bulk, tail; Vehtari et al. 2021) and the pooled posterior median, "
+                                          "5 % and 95 % quantiles of every element over the chains split R-hat covers "
+                                          "(rank_rhat_* JSON keys, five more families in <base>_rhat.npz).  One process only: "
+                                          "a sharded job writes null."),
     ("lanes_per_chain", int, 0, "Lanes of a wave64 a chain is spread over (0 = automatic)."),
 ]
 

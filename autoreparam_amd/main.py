@@ -260,10 +260,55 @@ def _convergence_report(kernel_results, model_config, flags, dev):
     if max(np.nan_to_num(split_max), np.nan_to_num(all_max)) > RHAT_WARN:
         util.print_("    WARNING: R-hat above {}: the chains have not converged to one distribution "
                     "(the elements: <base>_rhat.npz)".format(RHAT_WARN))
+    rank_keys = {}
+    if getattr(flags, "rank_normalized_rhat", False):
+        rank_keys = _rank_report(trace, k, spec, arrays, by_part)
     keys = {"split_rhat_max": _finite_or_none(split_max), "split_rhat_chains": n_split,
-            "rhat_max_all_chains": _finite_or_none(all_max) if streaming else None,
-            "diagnostics_time_sec": time.time() - clock}
+            "rhat_max_all_chains": _finite_or_none(all_max) if streaming else None}
+    keys.update(rank_keys)
+    keys["diagnostics_time_sec"] = time.time() - clock
     return keys, arrays
+
+
+def _rank_fit_chains(trace, k):
+    """The largest of k, k/2, k/4, ... leading chains whose z-score trace and workspace fit the free device memory."""
+    import torch
+    S, _, D = (int(v) for v in trace.shape)
+    free = torch.cuda.mem_get_info(trace.device)[0]
+    while k > 0 and S * k * D * 4 + diagnostics.rank_workspace_bytes(S, k, D, True) > free:
+        k //= 2
+    return k
+
+
+def _rank_report(trace, k, spec, arrays, by_part):
+    """--rank_normalized_rhat: the rank-normalised, folded split R-hat over the leading k chains of the device trace (fewer
+    where z and the workspace do not fit: the count is reported) and the pooled median / 5 % / 95 % quantiles, into
+    `arrays`; returns the five rank_rhat_* JSON keys.  The pooled ranks need every draw on one device: a sharded job
+    (world size > 1) writes null, says so once, and enters no collective."""
+    keys = {"rank_rhat_max": None, "rank_rhat_bulk_max": None, "rank_rhat_tail_max": None, "rank_rhat_chains": 0,
+            "rank_rhat_time_sec": None}
+    if parallel.world()[1] > 1:
+        util.print_("    rank-normalised R-hat: skipped, the chains of a sharded job are on several devices "
+                    "(the pooled ranks need all draws on one)")
+        return keys
+    clock = time.time()
+    k = _rank_fit_chains(trace, k) if k > 0 else 0
+    if k <= 0:
+        util.print_("    rank-normalised R-hat: no chains to rank")
+        return keys
+    r = diagnostics.rank_rhat(trace[:, :k])
+    by_part(arrays, (("rank_rhat_bulk", r.bulk), ("rank_rhat_tail", r.tail), ("posterior_median", r.median),
+                     ("posterior_q05", r.q05), ("posterior_q95", r.q95)))
+    top, at = _nan_max(r.rhat)
+    bulk_max, tail_max = _nan_max(r.bulk)[0], _nan_max(r.tail)[0]
+    util.print_("    rank-normalised split R-hat over {} chains: max {:.4f} (element {}; bulk {:.4f}, tail {:.4f})".format(
+        k, top, at, bulk_max, tail_max))
+    if np.nan_to_num(top) > RHAT_WARN:
+        util.print_("    WARNING: rank-normalised R-hat above {}: the chains have not converged to one distribution "
+                    "(the elements: <base>_rhat.npz)".format(RHAT_WARN))
+    keys.update(rank_rhat_max=_finite_or_none(top), rank_rhat_bulk_max=_finite_or_none(bulk_max),
+                rank_rhat_tail_max=_finite_or_none(tail_max), rank_rhat_chains=k, rank_rhat_time_sec=time.time() - clock)
+    return keys
 
 
 def save_rhat(file_path_base, arrays):

@@ -288,6 +288,29 @@ int arp_split_moments(const float* trace, int64_t n_samples, int64_t n_series, i
  * The five vectors are additive over chains, hence over ranks.  n_rows = 0 gives zeros. */
 int arp_moments_fold(const float* mean, const float* var, int64_t n_rows, int32_t D, double* sums, void* stream);
 
+/* Rank normalisation (build-specific; what the rank-normalised, folded split R-hat of Vehtari et al. 2021 needs: the
+ * result is a z-score trace that arp_split_moments / arp_moments_fold take unchanged) and order statistics of the pooled
+ * draws.  Trace addressing as arp_split_moments with n_series = n_chains * D: draw s of chain c, element d is
+ * trace[s * row_stride + c * D + d], row_stride >= n_chains * D.  The pool of element d is its N = n_samples * n_chains
+ * values x_(1) <= ... <= x_(N); N < 2^31.
+ *   median[d]       0.5f * (x_(floor((N+1)/2)) + x_(ceil((N+1)/2))), formed in float32                     [D], may be NULL
+ *   quantiles[q][d] x_(k), k = clamp(ceil(probs[q] * N), 1, N) in float64 (the inverted-CDF definition: an order
+ *                   statistic, no interpolation); probs is a HOST array of n_probs values       [n_probs][D], may be NULL
+ *   values ranked   v = x (fold = 0) or v = fabsf(x - median[d]) in float32 (fold = 1)
+ *   rank2           #{v' < v} + #{v' <= v} over the pool = 2 * (average 1-based rank) - 1; ties share it, -0 ties with
+ *                   +0, subnormals are distinct, +-inf order as numbers                     uint32 [S][C][D], may be NULL
+ *   z               Phi^-1((4 rank2 + 1) / (8 N + 2)) = Phi^-1((r - 3/8) / (N + 1/4)), formed from the integers in
+ *                   float64 and from the nearer tail, rounded to float32                         [S][C][D], required
+ * Every output is a function of the sorted pool alone: bitwise reproducible whatever the grid.  A NaN neither faults nor
+ * hangs; the results of an element that holds one are unspecified.  The workspace (arp_rank_workspace_bytes: two key
+ * buffers of the trace's size and the radix sort's counts; the same for both values of fold) is required and 256-byte
+ * aligned; returns 1 (arp_last_error) on a missing argument, a workspace too small or misaligned, or N >= 2^31. */
+int64_t arp_rank_workspace_bytes(int64_t n_samples, int64_t n_chains, int32_t D, int fold);
+int arp_rank_normalize(const float* trace, int64_t n_samples, int64_t n_chains, int32_t D, int64_t row_stride,
+                       int fold, float* z, uint32_t* rank2, float* median,
+                       const double* probs, int32_t n_probs, float* quantiles,
+                       void* workspace, int64_t workspace_bytes, void* stream);
+
 /* Test hook: the step-size adaptation recurrence of the chain kernels on SCRIPTED log acceptance ratios
  * (tfp.mcmc.DualAveragingStepSizeAdaptation / SimpleStepSizeAdaptation as wired at inference.py:224-226, 288-306;
  * SURVEY.md 8c known answer (7)).  For each of `n` independent rows, applies the update after transitions
