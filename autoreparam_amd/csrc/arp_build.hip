@@ -160,7 +160,7 @@ static int build_german(arp_model* m, const arp_dataset* d) {
   }
   m->D = 1 + 2 * F; m->n_groups = F;
   // [N][64] rows + outcomes (the 8- and 16-lane likelihoods), then the image the matrix-core likelihood copies
-  // into LDS with LDS-DMA (model_german.h, "tile image"): per 128 observations the rows with their 16-byte chunks
+  // into LDS with LDS-DMA (german_image.h, "tile image"): per 128 observations the rows with their 16-byte chunks
   // XOR-permuted, and one piece of outcomes
   const size_t plain = ((size_t)N * kGermanCols + N + 255) & ~(size_t)255;
   const int nt = (N + kGermanTileRows - 1) / kGermanTileRows;
@@ -173,12 +173,11 @@ static int build_german(arp_model* m, const arp_dataset* d) {
     for (int r = 0; r < kGermanTileRows; ++r) {
       const int n = t * kGermanTileRows + r;
       if (n >= N) break;
-      float* rowp = img + r * kGermanCols;   // chunk c of row r at chunk position c ^ (r & 11)
-      for (int f = 0; f < F; ++f) rowp[((((f >> 2) ^ (r & 11)) & 15) << 2) + (f & 3)] = d->X_host[(size_t)n * F + f];
-      img[32 * 256 + r] = d->y_host[n];
+      for (int f = 0; f < F; ++f) img[german_x_word(r, f)] = d->X_host[(size_t)n * F + f];
+      img[german_y_word(r)] = d->y_host[n];
     }
   }
-  // the bf16 x 3 image (model_german.h): usable when at most 8 columns are not exact in ONE bf16 piece
+  // the bf16 x 3 image (german_image.h): usable when at most 8 columns are not exact in ONE bf16 piece
   const size_t f32_floats = m->host_tables.size();
   std::vector<int> split;
   for (int f = 0; f < F; ++f) {
@@ -203,26 +202,21 @@ static int build_german(arp_model* m, const arp_dataset* d) {
       for (int r = 0; r < kBf3Rows; ++r) {
         const int n = t * kBf3Rows + r;
         if (n >= N) break;
-        // where observation r sits in a backward fragment: k-step s, lane group g, element jj
-        const int s_ = r >> 5, rr = r & 31;
-        const int g = rr < 16 ? rr >> 2 : (rr - 16) >> 2, jj = rr < 16 ? rr & 3 : 4 + ((rr - 16) & 3);
+        const Bf3Frag frag = bf3_frag(r);   // where observation r sits in a backward fragment
         for (int f = 0; f < F; ++f) {
           uint32_t h, mm_, l;
           bf3_split(d->X_host[(size_t)n * F + f], h, mm_, l);
-          put(img, kBf3XhF + (size_t)r * 128 + ((((size_t)f >> 3) ^ (((size_t)r >> 1) & 7)) << 4) + (f & 7) * 2, h);
-          put(img, kBf3XhB + (size_t)s_ * 4096 + (size_t)f * 64 + (((size_t)g ^ (((size_t)f >> 2) & 3)) << 4) + jj * 2, h);
+          put(img, bf3_xhf_byte(r, f), h);
+          put(img, bf3_xhb_byte(frag, f), h);
         }
         for (int q = 0; q < (int)split.size(); ++q) {
           uint32_t h, mm_, l;
           bf3_split(d->X_host[(size_t)n * F + split[q]], h, mm_, l);
-          const size_t rowb = kBf3XaF + (size_t)r * 64, sw = ((size_t)r >> 2) & 3;
-          put(img, rowb + ((0 ^ sw) << 4) + q * 2, mm_);       // [xm | xm | xl | 0]
-          put(img, rowb + ((1 ^ sw) << 4) + q * 2, mm_);
-          put(img, rowb + ((2 ^ sw) << 4) + q * 2, l);
-          for (int part = 0; part < 2; ++part) {                // output rows q (xm) and 8 + q (xl)
-            const size_t o = (size_t)part * 8 + q;
-            put(img, kBf3XaB + (size_t)s_ * 1024 + o * 64 + (((size_t)g ^ ((o >> 2) & 3)) << 4) + jj * 2, part ? l : mm_);
-          }
+          put(img, bf3_xaf_byte(r, 0, q), mm_);       // [xm | xm | xl | 0]
+          put(img, bf3_xaf_byte(r, 1, q), mm_);
+          put(img, bf3_xaf_byte(r, 2, q), l);
+          put(img, bf3_xab_byte(frag, q), mm_);       // output rows q (xm) and 8 + q (xl)
+          put(img, bf3_xab_byte(frag, 8 + q), l);
         }
         reinterpret_cast<float*>(img + kBf3Y)[r] = d->y_host[n];
       }

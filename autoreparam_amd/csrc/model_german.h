@@ -26,59 +26,16 @@
 //   d/dbt_d  = v_d exp((1-b_d) s_d) - zb_d e_d,   d/dbls_d = h_d + 0.5 - 0.5 exp(bls_d),   d/dols = sum h_d
 #pragma once
 #include "arp_device.h"
+#include "german_image.h"
 
 namespace arp {
 
-constexpr int kGermanCols = 64;   // padded row length of the device design matrix
-// Tile image of the matrix-core likelihood (built by arp_api.hip: build_german): the design matrix in tiles of 128
-// observations, each stored as the exact byte image of its LDS copy so that LDS-DMA (global_load_lds_dwordx4: 64 lanes
-// x 16 contiguous bytes per instruction, no registers, no VALU) moves it.  A tile is 32 pieces of 1 KiB = 4 rows of 64
-// floats; the 16-byte chunk c of row r is stored at chunk position c ^ (r & 11), followed by one piece with the 128
-// outcomes.  With that XOR both operand reads of the matrix-core products are bank-conflict free as ds_read_b128
-// (forward: 16 rows x one chunk of a 64-byte feature block; backward: 4 rows x 16 consecutive chunks per lane group),
-// checked lane by lane against the gfx950 bank rules (4 groups of 16 lanes, bank = dword address mod 64).
-constexpr int kGermanTileRows = 128;
 #ifndef ARP_GERMAN_VI_BLOCK
 #define ARP_GERMAN_VI_BLOCK 256
 #endif
 constexpr int kGermanViBlock = ARP_GERMAN_VI_BLOCK;   // threads of a VI workgroup (kernels.h: vi_kernel), 16 draws per wave: four waves,
 //   one per SIMD, and with 256 draws 4 sample groups x 8 row parts (one resident 128-row tile each) per learning rate:
 //   68 ms per fit against 80 ms with two-wave workgroups of two tiles (profiles/r05_vi_kernel.txt)
-constexpr int kGermanImgTile = 33 * 256;   // floats per tile of the image
-
-// Tile image of the bf16 x 3 likelihood (round 5; built by arp_api.hip: build_german_bf3).  Every f32 value is the exact
-// sum of three bf16 pieces x = h + m + l (8 + 8 + 8 significant bits, by truncation), and a product of two such values is
-// the sum of nine bf16 products, of which the six leading ones carry it to 2^-23: matrix-core work at 16 x the f32 rate.
-// The data make it cheaper still: a column of zeros and ones (54 one-hot columns and the intercept of German credit) IS
-// its h piece, so only the few SPLIT columns (the standardised numerics: at most 8) have m and l pieces at all, and all
-// their cross terms fit ONE extra K = 32 step per product:
-//   forward   eta = Xh (bh + bm + bl)  +  [Xm | Xm | Xl | 0] [bh ; bm ; bh ; 0]          (split columns only)
-//   backward  v   = Xh' (wh + wm + wl) +  [Xm ; Xl]' wh + [Xm ; Xl]' wm                   (16 extra output rows)
-// i.e. 7 v_mfma_f32_16x16x32_bf16 per 16 observations forward and 14 per 32 backward (224 cycles per 32 observations
-// against 2 048 on v_mfma_f32_16x16x4_f32), operands read from LDS with 11 ds_read_b128 per 32 observations and wave.
-// A tile holds 64 observations in 23 pieces of 1 KiB (the exact byte image of its LDS copy, moved by LDS-DMA):
-//   XhF [64 rows][64 features] bf16, 16-byte chunk c of row r at chunk c ^ ((r >> 1) & 7)           8 KiB  forward A operand
-//   XaF [64 rows][xm(8) | xm(8) | xl(8) | 0(8)] bf16, chunk g of row r at g ^ ((r >> 2) & 3)        4 KiB
-//   XhB [2 k-steps][64 features][4 lane groups g][8] bf16: element j of group g is observation
-//       32 s + (j < 4 ? 4 g + j : 16 + 4 g + j - 4) -- the order in which two forward blocks leave their residuals in a
-//       lane's registers --, chunk g of feature f at g ^ ((f >> 2) & 3)                             8 KiB  backward A operand
-//   XaB [2 k-steps][16 rows: xm of split column o, xl of split column o - 8][4][8] bf16, same order  2 KiB
-//   y   [64] f32                                                                                   256 B
-// (both operand reads are conflict free: 16 lanes x 16 bytes cover the 64 banks once).
-constexpr int kBf3Rows = 64;
-constexpr int kBf3Pieces = 23;
-constexpr int kBf3ImgTile = kBf3Pieces * 256;   // floats per tile of the image
-constexpr int kBf3XhF = 0, kBf3XaF = 8192, kBf3XhB = 12288, kBf3XaB = 20480, kBf3Y = 22528;   // byte offsets in a tile
-constexpr int kBf3MaxSplit = 8;
-
-// x = h + m + l exactly, each piece a bf16 (as the f32 bit pattern with a zero low half): truncation twice, the third
-// piece is what is left (at most 8 significant bits).  The same on host (the images) and device (beta, the residuals).
-__host__ __device__ inline void bf3_split(float x, uint32_t& h, uint32_t& m, uint32_t& l) {
-  union { float f; uint32_t u; } a, b_, c_;
-  a.f = x; h = a.u & 0xffff0000u;
-  b_.u = h; b_.f = x - b_.f; m = b_.u & 0xffff0000u;
-  c_.u = m; c_.f = b_.f - c_.f; l = c_.u;
-}
 
 enum GermanPrior { kGermanLogNormal = 0, kGermanGamma = 1 };   // prior of the feature scales (see the top of the file)
 
@@ -97,7 +54,7 @@ struct GermanArgs {
 // workgroups of a learning rate: a lane evaluates the tiles [tlo, thi) only and the prior terms of the log density and of
 // the gradient with weight `pw` (1 in the workgroup that owns row part 0, 0 elsewhere), so that the SUM over the row
 // parts of everything grad() and dparam() return is the whole model's -- they are affine in the likelihood's v.
-// BF3_: the likelihood on bf16 matrix cores with three-piece operands (above) instead of f32 matrix cores; K = 4 only.
+// BF3_: the likelihood on bf16 matrix cores with three-piece operands (german_image.h) instead of f32 matrix cores; K = 4 only.
 // PRIOR_: the prior of the scales, log-normal centred (german_credit_lognormalcentered) or Gamma
 // (german_credit_gammascale); the likelihood routines are shared.
 template <int K_, int NLS_, int W_ = kBlock / 64, bool PART_ = false, bool BF3_ = false, int PRIOR_ = kGermanLogNormal>
@@ -189,7 +146,7 @@ struct GermanLane {
   // K = 4 (matrix cores): [X buffer 0][outcomes 0][outcomes 1][X buffer 1] of the tile image, then a per-wave exchange area.
   static constexpr int kStride = kGermanCols;
   static constexpr int kRows = K_ == 4 ? kGermanTileRows : 64;
-  static constexpr int kBlkB = 16 * kGermanCols * 4;   // bytes of a 16-row block
+  static constexpr int kBlkB = kGermanBlkB;   // bytes of a 16-row block
   static constexpr int kXBufB = kGermanTileRows * kGermanCols * 4;
   static constexpr int kYBufB = 1024;
   static constexpr int kBufStep = kXBufB + 2 * kYBufB;   // X buffer 0 -> X buffer 1
@@ -296,14 +253,10 @@ struct GermanLane {
   template <int NEWER>
   static ARP_DEV void wait_rows(Rows4& R) {
     static_assert(NEWER == 0 || NEWER == 9, "one block = 9 LDS reads");
-    if (NEWER == 9)
-      asm volatile("s_waitcnt lgkmcnt(9)"
-                   : "+v"(R.a[0][0]), "+v"(R.a[0][1]), "+v"(R.a[1][0]), "+v"(R.a[1][1]), "+v"(R.b[0][0]),
-                     "+v"(R.b[0][1]), "+v"(R.b[1][0]), "+v"(R.b[1][1]), "+v"(R.y));
-    else
-      asm volatile("s_waitcnt lgkmcnt(0)"
-                   : "+v"(R.a[0][0]), "+v"(R.a[0][1]), "+v"(R.a[1][0]), "+v"(R.a[1][1]), "+v"(R.b[0][0]),
-                     "+v"(R.b[0][1]), "+v"(R.b[1][0]), "+v"(R.b[1][1]), "+v"(R.y));
+    asm volatile("s_waitcnt lgkmcnt(%9)"
+                 : "+v"(R.a[0][0]), "+v"(R.a[0][1]), "+v"(R.a[1][0]), "+v"(R.a[1][1]), "+v"(R.b[0][0]),
+                   "+v"(R.b[0][1]), "+v"(R.b[1][0]), "+v"(R.b[1][1]), "+v"(R.y)
+                 : "n"(NEWER));
   }
   template <bool LOGP>
   ARP_DEV void use_rows(const Rows4& R, const v2f (&b2)[4], v2f (&v2)[4], float& lp, int ra, int rows) const {
@@ -389,7 +342,7 @@ struct GermanLane {
   // register r, which is exactly the B operand of the backward product if its step s takes
   // row 4g+s from lane group g: no movement between the two products.
   //
-  // Tiles of 128 observations travel global memory -> LDS by LDS-DMA (see "tile image" above) into two buffers: while
+  // Tiles of 128 observations travel global memory -> LDS by LDS-DMA (german_image.h, "tile image") into two buffers: while
   // tile n is multiplied, tile n+1 lands.  One workgroup barrier per tile, taken in front of the tile's LAST backward
   // block: by then all of the wave's LDS reads of tile n are complete (the operands of that block are in registers),
   // so the same barrier publishes tile n+1 (every wave has waited for its own pieces) and frees tile n's buffer for
@@ -424,31 +377,24 @@ struct GermanLane {
   // LDS reads of the matrix-core path, pinned with inline asm a block ahead of their use (see the
   // note at Rows4: left to the scheduler they sink to the first use and the single wave per SIMD
   // waits out every LDS round trip with the matrix pipe idle).
-  // A operand of the forward product for block BLK (rows 16 BLK ..): lane (g, j) takes row j, columns 16g .. 16g+15
-  // (feature block g), chunk i from a_off[i] (the chunk XOR differs from lane to lane).
+  // The four reads of an operand for block BLK (rows 16 BLK ..).  A operand of the forward product: lane (g, j) takes
+  // row j, columns 16g .. 16g+15 (feature block g), chunk i from a_off[i] (the chunk XOR differs from lane to lane).
+  // A operand of the backward product: lane (g, j) takes rows 4g+s (s < 4) from b_off[s], columns 4j .. 4j+3:
+  // accumulator k of the product gets feature 4j+k on output row j, so a lane (g', chain) ends up with features
+  // 16g' + 4r + k in acc[k][r].
   template <int BLK>
-  static ARP_DEV void issue_a(const uint32_t (&a_off)[4], v4f (&xa)[4]) {
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(xa[0]) : "v"(a_off[0]), "n"(BLK * kBlkB));
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(xa[1]) : "v"(a_off[1]), "n"(BLK * kBlkB));
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(xa[2]) : "v"(a_off[2]), "n"(BLK * kBlkB));
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(xa[3]) : "v"(a_off[3]), "n"(BLK * kBlkB));
+  static ARP_DEV void issue_x(const uint32_t (&off)[4], v4f (&x)[4]) {
+    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(x[0]) : "v"(off[0]), "n"(BLK * kBlkB));
+    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(x[1]) : "v"(off[1]), "n"(BLK * kBlkB));
+    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(x[2]) : "v"(off[2]), "n"(BLK * kBlkB));
+    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(x[3]) : "v"(off[3]), "n"(BLK * kBlkB));
   }
   template <int BLK>
   static ARP_DEV void issue_y(uint32_t y_off, v4f& y4) {
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(y4) : "v"(y_off), "n"(BLK * 64));
+    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(y4) : "v"(y_off), "n"(BLK * kGermanYBlkB));
   }
-  // A operand of the backward product for block BLK: lane (g, j) takes rows 4g+s (s < 4) from b_off[s], columns
-  // 4j .. 4j+3: accumulator k of the product gets feature 4j+k on output row j, so a lane (g', chain) ends up with
-  // features 16g' + 4r + k in acc[k][r].
-  template <int BLK>
-  static ARP_DEV void issue_b(const uint32_t (&b_off)[4], v4f (&xb)[4]) {
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(xb[0]) : "v"(b_off[0]), "n"(BLK * kBlkB));
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(xb[1]) : "v"(b_off[1]), "n"(BLK * kBlkB));
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(xb[2]) : "v"(b_off[2]), "n"(BLK * kBlkB));
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(xb[3]) : "v"(b_off[3]), "n"(BLK * kBlkB));
-  }
-  template <int IMM>
-  static ARP_DEV void rd128(v4f& dst, uint32_t addr) { asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(IMM)); }
+  template <int IMM, class V>
+  static ARP_DEV void rd128(V& dst, uint32_t addr) { asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(IMM)); }
   // every LDS read older than the NEWER youngest has landed (LDS reads return in order); the operands are tied to the
   // statement so that no use of them moves above it
   template <int NEWER>
@@ -574,11 +520,11 @@ struct GermanLane {
   // the first reads of a tile: A(0), Y(0), A(1), Y(1), B(0)
   static ARP_DEV void first_reads(const uint32_t (&a_off)[4], const uint32_t (&b_off)[4], uint32_t y_off,
                                   v4f (&xa)[2][4], v4f (&xb)[2][4], v4f (&y4)[2]) {
-    issue_a<0>(a_off, xa[0]);
+    issue_x<0>(a_off, xa[0]);
     issue_y<0>(y_off, y4[0]);
-    issue_a<1>(a_off, xa[1]);
+    issue_x<1>(a_off, xa[1]);
     issue_y<1>(y_off, y4[1]);
-    issue_b<0>(b_off, xb[0]);
+    issue_x<0>(b_off, xb[0]);
     __builtin_amdgcn_sched_barrier(0);
   }
   // forward block 0 on its own (two chains: nothing to interleave with), then as the end of a phase
@@ -661,20 +607,18 @@ struct GermanLane {
       bB[4 * i] = f.x; bB[4 * i + 1] = f.y; bB[4 * i + 2] = f.z; bB[4 * i + 3] = f.w;
     }
     __builtin_amdgcn_wave_barrier();
-    // operand addresses in the current buffer (see "tile image"): chunk c of row r sits at chunk c ^ (r & 11)
+    // operand addresses in the current buffer (german_image.h)
     uint32_t a_off[4], b_off[4], y_off;
     {
       const uint32_t xb0 = tile_off + (uint32_t)buf * kBufStep;
       const uint32_t uj = (uint32_t)j, ug = (uint32_t)gk;
-      // forward: row j, chunks 4g + i
-      const uint32_t abase = xb0 + uj * 256u + (((ug << 2) ^ (uj & 8u)) << 4);
+      const uint32_t abase = xb0 + german_fwd_base(ug, uj), bbase = xb0 + german_bwd_base(ug);
 #pragma unroll
-      for (int i = 0; i < 4; ++i) a_off[i] = abase + ((((uint32_t)i) ^ (uj & 3u)) << 4);
-      // backward: rows 4g + s, chunk j;  (4g + s) & 11 = s | (g & 2) << 2
-      const uint32_t bbase = xb0 + ug * 1024u;
+      for (int i = 0; i < 4; ++i) a_off[i] = abase + german_fwd_chunk(uj, (uint32_t)i);
+      // german_bwd_row(ug, uj, s_), written in place: through the call the compiler arranges the sum differently
 #pragma unroll
       for (int s_ = 0; s_ < 4; ++s_) b_off[s_] = bbase + (uint32_t)s_ * 256u + ((uj ^ (uint32_t)s_ ^ ((ug & 2u) << 2)) << 4);
-      y_off = tile_off + kYBase + (uint32_t)buf * kYBufB + ug * 16u;
+      y_off = tile_off + kYBase + (uint32_t)buf * kYBufB + german_y_off(ug);
     }
     v4f acc[4];
 #pragma unroll
@@ -720,16 +664,16 @@ struct GermanLane {
         for (int i = 0; i < 4; ++i) a_off[i] += dx;
         y_off += dy;
         __builtin_amdgcn_sched_barrier(0);
-        issue_a<0>(a_off, xa[0]);
+        issue_x<0>(a_off, xa[0]);
         issue_y<0>(y_off, y4[0]);
         __builtin_amdgcn_sched_barrier(0);
         tail_quarter(xb[lb][2], w[2], acc);
 #pragma unroll
         for (int i = 0; i < 4; ++i) b_off[i] += dx;
         __builtin_amdgcn_sched_barrier(0);
-        issue_a<1>(a_off, xa[1]);
+        issue_x<1>(a_off, xa[1]);
         issue_y<1>(y_off, y4[1]);
-        issue_b<0>(b_off, xb[0]);
+        issue_x<0>(b_off, xb[0]);
         __builtin_amdgcn_sched_barrier(0);
         tail_quarter(xb[lb][3], w[3], acc);
       } else {
@@ -756,7 +700,7 @@ struct GermanLane {
     return lp;
   }
 
-  // ---- the bf16 x 3 likelihood (see the tile image at the top of the file) ----
+  // ---- the bf16 x 3 likelihood (see the tile image in german_image.h) ----
   typedef __bf16 bf8 __attribute__((ext_vector_type(8)));
   typedef uint32_t u4v __attribute__((ext_vector_type(4)));
   // this wave's share of tile n of the bf16 image into buffer `buf`: a contiguous run of ceil(23 / W) pieces, four per
@@ -859,14 +803,14 @@ struct GermanLane {
     for (int k = 0; k < 4; ++k) acc[k] = v4f{0.0f, 0.0f, 0.0f, 0.0f};
     accA = v4f{0.0f, 0.0f, 0.0f, 0.0f};
     v2f lp2[2] = {v2f{0.0f, 0.0f}, v2f{0.0f, 0.0f}};
-    // operand addresses relative to the buffer: row / feature / output row j, chunk g (XOR-permuted per row)
+    // operand addresses relative to the buffer (german_image.h)
     const uint32_t uj = (uint32_t)j, ug = (uint32_t)g;
-    const uint32_t a_h0 = kBf3XhF + uj * 128u + (((ug) ^ ((uj >> 1) & 7u)) << 4);          // kh = 0: chunk g
-    const uint32_t a_h1 = kBf3XhF + uj * 128u + (((4u + ug) ^ ((uj >> 1) & 7u)) << 4);     // kh = 1: chunk 4 + g
+    const uint32_t a_h0 = bf3_a_h(ug, uj, 0), a_h1 = bf3_a_h(ug, uj, 1);
+    // bf3_a_a, bf3_b_h, bf3_b_a (ug, uj), written in place: through the calls the compiler orders the XOR differently
     const uint32_t a_a = kBf3XaF + uj * 64u + ((ug ^ ((uj >> 2) & 3u)) << 4);
-    const uint32_t b_h = kBf3XhB + uj * 64u + ((ug ^ ((uj >> 2) & 3u)) << 4);              // + fb * 1024 + s * 4096
-    const uint32_t b_a = kBf3XaB + uj * 64u + ((ug ^ ((uj >> 2) & 3u)) << 4);              // + s * 1024
-    const uint32_t y_o = kBf3Y + ug * 16u;                                                 // + block * 64
+    const uint32_t b_h = kBf3XhB + uj * 64u + ((ug ^ ((uj >> 2) & 3u)) << 4);
+    const uint32_t b_a = kBf3XaB + uj * 64u + ((ug ^ ((uj >> 2) & 3u)) << 4);
+    const uint32_t y_o = bf3_y_o(ug);
 
     // The pipeline over the 64-observation tiles.  Per tile: the 16 forward reads (three fragments and the outcomes of
     // each of the four 16-observation blocks) were issued while the previous tile's last matrix-core instructions ran;
@@ -878,25 +822,27 @@ struct GermanLane {
     u4v F[4][3], Y[4], Bk[2][5];
     // operand reads: one address register per operand kind (buffer base + the lane's part), the block / k-step / feature
     // block as the instruction's immediate offset
-    auto rd = [](u4v& dst, uint32_t addr, auto off_tag) {
-      asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(decltype(off_tag)::value));
-    };
-#define ARP_OFF(x) std::integral_constant<int, (x)>{}
     auto fwd_reads = [&](uint32_t base) {
       const uint32_t p0 = base + a_h0, p1 = base + a_h1, pa = base + a_a, py = base + y_o;
-      rd(F[0][0], p0, ARP_OFF(0)); rd(F[0][1], p1, ARP_OFF(0)); rd(F[0][2], pa, ARP_OFF(0)); rd(Y[0], py, ARP_OFF(0));
-      rd(F[1][0], p0, ARP_OFF(2048)); rd(F[1][1], p1, ARP_OFF(2048)); rd(F[1][2], pa, ARP_OFF(1024)); rd(Y[1], py, ARP_OFF(64));
-      rd(F[2][0], p0, ARP_OFF(4096)); rd(F[2][1], p1, ARP_OFF(4096)); rd(F[2][2], pa, ARP_OFF(2048)); rd(Y[2], py, ARP_OFF(128));
-      rd(F[3][0], p0, ARP_OFF(6144)); rd(F[3][1], p1, ARP_OFF(6144)); rd(F[3][2], pa, ARP_OFF(3072)); rd(Y[3], py, ARP_OFF(192));
+      rd128<0>(F[0][0], p0); rd128<0>(F[0][1], p1); rd128<0>(F[0][2], pa); rd128<0>(Y[0], py);
+      rd128<kBf3BlkH>(F[1][0], p0); rd128<kBf3BlkH>(F[1][1], p1); rd128<kBf3BlkA>(F[1][2], pa); rd128<kBf3BlkY>(Y[1], py);
+      rd128<2 * kBf3BlkH>(F[2][0], p0); rd128<2 * kBf3BlkH>(F[2][1], p1); rd128<2 * kBf3BlkA>(F[2][2], pa); rd128<2 * kBf3BlkY>(Y[2], py);
+      rd128<3 * kBf3BlkH>(F[3][0], p0); rd128<3 * kBf3BlkH>(F[3][1], p1); rd128<3 * kBf3BlkA>(F[3][2], pa); rd128<3 * kBf3BlkY>(Y[3], py);
     };
-    auto bwd_reads = [&](uint32_t base) {
+    // the ten backward operand reads of a tile, one per slot: per k-step the four feature blocks of XhB, then XaB
+    auto bwd_read_slot = [&](int k, uint32_t base) {
       const uint32_t ph = base + b_h, pa = base + b_a;
-      rd(Bk[0][0], ph, ARP_OFF(0)); rd(Bk[0][1], ph, ARP_OFF(1024)); rd(Bk[0][2], ph, ARP_OFF(2048)); rd(Bk[0][3], ph, ARP_OFF(3072));
-      rd(Bk[0][4], pa, ARP_OFF(0));
-      rd(Bk[1][0], ph, ARP_OFF(4096)); rd(Bk[1][1], ph, ARP_OFF(5120)); rd(Bk[1][2], ph, ARP_OFF(6144)); rd(Bk[1][3], ph, ARP_OFF(7168));
-      rd(Bk[1][4], pa, ARP_OFF(1024));
+      if (k == 0) rd128<0>(Bk[0][0], ph);
+      if (k == 1) rd128<kBf3FbH>(Bk[0][1], ph);
+      if (k == 2) rd128<2 * kBf3FbH>(Bk[0][2], ph);
+      if (k == 3) rd128<3 * kBf3FbH>(Bk[0][3], ph);
+      if (k == 4) rd128<0>(Bk[0][4], pa);
+      if (k == 5) rd128<kBf3StepH>(Bk[1][0], ph);
+      if (k == 6) rd128<kBf3StepH + kBf3FbH>(Bk[1][1], ph);
+      if (k == 7) rd128<kBf3StepH + 2 * kBf3FbH>(Bk[1][2], ph);
+      if (k == 8) rd128<kBf3StepH + 3 * kBf3FbH>(Bk[1][3], ph);
+      if (k == 9) rd128<kBf3StepA>(Bk[1][4], pa);
     };
-#undef ARP_OFF
     // product i (0 .. 6) of forward block b: X_h's two halves against beta's three pieces, then the split columns' step
     auto fmm = [&](int b, int i, v4f e) {
       return i < 6 ? mm(F[b][i & 1], Bb[i & 1][i >> 1], e) : mm(F[b][2], Bba, e);
@@ -922,23 +868,6 @@ struct GermanLane {
         wo[0] = w01[0]; wo[1] = w01[1]; wo[2] = w23[0]; wo[3] = w23[1];
       }
     };
-#define ARP_OFF(x) std::integral_constant<int, (x)>{}
-    // the backward operand reads of the current tile, one per slot (issued beside the forward products)
-    auto bwd_read_slot = [&](int k, uint32_t base) {
-      const uint32_t ph = base + b_h, pa = base + b_a;
-      if (k == 0) rd(Bk[0][0], ph, ARP_OFF(0));
-      if (k == 1) rd(Bk[0][1], ph, ARP_OFF(1024));
-      if (k == 2) rd(Bk[0][2], ph, ARP_OFF(2048));
-      if (k == 3) rd(Bk[0][3], ph, ARP_OFF(3072));
-      if (k == 4) rd(Bk[0][4], pa, ARP_OFF(0));
-      if (k == 5) rd(Bk[1][0], ph, ARP_OFF(4096));
-      if (k == 6) rd(Bk[1][1], ph, ARP_OFF(5120));
-      if (k == 7) rd(Bk[1][2], ph, ARP_OFF(6144));
-      if (k == 8) rd(Bk[1][3], ph, ARP_OFF(7168));
-      if (k == 9) rd(Bk[1][4], pa, ARP_OFF(1024));
-    };
-#undef ARP_OFF
-
     // tile 0 has landed everywhere; tile 1 into the other buffer
     if (!res) {
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -969,7 +898,8 @@ struct GermanLane {
       float w[4][4];
       if constexpr (LOGP) {
         // the closing pass of a trajectory (one gradient in L): the log density's extra vector work is left to the scheduler
-        bwd_reads(base);
+#pragma unroll
+        for (int k = 0; k < 10; ++k) bwd_read_slot(k, base);
         auto forward = [&](auto mask_tag) {
           constexpr bool MASK = decltype(mask_tag)::value;
 #pragma unroll
@@ -1102,42 +1032,24 @@ struct GermanLane {
     else if constexpr (K == 4) lp = likelihood_mfma<LOGP>(beta, v);
     else lp = likelihood_generic<LOGP>(beta, v);
     ARP_T(7, tg);
+    // the prior terms carry the weight pw (row-part form; 1 otherwise)
+    const float w_ = pw();
     float lq = 0.0f, g_ols = 0.0f;
-    if constexpr (PART_) {
-      // row-part form: the prior terms carry the weight pw (the model's own formulas below with pw = 1)
-      const float w_ = pw();
-#pragma unroll
-      for (int i = 0; i < NLS; ++i) {
-        float e = fast_exp(-b[i] * bls[i]);
-        float zb = q[NG + NLS + i] * e;
-        float hb = fmaf(w_ * b[i], fmaf(zb, zb, -1.0f), v[i] * (1.0f - b[i]) * beta[i]);
-        bool ok = i < nown;
-        g[NG + NLS + i] = ok ? fmaf(v[i], fast_exp((1.0f - b[i]) * bls[i]), -w_ * zb * e) : 0.0f;
-        g[NG + i] = ok ? fmaf(-w_, r[i], hb) : 0.0f;
-        g_ols += ok ? fmaf(w_ * a[i], r[i], (1.0f - a[i]) * hb) : 0.0f;
-        if (LOGP) lq += ok ? fmaf(-0.5f * r[i], r[i], fmaf(-0.5f * zb, zb, -b[i] * bls[i])) : 0.0f;
-      }
-      g_ols = group_sum<K>(g_ols);
-      const float u0 = q[0] * s0i;
-      g[0] = fmaf(c0, g_ols, -w_ * u0 * s0i);
-      if (LOGP) lp += w_ * (group_sum<K>(lq) - 0.5f * u0 * u0);
-      return lp;
-    }
 #pragma unroll
     for (int i = 0; i < NLS; ++i) {
       float e = fast_exp(-b[i] * bls[i]);
       float zb = q[NG + NLS + i] * e;
-      float hb = fmaf(b[i], fmaf(zb, zb, -1.0f), v[i] * (1.0f - b[i]) * beta[i]);
+      float hb = fmaf(w_ * b[i], fmaf(zb, zb, -1.0f), v[i] * (1.0f - b[i]) * beta[i]);
       bool ok = i < nown;
-      g[NG + NLS + i] = ok ? fmaf(v[i], fast_exp((1.0f - b[i]) * bls[i]), -zb * e) : 0.0f;
-      g[NG + i] = ok ? hb - r[i] : 0.0f;
-      g_ols += ok ? fmaf(a[i], r[i], (1.0f - a[i]) * hb) : 0.0f;
+      g[NG + NLS + i] = ok ? fmaf(v[i], fast_exp((1.0f - b[i]) * bls[i]), -w_ * zb * e) : 0.0f;
+      g[NG + i] = ok ? fmaf(-w_, r[i], hb) : 0.0f;
+      g_ols += ok ? fmaf(w_ * a[i], r[i], (1.0f - a[i]) * hb) : 0.0f;
       if (LOGP) lq += ok ? fmaf(-0.5f * r[i], r[i], fmaf(-0.5f * zb, zb, -b[i] * bls[i])) : 0.0f;
     }
     g_ols = group_sum<K>(g_ols);
     const float u0 = q[0] * s0i;
-    g[0] = fmaf(c0, g_ols, -u0 * s0i);
-    if (LOGP) lp += group_sum<K>(lq) - 0.5f * u0 * u0;
+    g[0] = fmaf(c0, g_ols, -w_ * u0 * s0i);
+    if (LOGP) lp += w_ * (group_sum<K>(lq) - 0.5f * u0 * u0);
     ARP_T(5, tg);
     return lp;
   }
@@ -1185,23 +1097,19 @@ struct GermanLane {
   }
 
   ARP_DEV void dparam(const float (&q)[ND], const float (&g)[ND], float (&da)[ND], float (&db)[ND]) const {
+    const float ols = c0 * q[0];
+#pragma unroll
+    for (int i = 0; i < ND; ++i) { da[i] = 0.0f; db[i] = 0.0f; }
+    // (PART_: g is this row part's share of the gradient; the constant 1 of the two affine forms counts once)
+    db[0] = -2.302585092994046f * fmaf(q[0], g[0], pw());
     if constexpr (GAMMA) {
       // a is inert; bls is not reparameterised; beta: -s_d (bt_d g_bt_d + 1) with s_d = ols + bls_d
-      const float ols = c0 * q[0];
-#pragma unroll
-      for (int i = 0; i < ND; ++i) { da[i] = 0.0f; db[i] = 0.0f; }
-      db[0] = -2.302585092994046f * fmaf(q[0], g[0], pw());
 #pragma unroll
       for (int i = 0; i < NLS; ++i) {
         const bool ok = i < nown;
         db[NG + NLS + i] = ok ? -(q[NG + i] + ols) * fmaf(q[NG + NLS + i], g[NG + NLS + i], pw()) : 0.0f;
       }
     } else {
-      const float ols = c0 * q[0];
-#pragma unroll
-      for (int i = 0; i < ND; ++i) { da[i] = 0.0f; db[i] = 0.0f; }
-      // (PART_: g is this row part's share of the gradient; the constant 1 of the two affine forms counts once)
-      db[0] = -2.302585092994046f * fmaf(q[0], g[0], pw());
 #pragma unroll
       for (int i = 0; i < NLS; ++i) {
         bool ok = i < nown;
@@ -1212,41 +1120,28 @@ struct GermanLane {
     }
   }
 
+  // centred <-> working coordinates; beta's log scale is bls (log-normal) or ols + bls (Gamma, where bls maps to itself)
   ARP_DEV void to_centered(const float (&q)[ND], float (&x)[ND]) const {
     const float ols = c0 * q[0];
     x[0] = ols;
-    if constexpr (GAMMA) {   // bls maps to itself, beta's scale is exp(ols + bls)
 #pragma unroll
-      for (int i = 0; i < NLS; ++i) {
-        x[NG + i] = q[NG + i];
-        x[NG + NLS + i] = fast_exp((1.0f - b[i]) * (q[NG + i] + ols)) * q[NG + NLS + i];
-      }
-    } else {
-#pragma unroll
-      for (int i = 0; i < NLS; ++i) {
-        float bls = q[NG + i] + (1.0f - a[i]) * ols;
-        x[NG + i] = bls;
-        x[NG + NLS + i] = fast_exp((1.0f - b[i]) * bls) * q[NG + NLS + i];
-      }
+    for (int i = 0; i < NLS; ++i) {
+      float bls = q[NG + i];
+      if constexpr (!GAMMA) bls += (1.0f - a[i]) * ols;
+      x[NG + i] = bls;
+      x[NG + NLS + i] = fast_exp((1.0f - b[i]) * (GAMMA ? bls + ols : bls)) * q[NG + NLS + i];
     }
   }
   ARP_DEV void from_centered(const float (&x)[ND], float (&q)[ND]) const {
     const float ols = x[0];
     q[0] = ols / c0;
-    if constexpr (GAMMA) {
 #pragma unroll
-      for (int i = 0; i < NLS; ++i) {
-        const bool ok = i < nown;
-        q[NG + i] = ok ? x[NG + i] : 0.0f;
-        q[NG + NLS + i] = ok ? x[NG + NLS + i] * fast_exp(-(1.0f - b[i]) * (x[NG + i] + ols)) : 0.0f;
-      }
-    } else {
-#pragma unroll
-      for (int i = 0; i < NLS; ++i) {
-        bool ok = i < nown;
-        q[NG + i] = ok ? x[NG + i] - (1.0f - a[i]) * ols : 0.0f;
-        q[NG + NLS + i] = ok ? x[NG + NLS + i] * fast_exp(-(1.0f - b[i]) * x[NG + i]) : 0.0f;
-      }
+    for (int i = 0; i < NLS; ++i) {
+      const bool ok = i < nown;
+      float blt = x[NG + i];
+      if constexpr (!GAMMA) blt -= (1.0f - a[i]) * ols;
+      q[NG + i] = ok ? blt : 0.0f;
+      q[NG + NLS + i] = ok ? x[NG + NLS + i] * fast_exp(-(1.0f - b[i]) * (GAMMA ? x[NG + i] + ols : x[NG + i])) : 0.0f;
     }
   }
 };

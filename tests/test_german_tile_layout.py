@@ -1,4 +1,4 @@
-"""CPU: the layout contract between the German-credit tile image (arp_api.hip: build_german) and the matrix-core
+"""CPU: the layout contract between the German-credit tile image (arp_build.hip: build_german) and the matrix-core
 likelihood's LDS addresses (model_german.h: likelihood_mfma), restated in Python: every operand address a lane forms
 must hit the element the host stored there, and both ds_read_b128 access patterns must be bank-conflict free under the
 gfx950 rules (4 groups of 16 lanes, bank = dword address mod 64).  The GPU tests check the kernel itself against the oracle
