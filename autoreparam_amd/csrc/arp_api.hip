@@ -397,7 +397,7 @@ int arp_interleaved_run(arp_model* m, const arp_hmc_config* cfg, int n_leapfrog_
     return 1;
   }
   if (io->k0.grad && !io->k0.logp) {
-    // kernels that carry the gradient across the change of coordinates keep BOTH between calls
+    // radon_interleaved_kernel (radon_fast.h) carries the gradient across the change of coordinates and keeps BOTH between calls
     set_error("arp_interleaved_run: k0.logp is required whenever k0.grad is given (pass both or neither)");
     return 1;
   }
@@ -411,7 +411,7 @@ int arp_interleaved_run(arp_model* m, const arp_hmc_config* cfg, int n_leapfrog_
   const LaneOps* o = select_ops(m, cfg->lanes_per_chain, cfg->n_chains);
   if (!o) return 1;
   const auto fn = o->interleaved[m->param_kind[0] == kModeCP && m->param_kind[1] == kModeNCP];
-  // (kernels that carry the gradient from step to step need it to travel with the state, as it does between launches)
+  // (radon_interleaved_kernel carries the gradient from step to step: it has to travel with the state, as it does between launches)
   if (relay_prepare(m, cfg, o->K, io->k0.grad != nullptr, (hipStream_t)stream, &P)) return 1;
   fn(m->args, m->dev_ab[0], m->dev_ab[0] + m->D, m->dev_ab[1], m->dev_ab[1] + m->D, P, (hipStream_t)stream);
   const hipError_t launched = hipGetLastError();

@@ -48,10 +48,14 @@ struct LaneOps {
                     float* logp, float* grad, hipStream_t s) = nullptr;
   void (*transform)(const void* args, const float* a, const float* b, int dir, const float* in,
                     int C, int D, float* out, hipStream_t s) = nullptr;
-  // chain launcher by the handle's parameterisation, indexed by kModeVIP / kModeCP / kModeNCP / kModeB1: every slot holds
-  // the generic kernel in the general (a, b) form unless the lane model or its packed family has that form at compile time
+  // chain launcher by the handle's parameterisation, indexed by kModeVIP / kModeCP / kModeNCP / kModeB1.  Launch::ops():
+  // every slot holds the generic hmc_kernel, in the general (a, b) form unless the lane model has that form at compile time
+  // (HAS_MODES, HAS_MODE_B1).  A family with packed kernels (radon_lane_ops, election_lane_ops) fills all four with those
+  // and names no generic hmc_kernel: naming one is what compiles it
   HmcFn hmc[4] = {};
-  // [0] any pair of parameterisations, [1] the compile-time (CP, NCP) pair (the generic kernel again where there is none)
+  // [0] any pair of parameterisations: the generic interleaved_kernel in the general form, in every family;
+  // [1] the compile-time (CP, NCP) pair: generic where the lane model has HAS_MODES, the family's packed kernel where
+  // there is one, [0] again otherwise
   InterleavedFn interleaved[2] = {};
   // mean-field VI: `n_groups` learning rates x (P.G x P.R) workgroups of vi_block threads (kernels.h: vi_kernel)
   // coop: hipLaunchCooperativeKernel -- the runtime itself guarantees that every workgroup of the grid is resident (or
@@ -179,15 +183,23 @@ struct Launch {
   }
   template <class L, class = void> struct has_b1 : std::false_type {};
   template <class L> struct has_b1<L, std::enable_if_t<L::HAS_MODE_B1>> : std::true_type {};
-  static LaneOps ops() {
+  // The table on the generic kernels, with (ops) or without (base) the chain slots hmc and interleaved.  A family whose
+  // chain kernels are packed ones starts from base() and so names, and compiles, only the generic chain kernels it keeps.
+  // (One body for both, so that ops() goes on naming its kernels in the order the code objects have them in.)
+  static LaneOps base() { return table<false>(); }
+  static LaneOps ops() { return table<true>(); }
+  template <bool CHAIN>
+  static LaneOps table() {
     LaneOps o;
     o.K = Lane::K; o.NL = Lane::NGRP;
     o.logp_grad = &logp_grad; o.transform = &transform;
-    for (auto& f : o.hmc) f = &hmc<kModeVIP>;
-    for (auto& f : o.interleaved) f = &interleaved<kModeVIP, kModeVIP>;
+    if constexpr (CHAIN) {
+      for (auto& f : o.hmc) f = &hmc<kModeVIP>;
+      for (auto& f : o.interleaved) f = &interleaved<kModeVIP, kModeVIP>;
+    }
     set_vi(o);
-    if constexpr (has_b1<Lane>::value) o.hmc[kModeB1] = &hmc<kModeB1>;
-    if constexpr (Lane::HAS_MODES) {
+    if constexpr (CHAIN && has_b1<Lane>::value) o.hmc[kModeB1] = &hmc<kModeB1>;
+    if constexpr (CHAIN && Lane::HAS_MODES) {
       o.hmc[kModeCP] = &hmc<kModeCP>;
       o.hmc[kModeNCP] = &hmc<kModeNCP>;
       o.interleaved[1] = &interleaved<kModeCP, kModeNCP>;
@@ -246,47 +258,52 @@ void pk_hmc(const void* args, const float* a, const float* b, const HmcParams& P
       P, s, *(const typename T::Args*)args, AB ? a : nullptr, AB ? b : nullptr);
 }
 
-// Radon: the generic lane kernels serve the general VIP form, the packed kernels of radon_fast.h the two
-// compile-time parameterisations (centred, non-centred) and their interleaving.
+// Radon.  Where the packed layer of radon_fast.h applies it takes every plain HMC run (the two compile-time
+// parameterisations and the general form) and the (CP, NCP) interleaving; only interleaved[0], any pair of
+// parameterisations in the general form, stays on the generic interleaved_kernel.  The packed layer wants at least two
+// county pairs per lane: the 13- and 15-county states at 8 / 16 lanes per chain are all generic.
 template <int K, int NL>
 LaneOps radon_lane_ops() {
-  LaneOps o = Launch<RadonLane<K, NL>>::ops();
-  // (the packed layer wants at least two county pairs per lane: the 13- and 15-county states at 8 / 16 lanes per chain run
-  // on the generic kernels)
+  using G = Launch<RadonLane<K, NL>>;
   if constexpr (K >= 4 && NL >= 4) {
     using T = RadonPk<K, NL>;
+    LaneOps o = G::base();
     o.hmc[kModeCP] = &pk_hmc<T, kModeCP, false>;
     o.hmc[kModeNCP] = &pk_hmc<T, kModeNCP, false>;
     // cVIP / dVIP runs: a free per county (m has unit scale, so b is inert: "a free, b = 1" and the untied form are the
-    // same kernel).  The general form on the packed layer ("hmc_vip_pk") takes the generic kernel's kModeVIP slot
+    // same kernel, "hmc_vip_pk")
     o.hmc[kModeVIP] = o.hmc[kModeB1] = &pk_hmc<T, kModeVIP>;
+    o.interleaved[0] = &G::template interleaved<kModeVIP, kModeVIP>;
     o.interleaved[1] = [](const void* args, const float*, const float*, const float*, const float*,
                           const HmcParams& P, hipStream_t s) {
       pk_launch<K, radon_interleaved_kernel<T, PkBlock<T>::kStatsFit>, radon_interleaved_kernel<T>>(P, s, *(const RadonArgs*)args);
     };
+    return o;
+  } else {
+    return G::ops();
   }
-  return o;
 }
 
-// Election: the generic lane kernels serve the interleaved sampler in the general form, the packed kernels
-// (election_fast.h on pk_chain.h) every plain HMC run: the three compile-time parameterisations and the general per-element
-// (a, b), with the statistics accumulators in LDS where they fit (two workgroups per CU instead of three).
+// Election: the packed kernels (election_fast.h on pk_chain.h) serve every plain HMC run -- the three compile-time
+// parameterisations and the general per-element (a, b), "hmc_vip_pk", with the statistics accumulators in LDS where they
+// fit (two workgroups per CU instead of three) -- and the (CP, NCP) interleaving.  Only interleaved[0], any pair of
+// parameterisations in the general form, stays on the generic interleaved_kernel.
 template <int K, int NL>
 LaneOps election_lane_ops() {
-  LaneOps o = Launch<ElectionLane<K, NL>>::ops();
-  if constexpr (K >= 4) {
-    using T = ElectionPk<K, NL>;
-    o.hmc[kModeCP] = &pk_hmc<T, kModeCP>;
-    o.hmc[kModeNCP] = &pk_hmc<T, kModeNCP>;
-    o.hmc[kModeB1] = &pk_hmc<T, kModeB1>;
-    o.hmc[kModeVIP] = &pk_hmc<T, kModeVIP>;   // "hmc_vip_pk": the general form on the packed layer takes the generic kernel's slot
-    // --method=i: centred / non-centred interleaving on the packed layer (pk_chain.h: pk_interleaved_kernel)
-    o.interleaved[1] = [](const void* args, const float* a0, const float* b0, const float*, const float*,
-                          const HmcParams& P, hipStream_t s) {
-      pk_launch<K, pk_interleaved_kernel<T, kModeCP, kModeNCP, PkBlock<T>::kStatsFit>, pk_interleaved_kernel<T, kModeCP, kModeNCP>>(
-          P, s, *(const ElectionArgs*)args, a0, b0);
-    };
-  }
+  static_assert(K >= 4, "the packed kernels deal the top-level momenta out over the first slots of a chain");
+  using T = ElectionPk<K, NL>;
+  LaneOps o = Launch<ElectionLane<K, NL>>::base();
+  o.hmc[kModeVIP] = &pk_hmc<T, kModeVIP>;
+  o.hmc[kModeCP] = &pk_hmc<T, kModeCP>;
+  o.hmc[kModeNCP] = &pk_hmc<T, kModeNCP>;
+  o.hmc[kModeB1] = &pk_hmc<T, kModeB1>;
+  o.interleaved[0] = &Launch<ElectionLane<K, NL>>::template interleaved<kModeVIP, kModeVIP>;
+  // --method=i: centred / non-centred interleaving on the packed layer (pk_chain.h: pk_interleaved_kernel)
+  o.interleaved[1] = [](const void* args, const float* a0, const float* b0, const float*, const float*,
+                        const HmcParams& P, hipStream_t s) {
+    pk_launch<K, pk_interleaved_kernel<T, kModeCP, kModeNCP, PkBlock<T>::kStatsFit>, pk_interleaved_kernel<T, kModeCP, kModeNCP>>(
+        P, s, *(const ElectionArgs*)args, a0, b0);
+  };
   return o;
 }
 

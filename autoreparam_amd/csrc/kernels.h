@@ -402,11 +402,14 @@ ARP_DEV void stats_update_wave(const Lane& M, float* stage, const HmcParams& P, 
 
 // ---------------------------------------------------------------------------
 // Parameterisation modes.  MODE 0 evaluates the general VIP form with per-element
-// (a,b) held in registers; lane models that set HAS_MODES also provide
-// compile-time specialisations for the two parameterisations every run uses,
-// MODE 1 = centred (a=b=1) and MODE 2 = non-centred (a=b=0): fewer VALU ops per
-// group and no (a,b) registers.  MODE 3 (lane models with HAS_MODE_B1) is "a free,
-// b = 1": what the reference's tied cVIP / dVIP runs execute.
+// (a,b) held in registers.  Lane models that set HAS_MODES (electric, time_series)
+// also provide compile-time specialisations (grad_m, to_centered_m, from_centered_m)
+// for the two parameterisations every run uses, MODE 1 = centred (a=b=1) and
+// MODE 2 = non-centred (a=b=0): fewer VALU ops per group and no (a,b) registers.
+// MODE 3 (lane models with HAS_MODE_B1: time_series) is "a free, b = 1": what the
+// reference's tied cVIP / dVIP runs execute.  Radon and election
+// have these forms on the packed layer instead (radon_fast.h, election_fast.h on
+// pk_chain.h): their lane models are general-form only.
 // ---------------------------------------------------------------------------
 constexpr int kModeVIP = 0, kModeCP = 1, kModeNCP = 2, kModeB1 = 3;
 
@@ -416,13 +419,15 @@ ARP_DEV float lane_grad(const Lane& M, const float (&q)[Lane::ND], float (&g)[La
   else return M.template grad<LOGP>(q, g);
 }
 // One interior leapfrog step: gradient at q, full kick, drift -- q and p updated in place.
-// Lane models with HAS_FUSED do it in a single pass over their groups (the gradient of a
-// group is consumed as soon as it is formed, so no gradient array stays live in the loop).
+// Lane models with HAS_FUSED (radon, election: general form only) do it in a single pass over
+// their groups (the gradient of a group is consumed as soon as it is formed, so no gradient
+// array stays live in the loop).
 template <int MODE, class Lane>
 ARP_DEV void lane_kick_drift(const Lane& M, float (&q)[Lane::ND], float (&p)[Lane::ND],
                              const float (&eps)[Lane::ND]) {
   if constexpr (Lane::HAS_FUSED) {
-    M.template kick_drift<MODE>(q, p, eps);
+    static_assert(MODE == kModeVIP, "the fused pass exists in the general form only");
+    M.kick_drift(q, p, eps);
   } else {
     float g[Lane::ND];
     lane_grad<MODE, false>(M, q, g);
@@ -445,12 +450,10 @@ ARP_DEV void lane_from_centered(const Lane& M, const float (&x)[Lane::ND], float
 }
 
 // Make `M` evaluate the parameterisation the interleaved kernel switches to: the general form
-// reloads (a, b); a compile-time mode has nothing to reload unless the lane model derives
-// run-time state from (a, b) (election's top-level prior scales), which set_mode<> rebuilds.
+// reloads (a, b); a compile-time mode has nothing to reload.
 template <int MODE, class Lane>
 ARP_DEV void switch_param(Lane& M, const float* av, const float* bv) {
   if constexpr (MODE == kModeVIP || !Lane::HAS_MODES) M.set_param(av, bv);
-  else if constexpr (Lane::HAS_MODE_STATE) M.template set_mode<MODE>();
 }
 
 // ---------------------------------------------------------------------------
@@ -820,28 +823,17 @@ __global__ __launch_bounds__(kBlock, Lane::MINW) void interleaved_kernel(
     rng = Rng{rs[0], rs[1]};
   }
 
-  // The reference re-bootstraps logp/grad after every change of coordinates
-  // (interleaved.py:120-123, 136-139).  Where the CP <-> NCP map is a shear with unit Jacobian
-  // (Lane::HAS_CARRY) the log density is unchanged and the gradient follows by the chain rule, so
-  // it is carried across the change of coordinates instead of being recomputed: 2*num_ls instead of
-  // 2*num_ls + 2 gradient evaluations per step.  The carried pair is kept in grad/logp between launches.
-  constexpr bool CARRY = Lane::HAS_CARRY && M0 == kModeCP && M1 == kModeNCP;
-  float lp = 0.0f;
-  if (CARRY) {
-    if (P.step_base == 0 || !P.grad) {
-      lp = lane_grad<M0, true>(M, q, g);
-    } else {
-      load_row(M, P.grad + c * D, g);
-      lp = P.logp[c];
-    }
-  }
+  // Like the reference, this kernel re-bootstraps logp/grad after every change of coordinates
+  // (interleaved.py:120-123, 136-139), so it neither reads nor writes P.grad / P.logp.  (Radon's packed
+  // radon_interleaved_kernel carries the pair across its unit-Jacobian CP <-> NCP shear instead: radon_fast.h.)
+  float lp;
   int next_rec = P.rec_step, rec_row = P.rec_row, bpos = P.stats_bpos;
   __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): see hmc_kernel
   for (int s = 0; s < P.n_steps; ++s) {
     const long long n = P.step_base + s + 1;
     bool acc0, acc1;
     // --- parameterisation 0 ---
-    if (!CARRY) lp = lane_grad<M0, true>(M, q, g);
+    lp = lane_grad<M0, true>(M, q, g);
     load_row(M, s_eps[0], eps);
 #pragma unroll
     for (int i = 0; i < ND; ++i) eps[i] *= kap[0];
@@ -849,32 +841,23 @@ __global__ __launch_bounds__(kBlock, Lane::MINW) void interleaved_kernel(
     nacc0 += acc0 ? 1u : 0u;
     adapt_update(P, n, la, kap[0], es[0], la_[0]);
     // --- parameterisation 1 ---
-    if constexpr (CARRY) {
-      M.template carry<kModeCP>(q, g);
-    } else {
-      lane_to_centered<M0>(M, q, x);
-      switch_param<M1>(M, av1, bv1);
-      lane_from_centered<M1>(M, x, q);
-      lp = lane_grad<M1, true>(M, q, g);
-    }
+    lane_to_centered<M0>(M, q, x);
+    switch_param<M1>(M, av1, bv1);
+    lane_from_centered<M1>(M, x, q);
+    lp = lane_grad<M1, true>(M, q, g);
     load_row(M, s_eps[1], eps);
 #pragma unroll
     for (int i = 0; i < ND; ++i) eps[i] *= kap[1];
     la = hmc_transition<Lane, M1>(M, rng, P.L1, eps, q, g, lp, acc1, save);
     nacc1 += acc1 ? 1u : 0u;
     adapt_update(P, n, la, kap[1], es[1], la_[1]);
-    if constexpr (CARRY) {
-      M.template carry<kModeNCP>(q, g);
-    } else {
-      lane_to_centered<M1>(M, q, x);
-      switch_param<M0>(M, av0, bv0);
-      lane_from_centered<M0>(M, x, q);
-    }
+    lane_to_centered<M1>(M, q, x);
+    switch_param<M0>(M, av0, bv0);
+    lane_from_centered<M0>(M, x, q);
 
     if (s == next_rec && rec_row < P.n_samples) {
-      // x holds the centred state (CARRY: CP coordinates are the centred ones); q the
-      // parameterisation-0 state the reference records
-      const bool use_x = P.trace_centered && !CARRY;
+      // x holds the centred state; q the parameterisation-0 state the reference records
+      const bool use_x = P.trace_centered;
       if (P.trace && cw0 < P.trace_chains) {
         const int nv = min(nvalid, (int)(P.trace_chains - cw0) * D);
         float* wrow = P.trace + ((size_t)rec_row * P.trace_chains + cw0) * D;
@@ -903,13 +886,11 @@ __global__ __launch_bounds__(kBlock, Lane::MINW) void interleaved_kernel(
   long long cw2 = cw0;
   asm volatile("" : "+v"(cw2));
   store_row_wave(M, stage, P.q + cw2 * D, cl, D, nvalid, q);
-  if (CARRY && P.grad) store_row_wave(M, stage, P.grad + cw2 * D, cl, D, nvalid, g);
   uint32_t* rs2 = P.rng + ((size_t)c2 * kRngSlots + slot) * 4;
   if (live) {
     rs = rs2;
     rs[0] = rng.x; rs[1] = rng.c; rs[2] = 0u; rs[3] = 0u;
     if (slot == 0) {
-      if (CARRY && P.grad) P.logp[c2] = lp;
       P.adapt[c2 * 4 + 0] = kap[0]; P.adapt[c2 * 4 + 1] = es[0]; P.adapt[c2 * 4 + 2] = la_[0];
       P.adapt1[c2 * 4 + 0] = kap[1]; P.adapt1[c2 * 4 + 1] = es[1]; P.adapt1[c2 * 4 + 2] = la_[1];
       P.accept_count[c2] = nacc0; P.accept_count1[c2] = nacc1;

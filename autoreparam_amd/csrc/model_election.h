@@ -37,13 +37,10 @@ struct ElectionLane {
   // only the last slice can be padding: NL == ceil(groups / K) is enforced by the host
   ARP_DEV bool lvalid(int i) const { return i < NL - 1 ? true : last_ok; }
   bool last_ok;
-  static constexpr bool HAS_MODES = true;    // CP / NCP: (a, b) are compile-time constants, no al / be registers
-  static constexpr bool HAS_CARRY = false;
+  static constexpr bool HAS_MODES = false;   // the compile-time parameterisations run on the packed kernels of election_fast.h
   static constexpr bool HAS_FUSED = true;    // kick_drift below
   static constexpr bool HAS_VI = true;
-  static constexpr bool HAS_MODE_STATE = true;    // si / cs of the top-level scalars follow b (set_mode)
-  static constexpr bool HAS_MODE_B1 = true;
-  static constexpr int MOM_SPEC = 1;   // momentum stream layout 1 (kernels.h: hmc_transition, pk_chain.h)       // MODE 3: a free, b = 1 (tied cVIP / dVIP as the reference executes them)
+  static constexpr int MOM_SPEC = 1;   // momentum stream layout 1 (kernels.h: hmc_transition, pk_chain.h)
   // three waves per SIMD at K = 4 (LDS: 51 KB per workgroup, three fit a CU): the 4 reciprocals + 1 exponential per state
   // are dependent-latency bound, and a third wave buys 7 % even though the 168-register cap spills a few values
   static constexpr int MINW = K_ == 4 ? 3 : 2;
@@ -74,20 +71,14 @@ struct ElectionLane {
     n4 = tab[k]; y4 = tab[k + 1];
   }
   float al[NL], be[NL];
-  float d1, d2;     // sum over the lane's cells of (y - n) that carry b1 / b2: the cell-independent part of sum y eta - n eta
+  // sum over the lane's cells of (y - n) that carry b1 / b2.  Nothing reads them since the fast likelihood form moved to
+  // election_fast.h; they stay because init's pass over the cells that forms them (its laundered index, see cells) is part
+  // of every kernel of this lane, and taking it out is a change to those kernels
+  float d1, d2;
   float lat_last;   // 1 if the lane's last slice is a state effect, 0 if it is the cell-only group S or padding
   // (only the last slice can be anything but a latent, see lvalid)
   ARP_DEV float lat(int i) const { return i < NL - 1 ? 1.0f : lat_last; }
-  // (a, b) of slice i under the compile-time parameterisations
-  // (a non-latent slice has a = b = 0 in every mode: its prior terms vanish and q stays 0)
-  template <int MODE> ARP_DEV float A(int i) const { return MODE == 1 ? lat(i) : (MODE == 2 ? 0.0f : al[i]); }
-  template <int MODE> ARP_DEV float B(int i) const { return (MODE == 1 || MODE == 3) ? lat(i) : (MODE == 2 ? 0.0f : be[i]); }
-  // exp(-b_i ls): shared by all slices when b is uniform (always so for CP, NCP and the reference's tied cVIP/dVIP)
-  template <int MODE> ARP_DEV float E(int i, float ls, float eu) const {
-    if (MODE == 2) return 1.0f;
-    if (MODE == 1 || MODE == 3) return i < NL - 1 ? eu : (lat_last != 0.0f ? eu : 1.0f);
-    return buni ? eu : fast_exp(-be[i] * ls);
-  }
+  // (a non-latent slice has a = b = 0: its prior terms vanish and q stays 0)
   float si[4], cs[4];   // 1/s^b and s^(1-b) for mua, lsa, b1, b2
   float bbar; bool buni; // every state shares one b (always so for CP, NCP and the reference's tied cVIP/dVIP)
   int slot, S;
@@ -112,24 +103,14 @@ struct ElectionLane {
     lat_last = slot + K * (NL - 1) < S ? 1.0f : 0.0f;
     set_param(av, bv);
   }
-  // si, cs under CP (b = 1: xt = x) and NCP (b = 0: xt = x / s)
-  template <int MODE>
-  ARP_DEV void set_mode() {
-    const float sc[4] = {100.0f, 10.0f, 100.0f, 100.0f};
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      si[i] = (MODE == 1 || MODE == 3) ? 1.0f / sc[i] : 1.0f;
-      cs[i] = (MODE == 1 || MODE == 3) ? 1.0f : sc[i];
-    }
-  }
   ARP_DEV void set_param(const float* av, const float* bv) {
     const float l100 = 6.643856189774724f, l10 = 3.321928094887362f;  // log2
     const float lg[4] = {l100, l10, l100, l100};
     const float sc[4] = {100.0f, 10.0f, 100.0f, 100.0f};
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-      // b = 1 and b = 0 get the exact constants set_mode<> uses, so the general kernel, the compile-time forms
-      // and a run cut into several launches all see the same numbers
+      // b = 1 (xt = x) and b = 0 (xt = x / s) get exact constants, not exp2's result, so this kernel, the packed
+      // kernels' compile-time forms (election_fast.h) and a run cut into several launches all see the same numbers
       const float bb = bv[gmap[i]];
       const float e = __builtin_amdgcn_exp2f(-bb * lg[i]);
       si[i] = bb == 1.0f ? 1.0f / sc[i] : (bb == 0.0f ? 1.0f : e);
@@ -153,18 +134,17 @@ struct ElectionLane {
   // one exp and four reciprocals instead of four of each, and with a shared b the prior's
   // exp(-b lsa) is formed once per gradient.  (The closing gradient of a transition, which
   // also needs the log density, uses the overflow-proof form in grad<>.)
-  template <int MODE>
   ARP_DEV void kick_drift(float (&q)[ND], float (&p)[ND], const float (&eps)[ND]) const {
     const float mua = cs[0] * q[0], ls = cs[1] * q[1], b1 = cs[2] * q[2], b2 = cs[3] * q[3];
     const float sig = fast_exp(ls);
     const float E1 = fast_exp(-b1), E2 = fast_exp(-b2), E12 = E1 * E2;
-    const float eu = MODE == 2 ? 1.0f : fast_exp(-((MODE == 1 || MODE == 3) ? 1.0f : bbar) * ls);
+    const float eu = fast_exp(-bbar * ls);   // exp(-b ls) of every state where they share one b
     float g_mua = 0.0f, g_ls = 0.0f, g_b1 = 0.0f, g_b2 = 0.0f;
 #pragma unroll
     for (int i = 0; i < NL; ++i) {
       const float qt = q[NG + i];
-      const float ai = A<MODE>(i), bi = B<MODE>(i), li = lat(i);
-      const float e = E<MODE>(i, ls, eu);
+      const float ai = al[i], bi = be[i], li = lat(i);
+      const float e = buni ? eu : fast_exp(-be[i] * ls);
       const float z = (qt - ai * mua) * e;
       const float as = li * fmaf(sig, z, mua);
       const float t = fast_exp(-as);
@@ -197,63 +177,40 @@ struct ElectionLane {
     }
   }
 
+  // Gradient (and log density when LOGP).  The likelihood takes every cell through exp(-|eta|), overflow-proof for any
+  // state: logp_grad_kernel, the VI kernel and the interleaved kernel hand it arbitrary caller-supplied states.  (The
+  // form in which a state's four cells share exp(-a_t), as in kick_drift, is election_fast.h's.)
+  // (grad stays a forward: with the body folded into it the compiler swaps the operands of a few additions in
+  // logp_grad_kernel -- the same sums, but not the same listing, and this lane's kernels are held to their listings)
   template <bool LOGP>
-  ARP_DEV float grad(const float (&q)[ND], float (&g)[ND]) const { return grad_m<LOGP, 0>(q, g); }
-
-  // Gradient (and log density when LOGP).  Two forms of the likelihood part:
-  //  * SAFE (the general form MODE 0: logp_grad_kernel, the VI kernel, arbitrary caller-supplied states): every cell
-  //    through exp(-|eta|), overflow-proof for any state;
-  //  * fast (the compile-time parameterisations, i.e. the closing gradient of every CP / NCP / b = 1 transition): the
-  //    four cells of a state share exp(-a_t) as in kick_drift, and with rc = 1 / (1 + e^-eta) = sigmoid(eta)
-  //        softplus(eta) = eta - log(rc),  so  y eta - n softplus(eta) = (y - n) eta + n log(rc):
-  //    per cell one reciprocal and one logarithm, no exponential, no |.|, no select.  e^-eta overflows only for
-  //    logits below -88, where the log density comes out -inf and the proposal is rejected (TFP's non-finite rule).
-  template <bool LOGP, int MODE>
-  ARP_DEV float grad_m(const float (&q)[ND], float (&g)[ND]) const {
-    constexpr bool SAFE = MODE == 0;
+  ARP_DEV float grad(const float (&q)[ND], float (&g)[ND]) const { return grad_any<LOGP>(q, g); }
+  template <bool LOGP>
+  ARP_DEV float grad_any(const float (&q)[ND], float (&g)[ND]) const {
     const float mua = cs[0] * q[0], ls = cs[1] * q[1], b1 = cs[2] * q[2], b2 = cs[3] * q[3];
     const float sig = fast_exp(ls);
-    const float E1 = SAFE ? 0.0f : fast_exp(-b1), E2 = SAFE ? 0.0f : fast_exp(-b2), E12 = E1 * E2;
-    const float eu = MODE == 2 ? 1.0f : fast_exp(-((MODE == 1 || MODE == 3) ? 1.0f : bbar) * ls);
     float g_mua = 0.0f, g_ls = 0.0f, g_b1 = 0.0f, g_b2 = 0.0f, lp = 0.0f;
 #pragma unroll
     for (int i = 0; i < NL; ++i) {
-      const float ai = A<MODE>(i), bi = B<MODE>(i), li = lat(i);
-      const float e = MODE == 0 ? fast_exp(-be[i] * ls) : E<MODE>(i, ls, eu);
+      const float ai = al[i], bi = be[i], li = lat(i);
+      const float e = fast_exp(-be[i] * ls);
       float z = (q[NG + i] - ai * mua) * e;      // group S / padding: q = 0, a = 0 -> z = 0
       float as = li * fmaf(sig, z, mua);
       float4 n4, y4;
       cells(i, n4, y4);
       const float cn_[4] = {n4.x, n4.y, n4.z, n4.w}, cy_[4] = {y4.x, y4.y, y4.z, y4.w};
       float w[4];
-      if (SAFE) {
-        const float eta[4] = {as, as + b2, as + b1, as + b1 + b2};
+      const float eta[4] = {as, as + b2, as + b1, as + b1 + b2};
 #pragma unroll
-        for (int c = 0; c < 4; ++c) {
-          // sigmoid / softplus share exp(-|eta|)
-          float ex = fast_exp(-fabsf(eta[c]));
-          float rc = __builtin_amdgcn_rcpf(1.0f + ex);
-          float sg = eta[c] >= 0.0f ? rc : ex * rc;
-          w[c] = fmaf(-cn_[c], sg, cy_[c]);
-          if (LOGP) {
-            float sp = fmaxf(eta[c], 0.0f) + fast_log(1.0f + ex);
-            lp += fmaf(cy_[c], eta[c], -cn_[c] * sp);
-          }
+      for (int c = 0; c < 4; ++c) {
+        // sigmoid / softplus share exp(-|eta|)
+        float ex = fast_exp(-fabsf(eta[c]));
+        float rc = __builtin_amdgcn_rcpf(1.0f + ex);
+        float sg = eta[c] >= 0.0f ? rc : ex * rc;
+        w[c] = fmaf(-cn_[c], sg, cy_[c]);
+        if (LOGP) {
+          float sp = fmaxf(eta[c], 0.0f) + fast_log(1.0f + ex);
+          lp += fmaf(cy_[c], eta[c], -cn_[c] * sp);
         }
-      } else {
-        const float t = fast_exp(-as);
-        const float den[4] = {1.0f + t, fmaf(t, E2, 1.0f), fmaf(t, E1, 1.0f), fmaf(t, E12, 1.0f)};
-        float dn = 0.0f;
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-          const float rc = __builtin_amdgcn_rcpf(den[c]);
-          w[c] = fmaf(-cn_[c], rc, cy_[c]);
-          if (LOGP) {
-            lp = fmaf(cn_[c] * 0.6931471805599453f, __builtin_amdgcn_logf(rc), lp);    // n log(rc), v_log_f32 is log2
-            dn += cy_[c] - cn_[c];
-          }
-        }
-        if (LOGP) lp = fmaf(dn, as, lp);          // (y - n) eta, the part every cell of the state shares
       }
       float W = (w[0] + w[1]) + (w[2] + w[3]);
       g_b2 += w[1] + w[3];
@@ -264,7 +221,6 @@ struct ElectionLane {
       g_ls += fmaf(bi, fmaf(z, z, -1.0f), li * W * sig * z * (1.0f - bi));
       if (LOGP) lp += fmaf(-0.5f * z, z, -bi * ls);
     }
-    if (LOGP && !SAFE) lp = fmaf(d1, b1, fmaf(d2, b2, lp));   // (y - n) (b1 black + b2 female) over the lane's cells
     g_mua = group_sum<K>(g_mua);
     g_ls = group_sum<K>(g_ls);
     g_b1 = group_sum<K>(g_b1);
@@ -297,33 +253,18 @@ struct ElectionLane {
     }
   }
 
-  ARP_DEV void to_centered(const float (&q)[ND], float (&x)[ND]) const { to_centered_m<0>(q, x); }
-  ARP_DEV void from_centered(const float (&x)[ND], float (&q)[ND]) const { from_centered_m<0>(x, q); }
-  template <int MODE>
-  ARP_DEV void to_centered_m(const float (&q)[ND], float (&x)[ND]) const {
+  ARP_DEV void to_centered(const float (&q)[ND], float (&x)[ND]) const {
     const float mua = cs[0] * q[0], ls = cs[1] * q[1];
     x[0] = mua; x[1] = ls; x[2] = cs[2] * q[2]; x[3] = cs[3] * q[3];
-    const float sig = MODE == 2 ? fast_exp(ls) : 1.0f;
 #pragma unroll
-    for (int i = 0; i < NL; ++i) {
-      if (MODE == 1) x[NG + i] = q[NG + i];                             // a = b = 1: identity
-      else if (MODE == 2) x[NG + i] = lat(i) * fmaf(sig, q[NG + i], mua);   // a = b = 0: mua + sigma q
-      else if (MODE == 3) x[NG + i] = fmaf(lat(i) - al[i], mua, q[NG + i]);   // b = 1: q + (1 - a) mua
-      else x[NG + i] = fmaf(fast_exp((1.0f - be[i]) * ls), q[NG + i] - al[i] * mua, mua);
-    }
+    for (int i = 0; i < NL; ++i) x[NG + i] = fmaf(fast_exp((1.0f - be[i]) * ls), q[NG + i] - al[i] * mua, mua);
   }
-  template <int MODE>
-  ARP_DEV void from_centered_m(const float (&x)[ND], float (&q)[ND]) const {
+  ARP_DEV void from_centered(const float (&x)[ND], float (&q)[ND]) const {
     const float mua = x[0], ls = x[1];
     q[0] = mua / cs[0]; q[1] = ls / cs[1]; q[2] = x[2] / cs[2]; q[3] = x[3] / cs[3];
-    const float isig = MODE == 2 ? fast_exp(-ls) : 1.0f;
 #pragma unroll
-    for (int i = 0; i < NL; ++i) {
-      if (MODE == 1) q[NG + i] = lvalid(i) ? x[NG + i] : 0.0f;
-      else if (MODE == 2) q[NG + i] = lvalid(i) ? (x[NG + i] - mua) * isig : 0.0f;
-      else if (MODE == 3) q[NG + i] = lvalid(i) ? fmaf(al[i] - 1.0f, mua, x[NG + i]) : 0.0f;
-      else q[NG + i] = lvalid(i) ? fmaf(x[NG + i] - mua, fast_exp(-(1.0f - be[i]) * ls), al[i] * mua) : 0.0f;
-    }
+    for (int i = 0; i < NL; ++i)
+      q[NG + i] = lvalid(i) ? fmaf(x[NG + i] - mua, fast_exp(-(1.0f - be[i]) * ls), al[i] * mua) : 0.0f;
   }
 };
 

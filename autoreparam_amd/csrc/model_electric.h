@@ -52,8 +52,6 @@ struct ElectricLane {
   ARP_DEV bool lvalid(int i) const { return i < NL - 1 ? true : last_ok; }
   bool last_ok;
   static constexpr bool HAS_MODES = true;         // compile-time centred / non-centred forms (grad_m below)
-  static constexpr bool HAS_MODE_STATE = false;   // their scales of b are constants
-  static constexpr bool HAS_CARRY = false;
   static constexpr bool HAS_FUSED = false;
   static constexpr bool HAS_VI = true;
   static constexpr int MINW = 2;   // waves per SIMD the register allocator must leave room for

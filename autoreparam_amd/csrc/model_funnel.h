@@ -18,7 +18,6 @@ struct FunnelLane {
   static constexpr int NG = 1, NL = NL_, ND = NG + NL, NGRP = NL_, DCAP = 2, LBASE = 1;
   static_assert(K_ == 1 && NL_ == 1, "the funnel runs one lane per chain");
   static constexpr bool HAS_MODES = false;
-  static constexpr bool HAS_CARRY = false;
   static constexpr bool HAS_FUSED = false;
   static constexpr bool HAS_VI = true;
   static constexpr int MINW = 1;

@@ -70,7 +70,6 @@ struct GermanLane {
   static constexpr int DCAP = 1 + 2 * kGermanCols;   // upper bound of the flattened state dimension D
   static_assert(K_ * NLS_ == kGermanCols, "lanes x features per lane must cover the padded row");
   static constexpr bool HAS_MODES = false;
-  static constexpr bool HAS_CARRY = false;
   static constexpr bool HAS_FUSED = false;
   static constexpr int MINW = K_ >= 8 ? 2 : 1;   // waves per SIMD the register allocator must leave room for
   using Args = GermanArgs;

@@ -45,11 +45,9 @@ struct RadonLane {
   // VALU issue needs two resident waves per SIMD: cap the allocation at 256 VGPRs where the slice fits
   static constexpr int MINW = (NL_ <= 23) ? 2 : 1;
   static constexpr bool HAS_MODES = false;  // centred / non-centred runs use the packed kernels of radon_fast.h
-  static constexpr bool HAS_CARRY = false;
-  static constexpr bool HAS_FUSED = true;   // kick_drift below  // grad_m / to_centered_m / from_centered_m below
+  static constexpr bool HAS_FUSED = true;   // kick_drift below
   static constexpr bool HAS_VI = true;
   static constexpr int MOM_SPEC = 1;   // momentum stream layout 1 (kernels.h: hmc_transition, radon_fast.h)
-  static constexpr bool HAS_MODE_STATE = false;   // nothing but (a, b) depends on the parameterisation
   using Args = RadonArgs;
 
   static constexpr int LBASE = 3; // flattened index of m_0 (parts: mua, b1, b2, m[J])
@@ -125,80 +123,9 @@ struct RadonLane {
     return lp;
   }
 
-  // ---- compile-time parameterisations (kernels.h: kModeCP = 1, kModeNCP = 2) ----
-  // CP (a = 1):  r_j = mt_j - mu_j, m_j = mt_j, h_j = r_j.
-  // NCP (a = 0): r_j = mt_j, m_j = mt_j + mu_j, h_j = l_j.
-  // 8 VALU ops per county instead of 10, and no `a` registers.  Only the last
-  // slice of a lane can be padding (j >= J); CP masks its r there.
-  template <bool LOGP, int MODE>
-  ARP_DEV float grad_m(const float (&q)[ND], float (&g)[ND]) const {
-    const float mua = q[0], b1 = q[1], b2 = q[2];
-    const v2f vmua = {mua, mua}, vb1 = {b1, b1}, vnb2 = {-b2, -b2}, mhalf = {-0.5f, -0.5f}, mtwo = {-2.0f, -2.0f};
-    v2f acc_h = {0.0f, 0.0f}, acc_uh = {0.0f, 0.0f}, acc_ms = {0.0f, 0.0f}, lpv = {0.0f, 0.0f};
-#pragma unroll
-    for (int k = 0; k < NL / 2; ++k) {   // county pairs on the packed f32 pipe
-      const int i = 2 * k;
-      const v2f mt = {q[NG + i], q[NG + i + 1]};
-      const v2f mu = vfma(u2[k], vb1, vmua);
-      const v2f t = vfma(vnb2, sx2[k], sy2[k]);
-      v2f r, m;
-      if (MODE == 1) {
-        r = mt - mu;
-        if (i + 1 == NL - 1) r[1] = last_ok ? r[1] : 0.0f;
-        m = mt;
-      } else {
-        r = mt;
-        m = mt + mu;
-      }
-      const v2f l = vfma(-n2[k], m, t);
-      const v2f gm = l - r;
-      g[NG + i] = gm[0]; g[NG + i + 1] = gm[1];
-      const v2f h = (MODE == 1) ? r : l;
-      acc_h += h;
-      acc_uh = vfma(u2[k], h, acc_uh);
-      acc_ms = vfma(m, sx2[k], acc_ms);
-      if (LOGP) {
-        lpv = vfma(mhalf * r, r, lpv);
-        lpv = vfma(mhalf * m, vfma(n2[k], m, mtwo * t), lpv);
-      }
-    }
-    float s_h = acc_h[0] + acc_h[1], s_uh = acc_uh[0] + acc_uh[1], s_ms = acc_ms[0] + acc_ms[1];
-    float lp = lpv[0] + lpv[1];
-    if (NL & 1) {
-      constexpr int i = NL - 1;
-      const float mt = q[NG + i];
-      const float mu = fmaf(u2[i >> 1][0], b1, mua);
-      const float t = fmaf(-b2, sx2[i >> 1][0], sy2[i >> 1][0]);
-      float r, m;
-      if (MODE == 1) { r = last_ok ? mt - mu : 0.0f; m = mt; } else { r = mt; m = mt + mu; }
-      const float l = fmaf(-n2[i >> 1][0], m, t);
-      g[NG + i] = l - r;
-      const float h = (MODE == 1) ? r : l;
-      s_h += h;
-      s_uh = fmaf(u2[i >> 1][0], h, s_uh);
-      s_ms = fmaf(m, sx2[i >> 1][0], s_ms);
-      if (LOGP) {
-        lp = fmaf(-0.5f * r, r, lp);
-        lp = fmaf(-0.5f * m, fmaf(n2[i >> 1][0], m, -2.0f * t), lp);
-      }
-    }
-    s_h = group_sum<K>(s_h);
-    s_uh = group_sum<K>(s_uh);
-    s_ms = group_sum<K>(s_ms);
-    g[0] = s_h - mua;
-    g[1] = s_uh - b1;
-    g[2] = fmaf(-b2, sxx, sxy) - s_ms - b2;
-    if (LOGP) {
-      lp = group_sum<K>(lp);
-      lp += -0.5f * (mua * mua + b1 * b1 + b2 * b2) + b2 * (sxy - 0.5f * b2 * sxx);
-    }
-    return lp;
-  }
-
   // Interior leapfrog step in one pass (kernels.h: lane_kick_drift): for every county the
   // gradient is formed, kicked into p and the position drifted at once; the three
-  // top-level scalars follow after the group sums.  MODE 0 uses the `a` table.
-  template <int MODE>
+  // top-level scalars follow after the group sums.
   ARP_DEV void kick_drift(float (&q)[ND], float (&p)[ND], const float (&eps)[ND]) const {
     const float mua = q[0], b1 = q[1], b2 = q[2];
     const v2f vmua = {mua, mua}, vb1 = {b1, b1}, vnb2 = {-b2, -b2};
@@ -212,21 +139,11 @@ struct RadonLane {
       const v2f pv = {p[NG + i], p[NG + i + 1]};
       const v2f mu = vfma(u2[k], vb1, vmua);
       const v2f t = vfma(vnb2, sx2[k], sy2[k]);
-      v2f r, m, h;
-      if (MODE == 1) {
-        r = mt - mu;
-        if (i + 1 == NL - 1) r[1] = last_ok ? r[1] : 0.0f;
-        m = mt;
-      } else if (MODE == 2) {
-        r = mt;
-        m = mt + mu;
-      } else {
-        r = vfma(-a2[k], mu, mt);
-        m = r + mu;
-      }
+      const v2f r = vfma(-a2[k], mu, mt);
+      const v2f m = r + mu;
       const v2f l = vfma(-n2[k], m, t);
       const v2f gm = l - r;
-      h = (MODE == 1) ? r : ((MODE == 2) ? l : vfma(-a2[k], gm, l));
+      const v2f h = vfma(-a2[k], gm, l);
       acc_h += h;
       acc_uh = vfma(u2[k], h, acc_uh);
       acc_ms = vfma(m, sx2[k], acc_ms);
@@ -241,13 +158,11 @@ struct RadonLane {
       const float mt = q[NG + i];
       const float mu = fmaf(u2[i >> 1][0], b1, mua);
       const float t = fmaf(-b2, sx2[i >> 1][0], sy2[i >> 1][0]);
-      float r, m, h;
-      if (MODE == 1) { r = last_ok ? mt - mu : 0.0f; m = mt; }
-      else if (MODE == 2) { r = mt; m = mt + mu; }
-      else { r = fmaf(-a2[i >> 1][0], mu, mt); m = r + mu; }
+      const float r = fmaf(-a2[i >> 1][0], mu, mt);
+      const float m = r + mu;
       const float l = fmaf(-n2[i >> 1][0], m, t);
       const float gm = l - r;
-      h = (MODE == 1) ? r : ((MODE == 2) ? l : fmaf(-a2[i >> 1][0], gm, l));
+      const float h = fmaf(-a2[i >> 1][0], gm, l);
       s_h += h;
       s_uh = fmaf(u2[i >> 1][0], h, s_uh);
       s_ms = fmaf(m, sx2[i >> 1][0], s_ms);
@@ -262,50 +177,6 @@ struct RadonLane {
     p[0] = fmaf(eps[0], g0, p[0]); q[0] = fmaf(eps[0], p[0], mua);
     p[1] = fmaf(eps[1], g1, p[1]); q[1] = fmaf(eps[1], p[1], b1);
     p[2] = fmaf(eps[2], g2, p[2]); q[2] = fmaf(eps[2], p[2], b2);
-  }
-
-  // Change of coordinates CP <-> NCP of a state AND its gradient (interleaved kernel).  The map
-  // m = mt + mu(mua, b1) is a shear with unit Jacobian: the log density is unchanged and
-  //   d/dmt_j = d/dm_j,   d/dmua (NCP) = d/dmua (CP) + sum_j d/dm_j,   d/db1 likewise with u_j.
-  // FROM == 1: CP -> NCP, FROM == 2: NCP -> CP.
-  template <int FROM>
-  ARP_DEV void carry(float (&q)[ND], float (&g)[ND]) const {
-    float s = 0.0f, su = 0.0f;
-#pragma unroll
-    for (int i = 0; i < NL; ++i) {
-      const float mu = fmaf(u2[i >> 1][i & 1], q[1], q[0]);
-      const float gj = g[NG + i];               // 0 in padding slots
-      s += gj;
-      su = fmaf(u2[i >> 1][i & 1], gj, su);
-      const float qn = (FROM == 1) ? q[NG + i] - mu : q[NG + i] + mu;
-      q[NG + i] = lvalid(i) ? qn : 0.0f;
-    }
-    s = group_sum<K>(s);
-    su = group_sum<K>(su);
-    g[0] += (FROM == 1) ? s : -s;
-    g[1] += (FROM == 1) ? su : -su;
-  }
-
-  template <int MODE>
-  ARP_DEV void to_centered_m(const float (&q)[ND], float (&x)[ND]) const {
-#pragma unroll
-    for (int i = 0; i < ND; ++i) x[i] = q[i];
-    if (MODE == 2) {
-#pragma unroll
-      for (int i = 0; i < NL; ++i) x[NG + i] = q[NG + i] + fmaf(u2[i >> 1][i & 1], q[1], q[0]);
-    }
-  }
-  template <int MODE>
-  ARP_DEV void from_centered_m(const float (&x)[ND], float (&q)[ND]) const {
-#pragma unroll
-    for (int i = 0; i < ND; ++i) q[i] = x[i];
-    if (MODE == 2) {
-#pragma unroll
-      for (int i = 0; i < NL; ++i) q[NG + i] = lvalid(i) ? x[NG + i] - fmaf(u2[i >> 1][i & 1], x[1], x[0]) : 0.0f;
-    } else {
-#pragma unroll
-      for (int i = 0; i < NL; ++i) q[NG + i] = lvalid(i) ? x[NG + i] : 0.0f;
-    }
   }
 
   // d logp / d a_i and d logp / d b_i from the state gradient g (cVIP learns a):

@@ -30,7 +30,6 @@ struct RadonSdLane {
   static constexpr int NGRP = NLS_;   // groups owned by a lane (what the host matches against ceil(groups / K))
   static constexpr int DCAP = NG + 2 * K_ * NLS_;
   static constexpr bool HAS_MODES = false;
-  static constexpr bool HAS_CARRY = false;
   static constexpr bool HAS_FUSED = false;
   static constexpr bool HAS_VI = true;
   static constexpr int MINW = 2;   // waves per SIMD the register allocator must leave room for (the tables are in LDS)

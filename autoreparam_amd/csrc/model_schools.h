@@ -35,7 +35,6 @@ struct SchoolsLane {
   ARP_DEV bool lvalid(int i) const { return i < NL - 1 ? true : last_ok; }
   bool last_ok;
   static constexpr bool HAS_MODES = false;
-  static constexpr bool HAS_CARRY = false;
   static constexpr bool HAS_FUSED = false;
   static constexpr bool HAS_VI = true;
   static constexpr int MINW = 1;   // waves per SIMD the register allocator must leave room for

@@ -50,9 +50,7 @@ struct TimeSeriesLane {
   static constexpr int NGRP = NL_;
   static constexpr int DCAP = NG + K_ * NL_;
   static constexpr bool HAS_MODES = true;        // compile-time centred / non-centred / "a free, b = 1" forms (grad_m below)
-  static constexpr bool HAS_MODE_STATE = false;
   static constexpr bool HAS_MODE_B1 = true;
-  static constexpr bool HAS_CARRY = false;
   static constexpr bool HAS_FUSED = false;
   static constexpr bool HAS_VI = true;
   static constexpr int MINW = NL_ <= 16 ? 2 : 1;   // waves per SIMD the register allocator must leave room for

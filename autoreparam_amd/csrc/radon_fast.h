@@ -238,7 +238,7 @@ struct RadonPk {
 // Interleaved CP / NCP sampling (interleaved.Interleaved.one_step, interleaved.py:113-155): a centred transition,
 // the change of coordinates, a non-centred transition, the change back; each inner kernel keeps its own
 // step-size adaptation state (inference.py:288-306).  The gradient and log density are carried across the
-// shear instead of being recomputed (kernels.h: interleaved_kernel, CARRY), 2*num_ls gradient evaluations per step.
+// shear (`carry` above) instead of being recomputed as kernels.h: interleaved_kernel does, 2*num_ls gradient evaluations per step.
 template <class T, bool STATS = false>
 __global__ __launch_bounds__(kBlock, T::MINW) void radon_interleaved_kernel(RadonArgs A, HmcParams P) {
   constexpr int K = T::K, NP = T::NP, ND = T::ND;

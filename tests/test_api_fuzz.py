@@ -184,6 +184,123 @@ def test_randomised_calls_never_crash_and_always_explain(host_lib):
         assert L.arp_model_destroy(h) == 0
 
 
+# (a, b) of the four parameterisation kinds arp_model_set_param tells apart: centred, non-centred, "a free, b = 1", general
+PARAM_KINDS = [(1.0, 1.0), (0.0, 0.0), (0.5, 1.0), (0.5, 0.5)]
+# chain launches test_every_launcher_table_slot_is_filled makes: per model, over lanes_per_chain 0 / 4 / 8 / 16 where the
+# family has an instantiation for the test dataset.  Counted on the commit before the launcher tables were split (where
+# the same walk passes) and unchanged by the split: 6 per served lanes_per_chain.
+TABLE_WALK_CALLS = {"8schools": 18, "radon_MN": 24, "radon_PA": 24, "election": 24, "german": 24, "radon_sd_MN": 18,
+                    "funnel": 6, "electric": 18, "time_series": 24}     # 180 in all
+
+
+@pytest.mark.parametrize("name", MODELS)
+def test_every_launcher_table_slot_is_filled(host_lib, name):
+    """Every chain slot of the launcher table an instantiation exports (csrc/host_common.h: LaneOps::hmc by the four
+    parameterisation kinds, LaneOps::interleaved by (CP, NCP) pair or any other) is called once through the C API, with
+    one step.  Without a device each call must come back with HIP's own launch error: an empty slot would be a call
+    through a null pointer, a validation message would mean the slot was never reached."""
+    L = host_lib.lib()
+    sp, h, keep = _handle(host_lib, name)
+    f32p = host_lib._f32p
+    bufs = []
+
+    def ptr():
+        b, p = _fake(1 << 16)
+        bufs.append(b)
+        return p
+
+    def set_param(which, ab):
+        a, b = (np.full(sp.D, v, np.float32) for v in ab)
+        assert L.arp_model_set_param(h, which, a.ctypes.data_as(f32p), b.ctypes.data_as(f32p)) == 0
+
+    def launched(rc, what):
+        err = L.arp_last_error()
+        assert rc != 0 and err.startswith(b"launched: ") and len(err) > len(b"launched: "), (what, rc, err)
+
+    cfg = host_lib.HmcConfig()
+    cfg.n_chains, cfg.n_leapfrog, cfg.n_steps, cfg.thin, cfg.stats_batch = 64, 2, 1, 1, 1
+    io = host_lib.HmcIO()
+    io.q, io.grad, io.logp, io.adapt, io.rng, io.accept_count, io.eps0 = (ptr() for _ in range(7))
+    io2 = host_lib.InterleavedIO()
+    io2.k0 = io
+    io2.adapt1, io2.accept_count1, io2.eps0_1 = ptr(), ptr(), ptr()
+    calls = 0
+    for K in (0, 4, 8, 16):
+        cfg.lanes_per_chain = K
+        set_param(0, PARAM_KINDS[0])
+        if L.arp_hmc_run(h, 0, C.byref(cfg), C.byref(io), None) != 0 and L.arp_last_error().startswith(b"no kernel instantiation"):
+            assert K != 0, "every family serves its default lanes per chain"
+            continue
+        for ab in PARAM_KINDS:
+            set_param(0, ab)
+            launched(L.arp_hmc_run(h, 0, C.byref(cfg), C.byref(io), None), ("hmc", K, ab))
+            calls += 1
+        for ab0, ab1 in ((PARAM_KINDS[0], PARAM_KINDS[1]), (PARAM_KINDS[3], PARAM_KINDS[3])):
+            set_param(0, ab0)
+            set_param(1, ab1)
+            launched(L.arp_interleaved_run(h, C.byref(cfg), 2, C.byref(io2), None), ("interleaved", K, ab0, ab1))
+            calls += 1
+    print("%s: %d chain launches" % (name, calls))
+    assert calls == TABLE_WALK_CALLS[name]
+    assert L.arp_model_destroy(h) == 0
+
+
+_LISTING = """\
+\t.type\t_Zgone,@function
+_Zgone:                                 ; @_Zgone
+\ts_branch .LBB0_1
+.LBB0_1:
+\ts_endpgm
+.Lfunc_end0:
+\t.type\t_Zkept,@function
+_Zkept:                                 ; @_Zkept
+; %bb.0:
+\ts_cbranch_scc1 .LBB1_2
+\ts_getpc_b64 s[0:1]
+.Ltmp7:
+\ts_add_u32 s0, s0, .LBB1_2-.Ltmp7
+.LBB1_2:
+\ts_endpgm
+\t.section\t.rodata,"a",@progbits
+\t.amdhsa_kernel _Zkept
+\t\t.amdhsa_group_segment_fixed_size 1024
+\t\t.amdhsa_next_free_vgpr 20
+\t.end_amdhsa_kernel
+\t.text
+.Lfunc_end1:
+\t.size\t_Zkept, .Lfunc_end1-_Zkept
+\t.type\t_Zedited,@function
+_Zedited:
+\tv_add_f32_e32 v0, v1, v2
+\ts_endpgm
+.Lfunc_end2:
+\t.type\tsome_table,@object
+some_table:
+\t.long\t1
+"""
+
+
+def test_listing_diff_by_kernel_sees_through_renumbered_labels():
+    """tools/listing_diff.py --by-kernel on two hand-written listings: this tree's lost its first function, which
+    renumbers the local labels of the next (and its `.Ltmp`), and has one instruction changed in the third -- one function
+    only in the parent, one differing, one equal.  A changed descriptor line alone makes a kernel differ too."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("listing_diff", os.path.join(ROOT, "tools", "listing_diff.py"))
+    ld = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(ld)
+    this = _LISTING[_LISTING.index("\t.type\t_Zkept"):]
+    for old, new in ((".LBB1_", ".LBB0_"), (".Lfunc_end1", ".Lfunc_end0"), (".Lfunc_end2", ".Lfunc_end1"), (".Ltmp7", ".Ltmp3"),
+                     ("v_add_f32_e32 v0, v1, v2", "v_add_f32_e32 v0, v2, v1")):
+        assert old in this
+        this = this.replace(old, new)
+    assert set(ld.cut_functions(_LISTING)) == {"_Zgone", "_Zkept", "_Zedited"}
+    assert ld.cut_functions(_LISTING)["_Zkept"][1] == (".amdhsa_group_segment_fixed_size 1024", ".amdhsa_next_free_vgpr 20")
+    assert ld.by_kernel(_LISTING, this) == (["_Zgone"], [], ["_Zedited"], ["_Zkept"])
+    assert ld.by_kernel(this, _LISTING) == ([], ["_Zgone"], ["_Zedited"], ["_Zkept"])
+    lds = this.replace("fixed_size 1024", "fixed_size 2048")
+    assert ld.by_kernel(this, lds) == ([], [], ["_Zkept"], ["_Zedited"])
+
+
 def test_ess_workspace_size_is_a_whole_number_of_row_blocks(host_lib):
     """include/autoreparam.h: arp_ess_workspace_bytes sizes the workspace at which every listed series fits at once --
     64-row blocks, at least one (a single german-credit chain has 125 series, one parameter block of it 25)."""
