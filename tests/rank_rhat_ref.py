@@ -47,8 +47,10 @@ def rank2(v):
     out = np.empty(v.shape, np.uint32)
     for d in range(v.shape[-1]):
         col = v[..., d].reshape(-1)
-        srt = np.sort(col)
-        r = np.searchsorted(srt, col, side="left") + np.searchsorted(srt, col, side="right")
+        order = np.argsort(col, kind="stable")                            # (the needles in order: a pool of 2^21 draws
+        srt = col[order]                                                  # is searched in a fraction of the time)
+        r = np.empty(col.size, np.int64)
+        r[order] = np.searchsorted(srt, srt, side="left") + np.searchsorted(srt, srt, side="right")
         out[..., d] = r.reshape(v.shape[:-1])
     return out
 
@@ -65,15 +67,16 @@ def z_scores(r2, N):
 
 
 def rank_rhat(x):
-    """dict of [D] float64: bulk, tail, rhat = fmax, median, q05, q95 -- and the two float64 z traces [S, C, D]."""
+    """dict of [D] float64: bulk, tail, rhat = fmax, median, q05, q95 -- and the two float64 z traces [S, C, D] with the
+    rank2 [S, C, D] uint32 they come from."""
     x = np.asarray(x, np.float32)
     N = x.shape[0] * x.shape[1]
-    zb = z_scores(rank2(x), N)
-    zt = z_scores(rank2(folded(x)), N)
+    rb, rt = rank2(x), rank2(folded(x))
+    zb, zt = z_scores(rb, N), z_scores(rt, N)
     bulk, tail = rhat_ref.rhat(zb, True)[0], rhat_ref.rhat(zt, True)[0]
     q = quantiles(x, (0.05, 0.95)).astype(np.float64)
     return dict(bulk=bulk, tail=tail, rhat=np.fmax(bulk, tail), median=median(x).astype(np.float64), q05=q[0], q95=q[1],
-                z_bulk=zb, z_tail=zt)
+                z_bulk=zb, z_tail=zt, rank2_bulk=rb, rank2_tail=rt)
 
 
 def table_input(seed, S=400, Cn=64):

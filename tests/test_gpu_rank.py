@@ -30,8 +30,8 @@ RANK_FAMILIES = ("rank_rhat_bulk", "rank_rhat_tail", "posterior_median", "poster
 @functools.lru_cache(maxsize=None)
 def rank_family(S, Cn, D, seed=7):
     """The AR(1) family of tests/test_gpu_rhat.py with another offset and sign per element (a leak between segments
-    shows), and: 25 % of the rows repeat their predecessor within the chain, as rejections do; one chain is constant for
-    all S; element 1 has +0.0 and -0.0 mixed in; element 2 is constant everywhere; element 3 holds magnitudes from
+    shows), and: 25 % of the rows repeat their predecessor within the chain, as rejections do; one chain (of two or
+    more) is constant for all S; element 1 has +0.0 and -0.0 mixed in; element 2 is constant everywhere; element 3 holds magnitudes from
     subnormal to 1e30 of both signs."""
     from oracle import ess_ref
     rs = np.random.RandomState(seed)
@@ -48,21 +48,48 @@ def rank_family(S, Cn, D, seed=7):
     for s in range(1, S):
         rep = rs.rand(Cn) < 0.25
         x[s, rep] = x[s - 1, rep]
-    x[:, Cn // 2, :] = x[0, Cn // 2, :]
+    if Cn > 1:                                                # (a one-chain trace stays a varying one)
+        x[:, Cn // 2, :] = x[0, Cn // 2, :]
     if D >= 3:
         x[:, :, 2] = np.float32(2.5)
     x.setflags(write=False)
     return x
 
 
-@functools.lru_cache(maxsize=None)
-def reference(S, Cn, D, lo=0, hi=None):
-    """The yardstick on chains [lo, hi) of rank_family(S, Cn, D), computed once."""
-    x = rank_family(S, Cn, D)[:, lo:hi]
+def yardstick(x):
+    """What check_exact_and_z holds a device_run of the float32 trace x [S, C, D] to, raw and folded."""
     N = x.shape[0] * x.shape[1]
     r_raw, r_fold = ref.rank2(x), ref.rank2(ref.folded(x))
     return dict(x=x, N=N, rank2=(r_raw, r_fold), z=(ref.z_scores(r_raw, N), ref.z_scores(r_fold, N)),
                 median=ref.median(x), quantiles=ref.quantiles(x, PROBS))
+
+
+@functools.lru_cache(maxsize=None)
+def reference(S, Cn, D, lo=0, hi=None):
+    """The yardstick on chains [lo, hi) of rank_family(S, Cn, D), computed once."""
+    return yardstick(rank_family(S, Cn, D)[:, lo:hi])
+
+
+@functools.lru_cache(maxsize=None)
+def long_pool(S, Cn, D):
+    """A pool of more than 2^20 draws per element, generated without a loop over S.  Element 0: normal draws of scale 3
+    about -40, a quarter of the rows repeating their predecessor within the chain, one chain constant.  Element 1 (D = 2):
+    the float32 values 1 + k 2^-23, k uniform in 0..255 -- every key shares its upper three bytes (in passes 2 - 4 of the
+    sort one digit holds the whole segment, over all its tiles) and every value ties with N / 256 others."""
+    assert D in (1, 2)
+    rs = np.random.RandomState(S + Cn + D)
+    x = np.empty((S, Cn, D), np.float32)
+    v = (3.0 * rs.standard_normal((S, Cn)) - 40.0).astype(np.float32)
+    rep = rs.rand(S, Cn) < 0.25
+    rep[0] = False
+    src = np.maximum.accumulate(np.where(rep, 0, np.arange(S)[:, None]), axis=0)      # the last row that moved
+    v = np.take_along_axis(v, src, axis=0)
+    v[:, Cn // 2] = v[0, Cn // 2]
+    x[:, :, 0] = v
+    if D == 2:
+        x[:, :, 1] = (1.0 + rs.randint(0, 256, (S, Cn)) * 2.0 ** -23).astype(np.float32)
+    x.setflags(write=False)
+    return x
 
 
 def device_run(xd, fold):
@@ -151,6 +178,171 @@ def test_rank_rhat_against_the_yardstick(gpu, which):
     for name in ("median", "q05", "q95"):
         assert np.array_equal(getattr(got, name), want[name]), name
     assert np.array_equal(got.rows, np.full(x.shape[2], 2 * x.shape[1]))
+
+
+def both_folds(gpu, want, label, twice=True):
+    """check_exact_and_z of the trace want["x"] for fold = 0 and 1 (and, twice, the same bits from a second call)."""
+    import torch
+    xd = torch.as_tensor(np.array(want["x"]), device=gpu)
+    for fold in (0, 1):
+        got = device_run(xd, fold)
+        check_exact_and_z(got, want, fold, label)
+        if twice:
+            again = device_run(xd, fold)
+            assert all(np.array_equal(a.view(np.uint32), b.view(np.uint32)) for a, b in zip(got, again)), label
+
+
+@pytest.mark.parametrize("shape", [(1024, 1024, 1), (1025, 1024, 2), (2049, 1024, 1)])
+def test_pools_that_take_the_scan_past_one_chunk(gpu, shape):
+    """rank_scan_kernel walks a (segment, digit) row's tiles 256 at a time and adds `carry` to `row[j] = carry + ex`:
+    256 tiles fill the one chunk exactly (N = 2^20, also `valid == kTile` in every tile of the scatter), 257 put one
+    ragged tile into a second chunk, 513 take three.  A lost carry sends every key of tile 256 and later to the front of
+    its digit's run.  Element 1 of the middle shape keeps the whole segment in one digit in passes 2 - 4 and ties every
+    value with about 4 000 others (the galloping upper bound of rank_score_kernel over long runs).  The middle shape also
+    goes through diagnostics.rank_rhat."""
+    import torch
+    from autoreparam_amd import diagnostics
+    x = long_pool(*shape)
+    N = shape[0] * shape[1]
+    assert (N + 4095) // 4096 == {1024: 256, 1025: 257, 2049: 513}[shape[0]]
+    if shape[2] == 1:
+        both_folds(gpu, yardstick(x), "long pool %s" % (shape,), twice=False)
+        return
+    want = ref.rank_rhat(x)                                   # the ranks once: for the statistic and for the outputs
+    both_folds(gpu, dict(x=x, N=N, rank2=(want["rank2_bulk"], want["rank2_tail"]), z=(want["z_bulk"], want["z_tail"]),
+                         median=ref.median(x), quantiles=ref.quantiles(x, PROBS)), "long pool %s" % (shape,), twice=False)
+    got = diagnostics.rank_rhat(torch.as_tensor(np.array(x), device=gpu))
+    check_statistic(got.bulk, got.tail, got.rhat, want, "long pool %s" % (shape,))
+    for name in ("median", "q05", "q95"):
+        assert np.array_equal(getattr(got, name), want[name]), name
+
+
+@pytest.mark.parametrize("shape", [(40, 13, 129), (33, 9, 200), (17, 5, 256), (17, 5, 257)])
+def test_more_than_128_elements(gpu, shape):
+    """rank_key_kernel with blockIdx.y > 0: `d0 = blockIdx.y * dt` in the load and in the store
+    `keys[(d0 + dd) * N + i0 + r]`, a last block of 1, 72 or 128 elements (`cols = min(dt, D - d0)`, LDS pitch
+    `cols | 1`), three blocks at D = 257 -- where rank_order_stat_kernel takes a second workgroup (`d = blockIdx.x *
+    kThreads + threadIdx.x`).  Element d and element d - 128 have different pools, so a block stored to, or read from,
+    the segments of another cannot pass."""
+    want = reference(*shape)
+    srt = np.sort(ref.pools(want["x"]), axis=1)
+    assert all(not np.array_equal(srt[d], srt[d - 128]) for d in range(128, shape[2]))
+    both_folds(gpu, want, "family %s" % (shape,))
+
+
+def test_chain_sub_range_view_of_200_elements_is_bitwise_the_contiguous_result(gpu):
+    """xd[:, 2:7, :] of (33, 9, 200) in place: rank_key_kernel's `s * stride + c * D + d0 + dd` with stride > C D and
+    d0 = 128; the bits of the same chains passed contiguously, and the yardstick's values."""
+    import torch
+    S, Cn, D = 33, 9, 200
+    want = reference(S, Cn, D, 2, 7)
+    srt = np.sort(ref.pools(want["x"]), axis=1)
+    assert all(not np.array_equal(srt[d], srt[d - 128]) for d in range(128, D))
+    xd = torch.as_tensor(np.array(rank_family(S, Cn, D)), device=gpu)
+    view = xd[:, 2:7, :]
+    assert not view.is_contiguous()
+    for fold in (0, 1):
+        a, b = device_run(view, fold), device_run(view.contiguous(), fold)
+        assert all(np.array_equal(u.view(np.uint32), v.view(np.uint32)) for u, v in zip(a, b))
+        check_exact_and_z(a, want, fold, "view [:, 2:7, :] of (33, 9, 200)")
+
+
+@pytest.mark.parametrize("shape", [(9, 7, 3), (8, 8, 3), (13, 5, 3), (65, 63, 3), (64, 64, 3), (241, 17, 3), (128, 64, 3),
+                                   (4096, 1, 2), (1, 4097, 2)])
+def test_pools_at_the_edges_of_the_sort_tile_and_of_the_key_tile(gpu, shape):
+    """N = 63, 64, 65: `rows = min(kRows, N - i0)` of rank_key_kernel one short of, at and one past its 64 rows.
+    N = 4 095, 4 096, 4 097, 8 192: `valid = min(kTile, N - i0)` of rank_scatter_kernel with one 0xffffffff padding key,
+    none, a second tile of one key, two full tiles; `i < N` of rank_hist_kernel likewise.  (4096, 1, 2): one chain
+    (`s = i / C` with C = 1).  (1, 4097, 2): one row, with the row_stride = C D that diagnostics.rank_normalize passes
+    for S = 1."""
+    both_folds(gpu, reference(*shape), "family %s" % (shape,))
+
+
+def test_infinities_order_as_numbers(gpu):
+    """include/autoreparam.h: "+-inf order as numbers".  1 % of element 0 of (600, 40, 7) at +inf, 1 % at -inf: key_of
+    gives them the largest and the smallest keys of the pool, the median stays finite, and folded both are
+    |+-inf - median| = +inf -- one tie run at the top (ranked_value in rank_key_kernel and in rank_score_kernel)."""
+    x = np.array(rank_family(600, 40, 7))
+    u = np.random.RandomState(11).rand(600, 40)
+    x[:, :, 0][u < 0.01] = np.float32(np.inf)
+    x[:, :, 0][u > 0.99] = np.float32(-np.inf)
+    assert 150 < np.isposinf(x[:, :, 0]).sum() < 350 and 150 < np.isneginf(x[:, :, 0]).sum() < 350
+    want = yardstick(x)
+    assert np.isfinite(want["median"]).all() and np.isinf(want["quantiles"]).sum() == 0
+    n_inf = int(np.isinf(x[:, :, 0]).sum())
+    assert (want["rank2"][1][:, :, 0][np.isinf(x[:, :, 0])] == 2 * 24000 - n_inf).all()      # the folded tie at the top
+    both_folds(gpu, want, "(600, 40, 7) with +-inf in element 0")
+
+
+def test_nan_in_one_element_leaves_the_others_specified(gpu):
+    """include/autoreparam.h: "A NaN neither faults nor hangs; the results of an element that holds one are
+    unspecified."  NaNs of both signs in element 1 of (600, 40, 7): both folds return and synchronise (every loop of
+    rank_score_kernel halves or doubles a bounded range whatever the order of the keys), and every output of the six
+    other elements is the yardstick's on those elements alone.  Nothing is asserted about element 1."""
+    import torch
+    x = np.array(rank_family(600, 40, 7))
+    nans = np.array([0x7fc00000, 0xffc00000, 0x7f800001, 0xffffffff, 0x7fffffff], np.uint32).view(np.float32)
+    rs = np.random.RandomState(12)
+    for v in nans:
+        x[rs.randint(600), rs.randint(40), 1] = v
+    assert np.isnan(x[:, :, 1]).sum() >= 4 and not np.isnan(np.delete(x, 1, axis=2)).any()
+    keep = [0, 2, 3, 4, 5, 6]
+    want = yardstick(np.ascontiguousarray(x[:, :, keep]))
+    xd = torch.as_tensor(x, device=gpu)
+    assert np.array_equal(xd.cpu().numpy().view(np.uint32), x.view(np.uint32))      # (the payloads reach the device)
+    for fold in (0, 1):
+        z, r2, med, q = device_run(xd, fold)
+        torch.cuda.synchronize()
+        check_exact_and_z((z[:, :, keep], r2[:, :, keep], med[keep], q[:, keep]), want, fold,
+                          "(600, 40, 7) with NaN in element 1, elements %s" % (keep,))
+
+
+def test_argument_forms_of_the_c_api(gpu):
+    """arp_rank_normalize through ctypes on (64, 64, 3), N = 4 096: fold = 1 with median == NULL (`med = median ? median
+    : ws + L.med`) gives the bits of the call that passes a median; rank2 == NULL with quantiles (`if (rank2) rank2[e] =
+    r2`); quantiles == NULL with n_probs > 0 (`want_q`) returns 0 with the same z; probabilities at and beyond the clamp
+    `k = !(pk >= 1) ? 1 : pk >= N ? N : pk` give the yardstick's order statistics."""
+    import torch
+    from autoreparam_amd import _lib
+    L = _lib.lib()
+    S, Cn, D = 64, 64, 3
+    want = reference(S, Cn, D)
+    x = torch.as_tensor(np.array(want["x"]), device=gpu)
+    need = int(L.arp_rank_workspace_bytes(S, Cn, D, 1))
+    ws = torch.empty(need, dtype=torch.uint8, device=gpu)
+    assert need > 0 and ws.data_ptr() % 256 == 0
+    st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    probs = (-0.1, 0.0, 1e-12, 0.5, 1.0, 1.5)
+    pr = (C.c_double * len(probs))(*probs)
+
+    def call(fold, rank2=True, median=True, quantiles=True, n_probs=len(probs)):
+        z = torch.full((S, Cn, D), float("nan"), dtype=torch.float32, device=gpu)
+        r2 = torch.full((S, Cn, D), -1, dtype=torch.int32, device=gpu) if rank2 else None
+        med = torch.full((D,), float("nan"), dtype=torch.float32, device=gpu) if median else None
+        q = torch.full((len(probs), D), float("nan"), dtype=torch.float32, device=gpu) if quantiles else None
+        ptr = lambda t: C.c_void_p(t.data_ptr() if t is not None else 0)
+        rc = L.arp_rank_normalize(C.c_void_p(x.data_ptr()), S, Cn, D, Cn * D, fold, ptr(z), ptr(r2), ptr(med), pr, n_probs,
+                                  ptr(q), C.c_void_p(ws.data_ptr()), need, st)
+        assert rc == 0, L.arp_last_error()
+        torch.cuda.synchronize()
+        return [None if t is None else t.cpu().numpy() for t in (z, r2, med, q)]
+
+    same = lambda a, b: np.array_equal(a.view(np.uint32), b.view(np.uint32))
+    want_q = ref.quantiles(want["x"], probs)
+    srt = np.sort(ref.pools(want["x"]), axis=1)
+    assert np.array_equal(want_q, np.stack([srt[:, k] for k in (0, 0, 0, 2047, 4095, 4095)]))
+    for fold in (0, 1):
+        z, r2, med, q = call(fold)
+        assert np.array_equal(r2.view(np.uint32), want["rank2"][fold]) and np.array_equal(med, want["median"])
+        assert np.array_equal(q, want_q), fold
+        z_a, r2_a, _, q_a = call(fold, median=False)                      # fold = 1: the median lives in the workspace
+        assert same(z_a, z) and same(r2_a, r2) and same(q_a, q), fold
+        z_b, _, med_b, q_b = call(fold, rank2=False)
+        assert same(z_b, z) and same(med_b, med) and same(q_b, q), fold
+        z_c, r2_c, med_c, _ = call(fold, quantiles=False)
+        assert same(z_c, z) and same(r2_c, r2) and same(med_c, med), fold
+        z_d, _, _, _ = call(fold, rank2=False, median=False, quantiles=False)
+        assert same(z_d, z), fold
 
 
 @pytest.mark.parametrize("seed", [0, 1, 2])
