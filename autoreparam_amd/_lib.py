@@ -74,7 +74,7 @@ class ViIO(C.Structure):
 # every symbol include/autoreparam.h declares
 SYMBOLS = ["arp_version", "arp_last_error", "arp_model_create", "arp_model_destroy", "arp_model_dim",
            "arp_model_logp_const", "arp_model_set_param", "arp_model_set_option", "arp_logp_grad", "arp_transform",
-           "arp_hmc_run", "arp_interleaved_run", "arp_model_check", "arp_vi_run", "arp_vi_geometry", "arp_vi_attempts", "arp_relay_geometry", "arp_ess", "arp_ess_ws", "arp_ess_workspace_bytes",
+           "arp_hmc_run", "arp_interleaved_run", "arp_model_check", "arp_vi_run", "arp_vi_geometry", "arp_vi_attempts", "arp_relay_geometry", "arp_relay_schedule", "arp_ess", "arp_ess_ws", "arp_ess_workspace_bytes",
            "arp_moments_workspace_bytes", "arp_split_moments", "arp_moments_fold",
            "arp_rank_workspace_bytes", "arp_rank_normalize",
            "arp_adapt_probe", "arp_clock_probe"]
@@ -111,6 +111,8 @@ def lib():
     L.arp_vi_geometry.argtypes = [C.POINTER(C.c_int32)]
     L.arp_vi_attempts.argtypes = [C.POINTER(C.c_int32)]
     L.arp_relay_geometry.argtypes = [C.POINTER(C.c_int32)]
+    L.arp_relay_schedule.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int]
+    L.arp_relay_schedule.restype = C.c_int
     L.arp_model_check.argtypes = [C.c_void_p]
     L.arp_ess.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]
     L.arp_ess_ws.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]

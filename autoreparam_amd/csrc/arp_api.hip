@@ -287,10 +287,39 @@ static void fill_adapt(HmcParams& P, const arp_hmc_config* cfg) {
 // zeroed flag word per chain block that belongs to THIS launch alone -- a stream-ordered allocation, given back behind the
 // launch (relay_release), so launches of one handle that overlap on different streams never share a word -- and `segs` =
 // -1 (the launcher decides with its kernel's occupancy), a forced count (ARP_DEBUG=1 ARP_SEGMENTS=n) or 1 (`allowed` false).
+// How the steps are cut (host_common.h: relay_schedule, relay_cut) is the library's ratio unless ARP_DEBUG=1
+// ARP_SEGMENT_RATIO=percent or ARP_SEGMENT_LENS=n0,n1,... (which also forces the count) says otherwise.
 // no relay: the launch's steps in one segment (P.n_steps is set)
 static void relay_off(HmcParams& P) {
   P.segs = 1; P.seg_len = P.n_steps; P.seg_blocks = 0; P.seg_epoch = 0; P.seg_flags = nullptr;
   P.seg_ctrl = nullptr; P.seg_err_host = nullptr; P.seg_timeout = 6000000000ull; P.seg_fault = 0;
+  for (int& v : P.seg_start) v = 0;
+#ifdef ARP_EXP_RELAY_STAMPS
+  P.seg_stamps = nullptr;
+#endif
+}
+// ARP_SEGMENT_LENS: explicit segment lengths of a launch of n_steps; a list that is not one is refused, never replaced
+static int relay_explicit_cut(const char* list, int n_steps, arp::RelayCut* cut) {
+  long long sum = 0;
+  int n = 0;
+  for (const char* p = list; *p;) {
+    char* end = nullptr;
+    const long v = strtol(p, &end, 10);
+    if (end == p || (*end && *end != ',') || v < 1 || n == kSegTable) {
+      set_error("ARP_SEGMENT_LENS: want 1 to " + std::to_string(kSegTable) + " comma-separated lengths >= 1, got '" + list + "'");
+      return 1;
+    }
+    cut->lens[n++] = (int)(v < 0x7fffffff ? v : 0x7fffffff);
+    sum += v;
+    p = *end ? end + 1 : end;
+  }
+  if (sum != n_steps) {
+    set_error("ARP_SEGMENT_LENS: the lengths '" + std::string(list) + "' sum to " + std::to_string(sum) + ", the launch has " +
+              std::to_string(n_steps) + " steps");
+    return 1;
+  }
+  cut->n_lens = n;
+  return 0;
 }
 static int relay_prepare(arp_model* m, const arp_hmc_config* cfg, int K, bool allowed, hipStream_t stream, HmcParams* P) {
   relay_off(*P);
@@ -298,13 +327,25 @@ static int relay_prepare(arp_model* m, const arp_hmc_config* cfg, int K, bool al
   if (!allowed || cfg->n_steps < 256) return 0;
   int segs = -1, dbg = 0;
   if (debug_int("ARP_SEGMENTS", &dbg) && dbg >= 1 && dbg <= 64) segs = dbg;
+  arp::RelayCut& cut = arp::relay_cut();
+  cut = arp::RelayCut();
+  if (debug_int("ARP_SEGMENT_RATIO", &dbg) && dbg >= 1 && dbg <= 100) cut.ratio_pct = dbg;
+  if (const char* lens = debug_switch("ARP_SEGMENT_LENS")) {
+    if (relay_explicit_cut(lens, cfg->n_steps, &cut)) return 1;
+    segs = cut.n_lens;
+  }
   if (segs == 1) return 0;
   const long long blocks = ((long long)cfg->n_chains * K + kBlock - 1) / kBlock;
   // no kernel gets segments below one round of two workgroups per CU (relay_plan): spare those launches the allocation
   if (segs == -1 && blocks < 2LL * m->cus) return 0;
   // one zeroed flag word per chain block, then the launch's ticket counter and its failure word
   void* flags = nullptr;
-  const size_t bytes = ((size_t)blocks + 2) * sizeof(unsigned);
+  size_t bytes = ((size_t)blocks + 2) * sizeof(unsigned);
+#ifdef ARP_EXP_RELAY_STAMPS              // timing experiment only: kStamps words per workgroup behind the flags (kernels.h: relay_stamp)
+  const size_t stamps_at = (bytes + 7) / 8 * 8;
+  const int stamp_segs = segs > 0 ? segs : 8;
+  bytes = stamps_at + (size_t)stamp_segs * blocks * kStamps * sizeof(unsigned long long);
+#endif
   ARP_HIP_OK(hipMallocAsync(&flags, bytes, stream));
   const hipError_t zeroed = hipMemsetAsync(flags, 0, bytes, stream);
   if (zeroed != hipSuccess) {
@@ -314,6 +355,9 @@ static int relay_prepare(arp_model* m, const arp_hmc_config* cfg, int K, bool al
   P->segs = segs; P->seg_blocks = (int)blocks; P->seg_epoch = 0u; P->seg_flags = (unsigned*)flags;
   P->seg_ctrl = (unsigned*)flags + blocks;
   P->seg_err_host = m->relay_err_dev;
+#ifdef ARP_EXP_RELAY_STAMPS
+  P->seg_stamps = (unsigned long long*)((char*)flags + stamps_at);
+#endif
   // test hooks (ARP_DEBUG=1 only): a short time-out, and segments that never raise their flag -- the failure path on demand
   if (debug_int("ARP_RELAY_TIMEOUT_MS", &dbg) && dbg > 0) P->seg_timeout = 100000ull * (unsigned long long)dbg;
   if (debug_int("ARP_RELAY_FAULT", &dbg) && dbg == 1) P->seg_fault = 1;
@@ -329,6 +373,22 @@ static int relay_failed(arp_model* m, const char* where) {
   return 1;
 }
 static int relay_release(const HmcParams& P, hipStream_t stream) {
+#ifdef ARP_EXP_RELAY_STAMPS
+  // the launch's stamps into the file ARP_RELAY_STAMPS_OUT names (each launch overwrites it): segments, chain blocks, kStamps,
+  // then kStamps 64-bit words per ticket -- tools/relay_stamps.py reads it.  Waits for the launch: an experiment build only.
+  const char* out = P.seg_flags ? debug_switch("ARP_RELAY_STAMPS_OUT") : nullptr;
+  const RelayGeometry g = relay_last();
+  if (out && g.v[0] > 1) {
+    std::vector<unsigned long long> w(3 + (size_t)g.v[0] * g.v[1] * kStamps);
+    w[0] = (unsigned long long)g.v[0]; w[1] = (unsigned long long)g.v[1]; w[2] = kStamps;
+    ARP_HIP_OK(hipStreamSynchronize(stream));
+    ARP_HIP_OK(hipMemcpy(w.data() + 3, P.seg_stamps, (w.size() - 3) * sizeof(w[0]), hipMemcpyDeviceToHost));
+    if (FILE* f = fopen(out, "wb")) {
+      fwrite(w.data(), sizeof(w[0]), w.size(), f);
+      fclose(f);
+    }
+  }
+#endif
   if (P.seg_flags) ARP_HIP_OK(hipFreeAsync(P.seg_flags, stream));
   return 0;
 }
@@ -634,6 +694,17 @@ int arp_vi_attempts(int32_t* out1) {
   if (!out1) { set_error("arp_vi_attempts: null argument"); return 1; }
   *out1 = g_vi_attempts;
   return 0;
+}
+
+int arp_relay_schedule(int n_steps, int segs, int ratio_pct, int32_t* out, int cap) {
+  if (!out || n_steps < 1 || segs < 1 || segs > n_steps || segs > cap || ratio_pct > 100) {
+    set_error("arp_relay_schedule: want 1 <= segs <= n_steps, segs <= cap, ratio_pct <= 100 and a buffer");
+    return 0;
+  }
+  std::vector<int> len(segs);
+  relay_schedule(n_steps, segs, (ratio_pct > 0 ? ratio_pct : kSegRatioPct) / 100.0, len.data());
+  for (int s = 0; s < segs; ++s) out[s] = len[s];
+  return segs;
 }
 
 int arp_relay_geometry(int32_t* out3) {

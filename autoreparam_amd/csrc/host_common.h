@@ -93,6 +93,42 @@ inline RelayGeometry& relay_last() {
   static thread_local RelayGeometry g = {{1, 0, 0}};
   return g;
 }
+// The cut of a launch's n_steps into `segs` segments (1 <= segs <= n_steps), lengths proportional to ratio^s: a free slot
+// takes the next (segment, block) in line, so the launch ends with slots idle for about half a last-round segment -- a short
+// last round leaves a short tail, and the hand-overs stay `segs` per block (profiles/r07_relay_schedule.txt).  Every
+// segment gets one step, the rest goes out in proportion (rounded down), what the rounding leaves to the first segments:
+// the lengths sum to n_steps, never increase and are all >= 1.  ratio = 1 is the equal cut as it has always been,
+// ceil(n_steps / segs) steps each and the last segment what is left (where that leaves every segment a step).
+inline void relay_schedule(int n_steps, int segs, double ratio, int* len) {   // len[segs]
+  const int each = (n_steps + segs - 1) / segs;
+  if (ratio >= 1.0 && n_steps - (segs - 1) * each >= 1) {
+    for (int s = 0; s < segs; ++s) len[s] = s + 1 < segs ? each : n_steps - (segs - 1) * each;
+    return;
+  }
+  if (ratio > 1.0) ratio = 1.0;
+  double w = 1.0, sum = 0.0;
+  for (int s = 0; s < segs; ++s) { sum += w; w *= ratio; }
+  const int spare = n_steps - segs;
+  int left = spare;
+  w = 1.0;
+  for (int s = 0; s < segs; ++s) {
+    int extra = (int)((double)spare * (w / sum));
+    if (extra > left) extra = left;
+    len[s] = 1 + extra;
+    left -= extra;
+    w *= ratio;
+  }
+  for (int s = 0; left > 0; s = s + 1 < segs ? s + 1 : 0, --left) len[s] += 1;
+}
+// ratio of the library's own cut, in percent: chosen by measurement (profiles/r07_relay_schedule.txt)
+constexpr int kSegRatioPct = 70;
+// What the calling thread's next chain launch is asked to cut with (arp_api.hip: relay_prepare, right before the launcher
+// runs on the same thread): the ratio in percent, or explicit lengths (n_lens > 0: they sum to the launch's n_steps)
+struct RelayCut { int ratio_pct = kSegRatioPct; int n_lens = 0; int lens[kSegTable] = {}; };
+inline RelayCut& relay_cut() {
+  static thread_local RelayCut c;
+  return c;
+}
 template <class F>
 inline HmcParams relay_plan(const HmcParams& P, int blocks, F kernel) {
   HmcParams Q = P;
@@ -124,6 +160,13 @@ inline HmcParams relay_plan(const HmcParams& P, int blocks, F kernel) {
   Q.segs = segs;
   Q.seg_len = (P.n_steps + segs - 1) / segs;
   Q.seg_blocks = blocks;
+  if (segs > 1 && segs <= kSegTable) {
+    const RelayCut& cut = relay_cut();
+    int len[kSegTable];
+    relay_schedule(P.n_steps, segs, cut.ratio_pct / 100.0, len);
+    Q.seg_start[0] = 0;
+    for (int i = 0; i < segs; ++i) Q.seg_start[i + 1] = Q.seg_start[i] + (cut.n_lens == segs ? cut.lens[i] : len[i]);
+  }
   relay_last() = {{segs, blocks, occ_seen}};
   return Q;
 }

@@ -12,6 +12,7 @@ namespace arp {
 
 constexpr int kRngSlots = 16;    // rng buffer stride per chain (max lanes per chain)
 constexpr int kMaxD = 256;       // largest state dimension the chain kernels stage in LDS
+constexpr int kSegTable = 16;    // relay segments a launch can give lengths of their own (HmcParams::seg_start)
 
 struct HmcParams {
   int C, L, n_steps;
@@ -35,8 +36,9 @@ struct HmcParams {
   // interleaved kernel only: second transition kernel (parameterisation 1)
   int L1;
   float* adapt1; uint32_t* accept_count1; const float* eps0_1; uint8_t* trace_accept1; uint32_t* rec_accept1;
-  // Relay (radon_fast.h: radon_interleaved_kernel): the launch's n_steps cut into `segs` segments of seg_len steps, a workgroup
-  // per (segment, chain block); segment s of a block starts when seg_flags[block] == seg_epoch + s.  segs <= 1: one workgroup
+  // Relay (radon_fast.h: radon_interleaved_kernel): the launch's n_steps cut into `segs` segments, a workgroup per (segment,
+  // chain block); segment s takes the steps seg_start[s] .. seg_start[s + 1] (host_common.h: relay_schedule; more than
+  // kSegTable segments: seg_len steps each) and starts when seg_flags[block] == seg_epoch + s.  segs <= 1: one workgroup
   // per block takes all the steps.
   int segs, seg_len, seg_blocks;
   unsigned seg_epoch;
@@ -47,6 +49,10 @@ struct HmcParams {
   unsigned* seg_err_host;
   unsigned long long seg_timeout;   // ticks of the 100 MHz clock a segment waits for the one before it
   int seg_fault;                    // test hook (ARP_DEBUG=1 ARP_RELAY_FAULT=1): segments never raise their flag
+  int seg_start[kSegTable + 1];     // first step of every segment, then n_steps (segs <= kSegTable)
+#ifdef ARP_EXP_RELAY_STAMPS         // timing experiment only (tools/relay_stamps.py): kStamps words per ticket
+  unsigned long long* seg_stamps;
+#endif
 };
 
 // The recording schedule of the steps P describes -- a launch (arp_api.hip: fill_params) or one relay segment of it
@@ -77,14 +83,30 @@ __host__ __device__ __forceinline__ void rec_schedule(HmcParams& P) {
 // workgroups out in and whatever else shares the device.  The lowest unfinished ticket never waits on an unfinished one, so
 // the launch always advances (no reliance on in-order dispatch: round 5's form indexed with blockIdx).
 // relay_begin rewrites the kernel's OWN copy of the parameters to the segment's view (steps, first transition, recording
-// schedule -- rec_schedule, as arp_api.hip: fill_params calls it for the launch); relay_end raises the flag.  A wait is bounded (seg_timeout):
+// schedule -- rec_schedule, as arp_api.hip: fill_params calls it for the launch): P, which the kernel copies from the P0 it was
+// launched with.  seg_start is P0's table, read where the launch put it -- indexing the copy that is written to would send
+// the whole parameter block to scratch.  relay_end raises the flag.  A wait is bounded (seg_timeout):
 // on expiry the launch is marked failed -- device word for the other waiters, pinned host word for arp_model_check -- and
 // every workgroup still waiting returns at once (seg < 0).  Segments that ran before have stored their steps, so such a launch
 // leaves its chains partly advanced -- discard them.
 // ---------------------------------------------------------------------------
 struct RelayId { unsigned bid; int seg; };
-ARP_DEV RelayId relay_begin(HmcParams& P) {
+// Timing experiment only (-DARP_EXP_RELAY_STAMPS; tools/relay_stamps.py, profiles/r07_relay_schedule.txt): thread 0 of every
+// workgroup of a relay launch writes the 100 MHz clock at kernel entry (0), after the ticket wait (1), at the first step (2),
+// after the last step (3) and before exit (4), and where it ran (5), into the launch's kStamps words of its ticket.  The
+// default build compiles none of it.
+constexpr int kStamps = 6;
+ARP_DEV void relay_stamp(const HmcParams& P, RelayId r, int i) {
+#ifdef ARP_EXP_RELAY_STAMPS
+  if (P.segs > 1 && P.seg_stamps && r.seg >= 0 && threadIdx.x == 0)
+    P.seg_stamps[((size_t)r.seg * P.seg_blocks + r.bid) * kStamps + i] = __builtin_amdgcn_s_memrealtime();
+#endif
+}
+ARP_DEV RelayId relay_begin(HmcParams& P, const int* seg_start) {
   RelayId r{blockIdx.x, 0};
+#ifdef ARP_EXP_RELAY_STAMPS
+  const unsigned long long t_entry = __builtin_amdgcn_s_memrealtime();
+#endif
   if (P.segs > 1) {
     __shared__ unsigned s_relay[2];      // ticket, abort
     if (threadIdx.x == 0) {
@@ -99,8 +121,14 @@ ARP_DEV RelayId relay_begin(HmcParams& P) {
     r.bid = (unsigned)__builtin_amdgcn_readfirstlane((int)s_relay[0]);     // uniform: the segment's view stays in SGPRs
     r.seg = (int)(r.bid / (unsigned)P.seg_blocks);
     r.bid -= (unsigned)r.seg * (unsigned)P.seg_blocks;
-    const int start = r.seg * P.seg_len;
-    int n = min(P.seg_len, P.n_steps - start);
+    int start, n;
+    if (P.segs <= kSegTable) {
+      start = seg_start[r.seg];
+      n = seg_start[r.seg + 1] - start;
+    } else {
+      start = r.seg * P.seg_len;
+      n = min(P.seg_len, P.n_steps - start);
+    }
     P.n_steps = n < 0 ? 0 : n;
     P.step_base += start;
     if (r.seg > 0) {
@@ -128,6 +156,16 @@ ARP_DEV RelayId relay_begin(HmcParams& P) {
       __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
       if (__builtin_amdgcn_readfirstlane((int)s_relay[1])) r.seg = -1;
     }
+#ifdef ARP_EXP_RELAY_STAMPS
+    if (P.seg_stamps && r.seg >= 0 && threadIdx.x == 0) {
+      unsigned long long* const w = P.seg_stamps + ((size_t)r.seg * P.seg_blocks + r.bid) * kStamps;
+      w[0] = t_entry;
+      // HW_ID (wave, SIMD, CU, SH, SE) and XCC_ID: which slot of the device the workgroup held
+      w[5] = (unsigned long long)__builtin_amdgcn_s_getreg(4 | (31 << 11)) |
+             ((unsigned long long)__builtin_amdgcn_s_getreg(20 | (3 << 11)) << 32);
+    }
+    relay_stamp(P, r, 1);
+#endif
   }
   return r;
 }
@@ -143,6 +181,7 @@ ARP_DEV void relay_end(const HmcParams& P, RelayId r) {
     if (threadIdx.x == 0 && !P.seg_fault) {
       __hip_atomic_store(P.seg_flags + r.bid, P.seg_epoch + (unsigned)r.seg + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
+    relay_stamp(P, r, 4);
   }
 }
 
@@ -637,9 +676,10 @@ ARP_DEV void adapt_update(const HmcParams& P, long long n, float la,
 
 template <class Lane, int MODE = kModeVIP>
 __global__ __launch_bounds__(kBlock, Lane::MINW) void hmc_kernel(
-    typename Lane::Args A, const float* __restrict__ av, const float* __restrict__ bv, HmcParams P) {
+    typename Lane::Args A, const float* __restrict__ av, const float* __restrict__ bv, const HmcParams P0) {
   constexpr int K = Lane::K, ND = Lane::ND;
-  const RelayId rid = relay_begin(P);
+  HmcParams P = P0;     // the segment's view (relay_begin rewrites it); the launch's stays where the kernel got it
+  const RelayId rid = relay_begin(P, P0.seg_start);
   if (rid.seg < 0) return;                 // a hand-over timed out: leave the state as it is (kernels.h: relay_begin)
   long long t = (long long)rid.bid * kBlock + threadIdx.x;
   const int slot = (int)(t % K);
@@ -697,6 +737,7 @@ __global__ __launch_bounds__(kBlock, Lane::MINW) void hmc_kernel(
   if (threadIdx.x == 0) for (int k = 0; k < 16; ++k) exp_t()[k] = 0;
   ARP_T0(tk);
 #endif
+  relay_stamp(P, rid, 2);
   for (int s = 0; s < P.n_steps; ++s) {
     load_row(M, s_eps, eps);
 #pragma unroll
@@ -737,6 +778,7 @@ __global__ __launch_bounds__(kBlock, Lane::MINW) void hmc_kernel(
       rec_row += 1;
     }
   }
+  relay_stamp(P, rid, 3);
 
 #ifdef ARP_EXP_TIMING
   ARP_T(8, tk);
@@ -779,9 +821,10 @@ __global__ __launch_bounds__(kBlock, Lane::MINW) void hmc_kernel(
 template <class Lane, int M0 = kModeVIP, int M1 = kModeVIP>
 __global__ __launch_bounds__(kBlock, Lane::MINW) void interleaved_kernel(
     typename Lane::Args A, const float* __restrict__ av0, const float* __restrict__ bv0,
-    const float* __restrict__ av1, const float* __restrict__ bv1, HmcParams P) {
+    const float* __restrict__ av1, const float* __restrict__ bv1, const HmcParams P0) {
   constexpr int K = Lane::K, ND = Lane::ND;
-  const RelayId rid = relay_begin(P);
+  HmcParams P = P0;     // the segment's view (relay_begin rewrites it); the launch's stays where the kernel got it
+  const RelayId rid = relay_begin(P, P0.seg_start);
   if (rid.seg < 0) return;                 // a hand-over timed out: leave the state as it is (kernels.h: relay_begin)
   long long t = (long long)rid.bid * kBlock + threadIdx.x;
   const int slot = (int)(t % K);
@@ -829,6 +872,7 @@ __global__ __launch_bounds__(kBlock, Lane::MINW) void interleaved_kernel(
   float lp;
   int next_rec = P.rec_step, rec_row = P.rec_row, bpos = P.stats_bpos;
   __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): see hmc_kernel
+  relay_stamp(P, rid, 2);
   for (int s = 0; s < P.n_steps; ++s) {
     const long long n = P.step_base + s + 1;
     bool acc0, acc1;
@@ -880,6 +924,7 @@ __global__ __launch_bounds__(kBlock, Lane::MINW) void interleaved_kernel(
       rec_row += 1;
     }
   }
+  relay_stamp(P, rid, 3);
 
   long long c2 = c;
   asm volatile("" : "+v"(c2));

@@ -441,10 +441,11 @@ struct PkBlock {
 #endif
 template <class T, int MODE, bool STATS = false>
 __global__ __launch_bounds__(kBlock, (STATS || MODE == ARP_PK_VIP_MINW2) && T::MINW > 2 ? 2 : T::MINW) void pk_hmc_kernel(
-    typename T::Args A, const float* __restrict__ av, const float* __restrict__ bv, HmcParams P) {
+    typename T::Args A, const float* __restrict__ av, const float* __restrict__ bv, const HmcParams P0) {
   constexpr int K = T::K, NP = T::NP, ND = T::ND, NG = T::NG;
   // chain of this lane (a launch holds fewer than 2^31 / K chains: 32-bit lane arithmetic)
-  const RelayId rid = relay_begin(P);
+  HmcParams P = P0;     // the segment's view (relay_begin rewrites it); the launch's stays where the kernel got it
+  const RelayId rid = relay_begin(P, P0.seg_start);
   if (rid.seg < 0) return;                 // a hand-over timed out: leave the state as it is (kernels.h: relay_begin)
   const unsigned t = rid.bid * (unsigned)kBlock + threadIdx.x;
   const int slot = (int)(t % K);
@@ -501,6 +502,7 @@ __global__ __launch_bounds__(kBlock, (STATS || MODE == ARP_PK_VIP_MINW2) && T::M
 
   int next_rec = P.rec_step, rec_row = P.rec_row, bpos = P.stats_bpos;
   __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): nothing loaded is awaited inside the loop (kernels.h: hmc_kernel)
+  relay_stamp(P, rid, 2);
   for (int s = 0; s < P.n_steps; ++s) {
     bool acc;
     const float la = pk_transition<MODE>(M, rng, P.L, kappa, s_eps, qg, qc, gg_, gc, lp, acc, save);
@@ -550,6 +552,7 @@ __global__ __launch_bounds__(kBlock, (STATS || MODE == ARP_PK_VIP_MINW2) && T::M
       rec_row += 1;
     }
   }
+  relay_stamp(P, rid, 3);
 
   // the launch ends inside a batch: what the accumulators hold goes into s1 / s2 now, the batch mean when the batch ends
   if (STATS && n_acc > 0) pk_stats_fold(M, stage, s_stats, P, cw0, cl, D, nvalid, n_acc, rec_row == n_acc, false);
@@ -578,9 +581,10 @@ __global__ __launch_bounds__(kBlock, (STATS || MODE == ARP_PK_VIP_MINW2) && T::M
 // T additionally provides from_centered<MODE>.
 template <class T, int M0, int M1, bool STATS = false>
 __global__ __launch_bounds__(kBlock, STATS && T::MINW > 2 ? 2 : T::MINW) void pk_interleaved_kernel(
-    typename T::Args A, const float* __restrict__ av0, const float* __restrict__ bv0, HmcParams P) {
+    typename T::Args A, const float* __restrict__ av0, const float* __restrict__ bv0, const HmcParams P0) {
   constexpr int K = T::K, NP = T::NP, ND = T::ND, NG = T::NG;
-  const RelayId rid = relay_begin(P);
+  HmcParams P = P0;     // the segment's view (relay_begin rewrites it); the launch's stays where the kernel got it
+  const RelayId rid = relay_begin(P, P0.seg_start);
   if (rid.seg < 0) return;                 // a hand-over timed out: leave the state as it is (kernels.h: relay_begin)
   const unsigned t = rid.bid * (unsigned)kBlock + threadIdx.x;
   const int slot = (int)(t % K);
@@ -631,6 +635,7 @@ __global__ __launch_bounds__(kBlock, STATS && T::MINW > 2 ? 2 : T::MINW) void pk
   }
   int next_rec = P.rec_step, rec_row = P.rec_row, bpos = P.stats_bpos;
   __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
+  relay_stamp(P, rid, 2);
   for (int s = 0; s < P.n_steps; ++s) {
     const long long n = P.step_base + s + 1;
     bool acc0, acc1;
@@ -692,6 +697,7 @@ __global__ __launch_bounds__(kBlock, STATS && T::MINW > 2 ? 2 : T::MINW) void pk
       rec_row += 1;
     }
   }
+  relay_stamp(P, rid, 3);
   if (STATS && n_acc > 0) pk_stats_fold(M, stage, s_stats, P, cw0, cl, D, nvalid, n_acc, rec_row == n_acc, false);
   size_t c2 = (size_t)c;
   asm volatile("" : "+v"(c2));

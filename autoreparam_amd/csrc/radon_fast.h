@@ -240,9 +240,10 @@ struct RadonPk {
 // step-size adaptation state (inference.py:288-306).  The gradient and log density are carried across the
 // shear (`carry` above) instead of being recomputed as kernels.h: interleaved_kernel does, 2*num_ls gradient evaluations per step.
 template <class T, bool STATS = false>
-__global__ __launch_bounds__(kBlock, T::MINW) void radon_interleaved_kernel(RadonArgs A, HmcParams P) {
+__global__ __launch_bounds__(kBlock, T::MINW) void radon_interleaved_kernel(RadonArgs A, const HmcParams P0) {
   constexpr int K = T::K, NP = T::NP, ND = T::ND;
-  const RelayId rid = relay_begin(P);      // kernels.h: the launch's steps in segments, a workgroup per (segment, chain block)
+  HmcParams P = P0;     // the segment's view (relay_begin rewrites it); the launch's stays where the kernel got it
+  const RelayId rid = relay_begin(P, P0.seg_start);      // kernels.h: the launch's steps in segments, a workgroup per (segment, chain block)
   if (rid.seg < 0) return;                 // a hand-over timed out: leave the state as it is (kernels.h: relay_begin)
   const unsigned bid = rid.bid;
   const unsigned t = bid * (unsigned)kBlock + threadIdx.x;
@@ -302,6 +303,7 @@ __global__ __launch_bounds__(kBlock, T::MINW) void radon_interleaved_kernel(Rado
   }
   int next_rec = P.rec_step, rec_row = P.rec_row, bpos = P.stats_bpos;
   __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
+  relay_stamp(P, rid, 2);
   for (int s = 0; s < P.n_steps; ++s) {
     const long long n = P.step_base + s + 1;
     bool acc0, acc1;
@@ -348,6 +350,7 @@ __global__ __launch_bounds__(kBlock, T::MINW) void radon_interleaved_kernel(Rado
       rec_row += 1;
     }
   }
+  relay_stamp(P, rid, 3);
 
   if (STATS && n_acc > 0) pk_stats_fold(M, stage, s_stats, P, cw0, cl, D, nvalid, n_acc, rec_row == n_acc, false);
   size_t c2 = (size_t)c;

@@ -229,6 +229,15 @@ class Engine(object):
         _lib.check(self._L.arp_relay_geometry(out))
         return dict(zip(("segments", "chain_blocks", "workgroups_per_cu"), [int(v) for v in out]))
 
+    @staticmethod
+    def relay_schedule(n_steps, segs, ratio_pct=0):
+        """Segment lengths the library cuts a launch of n_steps into `segs` relay segments with (arp_relay_schedule):
+        proportional to (ratio_pct / 100)^s; ratio_pct 0: the library's own ratio.  Needs no device."""
+        out = (C.c_int32 * max(int(segs), 1))()
+        if _lib.lib().arp_relay_schedule(int(n_steps), int(segs), int(ratio_pct), out, len(out)) != int(segs) or segs < 1:
+            _lib.check(1)
+        return [int(v) for v in out]
+
     def vi_attempts(self):
         """Launches this thread's last vi_run needed (arp_vi_attempts): 1 unless a hand-off ran into its bound and the fit was retaken."""
         out = (C.c_int32 * 1)()

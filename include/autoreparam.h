@@ -248,6 +248,12 @@ int arp_model_check(arp_model* m);
  * the kernel one CU holds (0 where the question did not arise)}. */
 int arp_relay_geometry(int32_t* out3);
 
+/* The cut of a launch's n_steps into `segs` relay segments: lengths proportional to
+ * (ratio_pct / 100)^s -- ratio_pct <= 0: the ratio the library itself cuts with -- that sum to n_steps, never increase and
+ * are all >= 1; 100 is the equal cut.  Writes out[0 .. segs) (cap: the buffer's length) and returns segs, or 0 with
+ * arp_last_error set (segs < 1, segs > n_steps, segs > cap, ratio_pct > 100).  A pure function: needs no device. */
+int arp_relay_schedule(int n_steps, int segs, int ratio_pct, int32_t* out, int cap);
+
 /* Effective sample size of every series of a recorded trace (replaces tfp.mcmc.effective_sample_size with its
  * defaults, inference.py:240, 327): `trace` holds n_samples rows of `row_stride` floats, series i is column i
  * (i < n_series, e.g. n_series = C*D of a [S][C][D] trace); ess[i] = S / (-1 + 2 sum_k (S-k)/S rho_k) with the
