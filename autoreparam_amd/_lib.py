@@ -77,6 +77,7 @@ SYMBOLS = ["arp_version", "arp_last_error", "arp_model_create", "arp_model_destr
            "arp_hmc_run", "arp_interleaved_run", "arp_model_check", "arp_vi_run", "arp_vi_geometry", "arp_vi_attempts", "arp_relay_geometry", "arp_relay_schedule", "arp_ess", "arp_ess_ws", "arp_ess_workspace_bytes",
            "arp_moments_workspace_bytes", "arp_split_moments", "arp_moments_fold",
            "arp_rank_workspace_bytes", "arp_rank_normalize",
+           "arp_ess_multichain_workspace_bytes", "arp_ess_multichain",
            "arp_adapt_probe", "arp_clock_probe"]
 
 _lib = None
@@ -132,6 +133,11 @@ def lib():
                                      C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.c_int32, C.c_void_p,
                                      C.c_void_p, C.c_int64, C.c_void_p]
     L.arp_rank_normalize.restype = C.c_int
+    L.arp_ess_multichain_workspace_bytes.argtypes = [C.c_int64, C.c_int64, C.c_int32, C.c_int]
+    L.arp_ess_multichain_workspace_bytes.restype = C.c_int64
+    L.arp_ess_multichain.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int64, C.c_int, C.c_void_p,
+                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]
+    L.arp_ess_multichain.restype = C.c_int
     L.arp_clock_probe.argtypes = [C.c_int, C.c_void_p, C.c_void_p]
     L.arp_adapt_probe.argtypes = [C.POINTER(HmcConfig), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     _lib = L

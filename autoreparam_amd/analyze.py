@@ -97,6 +97,12 @@ def report_rhat(results, results_dir=None, model_name=None, threshold=1.01):
             fmt(r["split_rhat_max"][-1]), r["split_rhat_chains"][-1], fmt(r["rhat_max_all_chains"][-1]), rank_cols,
             r["diagnostics_time_sec"][-1], m, "" if worst is None or worst <= threshold else "   <-- NOT CONVERGED")
         lines.append(line)
+        if "ess_bulk_min" in r:                            # (--bulk_tail_ess runs only)
+            num = lambda v: "n/a" if v is None else "{:.1f}".format(v)
+            lines.append("      multi-chain ESS min: bulk {}, tail {}, mean {}; largest MCSE of a mean {} sd; over {} chains, {}".format(
+                num(r["ess_bulk_min"][-1]), num(r["ess_tail_min"][-1]), num(r["ess_mean_min"][-1]),
+                fmt(r["mcse_mean_over_sd_max"][-1]), r["bulk_tail_ess_chains"][-1],
+                "n/a" if r["bulk_tail_ess_time_sec"][-1] is None else "{:.3f}s".format(r["bulk_tail_ess_time_sec"][-1])))
         path = os.path.join(results_dir or ".", model_name or "", m + "_rhat.npz")
         if os.path.exists(path):
             z = np.load(path)

@@ -1,7 +1,9 @@
 """Convergence diagnostics across chains: the potential scale reduction factor R-hat (Gelman-Rubin; the split form of
 BDA3 / Stan / ArviZ, without rank normalisation) and the pooled posterior mean / sd of every element; and, on request,
 the rank-normalised, folded form of Vehtari, Gelman, Simpson, Carpenter, Buerkner 2021 (`rank_rhat`: what Stan, posterior
-and ArviZ report as R-hat now) with the pooled posterior median and 5 % / 95 % quantiles.
+and ArviZ report as R-hat now) with the pooled posterior median and 5 % / 95 % quantiles; and the numbers the same paper
+reports next to it, bulk-ESS, tail-ESS and the Monte-Carlo standard error of the mean (`bulk_tail_ess`), from one
+multi-chain autocorrelation estimator on the device (`arp_ess_multichain`).
 
 Build-specific (the reference runs 100 chains and reports the within-chain ESS only).  The per-chain moments come from
 one pass over a trace that is already on the device (`arp_split_moments`) or from the in-kernel statistics of a
@@ -23,6 +25,10 @@ Rhat = collections.namedtuple("Rhat", ["rhat", "mean", "sd", "rows", "constant_r
 # bulk, tail: the split R-hat of the rank-normalised and of the folded, rank-normalised trace; rhat = fmax of the two;
 # median, q05, q95: order statistics of the pooled draws; rows, constant_rows as above (of the bulk trace); [D] float64
 RankRhat = collections.namedtuple("RankRhat", ["bulk", "tail", "rhat", "median", "q05", "q95", "rows", "constant_rows"])
+
+# bulk, tail, mean: the multi-chain ESS of the rank-normalised trace, of the 5 % / 95 % indicators (the smaller) and of the
+# draws; mcse_mean = sd / sqrt(mean); sd: the pooled posterior sd; [D] float64
+BulkTailEss = collections.namedtuple("BulkTailEss", ["bulk", "tail", "mean", "mcse_mean", "sd"])
 
 
 def split_moments(trace, split=True):
@@ -142,6 +148,76 @@ def rank_normalize(trace, fold=False, probs=None, rank2=None):
                                         C.c_void_p(ws.data_ptr()), need, C.c_void_p(torch.cuda.current_stream().cuda_stream)))
         del ws
     return z, median, quantiles
+
+
+def ess_multichain_workspace_bytes(S, Cn, D, split=True):
+    """Bytes of device workspace `ess_multichain` takes for a [S, Cn, D] trace."""
+    from . import _lib
+    if S <= 0 or Cn <= 0 or D <= 0:
+        return 0
+    need = int(_lib.lib().arp_ess_multichain_workspace_bytes(S, Cn, D, int(bool(split))))
+    if need <= 0:
+        _lib.check(1)
+    return need
+
+
+def ess_multichain(trace, split=True, threshold=None, n_rho=0):
+    """(ess, max_t, rho) device tensors of a recorded [S, C, D] float32 trace on the GPU (`arp_ess_multichain`): the
+    multi-chain effective sample size of every element, ess [D] float32 (NaN for an element that never moved or with
+    fewer than four draws per row); max_t [D] int32, where Geyer's initial sequence was cut; rho [n_rho, D] float32 (None
+    for n_rho = 0), the pooled autocorrelations up to lag max_t + 1 and NaN beyond.  split: rows are half-chains.
+    threshold: an optional [D] float32 device tensor; the statistic is then that of the indicator x <= threshold[d],
+    which is never written out.  A leading or inner block of chains of a wider trace is taken in place, as rank_normalize
+    takes it; the workspace is owned here."""
+    from . import _lib
+    if not (trace.is_cuda and trace.dtype == torch.float32 and trace.dim() == 3):
+        raise ValueError("ess_multichain: a float32 [S, C, D] trace on the GPU is required (there is no CPU fallback)")
+    S, Cn, D = trace.shape
+    n_rho = int(n_rho)
+    if threshold is not None and not (threshold.is_cuda and threshold.dtype == torch.float32 and threshold.is_contiguous()
+                                      and tuple(threshold.shape) == (D,)):
+        raise ValueError("ess_multichain: threshold must be a contiguous float32 [D] tensor on the GPU")
+    ess = torch.full((D,), float("nan"), dtype=torch.float32, device=trace.device)
+    max_t = torch.zeros(D, dtype=torch.int32, device=trace.device)
+    rho = torch.full((n_rho, D), float("nan"), dtype=torch.float32, device=trace.device) if n_rho > 0 else None
+    if S == 0 or Cn == 0 or D == 0:
+        return ess, max_t, rho
+    in_place = trace.is_contiguous() or (trace.stride(2) == 1 and trace.stride(1) == D and S > 1)
+    x = trace if in_place else trace.contiguous()
+    row_stride = x.stride(0) if S > 1 else Cn * D
+    L = _lib.lib()
+    with torch.cuda.device(x.device):
+        need = ess_multichain_workspace_bytes(S, Cn, D, split)
+        ws = torch.empty(need, dtype=torch.uint8, device=x.device)
+        _lib.check(L.arp_ess_multichain(C.c_void_p(x.data_ptr()), S, Cn, D, row_stride, int(bool(split)),
+                                        C.c_void_p(threshold.data_ptr() if threshold is not None else 0),
+                                        C.c_void_p(ess.data_ptr()), C.c_void_p(max_t.data_ptr()),
+                                        C.c_void_p(rho.data_ptr() if rho is not None else 0), n_rho,
+                                        C.c_void_p(ws.data_ptr()), need, C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+        del ws
+    return ess, max_t, rho
+
+
+def bulk_tail_ess(trace):
+    """Bulk-ESS, tail-ESS and the Monte-Carlo standard error of the mean of every element of a [S, C, D] float32 trace on
+    the GPU (Vehtari et al. 2021) -> BulkTailEss: `bulk` is ess_multichain (split) of the rank-normalised z trace, `tail`
+    the smaller of ess_multichain of the indicators x <= q05 and x <= q95 (q: the pooled order statistic x_(ceil(p N)) of
+    rank_normalize -- posterior interpolates its quantile, one draw's rank away), `mean` that of the draws themselves,
+    mcse_mean = sd / sqrt(mean) with the pooled sd of split_moments -> fold -> rhat_from_sums."""
+    S = int(trace.shape[0])
+    z, _, q = rank_normalize(trace, fold=False, probs=(0.05, 0.95))
+    bulk = ess_multichain(z, True)[0]
+    del z
+    lo = ess_multichain(trace, True, threshold=q[0].contiguous())[0]
+    hi = ess_multichain(trace, True, threshold=q[1].contiguous())[0]
+    mean = ess_multichain(trace, True)[0]
+    sd = rhat_from_sums(fold(*split_moments(trace, True)), S // 2).sd
+
+    def f64(t):
+        return t.cpu().numpy().astype(np.float64)
+    lo, hi, mean = f64(lo), f64(hi), f64(mean)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return BulkTailEss(f64(bulk), np.minimum(lo, hi), mean, sd / np.sqrt(mean), sd)
 
 
 def rank_rhat(trace):

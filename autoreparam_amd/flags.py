@@ -46,6 +46,12 @@ _DEFS = [
                                           "5 % and 95 % quantiles of every element over the chains split R-hat covers "
                                           "(rank_rhat_* JSON keys, five more families in <base>_rhat.npz).  One process only: "
                                           "a sharded job writes null."),
+    ("bulk_tail_ess", bool, False, "Sampling runs, with --convergence_diagnostics: also the multi-chain bulk-ESS, tail-ESS "
+                                   "and Monte-Carlo standard error of the posterior mean of every element (Vehtari et al. "
+                                   "2021; what Stan, posterior and ArviZ report next to the rank-normalised R-hat) over the "
+                                   "chains split R-hat covers (ess_bulk_min, ess_tail_min, ess_mean_min, "
+                                   "mcse_mean_over_sd_max JSON keys, four more families in <base>_rhat.npz).  ess_min "
+                                   "stays the reference's per-chain figure.  One process only: a sharded job writes null."),
     ("lanes_per_chain", int, 0, "Lanes of a wave64 a chain is spread over (0 = automatic)."),
 ]
 

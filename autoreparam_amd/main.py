@@ -266,6 +266,8 @@ def _convergence_report(kernel_results, model_config, flags, dev):
     keys = {"split_rhat_max": _finite_or_none(split_max), "split_rhat_chains": n_split,
             "rhat_max_all_chains": _finite_or_none(all_max) if streaming else None}
     keys.update(rank_keys)
+    if getattr(flags, "bulk_tail_ess", False):
+        keys.update(_bulk_tail_report(trace, k, spec, arrays, by_part))
     keys["diagnostics_time_sec"] = time.time() - clock
     return keys, arrays
 
@@ -308,6 +310,58 @@ def _rank_report(trace, k, spec, arrays, by_part):
                     "(the elements: <base>_rhat.npz)".format(RHAT_WARN))
     keys.update(rank_rhat_max=_finite_or_none(top), rank_rhat_bulk_max=_finite_or_none(bulk_max),
                 rank_rhat_tail_max=_finite_or_none(tail_max), rank_rhat_chains=k, rank_rhat_time_sec=time.time() - clock)
+    return keys
+
+
+ESS_PER_CHAIN_WARN = 100    # Stan's rule: bulk- and tail-ESS of at least 100 per chain
+
+
+def _bulk_tail_fit_chains(trace, k):
+    """The largest of k, k/2, k/4, ... leading chains whose z-score trace and workspaces fit the free device memory (the
+    rank workspace and the ESS workspace are not alive together: the larger counts)."""
+    import torch
+    S, _, D = (int(v) for v in trace.shape)
+    free = torch.cuda.mem_get_info(trace.device)[0]
+    while k > 0 and S * k * D * 4 + max(diagnostics.rank_workspace_bytes(S, k, D, False),
+                                        diagnostics.ess_multichain_workspace_bytes(S, k, D, True)) > free:
+        k //= 2
+    return k
+
+
+def _bulk_tail_report(trace, k, spec, arrays, by_part):
+    """--bulk_tail_ess: the multi-chain bulk-ESS, tail-ESS, ESS of the mean and its Monte-Carlo standard error over the
+    leading k chains of the device trace (fewer where the z trace and the workspaces do not fit: the count is reported),
+    into `arrays`; returns the six JSON keys.  Like the pooled ranks, the pooled autocovariances need every draw on one
+    device: a sharded job (world size > 1) writes null, says so once, and enters no collective.  The reference's ess_min
+    (per chain) is not touched."""
+    keys = {"ess_bulk_min": None, "ess_tail_min": None, "ess_mean_min": None, "mcse_mean_over_sd_max": None,
+            "bulk_tail_ess_chains": 0, "bulk_tail_ess_time_sec": None}
+    if parallel.world()[1] > 1:
+        util.print_("    bulk / tail ESS: skipped, the chains of a sharded job are on several devices "
+                    "(the pooled ranks and autocovariances need all draws on one)")
+        return keys
+    clock = time.time()
+    k = _bulk_tail_fit_chains(trace, k) if k > 0 else 0
+    if k <= 0:
+        util.print_("    bulk / tail ESS: no chains to pool")
+        return keys
+    r = diagnostics.bulk_tail_ess(trace[:, :k])
+    by_part(arrays, (("ess_bulk", r.bulk), ("ess_tail", r.tail), ("ess_mean", r.mean), ("mcse_mean", r.mcse_mean)))
+
+    def nan_min(x):
+        return -_nan_max(-np.asarray(x, np.float64))[0]
+    bulk_min, tail_min, mean_min = nan_min(r.bulk), nan_min(r.tail), nan_min(r.mean)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        rel_max = _nan_max(r.mcse_mean / r.sd)[0]
+    util.print_("    multi-chain ESS over {} chains: bulk min {:.1f}, tail min {:.1f}, mean min {:.1f}; "
+                "largest MCSE of a mean {:.4f} posterior sd".format(k, bulk_min, tail_min, mean_min, rel_max))
+    low = [v for v in (bulk_min, tail_min) if np.isfinite(v)]
+    if low and min(low) < ESS_PER_CHAIN_WARN * k:
+        util.print_("    WARNING: bulk- or tail-ESS below {} per chain: the posterior summaries of these elements are not "
+                    "reliable yet (the elements: <base>_rhat.npz)".format(ESS_PER_CHAIN_WARN))
+    keys.update(ess_bulk_min=_finite_or_none(bulk_min), ess_tail_min=_finite_or_none(tail_min),
+                ess_mean_min=_finite_or_none(mean_min), mcse_mean_over_sd_max=_finite_or_none(rel_max),
+                bulk_tail_ess_chains=k, bulk_tail_ess_time_sec=time.time() - clock)
     return keys
 
 

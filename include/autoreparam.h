@@ -317,6 +317,37 @@ int arp_rank_normalize(const float* trace, int64_t n_samples, int64_t n_chains, 
                        const double* probs, int32_t n_probs, float* quantiles,
                        void* workspace, int64_t workspace_bytes, void* stream);
 
+/* Multi-chain effective sample size of every element (build-specific; the estimator of Vehtari et al. 2021 behind
+ * bulk-ESS, tail-ESS and the Monte-Carlo standard error of the mean, as Stan / posterior / ArviZ report them next to the
+ * rank-normalised R-hat).  Trace addressing as arp_rank_normalize.  Rows: split = 1 gives m = 2 n_chains rows of
+ * n = n_samples / 2 draws, [0, n) and [n_samples - n, n_samples) of every chain (an odd run drops its middle draw, as
+ * arp_split_moments does); split = 0 gives m = n_chains rows of n = n_samples.  With threshold, the value of a draw is
+ * 1.0f where x <= threshold[d] and 0.0f otherwise (a NaN is 0); no indicator trace is written.  Per element, in float64:
+ *   gamma_j(k) = (1/n) sum_{t < n-k} (x_t - mu_j)(x_{t+k} - mu_j) about row j's own mean,  Gamma(k) = mean_j gamma_j(k)
+ *   mean_var = Gamma(0) n / (n - 1),  var_plus = Gamma(0) + [m > 1] (sample variance of the mu_j, divisor m - 1)
+ *   rho(k) = 1 - (mean_var - Gamma(k)) / var_plus
+ *   Geyer's initial positive sequence: t = 0, E = 1, O = rho(1), r[0] = E, r[1] = O; while t < n - 5 and E + O > 0:
+ *     t += 2, E = rho(t), O = rho(t + 1), and r[t] = E, r[t+1] = O where E + O >= 0; then max_t = t and r[max_t] = E where
+ *     E > 0; every other r is 0.  Initial monotone sequence: for t = 2, 4, ... <= max_t - 2, a pair r[t] + r[t+1] above
+ *     the pair before it is replaced by that pair's mean, twice.
+ *   tau = max(-1 + 2 sum_{k < max_t} r[k] + r[max_t], 1 / log10(n m)),  ess[d] = n m / tau                 [D], required
+ *   max_t[d]     as above; 0 where ess is NaN                                                       [D], may be NULL
+ *   rho[k][d]    rho(k) before the monotone step for k <= min(max_t + 1, n_rho - 1), NaN beyond  [n_rho][D], may be NULL
+ * ess[d] is NaN where var_plus is not > 0 (an element that never moved) or n < 4; neither is an error.  The lagged
+ * products are float32 in windows of 128, every window added into float64, about means summed in float64: rho is good to
+ * 128 x 2^-24 of 1 at worst.  Every sum has a fixed order that depends on the shape alone: a result is bitwise
+ * reproducible, and the same for a block of chains taken in place (row_stride > n_chains * D) as for its contiguous
+ * copy.  A NaN or inf neither faults nor hangs; the results of an element that holds one are unspecified, the others'
+ * are not touched.  Lags are taken 16 at a time, for the elements the pooled sequence has not cut yet; every launch the
+ * longest cut could need is enqueued and the call never synchronises.  The workspace (arp_ess_multichain_workspace_bytes:
+ * the rows' means and one partial sum per workgroup, element and lag) is required and 256-byte aligned; returns 1
+ * (arp_last_error) on a missing argument, a workspace too small or misaligned, n_samples * n_chains >= 2^31, or more
+ * than 2^20 draws per row (the launches enqueued grow with n / 16: at most 2^17). */
+int64_t arp_ess_multichain_workspace_bytes(int64_t n_samples, int64_t n_chains, int32_t D, int split);
+int arp_ess_multichain(const float* trace, int64_t n_samples, int64_t n_chains, int32_t D, int64_t row_stride,
+                       int split, const float* threshold, float* ess, int32_t* max_t,
+                       float* rho, int32_t n_rho, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* Test hook: the step-size adaptation recurrence of the chain kernels on SCRIPTED log acceptance ratios
  * (tfp.mcmc.DualAveragingStepSizeAdaptation / SimpleStepSizeAdaptation as wired at inference.py:224-226, 288-306;
  * SURVEY.md 8c known answer (7)).  For each of `n` independent rows, applies the update after transitions
