@@ -147,3 +147,27 @@ def lib():
 def check(rc):
     if rc != 0:
         raise RuntimeError("autoreparam engine: " + lib().arp_last_error().decode("utf-8", "replace"))
+
+
+def ptr(t):
+    """The device pointer argument for tensor `t`; NULL for None."""
+    return C.c_void_p(t.data_ptr() if t is not None else 0)
+
+
+def stream():
+    """The stream argument of an entry point: torch's current stream on the current device."""
+    import torch
+    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def trace_view(trace, who):
+    """(x, S, C, D, row_stride) of a float32 [S, C, D] device trace as the diagnostics kernels read it: rows of C * D
+    adjacent floats, `row_stride` floats apart.  A contiguous trace and a leading or inner block of chains of a wider one
+    ([S, i:j, D] of [S, K, D]: rows stay rows, further apart) are taken in place, x is trace; anything else is copied."""
+    import torch
+    if not (trace.is_cuda and trace.dtype == torch.float32 and trace.dim() == 3):
+        raise ValueError(who + ": a float32 [S, C, D] trace on the GPU is required (there is no CPU fallback)")
+    S, Cn, D = trace.shape
+    in_place = trace.is_contiguous() or (trace.stride(2) == 1 and trace.stride(1) == D and S > 1)
+    x = trace if in_place else trace.contiguous()
+    return x, S, Cn, D, (x.stride(0) if S > 1 else Cn * D)

@@ -25,7 +25,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <algorithm>
-#include "host_common.h"
+#include "diag_host.h"
 
 #pragma clang fp contract(off)
 
@@ -282,44 +282,42 @@ extern "C" int arp_split_moments(const float* trace, int64_t n_samples, int64_t 
   // the long route needs its workspace; without one (or with one too small) the wide route takes any shape
   const int64_t need = arp_moments_workspace_bytes(n_samples, n_series, split ? 1 : 0);
   const bool use_long = need > 0 && workspace && workspace_bytes >= need;
-  if (need > 0 && workspace && workspace_bytes < need && forced_route() == 2) {
-    set_error("arp_split_moments: workspace too small (see arp_moments_workspace_bytes)");
-    return 1;
-  }
+  if (need > 0 && workspace && workspace_bytes < need && forced_route() == 2)
+    return !workspace_size_ok(false, "arp_split_moments", "see arp_moments_workspace_bytes");
   if (use_long) {
-    if (((uintptr_t)workspace & 255) != 0) { set_error("arp_split_moments: the workspace must be 256-byte aligned"); return 1; }
+    if (!workspace_aligned(workspace, "arp_split_moments")) return 1;
     const long long ns_pad = ns_padded(n_series);
     const int total = pt.P * pt.chunks;
     float* ws_mean = (float*)workspace;
     float* ws_m2 = ws_mean + (long long)total * ns_pad;
     const long long lanes_all = n4 / 4 + (n_series - n4);
-    const long long sblocks = (lanes_all + kThreads - 1) / kThreads;
+    const long long sblocks = blocks_for(lanes_all, kThreads);
     int per_block = (int)std::max<long long>(1, (long long)total * sblocks / kLongTargetBlocks);
     while ((total + per_block - 1) / per_block > 65535) ++per_block;
-    const unsigned gy = (unsigned)((total + per_block - 1) / per_block);
+    const unsigned gy = blocks_for(total, per_block);
     if (n4 > 0) {
       const long long lanes = n4 / 4;
-      hipLaunchKernelGGL(moments_chunk_kernel<4>, dim3((unsigned)((lanes + kThreads - 1) / kThreads), gy), dim3(kThreads), 0, st,
+      hipLaunchKernelGGL(moments_chunk_kernel<4>, dim3(blocks_for(lanes, kThreads), gy), dim3(kThreads), 0, st,
                          trace, (long long)row_stride, 0ll, lanes, pt, per_block, ns_pad, ws_mean, ws_m2);
     }
     if (n_series > n4) {
       const long long lanes = n_series - n4;
-      hipLaunchKernelGGL(moments_chunk_kernel<1>, dim3((unsigned)((lanes + kThreads - 1) / kThreads), gy), dim3(kThreads), 0, st,
+      hipLaunchKernelGGL(moments_chunk_kernel<1>, dim3(blocks_for(lanes, kThreads), gy), dim3(kThreads), 0, st,
                          trace, (long long)row_stride, n4, lanes, pt, per_block, ns_pad, ws_mean, ws_m2);
     }
-    hipLaunchKernelGGL(moments_merge_kernel, dim3((unsigned)((n_series + kThreads - 1) / kThreads)), dim3(kThreads), 0, st,
+    hipLaunchKernelGGL(moments_merge_kernel, dim3(blocks_for(n_series, kThreads)), dim3(kThreads), 0, st,
                        trace, (long long)row_stride, (const float*)ws_mean, (const float*)ws_m2, ns_pad, (long long)n_series, pt, mean, var);
     ARP_HIP_OK(hipGetLastError());
     return 0;
   }
   if (n4 > 0) {
     const long long lanes = n4 / 4;
-    hipLaunchKernelGGL(moments_wide_kernel<4>, dim3((unsigned)((lanes + kThreads - 1) / kThreads)), dim3(kThreads), 0, st, trace,
+    hipLaunchKernelGGL(moments_wide_kernel<4>, dim3(blocks_for(lanes, kThreads)), dim3(kThreads), 0, st, trace,
                        (long long)row_stride, 0ll, lanes, (long long)n_series, pt, mean, var);
   }
   if (n_series > n4) {
     const long long lanes = n_series - n4;
-    hipLaunchKernelGGL(moments_wide_kernel<1>, dim3((unsigned)((lanes + kThreads - 1) / kThreads)), dim3(kThreads), 0, st, trace,
+    hipLaunchKernelGGL(moments_wide_kernel<1>, dim3(blocks_for(lanes, kThreads)), dim3(kThreads), 0, st, trace,
                        (long long)row_stride, n4, lanes, (long long)n_series, pt, mean, var);
   }
   ARP_HIP_OK(hipGetLastError());

@@ -25,7 +25,10 @@
 //            leading and the lagged stream both read (ess_sweep_far; sums flushed into doubles every 128 samples).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include "host_common.h"
+#include <algorithm>
+#include <type_traits>
+#include "arp_device.h"
+#include "diag_host.h"
 #include "ess_tail.h"
 
 namespace arp {
@@ -122,7 +125,6 @@ __device__ __forceinline__ void ess_sweep_first(const EssSeries& x, long long S,
     constexpr int P = decltype(ph)::value;
 #pragma unroll
     for (int tl = 0; tl < LB; ++tl) {
-      constexpr int dummy = 0; (void)dummy;
       const int tt = (P * LB + tl) % W;
       const float y = v[tl] - r;
       acc[0] = fmaf(y, y, acc[0]); sy += y;
@@ -222,7 +224,6 @@ __device__ __forceinline__ void ess_sweep_dense(const EssSeries& x, long long S,
       if (tb + LB < S) ess_load<LB>(x, tb + LB, S, mean, buf[(P + 1) % 2]);
 #pragma unroll
       for (int tl = 0; tl < LB; ++tl) {
-        constexpr int dummy = 0; (void)dummy;
         const int tt = P * LB + tl;
         const float y = buf[P % 2][tl] - mean;
 #pragma unroll
@@ -231,6 +232,12 @@ __device__ __forceinline__ void ess_sweep_dense(const EssSeries& x, long long S,
       }
     });
   }
+}
+
+__device__ __forceinline__ double ess_readlane(double x, int lane) {
+  const unsigned long long b = __builtin_bit_cast(unsigned long long, x);
+  const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(b >> 32), lane), lo = (unsigned)__builtin_amdgcn_readlane((int)b, lane);
+  return __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
 }
 
 // Lags beyond W of ONE series, by the whole wave.  After the first sweep a wave typically holds a few series that are
@@ -369,10 +376,7 @@ __global__ __launch_bounds__(256, ARP_ESS_MINB) void ess_kernel(const float* __r
       pending &= pending - 1;
       const unsigned idx_u = __builtin_amdgcn_readlane((int)(x.boff >> 2), u);
       const float mean_u = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, mean), u));
-      const unsigned long long c0b = __builtin_bit_cast(unsigned long long, c0);
-      const unsigned long long c0u = ((unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)(c0b >> 32), u) << 32) |
-                                     (unsigned)__builtin_amdgcn_readlane((int)c0b, u);
-      const double add = ess_tail_cooperative(trace, stride, S, idx_u, mean_u, __builtin_bit_cast(double, c0u), tail_from, wbuf, lane);
+      const double add = ess_tail_cooperative(trace, stride, S, idx_u, mean_u, ess_readlane(c0, u), tail_from, wbuf, lane);
       if (lane == u) total += add;
     }
   } else if (defer.count) {
@@ -484,11 +488,6 @@ __device__ __forceinline__ float ess_rows_sum(float v) {       // over the four 
 __device__ __forceinline__ float ess_wave_sum(float v) {       // every lane gets the same total, fixed order
   v = ess_rows_sum(ess_row_sum(v));
   return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v)));
-}
-__device__ __forceinline__ double ess_readlane(double x, int lane) {
-  const unsigned long long b = __builtin_bit_cast(unsigned long long, x);
-  const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(b >> 32), lane), lo = (unsigned)__builtin_amdgcn_readlane((int)b, lane);
-  return __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
 }
 
 // physical LDS row of tile row t: one row of padding behind every 32, so that the 32 time slots of a series (32 rows
@@ -613,7 +612,6 @@ __global__ __launch_bounds__(kTileThreads, 1) void ess_tile_kernel(const float* 
         ess_pin(y0); ess_pin(y1);
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
-          constexpr int dummy = 0; (void)dummy;
           const int p = 8 * H + i;
           const v2f y = tb + p < t1 ? v2f{y0[i], y1[i]} - r : v2f{0.0f, 0.0f};
           acc[0] = vfma(y, y, acc[0]);
@@ -728,22 +726,21 @@ __global__ __launch_bounds__(kTileThreads, 1) void ess_tile_kernel(const float* 
   }
 }
 
-}  // namespace arp
-
-namespace arp {
 // workspace layout of arp_ess_ws: [count | idx | mean | c0 | total | from | rows], every array 256-byte aligned
 struct EssWsLayout {
-  size_t off_idx, off_mean, off_c0, off_total, off_from, off_rows;
-  static size_t up(size_t x) { return (x + 255) & ~(size_t)255; }
+  int64_t off_idx, off_mean, off_c0, off_total, off_from, off_rows;
   explicit EssWsLayout(int64_t n) {
-    off_idx = 256;
-    off_mean = off_idx + up((size_t)n * 4);
-    off_c0 = off_mean + up((size_t)n * 4);
-    off_total = off_c0 + up((size_t)n * 8);
-    off_from = off_total + up((size_t)n * 8);
-    off_rows = off_from + up((size_t)n * 4);
+    Carve w;
+    w.take(256);                       // count
+    off_idx = w.take(n * 4);
+    off_mean = w.take(n * 4);
+    off_c0 = w.take(n * 8);
+    off_total = w.take(n * 8);
+    off_from = w.take(n * 4);
+    off_rows = w.bytes();
   }
 };
+
 }  // namespace arp
 
 #ifdef ARP_ESS_PROF
@@ -761,7 +758,7 @@ extern "C" int64_t arp_ess_workspace_bytes(int64_t n_samples, int64_t n_series) 
   // series rows are gathered 64 at a time, so the row area holds a whole number of 64-row blocks (at least one):
   // a caller that allocates exactly this many bytes gets every listed series in ONE chunk, also for n_series < 64
   const size_t rows = ((size_t)n_series + 63) & ~(size_t)63;
-  return (int64_t)(EssWsLayout(n_series).off_rows + rows * (size_t)ess_row_floats(n_samples) * 4);
+  return (int64_t)((size_t)EssWsLayout(n_series).off_rows + rows * (size_t)ess_row_floats(n_samples) * 4);
 }
 
 extern "C" int arp_ess_ws(const float* trace, int64_t n_samples, int64_t n_series, int64_t row_stride, float* ess,
@@ -780,13 +777,10 @@ extern "C" int arp_ess_ws(const float* trace, int64_t n_samples, int64_t n_serie
   const long long SR = ess_row_floats(n_samples);
   if (long_series && workspace) {
     if (SR / 64 > 65535) { set_error("arp_ess_ws: at most 4 194 240 samples per series on the workspace path"); return 1; }
-    if (((uintptr_t)workspace & 255) != 0) { set_error("arp_ess_ws: the workspace must be 256-byte aligned"); return 1; }
+    if (!workspace_aligned(workspace, "arp_ess_ws")) return 1;
     const EssWsLayout Lw(n_series);
-    rows_cap = workspace_bytes > (int64_t)Lw.off_rows ? ((workspace_bytes - (int64_t)Lw.off_rows) / (SR * 4)) & ~63ll : 0;
-    if (rows_cap < 64) {
-      set_error("arp_ess_ws: workspace too small (the work lists and at least 64 series rows: see arp_ess_workspace_bytes)");
-      return 1;
-    }
+    rows_cap = workspace_bytes > Lw.off_rows ? ((workspace_bytes - Lw.off_rows) / (SR * 4)) & ~63ll : 0;
+    if (!workspace_size_ok(rows_cap >= 64, "arp_ess_ws", "the work lists and at least 64 series rows: see arp_ess_workspace_bytes")) return 1;
     if (rows_cap > n_series) rows_cap = (n_series + 63) & ~63ll;
     char* w = (char*)workspace;
     D = EssDefer{(unsigned*)w, (unsigned*)(w + Lw.off_idx), (float*)(w + Lw.off_mean), (double*)(w + Lw.off_c0),

@@ -1,17 +1,16 @@
 // Host-side plumbing shared by the API translation units: the opaque model
-// handle, error reporting and the per-model launcher tables.
+// handle and the per-model launcher tables (error reporting and the debug-switch gate: host_error.h).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <stdio.h>
 #include <stdlib.h>
-#include <string>
 #include <type_traits>
 #include <utility>
 #include <map>
 #include <mutex>
 #include <vector>
 #include "../../include/autoreparam.h"
+#include "host_error.h"
 #include "kernels.h"
 #include "model_radon.h"
 #include "radon_fast.h"
@@ -25,17 +24,6 @@
 #include "model_time_series.h"
 
 namespace arp {
-
-void set_error(const std::string& msg);
-
-#define ARP_HIP_OK(expr)                                                          \
-  do {                                                                            \
-    hipError_t e_ = (expr);                                                       \
-    if (e_ != hipSuccess) {                                                       \
-      ::arp::set_error(std::string(#expr) + ": " + hipGetErrorString(e_));        \
-      return 1;                                                                   \
-    }                                                                             \
-  } while (0)
 
 using HmcFn = void (*)(const void* args, const float* a, const float* b, const HmcParams& P, hipStream_t s);
 using InterleavedFn = void (*)(const void* args, const float* a0, const float* b0, const float* a1, const float* b1,
@@ -250,29 +238,6 @@ struct Launch {
     return o;
   }
 };
-
-// The one gate of the library's experiment and test switches: the value of the environment variable `name`, honoured under
-// ARP_DEBUG=1 only and announced on stderr -- a stray variable must not change which kernel a production run takes, and says
-// that it was ignored.  nullptr: unset, empty or ignored.  `note` ends the announcement; `said` (a switch that is asked for
-// on every call but announces itself once per process) holds whether it has.
-inline const char* debug_switch(const char* name, const char* note = "", bool* said = nullptr) {
-  const char* e = getenv(name);
-  if (!e || !e[0]) return nullptr;
-  const char* d = getenv("ARP_DEBUG");
-  if (!(d && d[0] == '1' && d[1] == 0)) {
-    fprintf(stderr, "libautoreparam_hip: %s=%s IGNORED (experiment switch; set ARP_DEBUG=1 to enable it)\n", name, e);
-    return nullptr;
-  }
-  if (!(said && *said)) fprintf(stderr, "libautoreparam_hip: DEBUG SWITCH %s=%s is in effect%s\n", name, e, note);
-  if (said) *said = true;
-  return e;
-}
-// integer experiment switch
-inline bool debug_int(const char* name, int* out) {
-  const char* e = debug_switch(name);
-  if (e) *out = atoi(e);
-  return e != nullptr;
-}
 
 // experiments only: ARP_STATS_LDS=0 sends statistics runs down the plane-per-sample route of kernels.h again (asked once
 // per process; any other value is the default and says nothing)

@@ -28,7 +28,7 @@
 #include <stdint.h>
 #include <math.h>
 #include <algorithm>
-#include "host_common.h"
+#include "diag_host.h"
 
 #pragma clang fp contract(off)
 
@@ -38,7 +38,6 @@ namespace {
 constexpr int kMcThreads = 256;
 constexpr int kLags = 16;                 // lags per block (even: a Geyer pair never straddles two blocks)
 constexpr int kFlush = 128;               // float products per window
-constexpr long long kMcMaxValues = 1ll << 35;
 constexpr long long kMcMaxRow = 1ll << 20;  // draws per row: at most 2^16 blocks, two launches each, are enqueued
 
 // what the Geyer loop of one element carries from block to block
@@ -303,47 +302,31 @@ __global__ __launch_bounds__(kMcThreads) void mcess_fold_kernel(McGeom G, int bl
   state[d] = st;
 }
 
-int64_t mc_align256(int64_t b) { return (b + 255) & ~(int64_t)255; }
-
 struct McLayout {
   int64_t state, active, mean, part, bytes;
   int n, P, blocks;
   long long n_wg;
+  // blocks: the last pair the loop can reach starts at the even lag after the largest even t < n - 5
+  McLayout(int64_t S, int64_t C, int64_t D, int split) {
+    P = split ? 2 : 1;
+    n = (int)(split ? S / 2 : S);
+    const long long n_series = C * D;
+    n_wg = (n_series + kMcThreads - 1) / kMcThreads;
+    int t_last = 0;
+    if (n > 5) t_last = 2 * ((n - 6) / 2) + 2;
+    blocks = t_last / kLags + 1;
+    const int64_t slots = std::min<int64_t>(D, kMcThreads);
+    Carve w;
+    state = w.take(D * (int64_t)sizeof(McState));
+    active = w.take(((int64_t)blocks + 1) * 4);
+    mean = w.take((int64_t)P * n_series * 8);
+    part = w.take((int64_t)kLags * P * n_wg * slots * 8);
+    bytes = w.bytes();
+  }
 };
 
-// blocks: the last pair the loop can reach starts at the even lag after the largest even t < n - 5
-McLayout mc_layout(int64_t S, int64_t C, int64_t D, int split) {
-  McLayout L;
-  L.P = split ? 2 : 1;
-  L.n = (int)(split ? S / 2 : S);
-  const long long n_series = C * D;
-  L.n_wg = (n_series + kMcThreads - 1) / kMcThreads;
-  int t_last = 0;
-  if (L.n > 5) t_last = 2 * ((L.n - 6) / 2) + 2;
-  L.blocks = t_last / kLags + 1;
-  const int64_t slots = std::min<int64_t>(D, kMcThreads);
-  int64_t at = 0;
-  L.state = at; at += mc_align256(D * (int64_t)sizeof(McState));
-  L.active = at; at += mc_align256(((int64_t)L.blocks + 1) * 4);
-  L.mean = at; at += mc_align256((int64_t)L.P * n_series * 8);
-  L.part = at; at += mc_align256((int64_t)kLags * L.P * L.n_wg * slots * 8);
-  L.bytes = at;
-  return L;
-}
-
 bool mc_shape_ok(int64_t n_samples, int64_t n_chains, int32_t D, int split, const char* who) {
-  if (n_samples <= 0 || n_chains <= 0 || D <= 0) {
-    set_error(std::string(who) + ": n_samples > 0, n_chains > 0 and D > 0 are required");
-    return false;
-  }
-  if (n_samples >= (1ll << 31) || n_chains >= (1ll << 31) || n_samples * n_chains >= (1ll << 31)) {
-    set_error(std::string(who) + ": at most 2^31 - 1 draws per element (n_samples * n_chains)");
-    return false;
-  }
-  if (n_samples * n_chains * D > kMcMaxValues) {
-    set_error(std::string(who) + ": at most 2^35 values per call");
-    return false;
-  }
+  if (!trace_shape_ok(n_samples, n_chains, D, who)) return false;
   if ((split ? n_samples / 2 : n_samples) > kMcMaxRow) {
     set_error(std::string(who) + ": at most 2^20 draws per row (n_samples, or n_samples / 2 with split)");
     return false;
@@ -357,7 +340,7 @@ bool mc_shape_ok(int64_t n_samples, int64_t n_chains, int32_t D, int split, cons
 extern "C" int64_t arp_ess_multichain_workspace_bytes(int64_t n_samples, int64_t n_chains, int32_t D, int split) {
   using namespace arp;
   if (!mc_shape_ok(n_samples, n_chains, D, split, "arp_ess_multichain_workspace_bytes")) return 0;
-  return mc_layout(n_samples, n_chains, D, split).bytes;
+  return McLayout(n_samples, n_chains, D, split).bytes;
 }
 
 extern "C" int arp_ess_multichain(const float* trace, int64_t n_samples, int64_t n_chains, int32_t D, int64_t row_stride,
@@ -370,12 +353,9 @@ extern "C" int arp_ess_multichain(const float* trace, int64_t n_samples, int64_t
     return 1;
   }
   if (n_rho < 0 || (n_rho > 0 && !rho)) { set_error("arp_ess_multichain: n_rho >= 0, and rho where n_rho > 0"); return 1; }
-  const McLayout L = mc_layout(n_samples, n_chains, D, split);
-  if (!workspace || workspace_bytes < L.bytes) {
-    set_error("arp_ess_multichain: workspace too small (see arp_ess_multichain_workspace_bytes)");
-    return 1;
-  }
-  if (((uintptr_t)workspace & 255) != 0) { set_error("arp_ess_multichain: the workspace must be 256-byte aligned"); return 1; }
+  const McLayout L(n_samples, n_chains, D, split);
+  if (!workspace_size_ok(workspace && workspace_bytes >= L.bytes, "arp_ess_multichain", "see arp_ess_multichain_workspace_bytes")) return 1;
+  if (!workspace_aligned(workspace, "arp_ess_multichain")) return 1;
   if (L.n_wg > 0x7fffffffll) { set_error("arp_ess_multichain: at most 2^39 series per call"); return 1; }
   hipStream_t st = (hipStream_t)stream;
   const int kNanBits = 0x7fc00000;

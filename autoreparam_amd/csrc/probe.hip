@@ -7,7 +7,7 @@
 // loop: cycles / realtime ticks x 100 MHz = the clock held, measured live on the box the numbers come from.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include "host_common.h"
+#include "host_error.h"
 
 namespace arp {
 

@@ -21,7 +21,7 @@
 #include <stdint.h>
 #include <math.h>
 #include <algorithm>
-#include "host_common.h"
+#include "diag_host.h"
 
 #pragma clang fp contract(off)
 
@@ -36,7 +36,6 @@ constexpr int kBins = 256;                         // 8-bit digits
 constexpr int kRows = 64;                          // rows (draws) of one key-pass tile
 constexpr int kCols = 128;                         // elements of one key-pass tile at most
 constexpr int kRankPerThread = 8;                  // draws per thread of the rank pass
-constexpr long long kMaxValues = 1ll << 35;        // values per call (grid sizes stay below 2^31 workgroups)
 
 // order-preserving key of a float: negative values bit-inverted, the others with the sign bit set; -0 is +0
 __device__ __forceinline__ uint32_t key_of(float v) {
@@ -275,41 +274,19 @@ __global__ __launch_bounds__(kThreads) void rank_score_kernel(const float* __res
   }
 }
 
-int64_t align256(int64_t b) { return (b + 255) & ~(int64_t)255; }
-
 struct Layout {
   int64_t keys_a, keys_b, hist, totals, med, bytes;
   uint32_t tiles;
+  Layout(int64_t N, int64_t D) : tiles(blocks_for(N, kTile)) {
+    Carve w;
+    keys_a = w.take(N * D * 4);
+    keys_b = w.take(N * D * 4);
+    hist = w.take(D * kBins * (int64_t)tiles * 4);
+    totals = w.take(D * kBins * 4);
+    med = w.take(D * 4);
+    bytes = w.bytes();
+  }
 };
-
-Layout make_layout(int64_t N, int64_t D) {
-  Layout L;
-  L.tiles = (uint32_t)((N + kTile - 1) / kTile);
-  int64_t at = 0;
-  L.keys_a = at; at += align256(N * D * 4);
-  L.keys_b = at; at += align256(N * D * 4);
-  L.hist = at; at += align256(D * kBins * (int64_t)L.tiles * 4);
-  L.totals = at; at += align256(D * kBins * 4);
-  L.med = at; at += align256(D * 4);
-  L.bytes = at;
-  return L;
-}
-
-bool shape_ok(int64_t n_samples, int64_t n_chains, int32_t D, const char* who) {
-  if (n_samples <= 0 || n_chains <= 0 || D <= 0) {
-    set_error(std::string(who) + ": n_samples > 0, n_chains > 0 and D > 0 are required");
-    return false;
-  }
-  if (n_samples >= (1ll << 31) || n_chains >= (1ll << 31) || n_samples * n_chains >= (1ll << 31)) {
-    set_error(std::string(who) + ": at most 2^31 - 1 draws per element (n_samples * n_chains)");
-    return false;
-  }
-  if (n_samples * n_chains * D > kMaxValues) {
-    set_error(std::string(who) + ": at most 2^35 values per call");
-    return false;
-  }
-  return true;
-}
 
 // keys (segments of N) sorted ascending; the result is in `a` again (four passes)
 void sort_segments(uint32_t* a, uint32_t* b, uint32_t* hist, uint32_t* totals, uint32_t N, int D, uint32_t tiles,
@@ -331,15 +308,15 @@ void sort_segments(uint32_t* a, uint32_t* b, uint32_t* hist, uint32_t* totals, u
 extern "C" int64_t arp_rank_workspace_bytes(int64_t n_samples, int64_t n_chains, int32_t D, int fold) {
   using namespace arp;
   (void)fold;                                   // the folded sort reuses the raw sort's buffers
-  if (!shape_ok(n_samples, n_chains, D, "arp_rank_workspace_bytes")) return 0;
-  return make_layout(n_samples * n_chains, D).bytes;
+  if (!trace_shape_ok(n_samples, n_chains, D, "arp_rank_workspace_bytes")) return 0;
+  return Layout(n_samples * n_chains, D).bytes;
 }
 
 extern "C" int arp_rank_normalize(const float* trace, int64_t n_samples, int64_t n_chains, int32_t D, int64_t row_stride,
                                   int fold, float* z, uint32_t* rank2, float* median, const double* probs, int32_t n_probs,
                                   float* quantiles, void* workspace, int64_t workspace_bytes, void* stream) {
   using namespace arp;
-  if (!shape_ok(n_samples, n_chains, D, "arp_rank_normalize")) return 1;
+  if (!trace_shape_ok(n_samples, n_chains, D, "arp_rank_normalize")) return 1;
   if (!trace || !z || row_stride < n_chains * D) {
     set_error("arp_rank_normalize: trace, z and row_stride >= n_chains * D are required");
     return 1;
@@ -347,12 +324,9 @@ extern "C" int arp_rank_normalize(const float* trace, int64_t n_samples, int64_t
   const bool want_q = quantiles && n_probs > 0;
   if (n_probs < 0 || (want_q && !probs)) { set_error("arp_rank_normalize: quantiles need n_probs >= 0 and probs"); return 1; }
   const int64_t N64 = n_samples * n_chains;
-  const Layout L = make_layout(N64, D);
-  if (!workspace || workspace_bytes < L.bytes) {
-    set_error("arp_rank_normalize: workspace too small (see arp_rank_workspace_bytes)");
-    return 1;
-  }
-  if (((uintptr_t)workspace & 255) != 0) { set_error("arp_rank_normalize: the workspace must be 256-byte aligned"); return 1; }
+  const Layout L(N64, D);
+  if (!workspace_size_ok(workspace && workspace_bytes >= L.bytes, "arp_rank_normalize", "see arp_rank_workspace_bytes")) return 1;
+  if (!workspace_aligned(workspace, "arp_rank_normalize")) return 1;
   hipStream_t st = (hipStream_t)stream;
   char* ws = (char*)workspace;
   uint32_t* keys_a = (uint32_t*)(ws + L.keys_a);
@@ -362,9 +336,9 @@ extern "C" int arp_rank_normalize(const float* trace, int64_t n_samples, int64_t
   float* med = median ? median : (float*)(ws + L.med);
   const uint32_t N = (uint32_t)N64, C = (uint32_t)n_chains;
   const int dt = std::min<int>(D, kCols);
-  const dim3 key_grid((unsigned)((N64 + kRows - 1) / kRows), (unsigned)((D + dt - 1) / dt));
+  const dim3 key_grid(blocks_for(N64, kRows), blocks_for(D, dt));
   if (key_grid.y > 65535u) { set_error("arp_rank_normalize: at most 65 535 * 128 elements per draw"); return 1; }
-  const unsigned d_blocks = (unsigned)((D + kThreads - 1) / kThreads);
+  const unsigned d_blocks = blocks_for(D, kThreads);
 
   // the raw pool, sorted: the order statistics, and the ranks themselves without fold
   hipLaunchKernelGGL(rank_key_kernel, key_grid, dim3(kThreads), 0, st, trace, (long long)row_stride, N, C, (int)D, dt,
@@ -388,7 +362,7 @@ extern "C" int arp_rank_normalize(const float* trace, int64_t n_samples, int64_t
   }
   const long long n_values = (long long)N64 * D;
   const long long per_block = (long long)kThreads * kRankPerThread;
-  hipLaunchKernelGGL(rank_score_kernel, dim3((unsigned)((n_values + per_block - 1) / per_block)), dim3(kThreads), 0, st, trace,
+  hipLaunchKernelGGL(rank_score_kernel, dim3(blocks_for(n_values, per_block)), dim3(kThreads), 0, st, trace,
                      (long long)row_stride, N, C, (int)D, n_values, fold ? (const float*)med : (const float*)nullptr,
                      (const uint32_t*)keys_a, z, rank2);
   ARP_HIP_OK(hipGetLastError());

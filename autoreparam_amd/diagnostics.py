@@ -36,9 +36,7 @@ def split_moments(trace, split=True):
     S // 2 draws (split) or P = 1.  A leading or inner block of chains of a wider trace is taken in place, as
     util.effective_sample_size does; the workspace of the long-trace route is owned here."""
     from . import _lib
-    if not (trace.is_cuda and trace.dtype == torch.float32 and trace.dim() == 3):
-        raise ValueError("split_moments: a float32 [S, C, D] trace on the GPU is required (there is no CPU fallback)")
-    S, Cn, D = trace.shape
+    x, S, Cn, D, row_stride = _lib.trace_view(trace, "split_moments")
     P = 2 if split else 1
     mean = torch.empty(P, Cn, D, dtype=torch.float32, device=trace.device)
     var = torch.empty(P, Cn, D, dtype=torch.float32, device=trace.device)
@@ -46,17 +44,12 @@ def split_moments(trace, split=True):
         return mean, var
     if S == 0:
         return mean.fill_(float("nan")), var.fill_(float("nan"))
-    in_place = trace.is_contiguous() or (trace.stride(2) == 1 and trace.stride(1) == D and S > 1)
-    x = trace if in_place else trace.contiguous()
-    row_stride = x.stride(0) if S > 1 else Cn * D
     L = _lib.lib()
     with torch.cuda.device(x.device):
         need = int(L.arp_moments_workspace_bytes(S, Cn * D, int(bool(split))))
         ws = torch.empty(need, dtype=torch.uint8, device=x.device) if need > 0 else None
-        _lib.check(L.arp_split_moments(C.c_void_p(x.data_ptr()), S, Cn * D, row_stride, int(bool(split)),
-                                       C.c_void_p(mean.data_ptr()), C.c_void_p(var.data_ptr()),
-                                       C.c_void_p(ws.data_ptr() if ws is not None else 0), need,
-                                       C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+        _lib.check(L.arp_split_moments(_lib.ptr(x), S, Cn * D, row_stride, int(bool(split)), _lib.ptr(mean), _lib.ptr(var),
+                                       _lib.ptr(ws), need, _lib.stream()))
         del ws
     return mean, var
 
@@ -74,9 +67,7 @@ def fold(mean, var):
     if D == 0:
         return sums
     with torch.cuda.device(mean.device):
-        _lib.check(_lib.lib().arp_moments_fold(C.c_void_p(m.data_ptr()), C.c_void_p(v.data_ptr()), m.shape[0], D,
-                                               C.c_void_p(sums.data_ptr()),
-                                               C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+        _lib.check(_lib.lib().arp_moments_fold(_lib.ptr(m), _lib.ptr(v), m.shape[0], D, _lib.ptr(sums), _lib.stream()))
     return sums
 
 
@@ -101,15 +92,20 @@ def from_stats(mean, var):
     return fold(mean, var)
 
 
-def rank_workspace_bytes(S, Cn, D, fold=False):
-    """Bytes of device workspace `rank_normalize` takes for a [S, Cn, D] trace (next to its [S, Cn, D] float32 result)."""
+def _workspace_bytes(symbol, S, Cn, D, flag):
+    """What the library's sizing function `symbol` asks for a [S, Cn, D] trace: 0 for an empty one, raises on a refusal."""
     from . import _lib
     if S <= 0 or Cn <= 0 or D <= 0:
         return 0
-    need = int(_lib.lib().arp_rank_workspace_bytes(S, Cn, D, int(bool(fold))))
+    need = int(getattr(_lib.lib(), symbol)(S, Cn, D, int(bool(flag))))
     if need <= 0:
         _lib.check(1)
     return need
+
+
+def rank_workspace_bytes(S, Cn, D, fold=False):
+    """Bytes of device workspace `rank_normalize` takes for a [S, Cn, D] trace (next to its [S, Cn, D] float32 result)."""
+    return _workspace_bytes("arp_rank_workspace_bytes", S, Cn, D, fold)
 
 
 def rank_normalize(trace, fold=False, probs=None, rank2=None):
@@ -121,9 +117,7 @@ def rank_normalize(trace, fold=False, probs=None, rank2=None):
     2 r - 1 as unsigned 32-bit words.  A leading or inner block of chains of a wider trace is taken in place, as
     split_moments takes it; the workspace is owned here."""
     from . import _lib
-    if not (trace.is_cuda and trace.dtype == torch.float32 and trace.dim() == 3):
-        raise ValueError("rank_normalize: a float32 [S, C, D] trace on the GPU is required (there is no CPU fallback)")
-    S, Cn, D = trace.shape
+    x, S, Cn, D, row_stride = _lib.trace_view(trace, "rank_normalize")
     probs = None if probs is None else [float(p) for p in probs]
     z = torch.empty(S, Cn, D, dtype=torch.float32, device=trace.device)
     median = torch.full((D,), float("nan"), dtype=torch.float32, device=trace.device)
@@ -133,32 +127,21 @@ def rank_normalize(trace, fold=False, probs=None, rank2=None):
         raise ValueError("rank_normalize: rank2 must be a contiguous int32 [S, C, D] tensor on the GPU")
     if S == 0 or Cn == 0 or D == 0:
         return z, median, quantiles
-    in_place = trace.is_contiguous() or (trace.stride(2) == 1 and trace.stride(1) == D and S > 1)
-    x = trace if in_place else trace.contiguous()
-    row_stride = x.stride(0) if S > 1 else Cn * D
     L = _lib.lib()
     with torch.cuda.device(x.device):
         need = rank_workspace_bytes(S, Cn, D, fold)
-        ws = torch.empty(need, dtype=torch.uint8, device=x.device)
+        ws = torch.empty(need, dtype=torch.uint8, device=x.device) if need > 0 else None
         pr = (C.c_double * len(probs))(*probs) if probs else None
-        _lib.check(L.arp_rank_normalize(C.c_void_p(x.data_ptr()), S, Cn, D, row_stride, int(bool(fold)),
-                                        C.c_void_p(z.data_ptr()), C.c_void_p(rank2.data_ptr() if rank2 is not None else 0),
-                                        C.c_void_p(median.data_ptr()), pr, len(probs) if probs else 0,
-                                        C.c_void_p(quantiles.data_ptr() if probs else 0),
-                                        C.c_void_p(ws.data_ptr()), need, C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+        _lib.check(L.arp_rank_normalize(_lib.ptr(x), S, Cn, D, row_stride, int(bool(fold)), _lib.ptr(z), _lib.ptr(rank2),
+                                        _lib.ptr(median), pr, len(probs) if probs else 0,
+                                        _lib.ptr(quantiles if probs else None), _lib.ptr(ws), need, _lib.stream()))
         del ws
     return z, median, quantiles
 
 
 def ess_multichain_workspace_bytes(S, Cn, D, split=True):
     """Bytes of device workspace `ess_multichain` takes for a [S, Cn, D] trace."""
-    from . import _lib
-    if S <= 0 or Cn <= 0 or D <= 0:
-        return 0
-    need = int(_lib.lib().arp_ess_multichain_workspace_bytes(S, Cn, D, int(bool(split))))
-    if need <= 0:
-        _lib.check(1)
-    return need
+    return _workspace_bytes("arp_ess_multichain_workspace_bytes", S, Cn, D, split)
 
 
 def ess_multichain(trace, split=True, threshold=None, n_rho=0):
@@ -170,9 +153,7 @@ def ess_multichain(trace, split=True, threshold=None, n_rho=0):
     which is never written out.  A leading or inner block of chains of a wider trace is taken in place, as rank_normalize
     takes it; the workspace is owned here."""
     from . import _lib
-    if not (trace.is_cuda and trace.dtype == torch.float32 and trace.dim() == 3):
-        raise ValueError("ess_multichain: a float32 [S, C, D] trace on the GPU is required (there is no CPU fallback)")
-    S, Cn, D = trace.shape
+    x, S, Cn, D, row_stride = _lib.trace_view(trace, "ess_multichain")
     n_rho = int(n_rho)
     if threshold is not None and not (threshold.is_cuda and threshold.dtype == torch.float32 and threshold.is_contiguous()
                                       and tuple(threshold.shape) == (D,)):
@@ -182,18 +163,13 @@ def ess_multichain(trace, split=True, threshold=None, n_rho=0):
     rho = torch.full((n_rho, D), float("nan"), dtype=torch.float32, device=trace.device) if n_rho > 0 else None
     if S == 0 or Cn == 0 or D == 0:
         return ess, max_t, rho
-    in_place = trace.is_contiguous() or (trace.stride(2) == 1 and trace.stride(1) == D and S > 1)
-    x = trace if in_place else trace.contiguous()
-    row_stride = x.stride(0) if S > 1 else Cn * D
     L = _lib.lib()
     with torch.cuda.device(x.device):
         need = ess_multichain_workspace_bytes(S, Cn, D, split)
-        ws = torch.empty(need, dtype=torch.uint8, device=x.device)
-        _lib.check(L.arp_ess_multichain(C.c_void_p(x.data_ptr()), S, Cn, D, row_stride, int(bool(split)),
-                                        C.c_void_p(threshold.data_ptr() if threshold is not None else 0),
-                                        C.c_void_p(ess.data_ptr()), C.c_void_p(max_t.data_ptr()),
-                                        C.c_void_p(rho.data_ptr() if rho is not None else 0), n_rho,
-                                        C.c_void_p(ws.data_ptr()), need, C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+        ws = torch.empty(need, dtype=torch.uint8, device=x.device) if need > 0 else None
+        _lib.check(L.arp_ess_multichain(_lib.ptr(x), S, Cn, D, row_stride, int(bool(split)), _lib.ptr(threshold),
+                                        _lib.ptr(ess), _lib.ptr(max_t), _lib.ptr(rho), n_rho, _lib.ptr(ws), need,
+                                        _lib.stream()))
         del ws
     return ess, max_t, rho
 

@@ -57,14 +57,8 @@ def effective_sample_size(states, max_chains_per_batch=None):
     engine's own kernel (`arp_ess`: direct auto-covariances up to the first negative one);
     anything else (the CPU tests) to the FFT form below."""
     if states.is_cuda and states.dtype == torch.float32:
-        import ctypes as C
         from . import _lib
-        S, Cn, D = states.shape
-        # a leading block of chains of a wider trace ([S, :k, D] of [S, K, D]) is taken in place: rows stay rows, the
-        # row stride says how far apart they are
-        in_place = states.is_contiguous() or (Cn > 0 and states.stride(2) == 1 and states.stride(1) == D and S > 1)
-        x = states if in_place else states.contiguous()
-        row_stride = x.stride(0) if S > 1 else Cn * D
+        x, S, Cn, D, row_stride = _lib.trace_view(states, "effective_sample_size")   # (a block of chains of a wider trace is taken in place)
         out = torch.empty(Cn, D, dtype=torch.float32, device=x.device)
         L = _lib.lib()
         with torch.cuda.device(x.device):
@@ -80,9 +74,8 @@ def effective_sample_size(states, max_chains_per_batch=None):
                                  device=x.device)
             ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
             ev[0].record()
-            _lib.check(L.arp_ess_ws(C.c_void_p(x.data_ptr()), S, Cn * D, row_stride, C.c_void_p(out.data_ptr()),
-                                    C.c_void_p(ws.data_ptr() if ws is not None else 0), ws.numel() if ws is not None else 0,
-                                    C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+            _lib.check(L.arp_ess_ws(_lib.ptr(x), S, Cn * D, row_stride, _lib.ptr(out), _lib.ptr(ws),
+                                    ws.numel() if ws is not None else 0, _lib.stream()))
             ev[1].record()
             del ws
         # bench.py reads the kernel time of the LAST call off these events (after the caller has synchronised anyway)

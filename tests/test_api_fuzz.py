@@ -80,6 +80,12 @@ def _fake(n_bytes):
     return buf, C.c_void_p(buf.ctypes.data)
 
 
+def _fake_aligned(n_bytes, off=0):
+    """The same with the address rounded up to 256 bytes (what the workspaces ask for), plus `off`."""
+    buf = np.zeros(max(8, n_bytes) + 512, np.uint8)
+    return buf, C.c_void_p(((buf.ctypes.data + 255) & ~255) + off)
+
+
 def test_randomised_calls_never_crash_and_always_explain(host_lib):
     L = host_lib.lib()
     rnd = random.Random(20261002)
@@ -97,11 +103,18 @@ def test_randomised_calls_never_crash_and_always_explain(host_lib):
     def err():
         return L.arp_last_error()
 
-    for it in range(3000):
+    def workspace(need):
+        """(pointer or None, bytes) as the `ess` kind draws them: absent, one byte short, whole; misaligned by 4"""
+        ws_bytes = rnd.choice([0, max(0, need - 1), need, need])
+        wsb, wsp = _fake_aligned(min(ws_bytes, 1 << 20), 4 if rnd.random() < 0.3 else 0)
+        keepalive.append(wsb)
+        return (wsp if ws_bytes else None), ws_bytes
+
+    for it in range(4500):
         name = rnd.choice(MODELS)
         sp, h, _ = handles[name]
         hh = h if rnd.random() < 0.9 else C.c_void_p(0)
-        kind = rnd.choice(["logp", "transform", "hmc", "inter", "vi", "ess", "adapt", "clock"])
+        kind = rnd.choice(["logp", "transform", "hmc", "inter", "vi", "ess", "adapt", "clock", "moments", "fold", "rank", "mcess"])
         del keepalive[:]
         L.arp_model_set_param(h, 0, np.ones(sp.D, np.float32).ctypes.data_as(host_lib._f32p),
                               np.ones(sp.D, np.float32).ctypes.data_as(host_lib._f32p))
@@ -166,6 +179,33 @@ def test_randomised_calls_never_crash_and_always_explain(host_lib):
                 wsp = C.c_void_p(wsp.value + 4)                        # misaligned workspace
             rc = L.arp_ess_ws(ptr(), S, n, rnd.choice([n, n - 1, 2 * n + 3]), ptr(),
                               wsp if ws_bytes else None, ws_bytes, None)
+        elif kind in ("moments", "rank", "mcess"):
+            S = rnd.choice([0, -3, 1, 7, 100, 1000, 50000, (1 << 21) + 2, 1 << 31, 10 ** 12])
+            Cn = rnd.choice([0, -1, 1, 4, 64, 1 << 15, 1 << 31])
+            D = rnd.choice([0, -2, 1, 7, 125, 300, 1 << 30])
+            stride = rnd.choice([Cn * D, Cn * D - 1, 2 * Cn * D + 3])
+            flag = rnd.choice([0, 1])                                  # split / fold
+            if kind == "moments":
+                need = L.arp_moments_workspace_bytes(S, Cn * D, flag)
+                assert need >= 0
+                wsp, ws_bytes = workspace(need)
+                rc = L.arp_split_moments(ptr(), S, Cn * D, stride, flag, ptr(), ptr(), wsp, ws_bytes, None)
+            elif kind == "rank":
+                need = L.arp_rank_workspace_bytes(S, Cn, D, flag)
+                assert need >= 0 and (need > 0 or len(err()) > 0)
+                wsp, ws_bytes = workspace(need)
+                n_probs = rnd.choice([0, 0, 2, -1])
+                probs = (C.c_double * 2)(0.05, 0.95) if rnd.random() < 0.8 else None
+                rc = L.arp_rank_normalize(ptr(), S, Cn, D, stride, flag, ptr(), ptr(0.3), ptr(0.5), probs, n_probs, ptr(0.7),
+                                          wsp, ws_bytes, None)
+            else:
+                need = L.arp_ess_multichain_workspace_bytes(S, Cn, D, flag)
+                assert need >= 0 and (need > 0 or len(err()) > 0)
+                wsp, ws_bytes = workspace(need)
+                rc = L.arp_ess_multichain(ptr(), S, Cn, D, stride, flag, ptr(0.3), ptr(), ptr(0.5), ptr(0.5),
+                                          rnd.choice([0, 0, 3, -1]), wsp, ws_bytes, None)
+        elif kind == "fold":
+            rc = L.arp_moments_fold(ptr(), ptr(), rnd.choice([0, -1, 5, 1 << 40]), rnd.choice([0, -1, 1, 125]), ptr(), None)
         elif kind == "adapt":
             cfg = host_lib.HmcConfig()
             cfg.n_steps = rnd.choice([-1, 0, 4])
@@ -311,3 +351,171 @@ def test_ess_workspace_size_is_a_whole_number_of_row_blocks(host_lib):
         assert sizes[0] > 64 * 4 * S                                   # one whole 64-row block even for one series
         assert sizes[4] - sizes[3] >= 64 * 4 * S                       # the 65th series opens a second block
         assert all(b >= a for a, b in zip(sizes, sizes[1:]))
+
+
+# arp_*_workspace_bytes of the diagnostics by (S, C, D): rank, multichain (split 1, split 0), moments (n = C D, split 1),
+# ess (n = C D).  A zero in the rank and multichain columns is a refusal (with a message).
+DIAG_WORKSPACE_BYTES = {
+    (1000, 4, 7): (238848, 3072, 2048, 2048, 0),
+    (33, 9, 200): (886272, 450048, 230912, 0, 0),
+    (50000, 16, 125): (825216512, 301568, 163840, 3211264, 410050304),
+    (5, 1, 1): (2816, 1024, 1024, 0, 0),
+    (65536, 32768, 5): (0, 0, 0, 335544320, 42954260736),
+}
+
+
+def test_diagnostics_refusals_and_workspace_sizes(host_lib, monkeypatch):
+    """The diagnostics entry points (csrc/diag.hip, rank.hip, mcess.hip, ess.hip) on arguments they must refuse: which
+    check fires and its exact words in arp_last_error(); and the workspace sizes they ask for.  A call that gets past
+    validation fails, without a device, with HIP's own words (which quote the failing expression: not pinned)."""
+    L = host_lib.lib()
+    keep = []
+
+    def p(n=1 << 12):
+        b, ptr = _fake(n)
+        keep.append(b)
+        return ptr
+
+    def ws(off=0):
+        b, ptr = _fake_aligned(1 << 12, off)
+        keep.append(b)
+        return ptr
+
+    for shape, (rank, mc1, mc0, mom, ess) in DIAG_WORKSPACE_BYTES.items():
+        S, Cn, D = shape
+        assert L.arp_rank_workspace_bytes(S, Cn, D, 0) == rank == L.arp_rank_workspace_bytes(S, Cn, D, 1), shape
+        assert L.arp_ess_multichain_workspace_bytes(S, Cn, D, 1) == mc1, shape
+        assert L.arp_ess_multichain_workspace_bytes(S, Cn, D, 0) == mc0, shape
+        assert L.arp_moments_workspace_bytes(S, Cn * D, 1) == mom, shape
+        assert L.arp_ess_workspace_bytes(S, Cn * D) == ess, shape
+    assert L.arp_rank_workspace_bytes(65536, 32768, 5, 0) == 0
+    assert L.arp_last_error() == b"arp_rank_workspace_bytes: at most 2^31 - 1 draws per element (n_samples * n_chains)"
+    assert L.arp_ess_multichain_workspace_bytes(65536, 32768, 5, 1) == 0
+    assert L.arp_last_error() == b"arp_ess_multichain_workspace_bytes: at most 2^31 - 1 draws per element (n_samples * n_chains)"
+
+    S, Cn, D = 1000, 4, 7
+    n = Cn * D
+    RANK, MC = 238848, 3072                       # their workspaces at this shape (above)
+    LS, LN = 50000, 2000                          # a trace of long series: the workspace routes of moments and ess
+    MOM, ESS = 3211264, 410050304
+    probs = (C.c_double * 2)(0.05, 0.95)
+
+    def moments(trace=True, S_=S, n_=n, stride=None, w=None, wb=0):
+        return L.arp_split_moments(p() if trace else None, S_, n_, n_ if stride is None else stride, 1, p(), p(), w, wb, None)
+
+    def fold(mean=True, n_rows=8, D_=D, sums=True):
+        return L.arp_moments_fold(p() if mean else None, p(), n_rows, D_, p() if sums else None, None)
+
+    def rank(trace=True, shape=(S, Cn, D), stride=None, w="ok", wb=RANK, z=True, pr=None, n_probs=0, q=False):
+        S_, C_, D_ = shape
+        return L.arp_rank_normalize(p() if trace else None, S_, C_, D_, C_ * D_ if stride is None else stride, 0,
+                                    p() if z else None, None, None, pr, n_probs, p() if q else None,
+                                    ws() if w == "ok" else w, wb, None)
+
+    def mcess(trace=True, shape=(S, Cn, D), stride=None, split=1, w="ok", wb=MC, ess=True, rho=False, n_rho=0):
+        S_, C_, D_ = shape
+        return L.arp_ess_multichain(p() if trace else None, S_, C_, D_, C_ * D_ if stride is None else stride, split, None,
+                                    p() if ess else None, None, p() if rho else None, n_rho, ws() if w == "ok" else w, wb, None)
+
+    def ess_ws(trace=True, S_=LS, n_=LN, stride=None, w=None, wb=0):
+        return L.arp_ess_ws(p() if trace else None, S_, n_, n_ if stride is None else stride, p(), w, wb, None)
+
+    MOMENTS_ARGS = b"arp_split_moments: trace/mean/var, n_samples > 0, n_series > 0 and row_stride >= n_series are required"
+    FOLD_ARGS = b"arp_moments_fold: sums, D > 0, n_rows >= 0 and (with rows) mean/var are required"
+    RANK_ARGS = b"arp_rank_normalize: trace, z and row_stride >= n_chains * D are required"
+    MC_ARGS = b"arp_ess_multichain: trace, ess and row_stride >= n_chains * D are required"
+    ESS_ARGS = b"arp_ess: trace/ess, n_samples > 0, n_series > 0 and row_stride >= n_series are required"
+    SHAPE = b": n_samples > 0, n_chains > 0 and D > 0 are required"
+    DRAWS = b": at most 2^31 - 1 draws per element (n_samples * n_chains)"
+    VALUES = b": at most 2^35 values per call"
+    RANK_SMALL = b"arp_rank_normalize: workspace too small (see arp_rank_workspace_bytes)"
+    RANK_ALIGN = b"arp_rank_normalize: the workspace must be 256-byte aligned"
+    MC_SMALL = b"arp_ess_multichain: workspace too small (see arp_ess_multichain_workspace_bytes)"
+    MC_ALIGN = b"arp_ess_multichain: the workspace must be 256-byte aligned"
+    MC_ROW = b"arp_ess_multichain: at most 2^20 draws per row (n_samples, or n_samples / 2 with split)"
+    ESS_SMALL = b"arp_ess_ws: workspace too small (the work lists and at least 64 series rows: see arp_ess_workspace_bytes)"
+    ESS_ALIGN = b"arp_ess_ws: the workspace must be 256-byte aligned"
+    two31 = (1 << 31, 1, 1)
+    two35 = (1 << 20, 1 << 10, 33)
+
+    table = [
+        # a null pointer
+        ("moments null", lambda: moments(trace=False), MOMENTS_ARGS),
+        ("fold null sums", lambda: fold(sums=False), FOLD_ARGS),
+        ("fold null mean", lambda: fold(mean=False), FOLD_ARGS),
+        ("rank null trace", lambda: rank(trace=False), RANK_ARGS),
+        ("rank null z", lambda: rank(z=False), RANK_ARGS),
+        ("mcess null trace", lambda: mcess(trace=False), MC_ARGS),
+        ("mcess null ess", lambda: mcess(ess=False), MC_ARGS),
+        ("ess null", lambda: ess_ws(trace=False), ESS_ARGS),
+        # a short stride
+        ("moments stride", lambda: moments(stride=n - 1), MOMENTS_ARGS),
+        ("rank stride", lambda: rank(stride=n - 1), RANK_ARGS),
+        ("mcess stride", lambda: mcess(stride=n - 1), MC_ARGS),
+        ("ess stride", lambda: ess_ws(stride=LN - 1), ESS_ARGS),
+        # a workspace too small, or none
+        ("rank short ws", lambda: rank(wb=RANK - 1), RANK_SMALL),
+        ("rank no ws", lambda: rank(w=None), RANK_SMALL),
+        ("mcess short ws", lambda: mcess(wb=MC - 1), MC_SMALL),
+        ("mcess no ws", lambda: mcess(w=None), MC_SMALL),
+        ("ess short ws", lambda: ess_ws(w=ws(), wb=1024), ESS_SMALL),
+        # a misaligned workspace; where it is also too small, which of the two is said
+        ("rank misaligned", lambda: rank(w=ws(4)), RANK_ALIGN),
+        ("rank misaligned + short", lambda: rank(w=ws(4), wb=RANK - 1), RANK_SMALL),
+        ("mcess misaligned", lambda: mcess(w=ws(4)), MC_ALIGN),
+        ("mcess misaligned + short", lambda: mcess(w=ws(4), wb=MC - 1), MC_SMALL),
+        ("ess misaligned", lambda: ess_ws(w=ws(4), wb=ESS), ESS_ALIGN),
+        ("ess misaligned + short", lambda: ess_ws(w=ws(4), wb=1024), ESS_ALIGN),
+        ("moments misaligned", lambda: moments(S_=LS, n_=LN, w=ws(4), wb=MOM), b"arp_split_moments: the workspace must be 256-byte aligned"),
+        # 2^31 draws per element, 2^35 values, 2^20 draws per row: before anything else, pointers included
+        ("rank shape", lambda: rank(shape=(S, 0, D)), b"arp_rank_normalize" + SHAPE),
+        ("mcess shape", lambda: mcess(shape=(S, Cn, -1)), b"arp_ess_multichain" + SHAPE),
+        ("rank 2^31", lambda: rank(trace=False, shape=two31), b"arp_rank_normalize" + DRAWS),
+        ("rank 2^31 product", lambda: rank(shape=(65536, 32768, 5)), b"arp_rank_normalize" + DRAWS),
+        ("mcess 2^31", lambda: mcess(trace=False, shape=two31), b"arp_ess_multichain" + DRAWS),
+        ("rank 2^35", lambda: rank(shape=two35, w=None), b"arp_rank_normalize" + VALUES),
+        ("mcess 2^35", lambda: mcess(shape=two35, w=None), b"arp_ess_multichain" + VALUES),
+        ("rank bytes 2^35", lambda: int(L.arp_rank_workspace_bytes(*two35, 0) == 0), b"arp_rank_workspace_bytes" + VALUES),
+        ("mcess bytes 2^35", lambda: int(L.arp_ess_multichain_workspace_bytes(*two35, 1) == 0),
+         b"arp_ess_multichain_workspace_bytes" + VALUES),
+        ("mcess 2^20 split", lambda: mcess(trace=False, shape=((1 << 21) + 2, 4, 7)), MC_ROW),
+        ("mcess 2^20 whole", lambda: mcess(shape=((1 << 20) + 1, 4, 7), split=0), MC_ROW),
+        ("mcess bytes 2^20", lambda: int(L.arp_ess_multichain_workspace_bytes((1 << 20) + 1, 4, 7, 0) == 0),
+         b"arp_ess_multichain_workspace_bytes: at most 2^20 draws per row (n_samples, or n_samples / 2 with split)"),
+        ("mcess 2^20 draws per row fit", lambda: mcess(shape=((1 << 21) + 1, 1, 1), w=None), MC_SMALL),
+        ("moments 2^30", lambda: moments(n_=1 << 30), b"arp_split_moments: at most 2^30 - 1 series per call"),
+        ("ess 2^30", lambda: ess_ws(n_=1 << 30), b"arp_ess: at most 2^30 - 1 series per call (32-bit lane offsets)"),
+        # n_rho without rho; quantiles without probs (after the pointers, before the workspace)
+        ("mcess n_rho", lambda: mcess(n_rho=3, w=None), b"arp_ess_multichain: n_rho >= 0, and rho where n_rho > 0"),
+        ("mcess n_rho < 0", lambda: mcess(rho=True, n_rho=-1), b"arp_ess_multichain: n_rho >= 0, and rho where n_rho > 0"),
+        ("mcess n_rho, null trace", lambda: mcess(trace=False, n_rho=3), MC_ARGS),
+        ("rank probs", lambda: rank(q=True, n_probs=2, w=None), b"arp_rank_normalize: quantiles need n_probs >= 0 and probs"),
+        # arp_moments_fold with D = 0
+        ("fold D = 0", lambda: fold(D_=0), FOLD_ARGS),
+        ("fold n_rows < 0", lambda: fold(n_rows=-1), FOLD_ARGS),
+        # past validation: no device
+        ("moments", lambda: moments(), None),
+        ("moments, long route", lambda: moments(S_=LS, n_=LN, w=ws(), wb=MOM), None),
+        ("moments, workspace too small: the wide route", lambda: moments(S_=LS, n_=LN, w=ws(), wb=MOM - 1), None),
+        ("fold", lambda: fold(), None),
+        ("fold, no rows", lambda: fold(mean=False, n_rows=0), None),
+        ("rank", lambda: rank(pr=probs, n_probs=2, q=True), None),
+        ("mcess", lambda: mcess(rho=True, n_rho=3), None),
+        ("mcess, three draws per row", lambda: mcess(shape=(7, 4, 7)), None),
+        ("ess", lambda: ess_ws(S_=S, n_=n), None),
+        ("ess, workspace", lambda: ess_ws(w=ws(), wb=ESS), None),
+        ("ess, long series without a workspace", lambda: ess_ws(), None),
+    ]
+    for what, call, message in table:
+        rc = call()
+        got = L.arp_last_error()
+        assert rc != 0 and len(got) > 0, what
+        if message is not None:
+            assert got == message, (what, got)
+        del keep[:]
+    # the long route of arp_split_moments forced (an experiment switch): only then is a workspace too small refused
+    monkeypatch.setenv("ARP_MOMENTS_ROUTE", "long")
+    assert moments(S_=LS, n_=LN, w=ws(), wb=MOM - 1) != 0
+    assert L.arp_last_error() == b"arp_split_moments: workspace too small (see arp_moments_workspace_bytes)"
+    assert moments(S_=LS, n_=LN, w=ws(4), wb=MOM - 1) != 0
+    assert L.arp_last_error() == b"arp_split_moments: workspace too small (see arp_moments_workspace_bytes)"

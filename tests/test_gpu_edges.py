@@ -166,6 +166,20 @@ def test_native_ess_matches_oracle_and_ar1(gpu):
     np.testing.assert_allclose(util.effective_sample_size(slow.to(gpu)).cpu().numpy(), ess_ref.ess_fft(slow.numpy()), rtol=2e-3)
 
 
+def test_ess_of_an_inner_block_of_chains_equals_its_copy(gpu):
+    """util.effective_sample_size reads an inner block of chains of a wider trace in place, rows a wider stride apart, as
+    split_moments, rank_normalize and ess_multichain do: bit for bit the result for the block's contiguous copy."""
+    from oracle import ess_ref
+    from autoreparam_amd import util
+    x = torch.as_tensor(ess_ref.ar1(40, (16, 5), [0.0, 0.3, 0.6, 0.9, -0.4], seed=11), dtype=torch.float32).to(gpu)
+    view = x[:, 3:11, :]
+    assert not view.is_contiguous()
+    in_place = util.effective_sample_size(view)
+    copied = util.effective_sample_size(view.contiguous())
+    assert in_place.shape == (8, 5) and torch.isfinite(copied).all()
+    assert torch.equal(in_place.view(torch.int32), copied.view(torch.int32))
+
+
 def test_long_series_ess_on_the_matrix_cores(gpu):
     """arp_ess_ws: series longer than the one-kernel path holds in LDS (S + 72 > 2 304) that are still positively
     correlated after the coalesced sweeps are finished by ess_tail_kernel (Toeplitz blocks on v_mfma_f32_16x16x4_f32)

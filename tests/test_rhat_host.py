@@ -203,3 +203,14 @@ def test_flag_defaults_on_and_parses_both_ways():
     assert f.convergence_diagnostics is True
     f.parse(["--noconvergence_diagnostics"]); assert f.convergence_diagnostics is False
     f.parse(["--convergence_diagnostics"]); assert f.convergence_diagnostics is True
+
+
+@pytest.mark.parametrize("name", ["split_moments", "rank_normalize", "ess_multichain"])
+def test_wrappers_refuse_what_is_not_a_float32_device_trace(name):
+    """Every wrapper of a diagnostics kernel names itself when it refuses a trace: one on the CPU, of another type, or not
+    [S, C, D] -- before anything is allocated or the library is loaded."""
+    from autoreparam_amd import diagnostics
+    message = re.escape(name + ": a float32 [S, C, D] trace on the GPU is required (there is no CPU fallback)")
+    for bad in (torch.zeros(4, 2, 3), torch.zeros(4, 2, 3, dtype=torch.float64), torch.zeros(4, 6)):
+        with pytest.raises(ValueError, match="^" + message + "$"):
+            getattr(diagnostics, name)(bad)
