@@ -103,6 +103,13 @@ def report_rhat(results, results_dir=None, model_name=None, threshold=1.01):
                 num(r["ess_bulk_min"][-1]), num(r["ess_tail_min"][-1]), num(r["ess_mean_min"][-1]),
                 fmt(r["mcse_mean_over_sd_max"][-1]), r["bulk_tail_ess_chains"][-1],
                 "n/a" if r["bulk_tail_ess_time_sec"][-1] is None else "{:.3f}s".format(r["bulk_tail_ess_time_sec"][-1])))
+        if "nested_rhat_max" in r:                         # (--superchain_size runs only)
+            lines.append("      nested R-hat max {} over {} superchains of {} ({} chains, {} left out; stationary floor {}); "
+                         "by step: first {}, last {}; {}".format(
+                fmt(r["nested_rhat_max"][-1]), r["nested_rhat_superchains"][-1], r["nested_rhat_superchain_size"][-1],
+                r["nested_rhat_chains"][-1], r["nested_rhat_left_out"][-1], fmt(r["nested_rhat_floor"][-1]),
+                fmt(r["nested_rhat_first_step_max"][-1]), fmt(r["nested_rhat_last_step_max"][-1]),
+                "n/a" if r["nested_rhat_time_sec"][-1] is None else "{:.3f}s".format(r["nested_rhat_time_sec"][-1])))
         path = os.path.join(results_dir or ".", model_name or "", m + "_rhat.npz")
         if os.path.exists(path):
             z = np.load(path)

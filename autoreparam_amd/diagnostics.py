@@ -3,7 +3,8 @@ BDA3 / Stan / ArviZ, without rank normalisation) and the pooled posterior mean /
 the rank-normalised, folded form of Vehtari, Gelman, Simpson, Carpenter, Buerkner 2021 (`rank_rhat`: what Stan, posterior
 and ArviZ report as R-hat now) with the pooled posterior median and 5 % / 95 % quantiles; and the numbers the same paper
 reports next to it, bulk-ESS, tail-ESS and the Monte-Carlo standard error of the mean (`bulk_tail_ess`), from one
-multi-chain autocorrelation estimator on the device (`arp_ess_multichain`).
+multi-chain autocorrelation estimator on the device (`arp_ess_multichain`); and nested R-hat over superchains (Margossian,
+Hoffman, Sountsov, Riou-Durand, Vehtari, Gelman 2024: `nested_fold`, `nested_step_sums`), the form for many short chains.
 
 Build-specific (the reference runs 100 chains and reports the within-chain ESS only).  The per-chain moments come from
 one pass over a trace that is already on the device (`arp_split_moments`) or from the in-kernel statistics of a
@@ -29,6 +30,10 @@ RankRhat = collections.namedtuple("RankRhat", ["bulk", "tail", "rhat", "median",
 # bulk, tail, mean: the multi-chain ESS of the rank-normalised trace, of the 5 % / 95 % indicators (the smaller) and of the
 # draws; mcse_mean = sd / sqrt(mean); sd: the pooled posterior sd; [D] float64
 BulkTailEss = collections.namedtuple("BulkTailEss", ["bulk", "tail", "mean", "mcse_mean", "sd"])
+
+# Nested R-hat, [D] float64: rhat = sqrt(1 + excess), excess = between / within (B / W: its stationary value is at most
+# 1 / M), superchains = K that counted, left_out = superchains with a non-finite row.  NaN where W = 0 or K < 2.
+NestedRhat = collections.namedtuple("NestedRhat", ["rhat", "excess", "between", "within", "superchains", "left_out"])
 
 
 def split_moments(trace, split=True):
@@ -211,3 +216,72 @@ def rank_rhat(trace):
     q = q.cpu().numpy().astype(np.float64)
     return RankRhat(bulk.rhat, tail.rhat, np.fmax(bulk.rhat, tail.rhat), median.cpu().numpy().astype(np.float64), q[0], q[1],
                     bulk.rows, bulk.constant_rows)
+
+
+def nested_fold(mean, var, M):
+    """The [6, D] float64 device tensor of `arp_moments_fold_nested` over the [C, D] per-chain moments (float32 on the
+    GPU; leading axes are flattened): superchains of M adjacent chains.  Rows: the superchains that count (all M chains
+    finite), sum of g, sum of g^2, sum of b, sum of w, superchains left out.  var = None: one draw per chain, every
+    within-chain variance is 0."""
+    from . import _lib
+    if not (mean.is_cuda and (var is None or (var.is_cuda and var.shape == mean.shape))):
+        raise ValueError("nested_fold: mean (and var, of the same shape) on the GPU are required (there is no CPU fallback)")
+    D = int(mean.shape[-1])
+    m = mean.reshape(-1, D).to(torch.float32).contiguous()
+    v = None if var is None else var.reshape(-1, D).to(torch.float32).contiguous()
+    sums = torch.empty(6, D, dtype=torch.float64, device=mean.device)
+    if D == 0:
+        return sums
+    with torch.cuda.device(mean.device):
+        _lib.check(_lib.lib().arp_moments_fold_nested(_lib.ptr(m), _lib.ptr(v), m.shape[0], D, int(M), _lib.ptr(sums),
+                                                      _lib.stream()))
+    return sums
+
+
+def _nested(k, sg, sgg, sb, sw):
+    """(rhat, excess, B, W) from sums over k superchains, float64 numpy of any one shape."""
+    with np.errstate(divide="ignore", invalid="ignore"):
+        nan = np.full_like(k, np.nan)
+        between = np.where(k >= 2, np.maximum(sgg - sg * sg / k, 0.0) / (k - 1), nan)
+        within = np.where(k >= 1, (sb + sw) / k, nan)
+        excess = np.where(within > 0, between / within, nan)
+        return np.sqrt(1.0 + excess), excess, between, within
+
+
+def nested_rhat_from_sums(sums):
+    """The statistic from the (all-reduced) [6, D] sums of `nested_fold` -> NestedRhat."""
+    s = np.asarray(sums.cpu() if torch.is_tensor(sums) else sums, np.float64)
+    rhat, excess, between, within = _nested(s[0], s[1], s[2], s[3], s[4])
+    return NestedRhat(rhat, excess, between, within, s[0], s[5])
+
+
+def nested_step_workspace_bytes(S, Cn, D, M):
+    """Bytes of device workspace `nested_step_sums` takes for a [S, Cn, D] trace (0: none)."""
+    from . import _lib
+    return int(_lib.lib().arp_nested_step_workspace_bytes(S, Cn, D, int(M)))
+
+
+def nested_step_sums(trace, M):
+    """The [4, S, D] float64 device tensor of `arp_nested_step_sums` for a recorded [S, C, D] float32 trace on the GPU: for
+    every row s the one-draw-per-chain sums over superchains of M adjacent chains -- the superchains that count, sum of g,
+    sum of g^2, sum of b.  A leading or inner block of chains of a wider trace is taken in place, as split_moments takes
+    it; the workspace is owned here."""
+    from . import _lib
+    x, S, Cn, D, row_stride = _lib.trace_view(trace, "nested_step_sums")
+    sums = torch.zeros(4, S, D, dtype=torch.float64, device=trace.device)
+    if S == 0 or Cn == 0 or D == 0:
+        return sums
+    L = _lib.lib()
+    with torch.cuda.device(x.device):
+        need = nested_step_workspace_bytes(S, Cn, D, M)
+        ws = torch.empty(need, dtype=torch.uint8, device=x.device) if need > 0 else None
+        _lib.check(L.arp_nested_step_sums(_lib.ptr(x), S, Cn, D, row_stride, int(M), _lib.ptr(sums), _lib.ptr(ws), need,
+                                          _lib.stream()))
+        del ws
+    return sums
+
+
+def nested_rhat_by_step(sums4):
+    """[S, D] float64 nested R-hat of every row from the (all-reduced) [4, S, D] sums of `nested_step_sums`."""
+    s = np.asarray(sums4.cpu() if torch.is_tensor(sums4) else sums4, np.float64)
+    return _nested(s[0], s[1], s[2], s[3], np.zeros_like(s[3]))[0]

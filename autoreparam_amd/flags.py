@@ -52,6 +52,13 @@ _DEFS = [
                                    "chains split R-hat covers (ess_bulk_min, ess_tail_min, ess_mean_min, "
                                    "mcse_mean_over_sd_max JSON keys, four more families in <base>_rhat.npz).  ess_min "
                                    "stays the reference's per-chain figure.  One process only: a sharded job writes null."),
+    ("superchain_size", int, 0, "Nested R-hat (Margossian et al. 2024): M >= 2 ties the initial population into "
+                                "num_chains / M superchains of M adjacent chains that start from one point (chain c takes "
+                                "the initial state of chain (c // M) * M) and run on their own random streams; with "
+                                "--convergence_diagnostics the run then reports nested R-hat over ALL chains, streaming "
+                                "and sharded jobs included, and its profile over the recorded steps (nested_rhat_* JSON "
+                                "keys and arrays in <base>_rhat.npz).  M must divide num_chains (and every rank's share) "
+                                "and leave at least two superchains.  0: off."),
     ("lanes_per_chain", int, 0, "Lanes of a wave64 a chain is spread over (0 = automatic)."),
 ]
 

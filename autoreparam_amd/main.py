@@ -268,6 +268,8 @@ def _convergence_report(kernel_results, model_config, flags, dev):
     keys.update(rank_keys)
     if getattr(flags, "bulk_tail_ess", False):
         keys.update(_bulk_tail_report(trace, k, spec, arrays, by_part))
+    if int(getattr(flags, "superchain_size", 0) or 0) >= 2:
+        keys.update(_nested_report(trace, moments, int(flags.superchain_size), dev, arrays, by_part))
     keys["diagnostics_time_sec"] = time.time() - clock
     return keys, arrays
 
@@ -311,6 +313,71 @@ def _rank_report(trace, k, spec, arrays, by_part):
     keys.update(rank_rhat_max=_finite_or_none(top), rank_rhat_bulk_max=_finite_or_none(bulk_max),
                 rank_rhat_tail_max=_finite_or_none(tail_max), rank_rhat_chains=k, rank_rhat_time_sec=time.time() - clock)
     return keys
+
+
+def nested_warn_level(K, M):
+    """The B / W above which nested R-hat over K superchains of M chains is reported as not converged: the stationary
+    floor 1 / M with three standard deviations of B's sampling noise over K superchains, sqrt(2 / (K - 1)) of itself, plus
+    the share of non-stationary variance RHAT_WARN stands for.  K may be an array; NaN where K < 2."""
+    K = np.asarray(K, np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return np.where(K >= 2, (1.0 + 3.0 * np.sqrt(2.0 / (K - 1.0))) / M + (RHAT_WARN ** 2 - 1.0), np.nan)
+
+
+def _nested_report(trace, moments, M, dev, arrays, by_part):
+    """--superchain_size M >= 2: nested R-hat (diagnostics.nested_fold -> nested_rhat_from_sums) over ALL chains of the job,
+    from the per-chain moments of the whole trace or, in a streaming run, from the in-kernel statistics (`moments`); and
+    its profile over the recorded steps, one draw per chain (diagnostics.nested_step_sums), over the whole superchains
+    among the chains whose trace is on the device.  Both sets of sums are additive over superchains and every rank holds
+    whole superchains: a sharded job reports real numbers.  Fills `arrays`, returns the nine JSON keys.
+    (A collective when ws > 1: every rank calls it.)"""
+    clock = time.time()
+    S, C_local, D = (int(v) for v in trace.shape)
+    if moments is not None:
+        mean, var = moments
+    else:
+        mean, var = (m[0] for m in diagnostics.split_moments(trace, split=False))
+    n_local = int(mean.shape[0])
+    local = diagnostics.nested_fold(mean, None if S == 1 else var, M)
+    t = parallel.all_reduce_sum(np.concatenate([local.cpu().numpy().ravel(), [float(n_local)]]), dev).cpu().numpy()
+    whole = diagnostics.nested_rhat_from_sums(t[:-1].reshape(6, D))
+    n_chains = int(round(t[-1]))
+    top, at = _nan_max(whole.rhat)
+    by_part(arrays, (("nested_rhat", whole.rhat),))
+    counted = int(whole.superchains.min()) if D else 0
+    left_out = int(whole.left_out.max()) if D else 0
+    floor = float(np.sqrt(1.0 + 1.0 / M))
+    util.print_("    nested R-hat over {} superchains of {} chains: max {:.4f} (element {}; stationary floor {:.4f}{})".format(
+        counted, M, top, at, floor, "; {} superchain(s) left out, not finite".format(left_out) if left_out else ""))
+    with np.errstate(invalid="ignore"):
+        alarm = bool(np.any(whole.excess > nested_warn_level(whole.superchains, M)))
+
+    # the profile: one draw per chain at every recorded step, over the leading whole superchains of the device trace
+    kk = (C_local // M) * M
+    local4 = diagnostics.nested_step_sums(trace[:, :kk], M).cpu().numpy() if kk > 0 else np.zeros((4, S, D))
+    t = parallel.all_reduce_sum(np.concatenate([local4.ravel(), [float(kk // M)]]), dev).cpu().numpy()
+    first = last = float("nan")
+    if int(round(t[-1])) >= 2 and S > 0:
+        sums4 = t[:-1].reshape(4, S, D)
+        by_step = diagnostics.nested_rhat_by_step(sums4)                       # [S, D]: not saved (tens of MB for a kept trace)
+        ok = np.isfinite(by_step)
+        arrays["nested_rhat_by_step_element"] = np.where(ok.any(axis=1), np.where(ok, by_step, -np.inf).argmax(axis=1), -1)
+        arrays["nested_rhat_by_step"] = np.where(ok.any(axis=1), np.where(ok, by_step, -np.inf).max(axis=1), np.nan)
+        first, last = float(arrays["nested_rhat_by_step"][0]), float(arrays["nested_rhat_by_step"][-1])
+        util.print_("    nested R-hat by step over {} superchains (one draw per chain): first {:.4f}, last {:.4f}".format(
+            int(round(t[-1])), first, last))
+        with np.errstate(invalid="ignore"):
+            alarm = alarm or bool(np.any(by_step[0] ** 2 - 1.0 > nested_warn_level(sums4[0, 0], M)))
+    else:
+        util.print_("    nested R-hat by step: fewer than two whole superchains have their trace on the device")
+    if alarm:
+        util.print_("    WARNING: nested R-hat above its stationary level (B / W > (1 + 3 sqrt(2 / (K - 1))) / M + {:.4f}): the "
+                    "superchains have not forgotten their starting points (the elements: <base>_rhat.npz)".format(
+                        RHAT_WARN ** 2 - 1.0))
+    return {"nested_rhat_max": _finite_or_none(top), "nested_rhat_superchains": counted, "nested_rhat_superchain_size": M,
+            "nested_rhat_chains": n_chains, "nested_rhat_floor": floor, "nested_rhat_left_out": left_out,
+            "nested_rhat_first_step_max": _finite_or_none(first), "nested_rhat_last_step_max": _finite_or_none(last),
+            "nested_rhat_time_sec": time.time() - clock}
 
 
 ESS_PER_CHAIN_WARN = 100    # Stan's rule: bulk- and tail-ESS of at least 100 per chain
@@ -368,7 +435,9 @@ def _bulk_tail_report(trace, k, spec, arrays, by_part):
 def save_rhat(file_path_base, arrays):
     """`<base>_rhat.npz` (build-specific): per latent part `split_rhat/<part>` and the pooled `posterior_mean/<part>`,
     `posterior_sd/<part>` over the chains the split statistic covers, [*event] each; a streaming run adds the same three
-    over ALL chains from the in-kernel statistics (`rhat_all_chains/`, `posterior_mean_all_chains/`, `posterior_sd_all_chains/`)."""
+    over ALL chains from the in-kernel statistics (`rhat_all_chains/`, `posterior_mean_all_chains/`, `posterior_sd_all_chains/`);
+    --superchain_size adds `nested_rhat/<part>` over all chains and the profile `nested_rhat_by_step` [S] (the largest
+    element of every recorded step) with `nested_rhat_by_step_element` [S] (which element that is)."""
     np.savez(file_path_base + "_rhat.npz", **arrays)
 
 
@@ -380,11 +449,45 @@ def _read_vi_fit(file_path):
         return json.load(f)
 
 
+def check_superchains(M, num_chains, world_size=1):
+    """--superchain_size M against the job: raises ValueError unless M = 0 (off) or M >= 2 divides num_chains into at
+    least two superchains, and every rank's shard (parallel.shard_bounds) holds whole superchains."""
+    M, num_chains, world_size = int(M), int(num_chains), int(world_size)
+    if M == 0:
+        return
+    if M < 2:
+        raise ValueError("--superchain_size must be 0 (off) or at least 2, not %d" % M)
+    if num_chains % M != 0:
+        raise ValueError("--superchain_size=%d does not divide --num_chains=%d" % (M, num_chains))
+    if num_chains // M < 2:
+        raise ValueError("--superchain_size=%d leaves %d superchain(s) of --num_chains=%d: nested R-hat needs at least two"
+                         % (M, num_chains // M, num_chains))
+    if world_size > 1 and num_chains % (M * world_size) != 0:
+        raise ValueError("--superchain_size=%d: the %d ranks of this job must hold whole superchains (--num_chains=%d is "
+                         "not a multiple of %d)" % (M, world_size, num_chains, M * world_size))
+
+
+def tie_superchains(parts, M, world_size=1):
+    """The initial population tied into superchains of M adjacent chains (Margossian et al. 2024): chain c takes the state
+    of chain (c // M) * M, for every latent part ([C, *event] arrays).  The chains' random streams are keyed by their
+    global id and stay their own, which is what makes tied chains part ways.  M = 0: `parts` itself, untouched."""
+    if int(M) == 0:
+        return parts
+    n = int(np.asarray(parts[0]).shape[0])
+    check_superchains(M, n, world_size)
+    leader = (np.arange(n) // int(M)) * int(M)
+    return [np.ascontiguousarray(np.asarray(p)[leader]) for p in parts]
+
+
 def _initial_population(fit, model_config, flags):
-    """num_chains draws from the fitted mean-field Normal (reference util.py:394-410), one array per latent part."""
+    """num_chains draws from the fitted mean-field Normal (reference util.py:394-410), one array per latent part; with
+    --superchain_size M tied into superchains (tie_superchains)."""
+    M = int(getattr(flags, "superchain_size", 0) or 0)
+    check_superchains(M, flags.num_chains, parallel.world()[1])               # (before anything is drawn or launched)
     names = _param_names(model_config)
-    return list(util.variational_inits_from_params(fit["learned_variational_params"], param_names=names,
-                                                   num_inits=flags.num_chains, seed=flags.seed).values())
+    population = list(util.variational_inits_from_params(fit["learned_variational_params"], param_names=names,
+                                                         num_inits=flags.num_chains, seed=flags.seed).values())
+    return tie_superchains(population, M, parallel.world()[1])
 
 
 def _settle_leapfrog_count(fit, tuning, flags):

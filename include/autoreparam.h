@@ -348,6 +348,39 @@ int arp_ess_multichain(const float* trace, int64_t n_samples, int64_t n_chains, 
                        int split, const float* threshold, float* ess, int32_t* max_t,
                        float* rho, int32_t n_rho, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* Nested R-hat over superchains (build-specific; Margossian et al. 2024: the convergence diagnostic for many short chains).
+ * The n_rows = K M chains form K superchains of M = `group` chains that are adjacent on the chain axis (superchain k owns
+ * rows k M ... k M + M - 1) and started from one point.  mean, var: [n_rows][D] float32 per-chain moments as for
+ * arp_moments_fold; var may be NULL (one draw per chain: every within-chain variance is 0 and only the means are tested).
+ * A superchain counts where all M of its rows have a finite mean and a finite var in column d; any other is left out
+ * whole.  With g_k = mean over its rows of mean, b_k = sum (mean - g_k)^2 / (M - 1) -- from deviations about a row of the
+ * group, never a difference of raw squares -- and w_k = mean over its rows of var, over the superchains that count:
+ *   sums[0][d] = their number, sums[1][d] = sum g_k, sums[2][d] = sum g_k^2, sums[3][d] = sum b_k, sums[4][d] = sum w_k,
+ *   sums[5][d] = the number of superchains left out.
+ * float64 accumulation in a fixed order (bitwise reproducible, no atomics); sums is a DEVICE [6][D] double buffer.  The six
+ * vectors are additive over superchains, hence over ranks that hold whole superchains; the host takes
+ * B = (sums[2] - sums[1]^2 / K) / (K - 1) in float64, good to ~ 2^-52 K gbar^2 / ((K - 1) B) of itself.  Any M from 2 to
+ * n_rows, any D >= 1; n_rows = 0 gives zeros.  One workgroup, no workspace.  Returns 1 (arp_last_error) on a missing
+ * argument, group < 2 or n_rows not a multiple of group. */
+int arp_moments_fold_nested(const float* mean, const float* var, int64_t n_rows, int32_t D, int64_t group,
+                            double* sums, void* stream);
+
+/* The same sums with ONE draw per chain, for every row of a recorded trace: the profile of nested R-hat over the sampling
+ * phase.  Trace addressing as arp_rank_normalize (draw s of chain c, element d is trace[s * row_stride + c * D + d],
+ * row_stride >= n_chains * D: a block of chains of a wider trace is read in place); n_chains = K group.  With g and b
+ * taken over the M draws of a superchain in row s, over the superchains whose M draws of (s, d) are all finite:
+ *   sums[0][s][d] = their number, sums[1][s][d] = sum g, sums[2][s][d] = sum g^2, sums[3][s][d] = sum b.
+ * sums is a DEVICE [4][n_samples][D] double buffer.  One pass over the trace, lanes along a superchain's contiguous
+ * M * D floats; float64 deviations from a draw of the group, partial (count, mean, M2) merged in a fixed order, no
+ * atomics: bitwise reproducible, and the same for a block of chains taken in place as for its contiguous copy.
+ * arp_nested_step_workspace_bytes is 0 where one workgroup per row fills the device; otherwise it is the size of the
+ * per-workgroup partial sums a second launch adds up, and the workspace is required and 256-byte aligned.  Returns 1
+ * (arp_last_error) on a missing argument, group < 2, n_chains not a multiple of group, a workspace too small or
+ * misaligned, or a shape arp_rank_normalize would refuse. */
+int64_t arp_nested_step_workspace_bytes(int64_t n_samples, int64_t n_chains, int32_t D, int64_t group);
+int arp_nested_step_sums(const float* trace, int64_t n_samples, int64_t n_chains, int32_t D, int64_t row_stride,
+                         int64_t group, double* sums, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* Test hook: the step-size adaptation recurrence of the chain kernels on SCRIPTED log acceptance ratios
  * (tfp.mcmc.DualAveragingStepSizeAdaptation / SimpleStepSizeAdaptation as wired at inference.py:224-226, 288-306;
  * SURVEY.md 8c known answer (7)).  For each of `n` independent rows, applies the update after transitions
