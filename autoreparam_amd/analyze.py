@@ -1,6 +1,6 @@
 """Pretty-printer for the result files main.py writes (reference analyze.py:30-185):
 
-    python -m autoreparam_amd.analyze --results_dir=. --model=radon_MN --elbos --ess --rhat --reparams
+    python -m autoreparam_amd.analyze --results_dir=. --model=radon_MN --elbos --ess --rhat --energy --reparams
 
 The reference's method list is stale (`cVIP_exp_tied`, analyze.py:19-26) and it expects a
 `num_leapfrog_steps` key that main.py only writes for interleaved runs; here every
@@ -123,9 +123,41 @@ def report_rhat(results, results_dir=None, model_name=None, threshold=1.01):
     return lines
 
 
+def report_energy(results, results_dir=None, model_name=None):
+    """Build-specific: the energy probe of every sampling run that recorded one (--energy_diagnostics; the last run of each
+    file): fresh-momentum trajectories from the run's final and recorded states, not a replay of the transitions the
+    sampler took -- and, where <method>_energy.npz is at hand, where the divergent ones started."""
+    lines = []
+    fmt = lambda v: "n/a" if v is None else "{:.4g}".format(v)
+
+    def row(d):
+        return ("{} of {} trajectories divergent (rate {}, {} not finite); energy error {} +/- {}; expected acceptance {}; "
+                "kinetic share of the energy variance {}").format(
+                    d["divergent_trajectories"], d["energy_probe_trajectories"], fmt(d["divergence_rate"]), d["energy_nonfinite"],
+                    fmt(d["energy_error_mean"]), fmt(d["energy_error_sd"]), fmt(d["energy_accept_prob"]),
+                    fmt(d["energy_kinetic_share"]))
+    for m, r in results.items():
+        if "divergence_rate" not in r:
+            continue
+        last = {k: v[-1] for k, v in r.items() if k.startswith(("divergen", "energy_"))}
+        lines.append("{}; {:.3f}s : {}{}".format(row(last), last["energy_time_sec"], m,
+                                                 "   <-- DIVERGENT" if last["divergent_trajectories"] else ""))
+        for j, d in enumerate(last.get("energy_by_kernel") or []):
+            lines.append("      kernel {}: {}".format(j, row(d)))
+        path = os.path.join(results_dir or ".", model_name or "", m + "_energy.npz")
+        if os.path.exists(path) and last["divergent_trajectories"]:
+            z = np.load(path)
+            for key in z.files:
+                if key.startswith("divergent_where/") and len(z[key]):
+                    v = np.asarray(z[key], np.float64).reshape(len(z[key]), -1)
+                    lines.append("      {}: over {} divergent start(s), mean {:.4g}, min {:.4g}, max {:.4g}".format(
+                        key, len(v), np.nanmean(v), np.nanmin(v), np.nanmax(v)))
+    return lines
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
-    for f in ("elbos", "ess", "reparams", "normalize_times", "rhat"):
+    for f in ("elbos", "ess", "reparams", "normalize_times", "rhat", "energy"):
         ap.add_argument("--" + f, action="store_true")
     ap.add_argument("--model", default="all")
     ap.add_argument("--results_dir", default="")
@@ -146,6 +178,8 @@ def main(argv=None):
             print("\n".join(report_ess(results, args.normalize_times)) + "\n")
         if args.rhat:
             print("\n".join(report_rhat(results, root, name)) + "\n")
+        if args.energy:
+            print("\n".join(report_energy(results, root, name)) + "\n")
 
 
 if __name__ == "__main__":

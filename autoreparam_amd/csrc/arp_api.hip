@@ -265,6 +265,22 @@ int arp_transform(arp_model* m, int which, int dir, const float* in, int n_chain
   return 0;
 }
 
+int arp_energy_probe(arp_model* m, int which, const float* x, int64_t n_rows, int n_leapfrog, const float* eps0,
+                     const float* kappa, uint64_t seed, int64_t row_offset, float* out4, float* p_out, float* q_out,
+                     int lanes_per_chain, void* stream) {
+  if (!m || which < 0 || which > 1 || !x || !eps0 || !out4 || n_rows < 1 || n_leapfrog < 1) {
+    set_error("arp_energy_probe: bad argument"); return 1;
+  }
+  // (the instantiation is chosen as arp_logp_grad chooses it; the chain count it decides by is an int)
+  if (n_rows > 0x7fffffffLL / 16) { set_error("arp_energy_probe: n_rows is too large for one launch"); return 1; }
+  const LaneOps* o = select_ops(m, lanes_per_chain, (int)n_rows);
+  if (!o) return 1;
+  o->probe(m->args, m->dev_ab[which], m->dev_ab[which] + m->D, x, n_rows, m->D, n_leapfrog, eps0, kappa, seed, row_offset,
+           out4, p_out, q_out, (hipStream_t)stream);
+  ARP_HIP_OK(hipGetLastError());
+  return 0;
+}
+
 // The step-size recurrences compare log alpha itself with log(target) (kernels.h: adapt_update), which equals TFP's
 // min(log alpha, 0) > log(target) only for a target below 1; a rate <= -1 would flip or zero the step.
 static int check_adapt(const arp_hmc_config* cfg) {

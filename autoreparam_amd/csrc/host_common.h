@@ -12,6 +12,7 @@
 #include "../../include/autoreparam.h"
 #include "host_error.h"
 #include "kernels.h"
+#include "energy_probe.h"
 #include "model_radon.h"
 #include "radon_fast.h"
 #include "election_fast.h"
@@ -57,6 +58,10 @@ struct LaneOps {
   bool vi_parts = false;
   int vi_tile_obs = 0;
   int (*vi_occ)() = nullptr;
+  // energy probe (energy_probe.h): one fresh-momentum trajectory per row of x[N][D], general (a, b) form, every family
+  void (*probe)(const void* args, const float* a, const float* b, const float* x, long long N, int D, int L,
+                const float* eps0, const float* kappa, uint64_t seed, long long row_offset, float* out4, float* p_out,
+                float* q_out, hipStream_t s) = nullptr;
 };
 
 // threads of a VI workgroup: 128 (two waves: with 16 - 32 workgroups per learning rate five learning rates cover
@@ -172,6 +177,13 @@ struct Launch {
     hipLaunchKernelGGL(transform_kernel<Lane>, dim3(blocks(C)), dim3(kBlock), 0, s,
                        *(const typename Lane::Args*)args, a, b, dir, in, C, D, out);
   }
+  static void probe(const void* args, const float* a, const float* b, const float* x, long long N, int D, int L,
+                    const float* eps0, const float* kappa, uint64_t seed, long long row_offset, float* out4, float* p_out,
+                    float* q_out, hipStream_t s) {
+    const long long nb = (N * Lane::K + kBlock - 1) / kBlock;
+    hipLaunchKernelGGL(energy_probe_kernel<Lane>, dim3((unsigned)nb), dim3(kBlock), 0, s,
+                       *(const typename Lane::Args*)args, a, b, x, N, D, L, eps0, kappa, seed, row_offset, out4, p_out, q_out);
+  }
   template <int MODE>
   static void hmc(const void* args, const float* a, const float* b, const HmcParams& P, hipStream_t s) {
     const HmcParams Q = relay_plan(P, blocks(P.C), hmc_kernel<Lane, MODE>);
@@ -235,6 +247,7 @@ struct Launch {
       o.hmc[kModeNCP] = &hmc<kModeNCP>;
       o.interleaved[1] = &interleaved<kModeCP, kModeNCP>;
     }
+    o.probe = &probe;   // named last: the kernels a translation unit already had keep their order
     return o;
   }
 };

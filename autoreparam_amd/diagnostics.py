@@ -4,7 +4,9 @@ the rank-normalised, folded form of Vehtari, Gelman, Simpson, Carpenter, Buerkne
 and ArviZ report as R-hat now) with the pooled posterior median and 5 % / 95 % quantiles; and the numbers the same paper
 reports next to it, bulk-ESS, tail-ESS and the Monte-Carlo standard error of the mean (`bulk_tail_ess`), from one
 multi-chain autocorrelation estimator on the device (`arp_ess_multichain`); and nested R-hat over superchains (Margossian,
-Hoffman, Sountsov, Riou-Durand, Vehtari, Gelman 2024: `nested_fold`, `nested_step_sums`), the form for many short chains.
+Hoffman, Sountsov, Riou-Durand, Vehtari, Gelman 2024: `nested_fold`, `nested_step_sums`), the form for many short chains;
+and the energy report of probed trajectories (`energy_sums`, `energy_from_sums` on Engine.energy_probe's output: divergent
+trajectories, energy-error moments, expected acceptance, the kinetic share of the energy variance).
 
 Build-specific (the reference runs 100 chains and reports the within-chain ESS only).  The per-chain moments come from
 one pass over a trace that is already on the device (`arp_split_moments`) or from the in-kernel statistics of a
@@ -34,6 +36,14 @@ BulkTailEss = collections.namedtuple("BulkTailEss", ["bulk", "tail", "mean", "mc
 # Nested R-hat, [D] float64: rhat = sqrt(1 + excess), excess = between / within (B / W: its stationary value is at most
 # 1 / M), superchains = K that counted, left_out = superchains with a non-finite row.  NaN where W = 0 or K < 2.
 NestedRhat = collections.namedtuple("NestedRhat", ["rhat", "excess", "between", "within", "superchains", "left_out"])
+
+# Energy report of probed trajectories (Engine.energy_probe).  divergence_rate = divergent / rows; divergent: the energy
+# error is not finite or above DIVERGENCE_THRESHOLD; nonfinite: the not-finite ones among them; error_mean, error_sd: of
+# the energy error over the other rows; accept_prob: mean of min(1, exp(-error)), divergent rows counting 0;
+# kinetic_share = (D / 2) / Var(E0).  NaN where there are too few rows.
+Energy = collections.namedtuple("Energy", ["divergence_rate", "divergent", "nonfinite", "rows", "error_mean", "error_sd",
+                                           "accept_prob", "kinetic_share"])
+DIVERGENCE_THRESHOLD = 1000.0     # Stan's: a trajectory whose energy error exceeds it is reported as divergent
 
 
 def split_moments(trace, split=True):
@@ -285,3 +295,46 @@ def nested_rhat_by_step(sums4):
     """[S, D] float64 nested R-hat of every row from the (all-reduced) [4, S, D] sums of `nested_step_sums`."""
     s = np.asarray(sums4.cpu() if torch.is_tensor(sums4) else sums4, np.float64)
     return _nested(s[0], s[1], s[2], s[3], np.zeros_like(s[3]))[0]
+
+
+def energy_sums(out4):
+    """The float64 [9] tensor of sums over the rows of `out4` ([N, 4]: logp and kinetic energy at the start and at the end
+    of a probed trajectory, Engine.energy_probe), additive over rows, hence over probe calls and ranks: plain torch
+    reductions on the device `out4` lives on (the probe's output never leaves the GPU for them).  With
+    the energy error dh = (lp0 - lp1) + (ke1 - ke0) formed in float64 and E0 = ke0 - lp0: rows; divergent rows (dh not finite
+    or above DIVERGENCE_THRESHOLD); rows with a non-finite dh; sum of dh and of dh^2 over the other rows; sum of
+    min(1, exp(-dh)), a divergent row counting 0; sum of E0 and of E0^2; sum of ke0."""
+    if not (torch.is_tensor(out4) and out4.dim() == 2 and out4.shape[1] == 4):
+        raise ValueError("energy_sums: an [N, 4] tensor is required")
+    o = out4.to(torch.float64)
+    lp0, ke0, lp1, ke1 = o[:, 0], o[:, 1], o[:, 2], o[:, 3]
+    dh = (lp0 - lp1) + (ke1 - ke0)
+    finite = torch.isfinite(dh)
+    divergent = ~finite | (dh > DIVERGENCE_THRESHOLD)
+    zero = torch.zeros_like(dh)
+    d = torch.where(divergent, zero, dh)
+    acc = torch.where(divergent, zero, torch.exp(-d).clamp(max=1.0))
+    e0 = ke0 - lp0
+    return torch.stack([torch.tensor(float(o.shape[0]), dtype=torch.float64, device=o.device),
+                        divergent.sum().to(torch.float64), (~finite).sum().to(torch.float64), d.sum(), (d * d).sum(),
+                        acc.sum(), e0.sum(), (e0 * e0).sum(), ke0.sum()])
+
+
+def energy_from_sums(sums, D):
+    """The report from the (all-reduced) [9] sums of `energy_sums` over trajectories of a D-dimensional state -> Energy.
+    kinetic_share = (D / 2) / Var(E0) is Betancourt's E-BFMI, E[Var(E | q)] / Var(E), with the numerator exact: given q the
+    energy varies by the kinetic energy alone, half a chi-square of D degrees of freedom, whose variance is D / 2.  Stan
+    estimates the same quantity from consecutive transitions (lag one), and that estimator reads about twice as large on a
+    well-mixed chain: its numerator is the mean squared change of E between two transitions, which for an accurate
+    integrator is that of a momentum resampling, E[(K' - K)^2] = 2 Var(K) = D, twice the numerator here.  Stan's customary
+    threshold (0.3) is therefore not this figure's, and none is applied."""
+    s = np.asarray(sums.cpu() if torch.is_tensor(sums) else sums, np.float64).reshape(9)
+    rows, divergent, nonfinite = int(round(s[0])), int(round(s[1])), int(round(s[2]))
+    good = rows - divergent
+    nan = float("nan")
+    error_mean = s[3] / good if good >= 1 else nan
+    error_sd = float(np.sqrt(max(s[4] - s[3] * s[3] / good, 0.0) / (good - 1))) if good >= 2 else nan
+    var_e0 = (s[7] - s[6] * s[6] / rows) / (rows - 1) if rows >= 2 else nan
+    share = 0.5 * D / var_e0 if np.isfinite(var_e0) and var_e0 > 0 else nan
+    return Energy(divergent / rows if rows else nan, divergent, nonfinite, rows, error_mean, error_sd,
+                  s[5] / rows if rows else nan, share)

@@ -127,6 +127,28 @@ class Engine(object):
                                              _ptr(out), _stream()))
         return out
 
+    def energy_probe(self, x, eps0, n_leapfrog, which=0, kappa=None, seed=0, row_offset=0, lanes=0, want_p=False,
+                     want_q=False):
+        """One fresh-momentum trajectory from every row of `x` [N, D] (parameterisation `which`) with the steps
+        eps0[d] * kappa[row] and `n_leapfrog` leapfrog steps (arp_energy_probe): returns out [N, 4] float32 =
+        (logp, kinetic energy) at the start and at the end, then the drawn momenta (want_p) and the end states (want_q),
+        [N, D] each.  Not a replay of a transition the sampler took; `x` is not changed.  The momenta depend on `lanes`."""
+        x = self._dev(x)
+        n = x.shape[0]
+        eps = eps0.to(self.device, torch.float32).contiguous() if torch.is_tensor(eps0) else self._dev(np.asarray(eps0, np.float32))
+        assert x.dim() == 2 and x.shape[1] == self.D and eps.shape == (self.D,)
+        kap = None if kappa is None else self._dev(kappa)
+        assert kap is None or kap.shape == (n,)
+        out = torch.empty(n, 4, dtype=torch.float32, device=self.device)
+        p = torch.empty_like(x) if want_p else None
+        q = torch.empty_like(x) if want_q else None
+        with torch.cuda.device(self.device):
+            _lib.check(self._L.arp_energy_probe(self._h, int(which), _ptr(x), n, int(n_leapfrog), _ptr(eps), _ptr(kap),
+                                                int(seed) & 0xFFFFFFFFFFFFFFFF, int(row_offset), _ptr(out), _ptr(p), _ptr(q),
+                                                int(lanes), _stream()))
+        extra = tuple(t for t in (p, q) if t is not None)
+        return (out,) + extra if extra else out
+
     # -- HMC ----------------------------------------------------------------
     def hmc_run(self, state, eps0, n_leapfrog, n_steps, which=0, seed=0, chain_offset=0,
                 adapt_kind=_lib.ADAPT_NONE, n_adapt=0, adapt_target=0.75, adapt_rate=0.05,

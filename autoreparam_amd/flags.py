@@ -59,6 +59,17 @@ _DEFS = [
                                 "and sharded jobs included, and its profile over the recorded steps (nested_rhat_* JSON "
                                 "keys and arrays in <base>_rhat.npz).  M must divide num_chains (and every rank's share) "
                                 "and leave at least two superchains.  0: off."),
+    ("energy_diagnostics", bool, False, "Sampling runs, with --convergence_diagnostics: probe the finished run's integrator "
+                                        "(arp_energy_probe): one fresh-momentum trajectory, with the run's own step sizes "
+                                        "and leapfrog count, from the final state of every chain and from "
+                                        "--energy_probe_steps recorded steps of the device trace -- not a replay of the "
+                                        "transitions the sampler took.  Reports the rate of divergent trajectories (energy "
+                                        "error not finite or above 1000, Stan's threshold), the energy error's mean and sd, "
+                                        "the expected acceptance and the kinetic share of the energy variance "
+                                        "(divergence_rate, energy_* JSON keys, <base>_energy.npz with the states where "
+                                        "trajectories diverged).  Sharded jobs included."),
+    ("energy_probe_steps", int, 8, "With --energy_diagnostics: how many evenly spaced recorded steps of the device trace "
+                                   "are probed (the first and the last among them; fewer if fewer were recorded)."),
     ("lanes_per_chain", int, 0, "Lanes of a wave64 a chain is spread over (0 = automatic)."),
 ]
 

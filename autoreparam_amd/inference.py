@@ -25,6 +25,35 @@ KernelResults = collections.namedtuple("KernelResults", ["inner_results", "new_s
 InterleavedKernelResults = collections.namedtuple("InterleavedKernelResults", ["cp_results", "ncp_results", "ess_info", "moments",
                                                                                "trace"], defaults=(None, None, None))
 
+
+# What an energy probe of the finished run needs (main._energy_report): the engine, the final state of every local chain
+# ([C, D] on the device, in the coordinates of parameterisation 0), the global id of the first of them and, per inner
+# kernel, its parameterisation slot, base step sizes, leapfrog count and the chains' step multipliers ([C] on the device).
+ProbeKernel = collections.namedtuple("ProbeKernel", ["which", "eps0", "n_leapfrog", "kappa"])
+ProbeContext = collections.namedtuple("ProbeContext", ["engine", "q", "chain_offset", "kernels"])
+
+
+class _Probed(object):
+    """Mixin of the result tuples a real run returns: the tuple keeps its fields, a ProbeContext rides along as the
+    attribute `probe` (a namedtuple itself takes no attributes) -- like ess_info and moments it belongs to the call that
+    produced it."""
+    probe = None
+
+
+class _ProbedKernelResults(_Probed, KernelResults):
+    pass
+
+
+class _ProbedInterleavedKernelResults(_Probed, InterleavedKernelResults):
+    pass
+
+
+def _with_probe(results, context):
+    out = (_ProbedInterleavedKernelResults if isinstance(results, InterleavedKernelResults) else _ProbedKernelResults)(*results)
+    out.probe = context
+    return out
+
+
 # transitions per launch: keeps a single launch well under a second at any size
 _MAX_STEPS_PER_LAUNCH = 4096
 
@@ -410,6 +439,8 @@ def hmc(target, model_config, step_size_init, initial_states, reparam, flags=FLA
     step_mult = st.adapt[:, 0].cpu().numpy()
     kernel_results = KernelResults(HmcInnerResults(accs[0]), step_mult, st.step, info, moments,
                                    trace if trace is not None else kept)
+    kernel_results = _with_probe(kernel_results, ProbeContext(eng, st.q, int(chain_offset), (
+        ProbeKernel(0, eps0, L, st.adapt[:, 0].contiguous()),)))
     if trace is not None:
         states_transformed = _device_parts(spec, trace)
         states_orig = _LazyOriginalStates(eng, spec, trace, 0)
@@ -460,4 +491,7 @@ def hmc_interleaved(model_config, target_cp, target_ncp, num_leapfrog_steps_cp, 
         cp_results=KernelResults(HmcInnerResults(accs[0]), st.adapt[:, 0].cpu().numpy(), st.step),
         ncp_results=KernelResults(HmcInnerResults(accs[1]), st.adapt1[:, 0].cpu().numpy(), st.step),
         ess_info=info, moments=moments, trace=trace if trace is not None else kept)
+    kr = _with_probe(kr, ProbeContext(eng, st.q, int(chain_offset), (
+        ProbeKernel(0, e_cp, int(num_leapfrog_steps_cp), st.adapt[:, 0].contiguous()),
+        ProbeKernel(1, e_ncp, int(num_leapfrog_steps_ncp), st.adapt1[:, 0].contiguous()))))
     return states, kr, ess

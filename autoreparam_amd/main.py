@@ -270,7 +270,109 @@ def _convergence_report(kernel_results, model_config, flags, dev):
         keys.update(_bulk_tail_report(trace, k, spec, arrays, by_part))
     if int(getattr(flags, "superchain_size", 0) or 0) >= 2:
         keys.update(_nested_report(trace, moments, int(flags.superchain_size), dev, arrays, by_part))
+    if getattr(flags, "energy_diagnostics", False):
+        energy_keys, energy_arrays = _energy_report(kernel_results, trace, spec, flags, dev)
+        keys.update(energy_keys)
+        if energy_arrays is not None:
+            arrays[ENERGY_ARRAYS] = energy_arrays          # (run_hmc / run_interleaved_hmc take it out again: save_energy)
     keys["diagnostics_time_sec"] = time.time() - clock
+    return keys, arrays
+
+
+ENERGY_ARRAYS = "energy/"            # where _convergence_report leaves the arrays of <base>_energy.npz among those of _rhat.npz
+ENERGY_WHERE_MAX = 1024              # divergent rows whose states <base>_energy.npz keeps
+
+
+def probe_steps(S, R):
+    """The recorded steps an energy probe visits: R evenly spaced of S, the first and the last among them; all S if S < R."""
+    S, R = int(S), int(R)
+    if S <= 0 or R <= 0:
+        return []
+    return sorted({int(round(v)) for v in np.linspace(0, S - 1, min(S, R))})
+
+
+def _energy_summary(e):
+    """The eight JSON keys of one diagnostics.Energy."""
+    return OrderedDict([
+        ("divergence_rate", _finite_or_none(e.divergence_rate)), ("divergent_trajectories", e.divergent),
+        ("energy_probe_trajectories", e.rows), ("energy_nonfinite", e.nonfinite),
+        ("energy_error_mean", _finite_or_none(e.error_mean)), ("energy_error_sd", _finite_or_none(e.error_sd)),
+        ("energy_accept_prob", _finite_or_none(e.accept_prob)), ("energy_kinetic_share", _finite_or_none(e.kinetic_share))])
+
+
+def _energy_report(kernel_results, trace, spec, flags, dev):
+    """--energy_diagnostics: probe the finished run's integrator (Engine.energy_probe) -- one fresh-momentum trajectory with
+    the run's own base steps, leapfrog count and per-chain step multipliers, NOT a replay of the transitions the sampler
+    took -- from (a) the final state of every chain of this rank and (b) --energy_probe_steps evenly spaced recorded steps
+    of the device trace (its chains are the rank's leading ones; recorded states are centred and go through the existing
+    transform).  The momentum stream of a row is keyed by the global chain id + num_chains x step index (the final state
+    counts as step S), under a seed derived from --seed.  --method=i probes both inner kernels, each with its own steps;
+    the top-level keys then pool the two.  The nine sums are additive: a sharded job reports real numbers.
+    Returns (JSON keys, arrays of <base>_energy.npz or None).  (A collective when ws > 1: every rank calls it.)"""
+    import torch
+    ctx = getattr(kernel_results, "probe", None)
+    if ctx is None:
+        return {}, None
+    clock = time.time()
+    eng, D = ctx.engine, int(spec.D)
+    S = int(trace.shape[0])
+    C_local = int(ctx.q.shape[0])
+    steps = [-1] + probe_steps(S, int(getattr(flags, "energy_probe_steps", 8)))     # (the same on every rank)
+    seed = (int(flags.seed) * 0x9E3779B97F4A7C15 + 0x454E5247) & 0xFFFFFFFFFFFFFFFF
+    centred_final = eng.transform(ctx.q, which=0, to_centered=True) if C_local > 0 else ctx.q
+    sums, errors, where = [], [], []
+    for j, kn in enumerate(ctx.kernels):
+        total = torch.zeros(9, dtype=torch.float64, device=ctx.q.device)
+        err = np.full((len(steps), C_local), np.nan, np.float32)
+        for i, s in enumerate(steps):
+            centred = centred_final if s < 0 else trace[s].contiguous()
+            n = int(centred.shape[0])
+            if n == 0:
+                continue
+            x = ctx.q if (s < 0 and kn.which == 0) else eng.transform(centred, which=kn.which, to_centered=False)
+            out = eng.energy_probe(x, kn.eps0, kn.n_leapfrog, which=kn.which, kappa=kn.kappa[:n], seed=seed + j,
+                                   row_offset=ctx.chain_offset + int(flags.num_chains) * (S if s < 0 else s),
+                                   lanes=flags.lanes_per_chain)
+            total += diagnostics.energy_sums(out)
+            o = out.to(torch.float64)
+            dh = (o[:, 0] - o[:, 2]) + (o[:, 3] - o[:, 1])
+            err[i, :n] = dh.to(torch.float32).cpu().numpy()
+            bad = torch.nonzero(~torch.isfinite(dh) | (dh > diagnostics.DIVERGENCE_THRESHOLD)).reshape(-1)[:ENERGY_WHERE_MAX]
+            if bad.numel():
+                rows = torch.cat([centred[bad].to(torch.float64), (bad + ctx.chain_offset).to(torch.float64)[:, None],
+                                  torch.full((bad.numel(), 1), float(s), dtype=torch.float64, device=bad.device),
+                                  torch.full((bad.numel(), 1), float(j), dtype=torch.float64, device=bad.device)], dim=1)
+                where.append(rows.cpu().numpy())
+        sums.append(total.cpu().numpy())
+        errors.append(err)
+    t = parallel.all_reduce_sum(np.concatenate(sums), dev).cpu().numpy().reshape(len(ctx.kernels), 9)
+    by_kernel = [diagnostics.energy_from_sums(row, D) for row in t]
+    pooled = diagnostics.energy_from_sums(t.sum(axis=0), D)
+    keys = _energy_summary(pooled)
+    if len(by_kernel) > 1:
+        keys["energy_by_kernel"] = [_energy_summary(e) for e in by_kernel]
+    util.print_("    energy probe over {} trajectories ({} probed step(s) and the final state): {} divergent, energy error "
+                "{:.4f} +/- {:.4f}, expected acceptance {:.4f}, kinetic share of the energy variance {:.4f}".format(
+                    pooled.rows, len(steps) - 1, pooled.divergent, pooled.error_mean, pooled.error_sd, pooled.accept_prob,
+                    pooled.kinetic_share))
+    if pooled.divergent > 0:
+        util.print_("    WARNING: {} of {} probed trajectories diverged (rate {:.4g}: energy error not finite or above {:g}): "
+                    "the integrator fails in part of this posterior -- try another parameterisation or a smaller step "
+                    "(where: <base>_energy.npz)".format(pooled.divergent, pooled.rows, pooled.divergence_rate,
+                                                        diagnostics.DIVERGENCE_THRESHOLD))
+    # the arrays: every chain of the job in chain order, the divergent rows of all ranks in rank order
+    local_where = np.concatenate(where, axis=0)[:ENERGY_WHERE_MAX] if where else np.zeros((0, D + 3))
+    all_where = parallel.all_gather_chains(local_where, None, dev).cpu().numpy()[:ENERGY_WHERE_MAX]
+    arrays = OrderedDict(steps=np.asarray(steps, np.int64))
+    for j, err in enumerate(errors):
+        whole = parallel.all_gather_chains(np.ascontiguousarray(err.T), int(flags.num_chains), dev).cpu().numpy().T
+        arrays["energy_error" if j == 0 else "energy_error_%d" % j] = np.ascontiguousarray(whole)
+    for name, part in zip(spec.part_names, spec.unpack(all_where[:, :D].astype(np.float32))):
+        arrays["divergent_where/%s" % name] = part
+    arrays["divergent_chain"] = all_where[:, D].astype(np.int64)
+    arrays["divergent_step"] = all_where[:, D + 1].astype(np.int64)
+    arrays["divergent_kernel"] = all_where[:, D + 2].astype(np.int64)
+    keys["energy_time_sec"] = time.time() - clock
     return keys, arrays
 
 
@@ -432,6 +534,25 @@ def _bulk_tail_report(trace, k, spec, arrays, by_part):
     return keys
 
 
+def save_energy(file_path_base, arrays):
+    """`<base>_energy.npz` (build-specific, --energy_diagnostics): `steps`, the probed recorded steps with -1 for the final
+    state; `energy_error` [len(steps), C] float32, the energy error of every probed trajectory (NaN where a chain has no
+    trace on the device; `energy_error_1`: the second inner kernel of --method=i); and of up to ENERGY_WHERE_MAX divergent
+    trajectories the centred state they started from, per latent part (`divergent_where/<part>`), with `divergent_chain`,
+    `divergent_step` and `divergent_kernel`."""
+    np.savez(file_path_base + "_energy.npz", **arrays)
+
+
+def _save_diagnostics(file_path_base, arrays):
+    """The side files of the convergence report: <base>_rhat.npz and, where the energy probe ran, <base>_energy.npz."""
+    if arrays is None:
+        return
+    energy = arrays.pop(ENERGY_ARRAYS, None)
+    save_rhat(file_path_base, arrays)
+    if energy is not None:
+        save_energy(file_path_base, energy)
+
+
 def save_rhat(file_path_base, arrays):
     """`<base>_rhat.npz` (build-specific): per latent part `split_rhat/<part>` and the pooled `posterior_mean/<part>`,
     `posterior_sd/<part>` over the chains the split statistic covers, [*event] each; a streaming run adds the same three
@@ -563,8 +684,7 @@ def run_hmc(model_config, results_dir, file_path, tuning=False, flags=FLAGS, out
                      acceptance_rate=float(acceptance_rate), mcmc_time_sec=mcmc_time, **extra)
     save_ess(file_path_base=file_path[:-5], samples=samples, param_names=_param_names(model_config),
              normalized_ess_final=normalized_ess_final, num_chains_to_save=flags.num_chains_to_save)
-    if rhat_arrays is not None:
-        save_rhat(file_path[:-5], rhat_arrays)
+    _save_diagnostics(file_path[:-5], rhat_arrays)
     return summary
 
 
@@ -662,8 +782,7 @@ def run_interleaved_hmc(model_config, results_dir, file_path, flags=FLAGS):
                      mcmc_time_sec=mcmc_time, **extra)
     save_ess(file_path_base=file_path[:-5], samples=samples, param_names=_param_names(model_config),
              normalized_ess_final=normalized_ess_final, num_chains_to_save=flags.num_chains_to_save)
-    if rhat_arrays is not None:
-        save_rhat(file_path[:-5], rhat_arrays)
+    _save_diagnostics(file_path[:-5], rhat_arrays)
     return kept
 
 

@@ -166,6 +166,22 @@ int arp_logp_grad(arp_model* m, int which, const float* x, int n_chains,
 int arp_transform(arp_model* m, int which, int dir, const float* in, int n_chains,
                   float* out, void* stream);
 
+/* Energy probe (build-specific): for every row of x [n_rows][D], a state in parameterisation `which`, draw a FRESH
+ * momentum and integrate ONE leapfrog trajectory of `n_leapfrog` steps with per-element steps eps0[d] * kappa[row]
+ * (kappa NULL: 1); out4 [n_rows][4] receives {logp at the start, kinetic energy at the start, logp at the end, kinetic
+ * energy at the end} as computed -- NaN and +-inf are results, nothing is clamped.  x is not changed and no Metropolis
+ * test is made.  What it is and is not: a fresh-momentum trajectory from the states handed in, NOT a replay of the
+ * transition the sampler took from them; at stationarity state and fresh momentum are independent, so the energy errors
+ * of probed trajectories have the distribution of the sampler's own next transitions.  The momentum of row r comes from a
+ * stream keyed by (seed, row_offset + r): rows [0, n) at row_offset k equal rows [k, k + n) at offset 0.  p_out / q_out
+ * (or NULL) [n_rows][D] receive the drawn momentum and the end state; p_out depends on the lanes per chain (every lane of
+ * a chain draws from a stream of its own), so a replay on the host takes its momenta from p_out.  Asynchronous; all array
+ * pointers are device pointers; the instantiation is chosen as arp_logp_grad chooses it.  Refused before any launch
+ * (non-zero, arp_last_error): a NULL handle, x, eps0 or out4, `which` outside 0 / 1, n_rows < 1, n_leapfrog < 1. */
+int arp_energy_probe(arp_model* m, int which, const float* x, int64_t n_rows, int n_leapfrog, const float* eps0,
+                     const float* kappa, uint64_t seed, int64_t row_offset, float* out4, float* p_out, float* q_out,
+                     int lanes_per_chain, void* stream);
+
 /* HMC segment (mcmc.HamiltonianMonteCarlo + step-size adaptation + sample_chain): `cfg->n_steps` transitions in ONE
  * launch.  (Internally a launch of 256 steps or more may hand its chains from workgroup to workgroup a few times -- DESIGN.md
  * section 3, relay segments --; chain state, counters and trace rows are bit for bit those of one workgroup per chain block.
