@@ -79,7 +79,8 @@ SYMBOLS = ["arp_version", "arp_last_error", "arp_model_create", "arp_model_destr
            "arp_rank_workspace_bytes", "arp_rank_normalize",
            "arp_ess_multichain_workspace_bytes", "arp_ess_multichain",
            "arp_moments_fold_nested", "arp_nested_step_workspace_bytes", "arp_nested_step_sums",
-           "arp_adapt_probe", "arp_clock_probe", "arp_energy_probe"]
+           "arp_adapt_probe", "arp_clock_probe", "arp_energy_probe",
+           "arp_trajectory_probe", "arp_jump_workspace_bytes", "arp_jump_sums"]
 
 _lib = None
 
@@ -109,6 +110,14 @@ def lib():
     L.arp_energy_probe.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_uint64,
                                    C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
     L.arp_energy_probe.restype = C.c_int
+    L.arp_trajectory_probe.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_uint64,
+                                       C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+    L.arp_trajectory_probe.restype = C.c_int
+    L.arp_jump_workspace_bytes.argtypes = [C.c_int64, C.c_int32, C.c_int32]
+    L.arp_jump_workspace_bytes.restype = C.c_int64
+    L.arp_jump_sums.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                C.c_int64, C.c_void_p]
+    L.arp_jump_sums.restype = C.c_int
     L.arp_hmc_run.argtypes = [C.c_void_p, C.c_int, C.POINTER(HmcConfig), C.POINTER(HmcIO), C.c_void_p]
     L.arp_interleaved_run.argtypes = [C.c_void_p, C.POINTER(HmcConfig), C.c_int,
                                       C.POINTER(InterleavedIO), C.c_void_p]

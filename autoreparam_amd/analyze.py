@@ -1,6 +1,6 @@
 """Pretty-printer for the result files main.py writes (reference analyze.py:30-185):
 
-    python -m autoreparam_amd.analyze --results_dir=. --model=radon_MN --elbos --ess --rhat --energy --reparams
+    python -m autoreparam_amd.analyze --results_dir=. --model=radon_MN --elbos --ess --rhat --energy --trajectory --reparams
 
 The reference's method list is stale (`cVIP_exp_tied`, analyze.py:19-26) and it expects a
 `num_leapfrog_steps` key that main.py only writes for interleaved runs; here every
@@ -155,9 +155,39 @@ def report_energy(results, results_dir=None, model_name=None):
     return lines
 
 
+def report_trajectory(results, results_dir=None, model_name=None):
+    """Build-specific: the trajectory-length profile of every sampling run that recorded one (--trajectory_profile; the
+    last run of each file), one table per inner kernel: for every leapfrog count the expected acceptance, the rate of
+    divergent trajectories and the worst element's expected squared jump distance, whole and per gradient.  Fresh-momentum
+    trajectories with the step sizes the run adapted for its own count, not a replay of the sampler's transitions; a
+    one-transition criterion, not an ESS."""
+    lines = []
+    fmt = lambda v: "n/a" if v is None else "{:.4g}".format(v)
+    for m, r in results.items():
+        if "trajectory_leapfrogs_max" not in r:
+            continue
+        last = {k: v[-1] for k, v in r.items() if k.startswith("trajectory_")}
+        kernels = last.get("trajectory_by_kernel") or [last]
+        for j, d in enumerate(kernels):
+            lines.append("{}{}: trajectory profile over {} trajectories, {:.3f}s: best {} leapfrog step(s), the run took {} "
+                         "(efficiency against the best {})".format(
+                             m, "" if len(kernels) == 1 else " kernel %d" % j, last["trajectory_probe_trajectories"],
+                             last["trajectory_time_sec"], fmt(d["trajectory_best_leapfrogs"]), d["trajectory_run_leapfrogs"],
+                             fmt(d["trajectory_efficiency_vs_best"])))
+            lines.append("    leapfrogs  accept  divergent  esjd_min (element)  per gradient")
+            for l in range(last["trajectory_leapfrogs_max"]):
+                mark = "  <-- best" if d["trajectory_best_leapfrogs"] == l + 1 else ""
+                mark += "  <-- this run" if d["trajectory_run_leapfrogs"] == l + 1 else ""
+                lines.append("    {:9d}  {:>6}  {:>9}  {:>8} ({:d})  {:>12}{}".format(
+                    l + 1, fmt(d["trajectory_accept_prob"][l]), fmt(d["trajectory_divergence_rate"][l]),
+                    fmt(d["trajectory_esjd_min"][l]), d["trajectory_esjd_min_element"][l],
+                    fmt(d["trajectory_esjd_min_per_gradient"][l]), mark))
+    return lines
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
-    for f in ("elbos", "ess", "reparams", "normalize_times", "rhat", "energy"):
+    for f in ("elbos", "ess", "reparams", "normalize_times", "rhat", "energy", "trajectory"):
         ap.add_argument("--" + f, action="store_true")
     ap.add_argument("--model", default="all")
     ap.add_argument("--results_dir", default="")
@@ -180,6 +210,8 @@ def main(argv=None):
             print("\n".join(report_rhat(results, root, name)) + "\n")
         if args.energy:
             print("\n".join(report_energy(results, root, name)) + "\n")
+        if args.trajectory:
+            print("\n".join(report_trajectory(results, root, name)) + "\n")
 
 
 if __name__ == "__main__":

@@ -281,6 +281,23 @@ int arp_energy_probe(arp_model* m, int which, const float* x, int64_t n_rows, in
   return 0;
 }
 
+int arp_trajectory_probe(arp_model* m, int which, const float* x, int64_t n_rows, int n_leapfrog_max, const float* eps0,
+                         const float* kappa, uint64_t seed, int64_t row_offset, float* energy_out, float* path_out,
+                         int path_centred, float* p_out, int lanes_per_chain, void* stream) {
+  if (!m || which < 0 || which > 1 || !x || !eps0 || !energy_out || n_rows < 1 || n_leapfrog_max < 1 || n_leapfrog_max > 256) {
+    set_error("arp_trajectory_probe: bad argument (a handle, x, eps0, energy_out, which in 0 / 1, n_rows >= 1 and "
+              "n_leapfrog_max in 1 ... 256 are required)");
+    return 1;
+  }
+  if (n_rows > 0x7fffffffLL / 16) { set_error("arp_trajectory_probe: n_rows is too large for one launch"); return 1; }
+  const LaneOps* o = select_ops(m, lanes_per_chain, (int)n_rows);
+  if (!o) return 1;
+  o->profile(m->args, m->dev_ab[which], m->dev_ab[which] + m->D, x, n_rows, m->D, n_leapfrog_max, eps0, kappa, seed,
+             row_offset, energy_out, path_out, path_centred, p_out, (hipStream_t)stream);
+  ARP_HIP_OK(hipGetLastError());
+  return 0;
+}
+
 // The step-size recurrences compare log alpha itself with log(target) (kernels.h: adapt_update), which equals TFP's
 // min(log alpha, 0) > log(target) only for a target below 1; a rate <= -1 would flip or zero the step.
 static int check_adapt(const arp_hmc_config* cfg) {

@@ -13,6 +13,7 @@
 #include "host_error.h"
 #include "kernels.h"
 #include "energy_probe.h"
+#include "trajectory_probe.h"
 #include "model_radon.h"
 #include "radon_fast.h"
 #include "election_fast.h"
@@ -62,6 +63,10 @@ struct LaneOps {
   void (*probe)(const void* args, const float* a, const float* b, const float* x, long long N, int D, int L,
                 const float* eps0, const float* kappa, uint64_t seed, long long row_offset, float* out4, float* p_out,
                 float* q_out, hipStream_t s) = nullptr;
+  // trajectory probe (trajectory_probe.h): the probe's trajectory with every step l = 1 ... Lmax recorded, every family
+  void (*profile)(const void* args, const float* a, const float* b, const float* x, long long N, int D, int Lmax,
+                  const float* eps0, const float* kappa, uint64_t seed, long long row_offset, float* energy_out,
+                  float* path_out, int path_centred, float* p_out, hipStream_t s) = nullptr;
 };
 
 // threads of a VI workgroup: 128 (two waves: with 16 - 32 workgroups per learning rate five learning rates cover
@@ -184,6 +189,14 @@ struct Launch {
     hipLaunchKernelGGL(energy_probe_kernel<Lane>, dim3((unsigned)nb), dim3(kBlock), 0, s,
                        *(const typename Lane::Args*)args, a, b, x, N, D, L, eps0, kappa, seed, row_offset, out4, p_out, q_out);
   }
+  static void profile(const void* args, const float* a, const float* b, const float* x, long long N, int D, int Lmax,
+                      const float* eps0, const float* kappa, uint64_t seed, long long row_offset, float* energy_out,
+                      float* path_out, int path_centred, float* p_out, hipStream_t s) {
+    const long long nb = (N * Lane::K + kBlock - 1) / kBlock;
+    hipLaunchKernelGGL(trajectory_probe_kernel<Lane>, dim3((unsigned)nb), dim3(kBlock), 0, s,
+                       *(const typename Lane::Args*)args, a, b, x, N, D, Lmax, eps0, kappa, seed, row_offset, energy_out,
+                       path_out, path_centred, p_out);
+  }
   template <int MODE>
   static void hmc(const void* args, const float* a, const float* b, const HmcParams& P, hipStream_t s) {
     const HmcParams Q = relay_plan(P, blocks(P.C), hmc_kernel<Lane, MODE>);
@@ -248,6 +261,7 @@ struct Launch {
       o.interleaved[1] = &interleaved<kModeCP, kModeNCP>;
     }
     o.probe = &probe;   // named last: the kernels a translation unit already had keep their order
+    o.profile = &profile;   // (and after probe, for the same reason)
     return o;
   }
 };

@@ -6,7 +6,9 @@ reports next to it, bulk-ESS, tail-ESS and the Monte-Carlo standard error of the
 multi-chain autocorrelation estimator on the device (`arp_ess_multichain`); and nested R-hat over superchains (Margossian,
 Hoffman, Sountsov, Riou-Durand, Vehtari, Gelman 2024: `nested_fold`, `nested_step_sums`), the form for many short chains;
 and the energy report of probed trajectories (`energy_sums`, `energy_from_sums` on Engine.energy_probe's output: divergent
-trajectories, energy-error moments, expected acceptance, the kinetic share of the energy variance).
+trajectories, energy-error moments, expected acceptance, the kinetic share of the energy variance); and the
+trajectory-length profile (`profile_from_sums` on Engine.trajectory_sums' output: the worst element's expected squared jump
+distance per gradient for every leapfrog count up to Lmax, from fresh-momentum trajectories with every step recorded).
 
 Build-specific (the reference runs 100 chains and reports the within-chain ESS only).  The per-chain moments come from
 one pass over a trace that is already on the device (`arp_split_moments`) or from the in-kernel statistics of a
@@ -43,6 +45,16 @@ NestedRhat = collections.namedtuple("NestedRhat", ["rhat", "excess", "between", 
 # kinetic_share = (D / 2) / Var(E0).  NaN where there are too few rows.
 Energy = collections.namedtuple("Energy", ["divergence_rate", "divergent", "nonfinite", "rows", "error_mean", "error_sd",
                                            "accept_prob", "kinetic_share"])
+# Trajectory-length profile from the jump sums of probed trajectories (Engine.trajectory_sums), one entry per leapfrog
+# count l = 1 ... Lmax ([Lmax] arrays): rows, divergent, nonfinite, left_out as energy_sums counts them per l;
+# accept_prob = mean alpha; esjd [Lmax, D] = J / (rows v), the Metropolis-weighted expected squared jump distance of
+# every element in units of its posterior variance (2 (1 - rho_1) at stationarity); esjd_min and esjd_min_element: the
+# worst element among those with a finite, positive variance (-1: none); per_gradient = esjd_min / l; best_leapfrogs: the
+# smallest l that attains the largest per_gradient (0: none is finite).  NaN where there is nothing to divide by.
+Profile = collections.namedtuple("Profile", ["leapfrogs", "rows", "divergent", "nonfinite", "left_out", "accept_prob",
+                                             "divergence_rate", "esjd", "esjd_min", "esjd_min_element", "per_gradient",
+                                             "best_leapfrogs"])
+JUMP_HEAD = 5                     # scalars in front of J in a row of the jump sums (csrc/jump.hip)
 DIVERGENCE_THRESHOLD = 1000.0     # Stan's: a trajectory whose energy error exceeds it is reported as divergent
 
 
@@ -338,3 +350,38 @@ def energy_from_sums(sums, D):
     share = 0.5 * D / var_e0 if np.isfinite(var_e0) and var_e0 > 0 else nan
     return Energy(divergent / rows if rows else nan, divergent, nonfinite, rows, error_mean, error_sd,
                   s[5] / rows if rows else nan, share)
+
+
+def profile_from_sums(sums, var):
+    """The trajectory-length profile from the (all-reduced) [Lmax, 5 + D] jump sums of Engine.trajectory_sums and the
+    run's pooled posterior variance `var` [D] -> Profile.  The worst element's expected squared jump distance per gradient
+    is the customary criterion for a trajectory length (Pasarica & Gelman 2010); it is the one-transition counterpart of
+    the min-ESS-per-gradient figure a set of tuning runs is compared by, not an ESS.  The trajectories behind the sums start
+    from fresh momenta (no replay of the sampler's transitions) and use the step sizes the run adapted for its own leapfrog
+    count; a run at another count would adapt others.  An empty or degenerate input gives NaN, never an exception."""
+    s = np.asarray(sums.cpu() if torch.is_tensor(sums) else sums, np.float64)
+    v = np.asarray(var.cpu() if torch.is_tensor(var) else var, np.float64).reshape(-1)
+    if s.ndim != 2 or s.shape[1] < JUMP_HEAD:
+        s = np.zeros((0, JUMP_HEAD + v.size))
+    Lmax, D = s.shape[0], s.shape[1] - JUMP_HEAD
+    if v.size != D:
+        v = np.full(D, np.nan)
+    leapfrogs = np.arange(1, Lmax + 1)
+    rows = s[:, 0]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        nan = np.full(Lmax, np.nan)
+        some = rows > 0
+        accept = np.where(some, s[:, 3] / rows, nan)
+        rate = np.where(some, s[:, 1] / rows, nan)
+        esjd = np.where(some[:, None], s[:, JUMP_HEAD:] / (rows[:, None] * v[None, :]), np.nan)
+    usable = np.isfinite(v) & (v > 0)
+    esjd_min, at = nan.copy(), np.full(Lmax, -1, np.int64)
+    for l in range(Lmax):
+        e = np.where(usable & np.isfinite(esjd[l]), esjd[l], np.inf)
+        if e.size and np.isfinite(e).any():
+            at[l] = int(e.argmin())
+            esjd_min[l] = e[at[l]]
+    per_gradient = esjd_min / leapfrogs
+    ok = np.isfinite(per_gradient)
+    best = int(leapfrogs[ok][per_gradient[ok].argmax()]) if ok.any() else 0    # (argmax: the first, hence smallest, l of a tie)
+    return Profile(leapfrogs, rows, s[:, 1], s[:, 2], s[:, 4], accept, rate, esjd, esjd_min, at, per_gradient, best)

@@ -149,6 +149,67 @@ class Engine(object):
         extra = tuple(t for t in (p, q) if t is not None)
         return (out,) + extra if extra else out
 
+    def _probe_args(self, x, eps0, kappa):
+        x = self._dev(x)
+        eps = eps0.to(self.device, torch.float32).contiguous() if torch.is_tensor(eps0) else self._dev(np.asarray(eps0, np.float32))
+        assert x.dim() == 2 and x.shape[1] == self.D and eps.shape == (self.D,)
+        kap = None if kappa is None else self._dev(kappa)
+        assert kap is None or kap.shape == (x.shape[0],)
+        return x, eps, kap
+
+    def trajectory_probe(self, x, eps0, n_leapfrog_max, which=0, kappa=None, seed=0, row_offset=0, lanes=0, want_path=True,
+                         path_centred=False, want_p=False):
+        """energy_probe's trajectory with every step recorded (arp_trajectory_probe): from every row of `x` [N, D]
+        (parameterisation `which`) one fresh-momentum trajectory of `n_leapfrog_max` steps of eps0[d] * kappa[row].
+        Returns energy [Lmax + 1, N, 2] float32 = (logp, kinetic energy) at l = 0 ... Lmax, then path [Lmax, N, D]
+        (want_path: the state after step l, centred or in the sampler's coordinates) and the drawn momenta [N, D]
+        (want_p: energy_probe's, bit for bit, for equal seed, offset and lanes).  Not a replay of a transition the sampler
+        took; `x` is not changed."""
+        x, eps, kap = self._probe_args(x, eps0, kappa)
+        n, Lmax = x.shape[0], int(n_leapfrog_max)
+        energy = torch.empty(max(Lmax, 0) + 1, n, 2, dtype=torch.float32, device=self.device)
+        path = torch.empty(max(Lmax, 0), n, self.D, dtype=torch.float32, device=self.device) if want_path else None
+        p = torch.empty_like(x) if want_p else None
+        with torch.cuda.device(self.device):
+            _lib.check(self._L.arp_trajectory_probe(self._h, int(which), _ptr(x), n, Lmax, _ptr(eps), _ptr(kap),
+                                                    int(seed) & 0xFFFFFFFFFFFFFFFF, int(row_offset), _ptr(energy), _ptr(path),
+                                                    1 if path_centred else 0, _ptr(p), int(lanes), _stream()))
+        extra = tuple(t for t in (path, p) if t is not None)
+        return (energy,) + extra if extra else energy
+
+    def trajectory_sums(self, x, eps0, n_leapfrog_max, which=0, kappa=None, seed=0, row_offset=0, lanes=0,
+                        max_path_bytes=1 << 30):
+        """The jump sums of a trajectory profile (arp_jump_sums over arp_trajectory_probe): returns (sums [Lmax, 5 + D]
+        float64, energy [Lmax + 1, N, 2] float32) on the device.  sums[l - 1] = rows, divergent, nonfinite, sum of alpha,
+        left_out, then per element the sum of alpha (x_l - x_0)^2 in centred coordinates, for a trajectory of l steps
+        (diagnostics.profile_from_sums reads them).  The rows are cut into chunks whose path buffer fits `max_path_bytes`;
+        a row's momentum stream is keyed by row_offset + its index, so the cut is invisible in every per-row output, and
+        the chunks' sums are added in order.  (With lanes = 0 the library chooses the lanes per chain by the row count of
+        a launch, and the momenta depend on them: name `lanes` where chunked and whole calls must agree bit for bit.)"""
+        x, eps, kap = self._probe_args(x, eps0, kappa)
+        n, Lmax, D = x.shape[0], int(n_leapfrog_max), self.D
+        sums = torch.zeros(max(Lmax, 0), 5 + D, dtype=torch.float64, device=self.device)
+        energy = torch.empty(max(Lmax, 0) + 1, n, 2, dtype=torch.float32, device=self.device)
+        if n == 0:
+            return sums, energy
+        chunk = max(1, min(n, int(max_path_bytes) // max(1, 4 * D * max(Lmax, 1))))
+        for lo in range(0, n, chunk):
+            hi = min(n, lo + chunk)
+            xs = x[lo:hi]
+            x0 = self.transform(xs, which=which, to_centered=True)
+            e, path = self.trajectory_probe(xs, eps, Lmax, which=which, kappa=None if kap is None else kap[lo:hi], seed=seed,
+                                            row_offset=int(row_offset) + lo, lanes=lanes, want_path=True, path_centred=True)
+            energy[:, lo:hi] = e
+            part = torch.empty_like(sums)
+            with torch.cuda.device(self.device):
+                need = int(self._L.arp_jump_workspace_bytes(hi - lo, D, Lmax))
+                ws = torch.empty(need, dtype=torch.uint8, device=self.device) if need > 0 else None
+                _lib.check(self._L.arp_jump_sums(_ptr(x0), _ptr(path), _ptr(e), hi - lo, D, Lmax, _ptr(part), _ptr(ws), need,
+                                                 _stream()))
+            sums += part
+            del ws, path
+        return sums, energy
+
     # -- HMC ----------------------------------------------------------------
     def hmc_run(self, state, eps0, n_leapfrog, n_steps, which=0, seed=0, chain_offset=0,
                 adapt_kind=_lib.ADAPT_NONE, n_adapt=0, adapt_target=0.75, adapt_rate=0.05,

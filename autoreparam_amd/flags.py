@@ -70,6 +70,14 @@ _DEFS = [
                                         "trajectories diverged).  Sharded jobs included."),
     ("energy_probe_steps", int, 8, "With --energy_diagnostics: how many evenly spaced recorded steps of the device trace "
                                    "are probed (the first and the last among them; fewer if fewer were recorded)."),
+    ("trajectory_profile", int, 0, "Sampling runs, with --convergence_diagnostics: LMAX in 1 ... 256 profiles the trajectory "
+                                   "length (arp_trajectory_probe, arp_jump_sums).  From the states --energy_diagnostics "
+                                   "probes, one fresh-momentum trajectory of LMAX leapfrog steps with the run's own step "
+                                   "sizes, every step recorded: the Metropolis-weighted expected squared jump distance of "
+                                   "the worst element, per gradient, for every leapfrog count 1 ... LMAX at once, and the "
+                                   "count that maximises it (trajectory_* JSON keys, <base>_trajectory.npz).  Not a replay "
+                                   "of the sampler's transitions; the step sizes are those adapted for the run's own "
+                                   "count; a one-transition criterion, not an ESS.  0: off."),
     ("lanes_per_chain", int, 0, "Lanes of a wave64 a chain is spread over (0 = automatic)."),
 ]
 
@@ -124,9 +132,22 @@ class FlagValues(object):
                 setattr(self, name, [v for v in val.split(",") if v != ""])
             elif t is int:
                 setattr(self, name, int(val))
+                if name == "trajectory_profile":
+                    check_trajectory_profile(self.trajectory_profile)
             else:
                 setattr(self, name, val)
         return rest
+
+
+TRAJECTORY_PROFILE_MAX = 256      # the largest --trajectory_profile (arp_trajectory_probe's n_leapfrog_max)
+
+
+def check_trajectory_profile(value):
+    """--trajectory_profile as an int in 0 ... TRAJECTORY_PROFILE_MAX; raises ValueError outside."""
+    value = int(value or 0)
+    if not 0 <= value <= TRAJECTORY_PROFILE_MAX:
+        raise ValueError("--trajectory_profile must lie in 0 (off) ... %d, not %d" % (TRAJECTORY_PROFILE_MAX, value))
+    return value
 
 
 FLAGS = FlagValues()

@@ -275,6 +275,12 @@ def _convergence_report(kernel_results, model_config, flags, dev):
         keys.update(energy_keys)
         if energy_arrays is not None:
             arrays[ENERGY_ARRAYS] = energy_arrays          # (run_hmc / run_interleaved_hmc take it out again: save_energy)
+    if int(getattr(flags, "trajectory_profile", 0) or 0) != 0:
+        pooled_sd = whole.sd if streaming else split.sd     # (already all-reduced)
+        profile_keys, profile_arrays = _trajectory_report(kernel_results, trace, spec, flags, dev, pooled_sd)
+        keys.update(profile_keys)
+        if profile_arrays is not None:
+            arrays[TRAJECTORY_ARRAYS] = profile_arrays     # (taken out again: save_trajectory)
     keys["diagnostics_time_sec"] = time.time() - clock
     return keys, arrays
 
@@ -373,6 +379,91 @@ def _energy_report(kernel_results, trace, spec, flags, dev):
     arrays["divergent_step"] = all_where[:, D + 1].astype(np.int64)
     arrays["divergent_kernel"] = all_where[:, D + 2].astype(np.int64)
     keys["energy_time_sec"] = time.time() - clock
+    return keys, arrays
+
+
+TRAJECTORY_ARRAYS = "trajectory/"    # where _convergence_report leaves the arrays of <base>_trajectory.npz
+
+
+def _trajectory_summary(p, run_leapfrogs):
+    """The per-kernel JSON keys of one diagnostics.Profile of a kernel that ran with `run_leapfrogs` leapfrog steps."""
+    vec = lambda a: [_finite_or_none(v) for v in a]
+    best, run = int(p.best_leapfrogs), int(run_leapfrogs)
+    efficiency = None                                      # (the run's count is not among the profiled ones)
+    if 1 <= run <= len(p.per_gradient) and best >= 1:
+        with np.errstate(divide="ignore", invalid="ignore"):
+            efficiency = _finite_or_none(p.per_gradient[run - 1] / p.per_gradient[best - 1])
+    return OrderedDict([
+        ("trajectory_accept_prob", vec(p.accept_prob)), ("trajectory_divergence_rate", vec(p.divergence_rate)),
+        ("trajectory_esjd_min", vec(p.esjd_min)), ("trajectory_esjd_min_element", [int(v) for v in p.esjd_min_element]),
+        ("trajectory_esjd_min_per_gradient", vec(p.per_gradient)),
+        ("trajectory_best_leapfrogs", best if best >= 1 else None), ("trajectory_run_leapfrogs", run),
+        ("trajectory_efficiency_vs_best", efficiency)])
+
+
+def _trajectory_report(kernel_results, trace, spec, flags, dev, pooled_sd):
+    """--trajectory_profile=LMAX: did the run use the right number of leapfrog steps?  From the rows the energy report
+    probes -- the final state of every chain of this rank and --energy_probe_steps recorded steps of the device trace, the
+    same row offsets, a seed constant of its own -- one fresh-momentum trajectory of LMAX steps with the run's own base
+    steps and per-chain multipliers, every step recorded (Engine.trajectory_sums): the Metropolis-weighted expected
+    squared jump distance of every element, in units of the run's pooled posterior variance, for every leapfrog count
+    1 ... LMAX at once, the worst element's per gradient, and the count that maximises it.  NOT a replay of the sampler's
+    transitions; the step sizes are those the run adapted for its own leapfrog count (a run at another count would adapt
+    others); a one-transition (lag-one) criterion, not an ESS.  --method=i profiles both inner kernels, each with its own
+    steps, and does not pool them into one recommendation.  The sums are additive: one all-reduce carries them.
+    Returns (JSON keys, arrays of <base>_trajectory.npz or None).  (A collective when ws > 1: every rank calls it.)"""
+    import torch
+    from .flags import check_trajectory_profile
+    Lmax = check_trajectory_profile(flags.trajectory_profile)
+    ctx = getattr(kernel_results, "probe", None)
+    if ctx is None or Lmax == 0:
+        return {}, None
+    clock = time.time()
+    eng, D = ctx.engine, int(spec.D)
+    S = int(trace.shape[0])
+    C_local = int(ctx.q.shape[0])
+    steps = [-1] + probe_steps(S, int(getattr(flags, "energy_probe_steps", 8)))     # (the same on every rank)
+    seed = (int(flags.seed) * 0x9E3779B97F4A7C15 + 0x54524A50) & 0xFFFFFFFFFFFFFFFF
+    centred_final = eng.transform(ctx.q, which=0, to_centered=True) if C_local > 0 else ctx.q
+    sums = []
+    for j, kn in enumerate(ctx.kernels):
+        total = torch.zeros(Lmax, 5 + D, dtype=torch.float64, device=ctx.q.device)
+        for s in steps:
+            centred = centred_final if s < 0 else trace[s].contiguous()
+            n = int(centred.shape[0])
+            if n == 0:
+                continue
+            x = ctx.q if (s < 0 and kn.which == 0) else eng.transform(centred, which=kn.which, to_centered=False)
+            part, _ = eng.trajectory_sums(x, kn.eps0, Lmax, which=kn.which, kappa=kn.kappa[:n], seed=seed + j,
+                                          row_offset=ctx.chain_offset + int(flags.num_chains) * (S if s < 0 else s),
+                                          lanes=flags.lanes_per_chain)
+            total += part.to(total.device)
+        sums.append(total.cpu().numpy().ravel())
+    t = parallel.all_reduce_sum(np.concatenate(sums), dev).cpu().numpy().reshape(len(ctx.kernels), Lmax, 5 + D)
+    var = np.asarray(pooled_sd, np.float64) ** 2
+    profiles = [diagnostics.profile_from_sums(row, var) for row in t]
+    summaries = [_trajectory_summary(p, kn.n_leapfrog) for p, kn in zip(profiles, ctx.kernels)]
+    keys = OrderedDict([("trajectory_leapfrogs_max", Lmax),
+                        ("trajectory_probe_trajectories", int(round(sum(float(p.rows[0]) for p in profiles))))])
+    if len(profiles) == 1:
+        keys.update(summaries[0])
+    else:
+        keys["trajectory_by_kernel"] = summaries
+    for j, (p, d) in enumerate(zip(profiles, summaries)):
+        best, run = d["trajectory_best_leapfrogs"], d["trajectory_run_leapfrogs"]
+        fig = lambda l: "n/a" if not (l and 1 <= l <= Lmax and np.isfinite(p.per_gradient[l - 1])) else "{:.4g}".format(p.per_gradient[l - 1])
+        util.print_("    trajectory profile{} over {} trajectories of {} leapfrog steps: the worst element's expected squared "
+                    "jump per gradient is largest at {} leapfrog step(s) ({}); this run took {} ({})".format(
+                        "" if len(profiles) == 1 else " of kernel %d" % j, int(round(float(p.rows[0]))) if len(p.rows) else 0,
+                        Lmax, best if best else "n/a", fig(best), run, fig(run)))
+    arrays = OrderedDict(leapfrogs=np.arange(1, Lmax + 1, dtype=np.int64))
+    for j, p in enumerate(profiles):
+        tag = "" if j == 0 else "_%d" % j
+        for name, part in zip(spec.part_names, spec.unpack(np.ascontiguousarray(p.esjd))):
+            arrays["esjd%s/%s" % (tag, name)] = part
+        arrays["accept_prob" + tag] = np.asarray(p.accept_prob, np.float64)
+        arrays["divergence_rate" + tag] = np.asarray(p.divergence_rate, np.float64)
+    keys["trajectory_time_sec"] = time.time() - clock
     return keys, arrays
 
 
@@ -543,14 +634,26 @@ def save_energy(file_path_base, arrays):
     np.savez(file_path_base + "_energy.npz", **arrays)
 
 
+def save_trajectory(file_path_base, arrays):
+    """`<base>_trajectory.npz` (build-specific, --trajectory_profile): `leapfrogs` = 1 ... LMAX; per latent part
+    `esjd/<part>` [LMAX, *event], the Metropolis-weighted expected squared jump distance of every element in units of its
+    pooled posterior variance for a trajectory of that many leapfrog steps; `accept_prob` and `divergence_rate` [LMAX].  The
+    second inner kernel of --method=i: `esjd_1/<part>`, `accept_prob_1`, `divergence_rate_1`."""
+    np.savez(file_path_base + "_trajectory.npz", **arrays)
+
+
 def _save_diagnostics(file_path_base, arrays):
-    """The side files of the convergence report: <base>_rhat.npz and, where the energy probe ran, <base>_energy.npz."""
+    """The side files of the convergence report: <base>_rhat.npz and, where the probes ran, <base>_energy.npz and
+    <base>_trajectory.npz."""
     if arrays is None:
         return
     energy = arrays.pop(ENERGY_ARRAYS, None)
+    trajectory = arrays.pop(TRAJECTORY_ARRAYS, None)
     save_rhat(file_path_base, arrays)
     if energy is not None:
         save_energy(file_path_base, energy)
+    if trajectory is not None:
+        save_trajectory(file_path_base, trajectory)
 
 
 def save_rhat(file_path_base, arrays):

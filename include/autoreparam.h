@@ -182,6 +182,43 @@ int arp_energy_probe(arp_model* m, int which, const float* x, int64_t n_rows, in
                      const float* kappa, uint64_t seed, int64_t row_offset, float* out4, float* p_out, float* q_out,
                      int lanes_per_chain, void* stream);
 
+/* Trajectory probe (build-specific): arp_energy_probe's trajectory with every intermediate step recorded.  For every row
+ * of x [n_rows][D], a state in parameterisation `which`, draw a FRESH momentum and integrate ONE leapfrog trajectory of
+ * `n_leapfrog_max` steps with per-element steps eps0[d] * kappa[row] (kappa NULL: 1).  energy_out
+ * [n_leapfrog_max + 1][n_rows][2] receives {logp, kinetic energy} at the start (l = 0) and after every step l -- the
+ * kinetic energy after the half kick that would close a trajectory of l steps, which goes into a temporary: the
+ * trajectory itself runs on undisturbed -- as computed: NaN and +-inf are results.  path_out (or NULL)
+ * [n_leapfrog_max][n_rows][D] receives the state after step l, centred (path_centred != 0) or in the coordinates of
+ * parameterisation `which` (0); the flag does not change the integrator's arithmetic.  p_out (or NULL) [n_rows][D]
+ * receives the drawn momentum: the stream of row r is keyed by (seed, row_offset + r) exactly as arp_energy_probe keys
+ * it, so with equal seed, offset and lanes per chain p_out is that function's bit for bit, and rows [0, n) at row_offset
+ * k equal rows [k, k + n) at offset 0.  x is not changed and no Metropolis test is made.
+ * What the profile built from it (arp_jump_sums) is and is not: the trajectories start from fresh momenta, they are NOT
+ * replays of the sampler's transitions; the step sizes are those the run adapted for its own leapfrog count, and a run at
+ * another count would adapt others; the expected squared jump distance is a one-transition (lag-one) criterion, not an
+ * effective sample size.
+ * Asynchronous; all array pointers are device pointers; the instantiation is chosen as arp_logp_grad chooses it.
+ * Refused before any launch (non-zero, arp_last_error): a NULL handle, x, eps0 or energy_out, `which` outside 0 / 1,
+ * n_rows < 1 or too large for one launch (arp_energy_probe's limit), n_leapfrog_max < 1 or > 256. */
+int arp_trajectory_probe(arp_model* m, int which, const float* x, int64_t n_rows, int n_leapfrog_max, const float* eps0,
+                         const float* kappa, uint64_t seed, int64_t row_offset, float* energy_out, float* path_out,
+                         int path_centred, float* p_out, int lanes_per_chain, void* stream);
+
+/* Fold of a trajectory probe (needs no model handle): from the centred start states x0 [n_rows][D], the centred path
+ * [n_leapfrog_max][n_rows][D] and the energies [n_leapfrog_max + 1][n_rows][2] of arp_trajectory_probe, sums
+ * [n_leapfrog_max][5 + D] float64, per leapfrog count l: rows; divergent rows (energy error dH = (lp_0 - lp_l) +
+ * (ke_l - ke_0), formed in float64, not finite or above 1000); rows whose dH is not finite; the sum of alpha = min(1,
+ * exp(-dH)), a divergent row counting 0; left_out; then for every element d the sum over rows of alpha (x_l,d - x_0,d)^2.
+ * A row with alpha = 0 is skipped; a term with alpha > 0 that is not finite is left out and counted in left_out.  All
+ * sums are additive over rows, hence over calls and ranks.  One pass over `path`; differences, squares and alpha in
+ * float64; fixed reduction order without atomics: two calls on the same input give bitwise equal sums.  The workspace
+ * (arp_jump_workspace_bytes; 0: none needed, NULL is fine) is the caller's, 256-byte aligned.  Asynchronous; device
+ * pointers.  Refused before any launch: a NULL x0, path, energy or sums, n_rows < 1 or above arp_energy_probe's limit,
+ * D < 1, n_leapfrog_max < 1 or > 256, a workspace that is too small or misaligned. */
+int64_t arp_jump_workspace_bytes(int64_t n_rows, int32_t D, int32_t n_leapfrog_max);
+int arp_jump_sums(const float* x0, const float* path, const float* energy, int64_t n_rows, int32_t D,
+                  int32_t n_leapfrog_max, double* sums, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* HMC segment (mcmc.HamiltonianMonteCarlo + step-size adaptation + sample_chain): `cfg->n_steps` transitions in ONE
  * launch.  (Internally a launch of 256 steps or more may hand its chains from workgroup to workgroup a few times -- DESIGN.md
  * section 3, relay segments --; chain state, counters and trace rows are bit for bit those of one workgroup per chain block.
