@@ -299,7 +299,8 @@ ARP_DEV void store_row_wave(const Lane& M, float* stage, float* gdst, int cl, in
 // Streaming statistics of a recorded sample (arp_hmc_io.stats, [6][C][D]): the wave stages its chains'
 // rows in LDS as store_row_wave does (stage_row_wave) and then walks the six component planes, whose
 // blocks for the wave's chains have the same [chains][D] shape, with 16-byte accesses.  x - ref keeps
-// the sums well conditioned in float32 (ref = the first recorded sample of that element).
+// the sums well conditioned in float32 (ref = the first recorded sample of that element until a batch ends:
+// stats_reref_staged).
 // The walk is a real function call: inlined, its temporaries push the chain kernels (which sit at
 // the 256-VGPR edge) into spilling inside the sampling loop even when no statistics are requested.
 __device__ __noinline__ void stats_update_staged(const float* stage, float* g, size_t comp, int nvalid, bool first,
@@ -423,9 +424,37 @@ __device__ __noinline__ void stats_fold_staged(const float* sm, const float* sM2
   }
 }
 
+// Conditioning.  ref starts as the first recorded sample (the mean of the first stretch folded), which sits many standard
+// deviations from the mean for some element of some chain: s1 then grows like n (mean - ref), every batch mean is a
+// difference of two such sums, and s2 - s1^2 / n, sb2 - sb1^2 / nb cancel (mean - ref)^2.  So after a batch end that
+// completes 1, 2, 4, 8, ... batches (stats_update_staged / stats_fold_staged have closed it) ref moves to the mean of the
+// n samples so far and the sums move with it, exactly in exact arithmetic: with h the shift ref actually takes (its
+// rounding included) and k the batches so far,
+//   s1 - n h,   s2 + h (n h - 2 s1),   cur = s1,   sb1 - k h,   sb2 + h (k h - 2 sb1)
+// -- the squared offset cancels a few times per run, each time a smaller one, instead of with every sample; the last move
+// leaves ref within sqrt(2 tau / n) sd of the mean, also where a first batch is shorter than the chain's memory.  The planes
+// keep their meaning and their formulas.  A function of its own, element by element: its registers would otherwise count
+// towards those of the per-sample walk, which adds to every chain kernel's (statistics).
+// Called at every batch end with nrec = the samples recorded so far.
+__device__ __noinline__ void stats_reref_staged(float* g, size_t comp, int nvalid, int nrec, int batch) {
+  const int kb = nrec / batch;
+  if (kb & (kb - 1)) return;
+  const int lane = threadIdx.x & 63;
+  const float fn = (float)nrec, fk = (float)kb, invn = 1.0f / fn;
+  for (int k = lane * 4; k < nvalid; k += 256) {        // the lane that wrote an element reads it back (same addresses)
+    for (int j = k; j < nvalid && j < k + 4; ++j) {
+      const float ref = g[j], s1 = g[comp + j], s2 = g[2 * comp + j], b1 = g[4 * comp + j], b2 = g[5 * comp + j];
+      const float nref = fmaf(s1, invn, ref), h = nref - ref;
+      const float t1 = fmaf(-fn, h, s1);
+      g[j] = nref; g[comp + j] = t1; g[2 * comp + j] = fmaf(h, fmaf(fn, h, -2.0f * s1), s2);
+      g[3 * comp + j] = t1; g[4 * comp + j] = fmaf(-fk, h, b1); g[5 * comp + j] = fmaf(h, fmaf(fk, h, -2.0f * b1), b2);
+    }
+  }
+}
+
 template <class Lane>
 ARP_DEV void stats_update_wave(const Lane& M, float* stage, const HmcParams& P, long long cw0, int cl, int D,
-                               int nvalid, const float (&v)[Lane::ND], bool first, bool batch_end) {
+                               int nvalid, const float (&v)[Lane::ND], int rec_row, bool batch_end) {
   float* row = stage + cl * D;
   if (M.slot == 0) {
 #pragma unroll
@@ -435,7 +464,8 @@ ARP_DEV void stats_update_wave(const Lane& M, float* stage, const HmcParams& P, 
   for (int i = 0; i < Lane::NL; ++i)
     if (M.lvalid(i)) (row + M.lbase(i))[Lane::loff(i)] = v[Lane::NG + i];
   __builtin_amdgcn_wave_barrier();
-  stats_update_staged(stage, P.stats + cw0 * D, (size_t)P.C * D, nvalid, first, batch_end, 1.0f / (float)P.stats_batch);
+  stats_update_staged(stage, P.stats + cw0 * D, (size_t)P.C * D, nvalid, rec_row == 0, batch_end, 1.0f / (float)P.stats_batch);
+  if (batch_end) stats_reref_staged(P.stats + cw0 * D, (size_t)P.C * D, nvalid, rec_row + 1, P.stats_batch);
   __builtin_amdgcn_wave_barrier();
 }
 
@@ -757,7 +787,7 @@ __global__ __launch_bounds__(kBlock, Lane::MINW) void hmc_kernel(
           store_row_wave<true>(M, stage, P.trace + ((size_t)rec_row * P.trace_chains + cw0) * D, cl, D, nv, v);
         }
         if (P.stats) {
-          stats_update_wave(M, stage, P, cw0, cl, D, nvalid, v, rec_row == 0, bpos + 1 == P.stats_batch);
+          stats_update_wave(M, stage, P, cw0, cl, D, nvalid, v, rec_row, bpos + 1 == P.stats_batch);
           bpos = bpos + 1 == P.stats_batch ? 0 : bpos + 1;
         }
       };
@@ -910,8 +940,8 @@ __global__ __launch_bounds__(kBlock, Lane::MINW) void interleaved_kernel(
       }
       if (P.stats) {
         const bool bend = bpos + 1 == P.stats_batch;
-        if (use_x) stats_update_wave(M, stage, P, cw0, cl, D, nvalid, x, rec_row == 0, bend);
-        else stats_update_wave(M, stage, P, cw0, cl, D, nvalid, q, rec_row == 0, bend);
+        if (use_x) stats_update_wave(M, stage, P, cw0, cl, D, nvalid, x, rec_row, bend);
+        else stats_update_wave(M, stage, P, cw0, cl, D, nvalid, q, rec_row, bend);
         bpos = bend ? 0 : bpos + 1;
       }
       if (live && slot == 0) {

@@ -390,9 +390,10 @@ ARP_DEV void pk_stats_accumulate(float* s_stats, int n, const float (&xg)[T::NG]
 
 // Fold the n samples the accumulators hold into the planes; `stage` is the wave's parked-state region (dead between
 // transitions), which holds two row blocks (pk_save_wave_floats >= 2 stage_floats, checked in PkBlock).
+// nrec = the samples recorded so far, these n included (the first fold of a run has nrec == n).
 template <class T>
 ARP_DEV void pk_stats_fold(const T& M, float* stage, const float* s_stats, const HmcParams& P, long long cw0, int cl, int D,
-                           int nvalid, int n, bool first, bool batch_end) {
+                           int nvalid, int n, int nrec, bool batch_end) {
   constexpr int K = T::K, NP = T::NP, NG = T::NG, NL = T::NL;
   int tid = threadIdx.x;
   asm volatile("" : "+v"(tid));
@@ -413,8 +414,9 @@ ARP_DEV void pk_stats_fold(const T& M, float* stage, const float* s_stats, const
     if (2 * k + 1 < NL && M.lvalid(2 * k + 1)) { em[K * (2 * k + 1)] = v.y; eM[K * (2 * k + 1)] = v.w; }
   }
   __builtin_amdgcn_wave_barrier();
-  stats_fold_staged(stage, stage + stage_floats<T>(), P.stats + cw0 * D, (size_t)P.C * D, nvalid, (float)n, first, batch_end,
+  stats_fold_staged(stage, stage + stage_floats<T>(), P.stats + cw0 * D, (size_t)P.C * D, nvalid, (float)n, nrec == n, batch_end,
                     1.0f / (float)P.stats_batch);
+  if (batch_end) stats_reref_staged(P.stats + cw0 * D, (size_t)P.C * D, nvalid, nrec, P.stats_batch);
   __builtin_amdgcn_wave_barrier();
 }
 
@@ -530,14 +532,14 @@ __global__ __launch_bounds__(kBlock, (STATS || MODE == ARP_PK_VIP_MINW2) && T::M
           pk_stats_accumulate<T>(s_stats, ++n_acc, xg, xc);
           const bool bend = bpos + 1 == P.stats_batch;
           if (bend) {
-            pk_stats_fold(M, stage, s_stats, P, cw0, cl, D, nvalid, n_acc, rec_row + 1 == n_acc, true);
+            pk_stats_fold(M, stage, s_stats, P, cw0, cl, D, nvalid, n_acc, rec_row + 1, true);
             n_acc = 0;
           }
           bpos = bend ? 0 : bpos + 1;
         } else if (P.stats) {
           float x[ND];
           T::pack(xg, xc, x);
-          stats_update_wave(M, stage, P, cw0, cl, D, nvalid, x, rec_row == 0, bpos + 1 == P.stats_batch);
+          stats_update_wave(M, stage, P, cw0, cl, D, nvalid, x, rec_row, bpos + 1 == P.stats_batch);
           bpos = bpos + 1 == P.stats_batch ? 0 : bpos + 1;
         }
       }
@@ -555,7 +557,7 @@ __global__ __launch_bounds__(kBlock, (STATS || MODE == ARP_PK_VIP_MINW2) && T::M
   relay_stamp(P, rid, 3);
 
   // the launch ends inside a batch: what the accumulators hold goes into s1 / s2 now, the batch mean when the batch ends
-  if (STATS && n_acc > 0) pk_stats_fold(M, stage, s_stats, P, cw0, cl, D, nvalid, n_acc, rec_row == n_acc, false);
+  if (STATS && n_acc > 0) pk_stats_fold(M, stage, s_stats, P, cw0, cl, D, nvalid, n_acc, rec_row, false);
   size_t c2 = (size_t)c;
   asm volatile("" : "+v"(c2));
   const long long cw2 = cw0;
@@ -674,7 +676,7 @@ __global__ __launch_bounds__(kBlock, STATS && T::MINW > 2 ? 2 : T::MINW) void pk
         if (use_x) pk_stats_accumulate<T>(s_stats, n_acc, xg, xc); else pk_stats_accumulate<T>(s_stats, n_acc, qg, qc);
         const bool bend = bpos + 1 == P.stats_batch;
         if (bend) {
-          pk_stats_fold(M, stage, s_stats, P, cw0, cl, D, nvalid, n_acc, rec_row + 1 == n_acc, true);
+          pk_stats_fold(M, stage, s_stats, P, cw0, cl, D, nvalid, n_acc, rec_row + 1, true);
           n_acc = 0;
         }
         bpos = bend ? 0 : bpos + 1;
@@ -682,7 +684,7 @@ __global__ __launch_bounds__(kBlock, STATS && T::MINW > 2 ? 2 : T::MINW) void pk
         float x[ND];
         if (use_x) T::pack(xg, xc, x); else T::pack(qg, qc, x);
         const bool bend = bpos + 1 == P.stats_batch;
-        stats_update_wave(M, stage, P, cw0, cl, D, nvalid, x, rec_row == 0, bend);
+        stats_update_wave(M, stage, P, cw0, cl, D, nvalid, x, rec_row, bend);
         bpos = bend ? 0 : bpos + 1;
       }
       if (live && slot == 0) {
@@ -698,7 +700,7 @@ __global__ __launch_bounds__(kBlock, STATS && T::MINW > 2 ? 2 : T::MINW) void pk
     }
   }
   relay_stamp(P, rid, 3);
-  if (STATS && n_acc > 0) pk_stats_fold(M, stage, s_stats, P, cw0, cl, D, nvalid, n_acc, rec_row == n_acc, false);
+  if (STATS && n_acc > 0) pk_stats_fold(M, stage, s_stats, P, cw0, cl, D, nvalid, n_acc, rec_row, false);
   size_t c2 = (size_t)c;
   asm volatile("" : "+v"(c2));
   const long long cw2 = cw0;

@@ -327,7 +327,7 @@ __global__ __launch_bounds__(kBlock, T::MINW) void radon_interleaved_kernel(Rado
         pk_stats_accumulate<T>(s_stats, ++n_acc, qg, qc);
         const bool bend = bpos + 1 == P.stats_batch;
         if (bend) {
-          pk_stats_fold(M, stage, s_stats, P, cw0, cl, D, nvalid, n_acc, rec_row + 1 == n_acc, true);
+          pk_stats_fold(M, stage, s_stats, P, cw0, cl, D, nvalid, n_acc, rec_row + 1, true);
           n_acc = 0;
         }
         bpos = bend ? 0 : bpos + 1;
@@ -335,7 +335,7 @@ __global__ __launch_bounds__(kBlock, T::MINW) void radon_interleaved_kernel(Rado
         float x[ND];
         T::pack(qg, qc, x);
         const bool bend = bpos + 1 == P.stats_batch;
-        stats_update_wave(M, stage, P, cw0, cl, D, nvalid, x, rec_row == 0, bend);
+        stats_update_wave(M, stage, P, cw0, cl, D, nvalid, x, rec_row, bend);
         bpos = bend ? 0 : bpos + 1;
       }
       if (live && slot == 0) {
@@ -352,7 +352,7 @@ __global__ __launch_bounds__(kBlock, T::MINW) void radon_interleaved_kernel(Rado
   }
   relay_stamp(P, rid, 3);
 
-  if (STATS && n_acc > 0) pk_stats_fold(M, stage, s_stats, P, cw0, cl, D, nvalid, n_acc, rec_row == n_acc, false);
+  if (STATS && n_acc > 0) pk_stats_fold(M, stage, s_stats, P, cw0, cl, D, nvalid, n_acc, rec_row, false);
   size_t c2 = (size_t)c;
   asm volatile("" : "+v"(c2));
   const long long cw2 = cw0;

@@ -367,7 +367,13 @@ def clock_probe(device, ms=10.0):
 
 def stats_summary(stats, n, batch):
     """(mean, var, ess) [C, D] float64 tensors from an `arp_hmc_io.stats` buffer after `n` recorded samples:
-    mean = ref + s1/n, var = (s2 - s1^2/n)/(n-1), ESS by batch means, n var / (batch var(batch means)), capped at n."""
+    mean = ref + s1/n, var = (s2 - s1^2/n)/(n-1), ESS by batch means, n var / (batch var(batch means)), capped at n.
+    Accuracy of the float32 planes against the float64 statistics of the same samples, measured at n = 16 384 with batch
+    2 048 and 64 (tests/test_gpu_stats.py; DESIGN.md has the table): plane-per-sample route mean within 3.4e-7 (max|x| + 1),
+    variance within 2.4e-7 (max|x| + 1)^2 (1.1e-5 relative), ESS within 1.5e-5, the same for first recorded samples < 1,
+    1 - 3 and 3 - 10 sd from the mean (3 - 10 sd: mean 2.3e-6 sd, variance 1.1e-5, ESS 1.2e-5 relative); at 10 sd the float32
+    restatement reads 3.7e-7 (max|x| + 1)^2 and ESS 9.2e-4.  LDS route: mean 4.8e-7, variance 7.7e-8, ESS 6.3e-4 at batch 2 048
+    (2e-6 at batch 64)."""
     ref, s1, s2, _, sb1, sb2 = (stats[k].to(torch.float64) for k in range(6))
     mean = ref + s1 / n
     var = ((s2 - s1 * s1 / n) / max(n - 1, 1)).clamp_min(0)

@@ -117,10 +117,12 @@ typedef struct arp_hmc_io {
                               * the start of the current batch, sb1 = sum of batch means (of x - ref), sb2 = sum of their
                               * squares}; zero it before the first call.  mean = ref + s1/n, var = (s2 - s1^2/n)/(n-1),
                               * batch-means ESS = n var / (stats_batch var(batch means)).  ref is chosen by
-                              * the kernel on the first call that records and is only meaningful through these formulas (the
+                              * the kernel and is only meaningful through these formulas (until the first batch ends the
                               * first recorded sample, or -- kernels that keep the running moments of a batch in LDS and touch
-                              * the planes once per batch or launch -- the mean of the first stretch they fold); the planes are
-                              * sums, so they are exact to rounding however a run is cut into launches */
+                              * the planes once per batch or launch -- the mean of the first stretch they fold; from then on
+                              * the mean of the first batch, every sum re-referenced to it in place, which keeps the float32
+                              * sums conditioned); the planes are sums, so they are exact to rounding however a run is cut
+                              * into launches */
   uint32_t* rec_accept_count; /* [C] in/out or NULL: accepted transitions among the recorded ones (sum of is_accepted) */
 } arp_hmc_io;
 
