@@ -12,10 +12,13 @@ namespace arp {
 static thread_local std::string g_err;
 void set_error(const std::string& msg) { g_err = msg; }
 
-// geometry of the last arp_vi_run of this thread (arp_vi_geometry: a measurement hook)
+// The measurement records, per thread as the ABI defines them, each assigned by its entry point from what the call handed back:
+// what the last chain launch did (arp_relay_geometry), the geometry of the last arp_vi_run (arp_vi_geometry) and the launches it
+// needed per chunk, at most (arp_vi_attempts)
+static thread_local RelayGeometry g_relay_geometry = {{1, 0, 0}};
 struct ViGeometry { int v[6]; };
 static thread_local ViGeometry g_vi_geometry = {{0, 0, 0, 0, 0, 0}};
-static thread_local int g_vi_attempts = 0;      // launches the calling thread's last arp_vi_run needed per chunk, at most (arp_vi_attempts)
+static thread_local int g_vi_attempts = 0;
 // arp_vi_run launches whose workgroups wait for each other hold this from the launch to the end of the launch: two such
 // launches from two threads of a process would share the device's workgroup slots, and a group that is only partly
 // resident waits for slots the other launch's waiting groups hold
@@ -275,7 +278,7 @@ int arp_energy_probe(arp_model* m, int which, const float* x, int64_t n_rows, in
   if (n_rows > 0x7fffffffLL / 16) { set_error("arp_energy_probe: n_rows is too large for one launch"); return 1; }
   const LaneOps* o = select_ops(m, lanes_per_chain, (int)n_rows);
   if (!o) return 1;
-  o->probe(m->args, m->dev_ab[which], m->dev_ab[which] + m->D, x, n_rows, m->D, n_leapfrog, eps0, kappa, seed, row_offset,
+  o->probe(m->args, m->dev_ab[which], m->dev_ab[which] + m->D, {x, n_rows, m->D, eps0, kappa, seed, row_offset}, n_leapfrog,
            out4, p_out, q_out, (hipStream_t)stream);
   ARP_HIP_OK(hipGetLastError());
   return 0;
@@ -292,8 +295,8 @@ int arp_trajectory_probe(arp_model* m, int which, const float* x, int64_t n_rows
   if (n_rows > 0x7fffffffLL / 16) { set_error("arp_trajectory_probe: n_rows is too large for one launch"); return 1; }
   const LaneOps* o = select_ops(m, lanes_per_chain, (int)n_rows);
   if (!o) return 1;
-  o->profile(m->args, m->dev_ab[which], m->dev_ab[which] + m->D, x, n_rows, m->D, n_leapfrog_max, eps0, kappa, seed,
-             row_offset, energy_out, path_out, path_centred, p_out, (hipStream_t)stream);
+  o->profile(m->args, m->dev_ab[which], m->dev_ab[which] + m->D, {x, n_rows, m->D, eps0, kappa, seed, row_offset},
+             n_leapfrog_max, energy_out, path_out, path_centred, p_out, (hipStream_t)stream);
   ARP_HIP_OK(hipGetLastError());
   return 0;
 }
@@ -312,118 +315,6 @@ static void fill_adapt(HmcParams& P, const arp_hmc_config* cfg) {
   P.adapt_target = cfg->adapt_target; P.adapt_rate = cfg->adapt_rate;
   P.adapt_log_target = logf(cfg->adapt_target > 0.f ? cfg->adapt_target : 1e-30f);
   P.adapt_inv_opr = 1.0f / (1.0f + cfg->adapt_rate);
-}
-
-// Relay segments (kernels.h: relay_begin; host_common.h: relay_plan): a launch's steps cut into segments that are handed
-// from workgroup to workgroup inside the launch, so that a CU that is free takes the next (segment, chain block) in line
-// instead of idling behind a slower one (profiles/r05_relay_segments.txt).  This gives the launcher what it needs: one
-// zeroed flag word per chain block that belongs to THIS launch alone -- a stream-ordered allocation, given back behind the
-// launch (relay_release), so launches of one handle that overlap on different streams never share a word -- and `segs` =
-// -1 (the launcher decides with its kernel's occupancy), a forced count (ARP_DEBUG=1 ARP_SEGMENTS=n) or 1 (`allowed` false).
-// How the steps are cut (host_common.h: relay_schedule, relay_cut) is the library's ratio unless ARP_DEBUG=1
-// ARP_SEGMENT_RATIO=percent or ARP_SEGMENT_LENS=n0,n1,... (which also forces the count) says otherwise.
-// no relay: the launch's steps in one segment (P.n_steps is set)
-static void relay_off(HmcParams& P) {
-  P.segs = 1; P.seg_len = P.n_steps; P.seg_blocks = 0; P.seg_epoch = 0; P.seg_flags = nullptr;
-  P.seg_ctrl = nullptr; P.seg_err_host = nullptr; P.seg_timeout = 6000000000ull; P.seg_fault = 0;
-  for (int& v : P.seg_start) v = 0;
-#ifdef ARP_EXP_RELAY_STAMPS
-  P.seg_stamps = nullptr;
-#endif
-}
-// ARP_SEGMENT_LENS: explicit segment lengths of a launch of n_steps; a list that is not one is refused, never replaced
-static int relay_explicit_cut(const char* list, int n_steps, arp::RelayCut* cut) {
-  long long sum = 0;
-  int n = 0;
-  for (const char* p = list; *p;) {
-    char* end = nullptr;
-    const long v = strtol(p, &end, 10);
-    if (end == p || (*end && *end != ',') || v < 1 || n == kSegTable) {
-      set_error("ARP_SEGMENT_LENS: want 1 to " + std::to_string(kSegTable) + " comma-separated lengths >= 1, got '" + list + "'");
-      return 1;
-    }
-    cut->lens[n++] = (int)(v < 0x7fffffff ? v : 0x7fffffff);
-    sum += v;
-    p = *end ? end + 1 : end;
-  }
-  if (sum != n_steps) {
-    set_error("ARP_SEGMENT_LENS: the lengths '" + std::string(list) + "' sum to " + std::to_string(sum) + ", the launch has " +
-              std::to_string(n_steps) + " steps");
-    return 1;
-  }
-  cut->n_lens = n;
-  return 0;
-}
-static int relay_prepare(arp_model* m, const arp_hmc_config* cfg, int K, bool allowed, hipStream_t stream, HmcParams* P) {
-  relay_off(*P);
-  arp::relay_device_cus() = m->cus;
-  if (!allowed || cfg->n_steps < 256) return 0;
-  int segs = -1, dbg = 0;
-  if (debug_int("ARP_SEGMENTS", &dbg) && dbg >= 1 && dbg <= 64) segs = dbg;
-  arp::RelayCut& cut = arp::relay_cut();
-  cut = arp::RelayCut();
-  if (debug_int("ARP_SEGMENT_RATIO", &dbg) && dbg >= 1 && dbg <= 100) cut.ratio_pct = dbg;
-  if (const char* lens = debug_switch("ARP_SEGMENT_LENS")) {
-    if (relay_explicit_cut(lens, cfg->n_steps, &cut)) return 1;
-    segs = cut.n_lens;
-  }
-  if (segs == 1) return 0;
-  const long long blocks = ((long long)cfg->n_chains * K + kBlock - 1) / kBlock;
-  // no kernel gets segments below one round of two workgroups per CU (relay_plan): spare those launches the allocation
-  if (segs == -1 && blocks < 2LL * m->cus) return 0;
-  // one zeroed flag word per chain block, then the launch's ticket counter and its failure word
-  void* flags = nullptr;
-  size_t bytes = ((size_t)blocks + 2) * sizeof(unsigned);
-#ifdef ARP_EXP_RELAY_STAMPS              // timing experiment only: kStamps words per workgroup behind the flags (kernels.h: relay_stamp)
-  const size_t stamps_at = (bytes + 7) / 8 * 8;
-  const int stamp_segs = segs > 0 ? segs : 8;
-  bytes = stamps_at + (size_t)stamp_segs * blocks * kStamps * sizeof(unsigned long long);
-#endif
-  ARP_HIP_OK(hipMallocAsync(&flags, bytes, stream));
-  const hipError_t zeroed = hipMemsetAsync(flags, 0, bytes, stream);
-  if (zeroed != hipSuccess) {
-    (void)hipFreeAsync(flags, stream);
-    ARP_HIP_OK(zeroed);
-  }
-  P->segs = segs; P->seg_blocks = (int)blocks; P->seg_epoch = 0u; P->seg_flags = (unsigned*)flags;
-  P->seg_ctrl = (unsigned*)flags + blocks;
-  P->seg_err_host = m->relay_err_dev;
-#ifdef ARP_EXP_RELAY_STAMPS
-  P->seg_stamps = (unsigned long long*)((char*)flags + stamps_at);
-#endif
-  // test hooks (ARP_DEBUG=1 only): a short time-out, and segments that never raise their flag -- the failure path on demand
-  if (debug_int("ARP_RELAY_TIMEOUT_MS", &dbg) && dbg > 0) P->seg_timeout = 100000ull * (unsigned long long)dbg;
-  if (debug_int("ARP_RELAY_FAULT", &dbg) && dbg == 1) P->seg_fault = 1;
-  return 0;
-}
-// a relay launch of this handle whose hand-over timed out (kernels.h: relay_begin) since the last look: report it once
-static int relay_failed(arp_model* m, const char* where) {
-  if (!m || !m->relay_err) return 0;
-  if (__atomic_load_n(m->relay_err, __ATOMIC_ACQUIRE) == 0u) return 0;
-  __atomic_store_n(m->relay_err, 0u, __ATOMIC_RELEASE);
-  set_error(std::string(where) + ": a relay hand-over inside an earlier chain launch of this handle timed out (was the device "
-            "taken away for a minute?); that launch left its chains partly advanced -- discard them");
-  return 1;
-}
-static int relay_release(const HmcParams& P, hipStream_t stream) {
-#ifdef ARP_EXP_RELAY_STAMPS
-  // the launch's stamps into the file ARP_RELAY_STAMPS_OUT names (each launch overwrites it): segments, chain blocks, kStamps,
-  // then kStamps 64-bit words per ticket -- tools/relay_stamps.py reads it.  Waits for the launch: an experiment build only.
-  const char* out = P.seg_flags ? debug_switch("ARP_RELAY_STAMPS_OUT") : nullptr;
-  const RelayGeometry g = relay_last();
-  if (out && g.v[0] > 1) {
-    std::vector<unsigned long long> w(3 + (size_t)g.v[0] * g.v[1] * kStamps);
-    w[0] = (unsigned long long)g.v[0]; w[1] = (unsigned long long)g.v[1]; w[2] = kStamps;
-    ARP_HIP_OK(hipStreamSynchronize(stream));
-    ARP_HIP_OK(hipMemcpy(w.data() + 3, P.seg_stamps, (w.size() - 3) * sizeof(w[0]), hipMemcpyDeviceToHost));
-    if (FILE* f = fopen(out, "wb")) {
-      fwrite(w.data(), sizeof(w[0]), w.size(), f);
-      fclose(f);
-    }
-  }
-#endif
-  if (P.seg_flags) ARP_HIP_OK(hipFreeAsync(P.seg_flags, stream));
-  return 0;
 }
 
 static int fill_params(arp_model* m, const arp_hmc_config* cfg, const arp_hmc_io* io, bool need_cache, HmcParams* Pp) {
@@ -456,30 +347,28 @@ static int fill_params(arp_model* m, const arp_hmc_config* cfg, const arp_hmc_io
   P.trace_chains = (cfg->trace_chains > 0 && cfg->trace_chains < cfg->n_chains) ? cfg->trace_chains : cfg->n_chains;
   P.L1 = 0; P.adapt1 = nullptr; P.accept_count1 = nullptr; P.eps0_1 = nullptr; P.trace_accept1 = nullptr;
   P.rec_accept1 = nullptr;
-  relay_off(P);
+  relay_off(P);      // (the launcher's relay_plan writes the segments in, where it decides on any: relay_host.h)
   return 0;
 }
 
 int arp_model_check(arp_model* m) {
   if (!m) { set_error("arp_model_check: null argument"); return 1; }
-  return relay_failed(m, "arp_model_check");
+  return relay_failed(m->relay_err, "arp_model_check");
 }
 
 int arp_hmc_run(arp_model* m, int which, const arp_hmc_config* cfg, const arp_hmc_io* io, void* stream) {
   if (!m || !cfg || !io || which < 0 || which > 1) { set_error("arp_hmc_run: null argument"); return 1; }
-  if (relay_failed(m, "arp_hmc_run")) return 1;
+  if (relay_failed(m->relay_err, "arp_hmc_run")) return 1;
   HmcParams P;
   if (fill_params(m, cfg, io, true, &P)) return 1;
   if (cfg->n_steps == 0) return 0;
   const LaneOps* o = select_ops(m, cfg->lanes_per_chain, cfg->n_chains);
   if (!o) return 1;
-  if (relay_prepare(m, cfg, o->K, true, (hipStream_t)stream, &P)) return 1;
+  RelayAsk ask;
+  if (relay_prepare(m->cus, m->relay_err_dev, cfg, o->K, true, (hipStream_t)stream, &ask)) return 1;
   // (kModeVIP too: where a family has the general form on the packed layer, "hmc_vip_pk", it sits in that slot -- host_common.h)
-  o->hmc[m->param_kind[which]](m->args, m->dev_ab[which], m->dev_ab[which] + m->D, P, (hipStream_t)stream);
-  const hipError_t launched = hipGetLastError();
-  if (relay_release(P, (hipStream_t)stream)) return 1;
-  ARP_HIP_OK(launched);
-  return 0;
+  g_relay_geometry = o->hmc[m->param_kind[which]](m->args, m->dev_ab[which], m->dev_ab[which] + m->D, P, ask, (hipStream_t)stream);
+  return relay_release(ask, g_relay_geometry, hipGetLastError(), (hipStream_t)stream);
 }
 
 int arp_interleaved_run(arp_model* m, const arp_hmc_config* cfg, int n_leapfrog_1,
@@ -494,7 +383,7 @@ int arp_interleaved_run(arp_model* m, const arp_hmc_config* cfg, int n_leapfrog_
     set_error("arp_interleaved_run: k0.logp is required whenever k0.grad is given (pass both or neither)");
     return 1;
   }
-  if (relay_failed(m, "arp_interleaved_run")) return 1;
+  if (relay_failed(m->relay_err, "arp_interleaved_run")) return 1;
   HmcParams P;
   if (fill_params(m, cfg, &io->k0, false, &P)) return 1;
   if (io->trace_accept1 && !P.n_samples) P.n_samples = cfg->n_samples;
@@ -505,12 +394,10 @@ int arp_interleaved_run(arp_model* m, const arp_hmc_config* cfg, int n_leapfrog_
   if (!o) return 1;
   const auto fn = o->interleaved[m->param_kind[0] == kModeCP && m->param_kind[1] == kModeNCP];
   // (radon_interleaved_kernel carries the gradient from step to step: it has to travel with the state, as it does between launches)
-  if (relay_prepare(m, cfg, o->K, io->k0.grad != nullptr, (hipStream_t)stream, &P)) return 1;
-  fn(m->args, m->dev_ab[0], m->dev_ab[0] + m->D, m->dev_ab[1], m->dev_ab[1] + m->D, P, (hipStream_t)stream);
-  const hipError_t launched = hipGetLastError();
-  if (relay_release(P, (hipStream_t)stream)) return 1;
-  ARP_HIP_OK(launched);
-  return 0;
+  RelayAsk ask;
+  if (relay_prepare(m->cus, m->relay_err_dev, cfg, o->K, io->k0.grad != nullptr, (hipStream_t)stream, &ask)) return 1;
+  g_relay_geometry = fn(m->args, m->dev_ab[0], m->dev_ab[0] + m->D, m->dev_ab[1], m->dev_ab[1] + m->D, P, ask, (hipStream_t)stream);
+  return relay_release(ask, g_relay_geometry, hipGetLastError(), (hipStream_t)stream);
 }
 
 // arp_vi_run's arguments, the instantiation that serves them (*op), the kernel's view of them (P: all but the geometry and the
@@ -649,14 +536,14 @@ static int vi_snapshot(float* snap, float* const (&rows)[4], size_t first, size_
 // The learning rates, plan.groups_per_launch per launch.  A launch whose hand-offs ran into their bound (the device was
 // shared with kernels of other queues or processes for that long: no launch mode guarantees residency against THOSE) is not
 // an error yet: the parameters it started from are kept, and it is taken again with four times the bound -- 2 s, 8 s, 32 s
-// -- before the call gives up.  A fit under contention is slower, not failed; an undisturbed one never takes the second launch.
+// -- before the call gives up.  A fit under contention is slower, not failed; an undisturbed one never takes the second launch
+// (*attempts: the launches a chunk needed, at most).
 static int vi_launch_chunks(arp_model* m, int which, const LaneOps* o, const arp_vi_config* cfg, const arp_vi_io* io,
-                            const ViPlan& plan, ViParams P, std::unique_lock<std::mutex>& one_at_a_time, hipStream_t stream) {
+                            const ViPlan& plan, ViParams P, std::unique_lock<std::mutex>& one_at_a_time, hipStream_t stream, int* attempts) {
   const int GR = plan.GR, groups_per_launch = plan.groups_per_launch;
   const size_t rowf = (size_t)m->D;
   int dbg = 0, fault_attempts = 0;      // test hook (ARP_DEBUG=1): treat the first n launches of every chunk as timed out
   if (debug_int("ARP_VI_FAULT_ATTEMPTS", &dbg) && dbg > 0) fault_attempts = dbg;
-  g_vi_attempts = 0;
   for (int lr0 = 0; lr0 < cfg->n_lr; lr0 += groups_per_launch) {
     const int ng = std::min(groups_per_launch, cfg->n_lr - lr0);
     float* const rows[4] = {io->loc, io->rho, io->w, (io->wb && cfg->learn_a) ? io->wb : nullptr};
@@ -680,7 +567,7 @@ static int vi_launch_chunks(arp_model* m, int which, const LaneOps* o, const arp
         launched = o->vi(m->args, m->dev_ab[which], m->dev_ab[which] + m->D, P, ng, false, stream);
       }
       ARP_HIP_OK(launched);
-      g_vi_attempts = std::max(g_vi_attempts, attempt + 1);
+      *attempts = std::max(*attempts, attempt + 1);
       if (GR <= 1) break;
       // the hand-offs' waits are bounded: a group that was not resident together reports it here instead of hanging
       int err = 0;
@@ -714,13 +601,17 @@ int arp_vi_run(arp_model* m, int which, const arp_vi_config* cfg, const arp_vi_i
   P.G = plan.G; P.R = plan.R; P.xch_tp = plan.Tp;
   P.err = (int*)m->vi_ws;
   P.xch = plan.GR > 1 ? (unsigned long long*)((char*)m->vi_ws + 256) : nullptr;
-  g_vi_geometry = {plan.B, plan.G, plan.R, plan.groups_per_launch,
-                   (int)std::min<long long>((long long)cfg->n_lr * plan.GR, plan.capacity), plan.occ};
   // plain launches of waiting workgroups: one at a time in this process, from here to the end of the call
   std::unique_lock<std::mutex> one_at_a_time(g_vi_launch_mutex, std::defer_lock);
   if (plan.GR > 1 && !plan.coop) one_at_a_time.lock();
-  if (grow_device((void**)&m->vi_snap, &m->vi_snap_floats, plan.snap_floats, sizeof(float), st)) return 1;
-  return vi_launch_chunks(m, which, o, cfg, io, plan, P, one_at_a_time, st);
+  int attempts = 0;
+  const int rc = grow_device((void**)&m->vi_snap, &m->vi_snap_floats, plan.snap_floats, sizeof(float), st) ||
+                 vi_launch_chunks(m, which, o, cfg, io, plan, P, one_at_a_time, st, &attempts);
+  // this thread's records of the call, failed or not: the plan's geometry, and the launches its chunks took
+  g_vi_geometry = {plan.B, plan.G, plan.R, plan.groups_per_launch,
+                   (int)std::min<long long>((long long)cfg->n_lr * plan.GR, plan.capacity), plan.occ};
+  g_vi_attempts = attempts;
+  return rc;
 }
 
 int arp_vi_attempts(int32_t* out1) {
@@ -742,7 +633,7 @@ int arp_relay_schedule(int n_steps, int segs, int ratio_pct, int32_t* out, int c
 
 int arp_relay_geometry(int32_t* out3) {
   if (!out3) { set_error("arp_relay_geometry: null argument"); return 1; }
-  for (int i = 0; i < 3; ++i) out3[i] = relay_last().v[i];
+  for (int i = 0; i < 3; ++i) out3[i] = g_relay_geometry.v[i];
   return 0;
 }
 

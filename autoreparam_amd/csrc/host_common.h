@@ -6,12 +6,11 @@
 #include <stdlib.h>
 #include <type_traits>
 #include <utility>
-#include <map>
-#include <mutex>
 #include <vector>
 #include "../../include/autoreparam.h"
 #include "host_error.h"
 #include "kernels.h"
+#include "relay_host.h"
 #include "energy_probe.h"
 #include "trajectory_probe.h"
 #include "model_radon.h"
@@ -27,9 +26,13 @@
 
 namespace arp {
 
-using HmcFn = void (*)(const void* args, const float* a, const float* b, const HmcParams& P, hipStream_t s);
-using InterleavedFn = void (*)(const void* args, const float* a0, const float* b0, const float* a1, const float* b1,
-                              const HmcParams& P, hipStream_t s);
+// chain launchers: the kernel's parameters without a relay, what the entry point asks of one, and back what the launch did
+using HmcFn = RelayGeometry (*)(const void* args, const float* a, const float* b, const HmcParams& P, const RelayAsk& ask,
+                                hipStream_t s);
+using InterleavedFn = RelayGeometry (*)(const void* args, const float* a0, const float* b0, const float* a1, const float* b1,
+                                        const HmcParams& P, const RelayAsk& ask, hipStream_t s);
+// the rows both probes walk: x[N][D], row 0 being row `row_offset` of the caller's, their step sizes and the generator's seed
+struct ProbeRows { const float* x; long long N; int D; const float* eps0; const float* kappa; uint64_t seed; long long row_offset; };
 
 // Launchers a model family exports for one (lanes-per-chain, slice-size) pair.
 struct LaneOps {
@@ -60,12 +63,10 @@ struct LaneOps {
   int vi_tile_obs = 0;
   int (*vi_occ)() = nullptr;
   // energy probe (energy_probe.h): one fresh-momentum trajectory per row of x[N][D], general (a, b) form, every family
-  void (*probe)(const void* args, const float* a, const float* b, const float* x, long long N, int D, int L,
-                const float* eps0, const float* kappa, uint64_t seed, long long row_offset, float* out4, float* p_out,
+  void (*probe)(const void* args, const float* a, const float* b, const ProbeRows& r, int L, float* out4, float* p_out,
                 float* q_out, hipStream_t s) = nullptr;
   // trajectory probe (trajectory_probe.h): the probe's trajectory with every step l = 1 ... Lmax recorded, every family
-  void (*profile)(const void* args, const float* a, const float* b, const float* x, long long N, int D, int Lmax,
-                  const float* eps0, const float* kappa, uint64_t seed, long long row_offset, float* energy_out,
+  void (*profile)(const void* args, const float* a, const float* b, const ProbeRows& r, int Lmax, float* energy_out,
                   float* path_out, int path_centred, float* p_out, hipStream_t s) = nullptr;
 };
 
@@ -73,101 +74,6 @@ struct LaneOps {
 // 80 - 160 CUs) unless the lane model names its own
 template <class L, class = void> struct lane_vi_block { static constexpr int value = 128; };
 template <class L> struct lane_vi_block<L, std::void_t<decltype(L::VI_BLOCK)>> { static constexpr int value = L::VI_BLOCK; };
-
-// Relay segments (kernels.h: relay_begin): the API hands a launcher the flags, the epoch and `segs` = -1 (allowed, not yet
-// decided), a forced count (experiments) or 1 (not allowed); the launcher knows its kernel and decides with its occupancy:
-// segments pay where the chain blocks are at least one round of resident workgroups (profiles/r05_relay_segments.txt) --
-// 8 from 512 steps per launch on, 4 from 256.
-// CUs of the device the calling thread's launch goes to: relay_prepare sets it from the handle (its device, cached at
-// arp_model_create) right before the launcher runs on the same thread
-inline int& relay_device_cus() {
-  static thread_local int cus = 0;
-  return cus;
-}
-// what the calling thread's last chain launch did (arp_relay_geometry, a measurement hook): segments, chain blocks, workgroups of
-// the kernel one CU holds (0 where the launcher did not have to ask)
-struct RelayGeometry { int v[3]; };
-inline RelayGeometry& relay_last() {
-  static thread_local RelayGeometry g = {{1, 0, 0}};
-  return g;
-}
-// The cut of a launch's n_steps into `segs` segments (1 <= segs <= n_steps), lengths proportional to ratio^s: a free slot
-// takes the next (segment, block) in line, so the launch ends with slots idle for about half a last-round segment -- a short
-// last round leaves a short tail, and the hand-overs stay `segs` per block (profiles/r07_relay_schedule.txt).  Every
-// segment gets one step, the rest goes out in proportion (rounded down), what the rounding leaves to the first segments:
-// the lengths sum to n_steps, never increase and are all >= 1.  ratio = 1 is the equal cut as it has always been,
-// ceil(n_steps / segs) steps each and the last segment what is left (where that leaves every segment a step).
-inline void relay_schedule(int n_steps, int segs, double ratio, int* len) {   // len[segs]
-  const int each = (n_steps + segs - 1) / segs;
-  if (ratio >= 1.0 && n_steps - (segs - 1) * each >= 1) {
-    for (int s = 0; s < segs; ++s) len[s] = s + 1 < segs ? each : n_steps - (segs - 1) * each;
-    return;
-  }
-  if (ratio > 1.0) ratio = 1.0;
-  double w = 1.0, sum = 0.0;
-  for (int s = 0; s < segs; ++s) { sum += w; w *= ratio; }
-  const int spare = n_steps - segs;
-  int left = spare;
-  w = 1.0;
-  for (int s = 0; s < segs; ++s) {
-    int extra = (int)((double)spare * (w / sum));
-    if (extra > left) extra = left;
-    len[s] = 1 + extra;
-    left -= extra;
-    w *= ratio;
-  }
-  for (int s = 0; left > 0; s = s + 1 < segs ? s + 1 : 0, --left) len[s] += 1;
-}
-// ratio of the library's own cut, in percent: chosen by measurement (profiles/r07_relay_schedule.txt)
-constexpr int kSegRatioPct = 70;
-// What the calling thread's next chain launch is asked to cut with (arp_api.hip: relay_prepare, right before the launcher
-// runs on the same thread): the ratio in percent, or explicit lengths (n_lens > 0: they sum to the launch's n_steps)
-struct RelayCut { int ratio_pct = kSegRatioPct; int n_lens = 0; int lens[kSegTable] = {}; };
-inline RelayCut& relay_cut() {
-  static thread_local RelayCut c;
-  return c;
-}
-template <class F>
-inline HmcParams relay_plan(const HmcParams& P, int blocks, F kernel) {
-  HmcParams Q = P;
-  int segs = P.segs;
-  int occ_seen = 0;
-  if (segs == -1) {
-    static std::mutex mu;
-    static std::map<const void*, int> occ_of;
-    int occ = 0;
-    {
-      std::lock_guard<std::mutex> lock(mu);
-      auto it = occ_of.find((const void*)kernel);
-      if (it == occ_of.end()) {
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kernel, kBlock, 0) != hipSuccess) occ = 0;
-        occ_of[(const void*)kernel] = occ;
-      } else {
-        occ = it->second;
-      }
-    }
-    occ_seen = occ;
-    const long long slots = (long long)occ * relay_device_cus();
-    segs = (slots > 0 && blocks >= slots) ? (P.n_steps >= 512 ? 8 : (P.n_steps >= 256 ? 4 : 1)) : 1;
-    // one workgroup per CU (German credit and time_series at 4 lanes per chain: 100 - 155 KB of LDS): a workgroup that waits for
-    // its block holds the whole CU, and every hand-over invalidates the XCD's L2 under the tile stream -- measured + 0.1 % and
-    // + 4.2 % (tools/experiments/relay_ab.py), so these launches stay whole
-    if (occ < 2) segs = 1;
-  }
-  if (segs < 1 || !P.seg_flags || blocks > P.seg_blocks) segs = 1;      // (seg_blocks arrives as the flags' capacity)
-  Q.segs = segs;
-  Q.seg_len = (P.n_steps + segs - 1) / segs;
-  Q.seg_blocks = blocks;
-  if (segs > 1 && segs <= kSegTable) {
-    const RelayCut& cut = relay_cut();
-    int len[kSegTable];
-    relay_schedule(P.n_steps, segs, cut.ratio_pct / 100.0, len);
-    Q.seg_start[0] = 0;
-    for (int i = 0; i < segs; ++i) Q.seg_start[i + 1] = Q.seg_start[i] + (cut.n_lens == segs ? cut.lens[i] : len[i]);
-  }
-  relay_last() = {{segs, blocks, occ_seen}};
-  return Q;
-}
 
 template <class Lane>
 struct Launch {
@@ -182,33 +88,26 @@ struct Launch {
     hipLaunchKernelGGL(transform_kernel<Lane>, dim3(blocks(C)), dim3(kBlock), 0, s,
                        *(const typename Lane::Args*)args, a, b, dir, in, C, D, out);
   }
-  static void probe(const void* args, const float* a, const float* b, const float* x, long long N, int D, int L,
-                    const float* eps0, const float* kappa, uint64_t seed, long long row_offset, float* out4, float* p_out,
+  static void probe(const void* args, const float* a, const float* b, const ProbeRows& r, int L, float* out4, float* p_out,
                     float* q_out, hipStream_t s) {
-    const long long nb = (N * Lane::K + kBlock - 1) / kBlock;
-    hipLaunchKernelGGL(energy_probe_kernel<Lane>, dim3((unsigned)nb), dim3(kBlock), 0, s,
-                       *(const typename Lane::Args*)args, a, b, x, N, D, L, eps0, kappa, seed, row_offset, out4, p_out, q_out);
+    const long long nb = (r.N * Lane::K + kBlock - 1) / kBlock;
+    hipLaunchKernelGGL(energy_probe_kernel<Lane>, dim3((unsigned)nb), dim3(kBlock), 0, s, *(const typename Lane::Args*)args,
+                       a, b, r.x, r.N, r.D, L, r.eps0, r.kappa, r.seed, r.row_offset, out4, p_out, q_out);
   }
-  static void profile(const void* args, const float* a, const float* b, const float* x, long long N, int D, int Lmax,
-                      const float* eps0, const float* kappa, uint64_t seed, long long row_offset, float* energy_out,
+  static void profile(const void* args, const float* a, const float* b, const ProbeRows& r, int Lmax, float* energy_out,
                       float* path_out, int path_centred, float* p_out, hipStream_t s) {
-    const long long nb = (N * Lane::K + kBlock - 1) / kBlock;
-    hipLaunchKernelGGL(trajectory_probe_kernel<Lane>, dim3((unsigned)nb), dim3(kBlock), 0, s,
-                       *(const typename Lane::Args*)args, a, b, x, N, D, Lmax, eps0, kappa, seed, row_offset, energy_out,
-                       path_out, path_centred, p_out);
+    const long long nb = (r.N * Lane::K + kBlock - 1) / kBlock;
+    hipLaunchKernelGGL(trajectory_probe_kernel<Lane>, dim3((unsigned)nb), dim3(kBlock), 0, s, *(const typename Lane::Args*)args,
+                       a, b, r.x, r.N, r.D, Lmax, r.eps0, r.kappa, r.seed, r.row_offset, energy_out, path_out, path_centred, p_out);
   }
   template <int MODE>
-  static void hmc(const void* args, const float* a, const float* b, const HmcParams& P, hipStream_t s) {
-    const HmcParams Q = relay_plan(P, blocks(P.C), hmc_kernel<Lane, MODE>);
-    hipLaunchKernelGGL((hmc_kernel<Lane, MODE>), dim3(blocks(P.C) * Q.segs), dim3(kBlock), 0, s,
-                       *(const typename Lane::Args*)args, a, b, Q);
+  static RelayGeometry hmc(const void* args, const float* a, const float* b, const HmcParams& P, const RelayAsk& ask, hipStream_t s) {
+    return relay_launch(hmc_kernel<Lane, MODE>, blocks(P.C), P, ask, s, *(const typename Lane::Args*)args, a, b);
   }
   template <int M0, int M1>
-  static void interleaved(const void* args, const float* a0, const float* b0, const float* a1, const float* b1,
-                          const HmcParams& P, hipStream_t s) {
-    const HmcParams Q = relay_plan(P, blocks(P.C), interleaved_kernel<Lane, M0, M1>);
-    hipLaunchKernelGGL((interleaved_kernel<Lane, M0, M1>), dim3(blocks(P.C) * Q.segs), dim3(kBlock), 0, s,
-                       *(const typename Lane::Args*)args, a0, b0, a1, b1, Q);
+  static RelayGeometry interleaved(const void* args, const float* a0, const float* b0, const float* a1, const float* b1,
+                                   const HmcParams& P, const RelayAsk& ask, hipStream_t s) {
+    return relay_launch(interleaved_kernel<Lane, M0, M1>, blocks(P.C), P, ask, s, *(const typename Lane::Args*)args, a0, b0, a1, b1);
   }
   static constexpr int kViB = lane_vi_block<Lane>::value;
   static hipError_t vi(const void* args, const float* a, const float* b, const ViParams& P, int n_groups, bool coop, hipStream_t s) {
@@ -274,23 +173,22 @@ inline bool stats_lds_enabled() {
   return on;
 }
 
-// Launch of a packed chain kernel (pk_chain.h) over the chain blocks of K lanes per chain (x the segments relay_plan decides
-// for the kernel it is given: its occupancy cache is keyed by the kernel's address), the kernel's own arguments first, P last.
+// Launch of a packed chain kernel (pk_chain.h) over the chain blocks of K lanes per chain (relay_launch: x the segments
+// relay_plan decides for the kernel it is given), the kernel's own arguments first, the parameters last.
 // A run that accumulates statistics takes StatsLds, the instantiation with the accumulators in LDS (the same kernel as Plain
 // where they do not fit: PkBlock::kStatsFit).  (StatsLds is named first because a translation unit emits its kernels in the
 // order they are first named: the code objects stay byte for byte what they were.)
 template <int K, auto StatsLds, auto Plain, class... Args>
-void pk_launch(const HmcParams& P, hipStream_t s, const Args&... args) {
+RelayGeometry pk_launch(const HmcParams& P, const RelayAsk& ask, hipStream_t s, const Args&... args) {
   const int nb = (int)(((long long)P.C * K + kBlock - 1) / kBlock);
   const auto kernel = (StatsLds != Plain && P.stats && stats_lds_enabled()) ? StatsLds : Plain;
-  const HmcParams Q = relay_plan(P, nb, kernel);
-  hipLaunchKernelGGL(kernel, dim3(nb * Q.segs), dim3(kBlock), 0, s, args..., Q);
+  return relay_launch(kernel, nb, P, ask, s, args...);
 }
 // pk_hmc_kernel in one compile-time parameterisation; AB: the kernel reads the handle's (a, b) arrays
 template <class T, int MODE, bool AB = true>
-void pk_hmc(const void* args, const float* a, const float* b, const HmcParams& P, hipStream_t s) {
-  pk_launch<T::K, pk_hmc_kernel<T, MODE, PkBlock<T>::kStatsFit>, pk_hmc_kernel<T, MODE>>(
-      P, s, *(const typename T::Args*)args, AB ? a : nullptr, AB ? b : nullptr);
+RelayGeometry pk_hmc(const void* args, const float* a, const float* b, const HmcParams& P, const RelayAsk& ask, hipStream_t s) {
+  return pk_launch<T::K, pk_hmc_kernel<T, MODE, PkBlock<T>::kStatsFit>, pk_hmc_kernel<T, MODE>>(
+      P, ask, s, *(const typename T::Args*)args, AB ? a : nullptr, AB ? b : nullptr);
 }
 
 // Radon.  Where the packed layer of radon_fast.h applies it takes every plain HMC run (the two compile-time
@@ -310,8 +208,9 @@ LaneOps radon_lane_ops() {
     o.hmc[kModeVIP] = o.hmc[kModeB1] = &pk_hmc<T, kModeVIP>;
     o.interleaved[0] = &G::template interleaved<kModeVIP, kModeVIP>;
     o.interleaved[1] = [](const void* args, const float*, const float*, const float*, const float*,
-                          const HmcParams& P, hipStream_t s) {
-      pk_launch<K, radon_interleaved_kernel<T, PkBlock<T>::kStatsFit>, radon_interleaved_kernel<T>>(P, s, *(const RadonArgs*)args);
+                          const HmcParams& P, const RelayAsk& ask, hipStream_t s) {
+      return pk_launch<K, radon_interleaved_kernel<T, PkBlock<T>::kStatsFit>, radon_interleaved_kernel<T>>(
+          P, ask, s, *(const RadonArgs*)args);
     };
     return o;
   } else {
@@ -335,9 +234,9 @@ LaneOps election_lane_ops() {
   o.interleaved[0] = &Launch<ElectionLane<K, NL>>::template interleaved<kModeVIP, kModeVIP>;
   // --method=i: centred / non-centred interleaving on the packed layer (pk_chain.h: pk_interleaved_kernel)
   o.interleaved[1] = [](const void* args, const float* a0, const float* b0, const float*, const float*,
-                        const HmcParams& P, hipStream_t s) {
-    pk_launch<K, pk_interleaved_kernel<T, kModeCP, kModeNCP, PkBlock<T>::kStatsFit>, pk_interleaved_kernel<T, kModeCP, kModeNCP>>(
-        P, s, *(const ElectionArgs*)args, a0, b0);
+                        const HmcParams& P, const RelayAsk& ask, hipStream_t s) {
+    return pk_launch<K, pk_interleaved_kernel<T, kModeCP, kModeNCP, PkBlock<T>::kStatsFit>, pk_interleaved_kernel<T, kModeCP, kModeNCP>>(
+        P, ask, s, *(const ElectionArgs*)args, a0, b0);
   };
   return o;
 }

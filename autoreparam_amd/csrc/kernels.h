@@ -37,7 +37,7 @@ struct HmcParams {
   int L1;
   float* adapt1; uint32_t* accept_count1; const float* eps0_1; uint8_t* trace_accept1; uint32_t* rec_accept1;
   // Relay (radon_fast.h: radon_interleaved_kernel): the launch's n_steps cut into `segs` segments, a workgroup per (segment,
-  // chain block); segment s takes the steps seg_start[s] .. seg_start[s + 1] (host_common.h: relay_schedule; more than
+  // chain block); segment s takes the steps seg_start[s] .. seg_start[s + 1] (relay_host.h: relay_schedule; more than
   // kSegTable segments: seg_len steps each) and starts when seg_flags[block] == seg_epoch + s.  segs <= 1: one workgroup
   // per block takes all the steps.
   int segs, seg_len, seg_blocks;

@@ -680,7 +680,7 @@ def test_relay_segments_in_every_chain_kernel(gpu, monkeypatch, mname, kind, cha
 
 
 def test_relay_rule(gpu, monkeypatch):
-    """Which launches the library cuts into relay segments (host_common.h: relay_plan), read back through arp_relay_geometry: 8
+    """Which launches the library cuts into relay segments (relay_host.h: relay_plan), read back through arp_relay_geometry: 8
     from 512 steps per launch on and 4 from 256 where the chain blocks are at least one round of the kernel's resident
     workgroups; none for shorter launches, for fewer blocks, or for kernels that hold a whole CU per workgroup."""
     from autoreparam_amd import engine, _lib

@@ -1,4 +1,4 @@
-"""The relay's cut of a launch into segments of unequal length (host_common.h: relay_schedule; kernels.h: relay_begin reads
+"""The relay's cut of a launch into segments of unequal length (relay_host.h: relay_schedule; kernels.h: relay_begin reads
 HmcParams::seg_start): the schedule's properties through arp_relay_schedule (no device), and on the GPU every cut -- the
 library's taper and explicit lists -- against the launch with one workgroup per chain block, bit for bit."""
 import numpy as np
@@ -203,3 +203,62 @@ def test_a_list_that_is_not_the_launch_is_refused(gpu, monkeypatch):
             eng.interleaved_run(st, e, e, 4, 4, 256, seed=9, adapt_kind=_lib.ADAPT_SIMPLE, lanes=4)
         torch.cuda.synchronize()
         assert np.array_equal(st.q.cpu().numpy(), q0)
+
+
+@pytest.mark.gpu
+def test_a_forced_cut_and_the_record_belong_to_one_launch_of_one_thread(gpu, monkeypatch):
+    """What a launch is asked to cut with travels with that call alone, and arp_relay_geometry is the calling thread's last
+    chain launch.  radon PA interleaved, 32 768 chains at the default 4 lanes per chain: 512 chain blocks, one round of two
+    resident workgroups per CU -- the smallest launch the library segments on its own (test_gpu_hmc.py: test_relay_rule).  An
+    explicit cut gives 3 segments; the same launch without the switch gives the library's 4, the same bits; another thread's
+    small launch on a handle of its own reports {1, its blocks, 0} there and leaves this thread's record alone; a launch of
+    255 steps then stays whole."""
+    import threading
+    from autoreparam_amd import engine, _lib
+    sp = helpers.spec("radon_PA")
+    eng = engine.Engine(sp, gpu)
+    eng.set_param(0, "CP"); eng.set_param(1, "NCP")
+    chains = 32768
+    q0 = helpers.states(sp, chains, seed=1, scale=0.05)
+    e = np.full(sp.D, 1e-3, np.float32)
+
+    def run(T):
+        st = engine.ChainState(torch.as_tensor(q0, device=gpu))
+        eng.interleaved_run(st, e, e, 1, 1, T, seed=1, adapt_kind=_lib.ADAPT_SIMPLE, n_adapt=0)
+        torch.cuda.synchronize()
+        eng.check()
+        return eng.relay_geometry(), [t.cpu().numpy() for t in (st.q, st.grad, st.logp, st.adapt, st.adapt1, st.accept_count,
+                                                                 st.accept_count1, st.rng)]
+
+    _set(monkeypatch, {"ARP_SEGMENT_LENS": "100,100,100"})
+    g, forced = run(300)
+    assert g["segments"] == 3 and g["chain_blocks"] == 512
+    _set(monkeypatch, {})
+    g, own = run(300)
+    assert g == {"segments": 4, "chain_blocks": 512, "workgroups_per_cu": 2}
+    assert np.isfinite(own[0]).all() and own[5].sum() > 0
+    for k, (x, y) in enumerate(zip(forced, own)):
+        assert np.array_equal(x, y, equal_nan=True), k
+
+    other = {}
+
+    def small_launch():
+        try:
+            gsp = helpers.spec("german")
+            geng = engine.Engine(gsp, gpu)                  # a handle of that thread's own
+            with torch.cuda.stream(torch.cuda.Stream(device=gpu)):
+                st = engine.ChainState(torch.as_tensor(helpers.states(gsp, 64, seed=2, scale=0.05), device=gpu))
+                geng.hmc_run(st, np.full(gsp.D, 1e-3, np.float32), 1, 8, seed=2, lanes=4)
+                torch.cuda.current_stream().synchronize()
+            other["geometry"] = geng.relay_geometry()
+        except Exception as exc:                            # noqa: BLE001 -- reported below, in the main thread
+            other["error"] = repr(exc)
+
+    t = threading.Thread(target=small_launch)
+    t.start(); t.join(timeout=120)
+    assert not t.is_alive() and "error" not in other, other
+    assert other["geometry"] == {"segments": 1, "chain_blocks": 1, "workgroups_per_cu": 0}      # 64 chains x 4 lanes: one block
+    assert eng.relay_geometry() == g
+
+    g, _ = run(255)
+    assert g["segments"] == 1 and g["chain_blocks"] == 512
