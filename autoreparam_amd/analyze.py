@@ -1,6 +1,6 @@
 """Pretty-printer for the result files main.py writes (reference analyze.py:30-185):
 
-    python -m autoreparam_amd.analyze --results_dir=. --model=radon_MN --elbos --ess --rhat --energy --trajectory --reparams
+    python -m autoreparam_amd.analyze --results_dir=. --model=radon_MN --elbos --ess --rhat --energy --trajectory --geometry --reparams
 
 The reference's method list is stale (`cVIP_exp_tied`, analyze.py:19-26) and it expects a
 `num_leapfrog_steps` key that main.py only writes for interleaved runs; here every
@@ -185,9 +185,48 @@ def report_trajectory(results, results_dir=None, model_name=None):
     return lines
 
 
+def report_geometry(results, results_dir=None, model_name=None):
+    """Build-specific: the posterior geometry report of every sampling run that recorded one (--geometry_diagnostics; the
+    last run of each file), one line per inner kernel: the three condition numbers, the most correlated pair and the
+    strongest scale coupling -- and, where <method>_geometry.npz is at hand, the elements that carry the stiff direction.
+    A second-order summary pooled over chains, not a local metric; unconverged chains inflate it."""
+    lines = []
+    fmt = lambda v: "n/a" if v is None else "{:.4g}".format(v)
+    for m, r in results.items():
+        if "geometry_rows" not in r:
+            continue
+        last = {k: v[-1] for k, v in r.items() if k.startswith("geometry_")}
+        kernels = last.get("geometry_by_kernel") or [last]
+        for j, d in enumerate(kernels):
+            lines.append("{}{}: condition number {} in the sampler's coordinates ({} scaled by its steps), {} centred; largest "
+                         "|correlation| {} ({}); largest scale coupling {} ({}); {} draws of {} chains, {} left out; {}".format(
+                             m, "" if len(kernels) == 1 else " kernel %d" % j, fmt(d["geometry_condition_number"]),
+                             fmt(d["geometry_condition_number_step_scaled"]), fmt(last["geometry_condition_number_centred"]),
+                             fmt(d["geometry_max_abs_correlation"]), " ~ ".join(d["geometry_max_correlation_pair"] or ["n/a"]),
+                             fmt(d["geometry_max_scale_coupling"]), " -> ".join(d["geometry_max_scale_coupling_pair"] or ["n/a"]),
+                             last["geometry_rows"], last["geometry_chains"], last["geometry_rows_left_out"],
+                             "n/a" if last.get("geometry_time_sec") is None else "{:.3f}s".format(last["geometry_time_sec"])))
+        path = os.path.join(results_dir or ".", model_name or "", m + "_geometry.npz")
+        if os.path.exists(path):
+            z = np.load(path)
+            names = [str(n) for n in z["elements"]]
+            for j in range(len(kernels)):
+                tag = "" if j == 0 else "_%d" % j
+                parts = [np.asarray(z[key], np.float64).reshape(-1) for key in z.files
+                         if key.startswith("stiffest_direction%s/" % tag)]
+                if not parts:
+                    continue
+                v = np.concatenate(parts)
+                top = np.argsort(-np.abs(v))[:3]
+                lines.append("      stiffest direction{}: {}".format(
+                    "" if len(kernels) == 1 else " of kernel %d" % j,
+                    ", ".join("{} {:+.3f}".format(names[i] if i < len(names) else i, v[i]) for i in top)))
+    return lines
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
-    for f in ("elbos", "ess", "reparams", "normalize_times", "rhat", "energy", "trajectory"):
+    for f in ("elbos", "ess", "reparams", "normalize_times", "rhat", "energy", "trajectory", "geometry"):
         ap.add_argument("--" + f, action="store_true")
     ap.add_argument("--model", default="all")
     ap.add_argument("--results_dir", default="")
@@ -212,6 +251,8 @@ def main(argv=None):
             print("\n".join(report_energy(results, root, name)) + "\n")
         if args.trajectory:
             print("\n".join(report_trajectory(results, root, name)) + "\n")
+        if args.geometry:
+            print("\n".join(report_geometry(results, root, name)) + "\n")
 
 
 if __name__ == "__main__":

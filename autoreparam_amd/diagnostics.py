@@ -8,7 +8,10 @@ Hoffman, Sountsov, Riou-Durand, Vehtari, Gelman 2024: `nested_fold`, `nested_ste
 and the energy report of probed trajectories (`energy_sums`, `energy_from_sums` on Engine.energy_probe's output: divergent
 trajectories, energy-error moments, expected acceptance, the kinetic share of the energy variance); and the
 trajectory-length profile (`profile_from_sums` on Engine.trajectory_sums' output: the worst element's expected squared jump
-distance per gradient for every leapfrog count up to Lmax, from fresh-momentum trajectories with every step recorded).
+distance per gradient for every leapfrog count up to Lmax, from fresh-momentum trajectories with every step recorded);
+and the posterior geometry report (`gram_sums` on `arp_gram_sums`, the cross moments of a trace on the matrix cores;
+`geometry_from_sums`: correlation matrix, its condition number, the stiff and the soft direction, the step-scaled
+condition number; `scale_coupling`, `coupling_from_sums`: the funnel detector).
 
 Build-specific (the reference runs 100 chains and reports the within-chain ESS only).  The per-chain moments come from
 one pass over a trace that is already on the device (`arp_split_moments`) or from the in-kernel statistics of a
@@ -54,8 +57,23 @@ Energy = collections.namedtuple("Energy", ["divergence_rate", "divergent", "nonf
 Profile = collections.namedtuple("Profile", ["leapfrogs", "rows", "divergent", "nonfinite", "left_out", "accept_prob",
                                              "divergence_rate", "esjd", "esjd_min", "esjd_min_element", "per_gradient",
                                              "best_leapfrogs"])
+# Posterior geometry from the cross moments of `gram_sums` (geometry_from_sums).  rows, rows_left_out: the counts (NaN for
+# rows_left_out where D = 1 leaves no room for it); mean, sd [D] float64 (sd NaN for an element left out); left_out: the
+# indices of the elements whose variance is not finite or not > 0, kept: the others, k of them; cov, correlation [k, k] and
+# eigenvalues [k] (ascending, of the correlation matrix) over the kept elements; condition_number = largest / smallest
+# eigenvalue (inf when the smallest is <= 0, NaN when k = 0); softest_direction, stiffest_direction [D]: the unit eigenvectors
+# of the largest and the smallest eigenvalue, zeros at the elements left out; max_abs_correlation and
+# max_correlation_pair (i, j) in the indices of all D elements, (-1, -1) when k < 2; step_scaled_eigenvalues [k] and
+# step_scaled_condition_number: of diag(1 / eps0) cov diag(1 / eps0), None / NaN without eps0.
+Geometry = collections.namedtuple("Geometry", ["rows", "rows_left_out", "mean", "sd", "kept", "left_out", "cov", "correlation",
+                                               "eigenvalues", "condition_number", "softest_direction", "stiffest_direction",
+                                               "max_abs_correlation", "max_correlation_pair", "step_scaled_eigenvalues",
+                                               "step_scaled_condition_number"])
 JUMP_HEAD = 5                     # scalars in front of J in a row of the jump sums (csrc/jump.hip)
 DIVERGENCE_THRESHOLD = 1000.0     # Stan's: a trajectory whose energy error exceeds it is reported as divergent
+GRAM_WINDOW = 256                 # rows a float32 accumulator of arp_gram_sums runs over (csrc/gram.hip: kGramWindow)
+GRAM_MAX_D = 512                  # the widest matrix arp_gram_sums takes
+COUPLING_FLOOR = 1e-12            # v = 0.5 log(u^2 + this): keeps the log finite at u = 0 (scale_coupling)
 
 
 def split_moments(trace, split=True):
@@ -385,3 +403,147 @@ def profile_from_sums(sums, var):
     ok = np.isfinite(per_gradient)
     best = int(leapfrogs[ok][per_gradient[ok].argmax()]) if ok.any() else 0    # (argmax: the first, hence smallest, l of a tie)
     return Profile(leapfrogs, rows, s[:, 1], s[:, 2], s[:, 4], accept, rate, esjd, esjd_min, at, per_gradient, best)
+
+
+def gram_sums(trace_or_matrix, shift=None):
+    """The [D + 2, D] float64 device tensor of `arp_gram_sums` for a recorded [S, C, D] float32 trace or a plain [n, D]
+    float32 matrix on the GPU: rows 0 ... D - 1 hold G = sum_r u_r u_r^T with u_r = x_r - shift (float32, one rounding)
+    over the rows without a non-finite element, row D the sum of u_r, row D + 1 the rows that counted and the rows left
+    out.  shift: a [D] float32 device tensor or None (zeros).  Additive over rows, hence over calls and ranks that use
+    one shift.  A leading or inner block of chains of a wider trace, and a matrix whose rows are further apart than D, are
+    read in place; the workspace is owned here.  An empty input gives zeros."""
+    from . import _lib
+    x = trace_or_matrix
+    if torch.is_tensor(x) and x.dim() == 2:
+        if not (x.is_cuda and x.dtype == torch.float32):
+            raise ValueError("gram_sums: a float32 [S, C, D] trace or [n, D] matrix on the GPU is required (there is no CPU fallback)")
+        n, D = (int(v) for v in x.shape)
+        if not (x.is_contiguous() or (x.stride(1) == 1 and x.stride(0) >= D)):
+            x = x.contiguous()
+        S, Cn, row_stride = n, 1, (int(x.stride(0)) if n > 1 else D)
+    else:
+        x, S, Cn, D, row_stride = _lib.trace_view(x, "gram_sums")
+    if shift is not None and not (torch.is_tensor(shift) and shift.is_cuda and shift.dtype == torch.float32
+                                  and shift.is_contiguous() and tuple(shift.shape) == (D,)):
+        raise ValueError("gram_sums: shift must be a contiguous float32 [D] tensor on the GPU")
+    sums = torch.zeros(D + 2, D, dtype=torch.float64, device=x.device)
+    if S == 0 or Cn == 0 or D == 0:
+        return sums
+    L = _lib.lib()
+    with torch.cuda.device(x.device):
+        need = int(L.arp_gram_workspace_bytes(S, Cn, D))
+        ws = torch.empty(need, dtype=torch.uint8, device=x.device) if need > 0 else None
+        _lib.check(L.arp_gram_sums(_lib.ptr(x), S, Cn, D, row_stride, _lib.ptr(shift), _lib.ptr(sums), _lib.ptr(ws), need,
+                                   _lib.stream()))
+        del ws
+    return sums
+
+
+def _moments_from_sums(sums):
+    """(n, left out, m = mean of u, cov) in float64 from [D + 2, D] sums; cov is NaN throughout for n < 2."""
+    s = np.asarray(sums.cpu() if torch.is_tensor(sums) else sums, np.float64)
+    if s.ndim != 2 or s.shape[0] != s.shape[1] + 2:
+        raise ValueError("a [D + 2, D] array of sums is required")
+    D = s.shape[1]
+    n = float(s[D + 1, 0])
+    left = float(s[D + 1, 1]) if D > 1 else float("nan")
+    with np.errstate(divide="ignore", invalid="ignore"):
+        m = s[D] / n if n >= 1 else np.full(D, np.nan)
+        cov = (s[:D] - n * np.outer(m, m)) / (n - 1.0) if n >= 2 else np.full((D, D), np.nan)
+    return n, left, m, cov
+
+
+def _condition(eig):
+    """largest / smallest of ascending eigenvalues: inf when the smallest is <= 0, NaN for none."""
+    if eig.size == 0 or not np.all(np.isfinite(eig)):
+        return float("nan")
+    return float(eig[-1] / eig[0]) if eig[0] > 0 else float("inf")
+
+
+def geometry_from_sums(sums, eps0=None, shift=None):
+    """The shape of the posterior, in the coordinates the sums were taken in, from the (all-reduced) [D + 2, D] sums of
+    `gram_sums` -> Geometry; pure numpy float64.  shift: what gram_sums subtracted (None: zeros), added back to the mean.
+    eps0: the run's per-element base steps; with them the eigenvalues and the condition number of
+    diag(1 / eps0) cov diag(1 / eps0), the shape the integrator works in with the run's own steps -- its square root is
+    the customary estimate of leapfrogs per independent draw.  A second-order summary pooled over chains: not a local
+    metric, and chains that have not converged inflate it.  Degenerate input (no rows, one row, constant columns) gives
+    NaN and empty matrices, never an exception."""
+    n, left, m, cov = _moments_from_sums(sums)
+    D = m.size
+    sh = np.zeros(D) if shift is None else np.asarray(shift.cpu() if torch.is_tensor(shift) else shift, np.float64).reshape(D)
+    var = np.diag(cov).copy()
+    ok = np.isfinite(var) & (var > 0)
+    kept, out = np.flatnonzero(ok), np.flatnonzero(~ok)
+    k = kept.size
+    sd_k = np.sqrt(var[kept])
+    sd = np.full(D, np.nan)
+    sd[kept] = sd_k
+    c = cov[np.ix_(kept, kept)]
+    c = 0.5 * (c + c.T)
+    R = c / np.outer(sd_k, sd_k)
+    if k:
+        np.fill_diagonal(R, 1.0)
+    soft, stiff = np.zeros(D), np.zeros(D)
+    eig = np.zeros(0)
+    if k and np.all(np.isfinite(R)):
+        eig, vec = np.linalg.eigh(R)
+        soft[kept], stiff[kept] = vec[:, -1], vec[:, 0]
+    elif k:
+        eig = np.full(k, np.nan)
+    worst, pair = float("nan"), (-1, -1)
+    if k >= 2 and np.all(np.isfinite(R)):
+        off = np.abs(R - np.diag(np.diag(R)))
+        i, j = np.unravel_index(int(off.argmax()), off.shape)
+        worst, pair = float(off[i, j]), (int(kept[min(i, j)]), int(kept[max(i, j)]))
+    scaled, scaled_cond = None, float("nan")
+    if eps0 is not None:
+        e = np.asarray(eps0.cpu() if torch.is_tensor(eps0) else eps0, np.float64).reshape(D)[kept]
+        with np.errstate(divide="ignore", invalid="ignore"):
+            a = c / np.outer(e, e)
+        scaled = np.linalg.eigvalsh(a) if k and np.all(np.isfinite(a)) else np.full(k, np.nan)
+        scaled_cond = _condition(scaled)
+    return Geometry(n, left, sh + m, sd, kept, out, c, R, eig, _condition(eig), soft, stiff, worst, pair, scaled, scaled_cond)
+
+
+def scale_coupling(rows, mean, sd):
+    """The funnel detector's raw sums.  rows: [n, D] (or [S, C, D]) float32 on the GPU; mean, sd: [D] (numpy or tensor),
+    pass one's pooled figures.  In float32 on the device u = (x - mean) / sd and v = 0.5 log(u^2 + COUPLING_FLOOR); the
+    [2 D + 2, 2 D] float64 sums of `gram_sums` over the [n, 2 D] matrix [u, v] with a NULL shift are returned, so that calls
+    and ranks can add them (`coupling_from_sums` turns them into K).  An element whose sd is not finite or not > 0 takes
+    u = 0: it is constant and its couplings come out as 0.  A funnel is invisible to linear correlation -- x_j ~ N(0, e^y)
+    is uncorrelated with y -- but log |x_j| is linear in y.  2 D <= GRAM_MAX_D."""
+    if not (torch.is_tensor(rows) and rows.is_cuda and rows.dtype == torch.float32 and rows.dim() in (2, 3)):
+        raise ValueError("scale_coupling: float32 [n, D] rows on the GPU are required (there is no CPU fallback)")
+    D = int(rows.shape[-1])
+    if 2 * D > GRAM_MAX_D:
+        raise ValueError("scale_coupling: at most %d elements" % (GRAM_MAX_D // 2))
+    x = rows.reshape(-1, D)
+    vec = lambda a: torch.as_tensor(np.asarray(a.cpu() if torch.is_tensor(a) else a, np.float64).reshape(D)).to(x.device)
+    mean64, sd64 = vec(mean), vec(sd)
+    ok = torch.isfinite(sd64) & (sd64 > 0) & torch.isfinite(mean64)
+    m32 = torch.where(ok, mean64, torch.zeros_like(mean64)).to(torch.float32)
+    s32 = torch.where(ok, sd64, torch.ones_like(sd64)).to(torch.float32)
+    both = torch.empty(x.shape[0], 2 * D, dtype=torch.float32, device=x.device)
+    u = both[:, :D]
+    torch.sub(x, m32, out=u)
+    u.div_(s32)
+    u[:, ~ok] = 0.0
+    v = both[:, D:]
+    torch.mul(u, u, out=v)
+    v.add_(COUPLING_FLOOR).log_().mul_(0.5)
+    return gram_sums(both)
+
+
+def coupling_from_sums(sums):
+    """K [D, D] float64 from the (all-reduced) [2 D + 2, 2 D] sums of `scale_coupling`: K[i][j] = the correlation of u_i
+    with v_j = log |u_j|, how strongly element i drives the SCALE of element j; the diagonal (an element with its own
+    log-magnitude) is set to 0, and so is every entry of an element without a finite, positive variance."""
+    n, _, _, cov = _moments_from_sums(sums)
+    D = cov.shape[0] // 2
+    var = np.diag(cov)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        K = cov[:D, D:] / np.sqrt(np.outer(var[:D], var[D:]))
+    ok = np.isfinite(var) & (var > 0)
+    K = np.where(np.outer(ok[:D], ok[D:]) & np.isfinite(K), K, 0.0)
+    np.fill_diagonal(K, 0.0)
+    return K

@@ -78,6 +78,15 @@ _DEFS = [
                                    "count that maximises it (trajectory_* JSON keys, <base>_trajectory.npz).  Not a replay "
                                    "of the sampler's transitions; the step sizes are those adapted for the run's own "
                                    "count; a one-transition criterion, not an ESS.  0: off."),
+    ("geometry_diagnostics", bool, False, "Sampling runs, with --convergence_diagnostics: the posterior geometry report -- why "
+                                          "this parameterisation mixes the way it does.  The cross-element second moments of "
+                                          "the recorded draws (arp_gram_sums, on the matrix cores) over the chains split R-hat "
+                                          "covers, centred and in the sampler's own coordinates: the condition number of the "
+                                          "correlation matrix, the same for the covariance scaled by the run's base steps, the "
+                                          "most correlated pair of elements, the stiff and the soft direction, and the scale "
+                                          "coupling of every pair, which sees the funnels that linear correlation does not "
+                                          "(geometry_* JSON keys, <base>_geometry.npz).  A second-order summary pooled over "
+                                          "chains, not a local metric; unconverged chains inflate it.  Sharded jobs included."),
     ("lanes_per_chain", int, 0, "Lanes of a wave64 a chain is spread over (0 = automatic)."),
 ]
 

@@ -281,6 +281,11 @@ def _convergence_report(kernel_results, model_config, flags, dev):
         keys.update(profile_keys)
         if profile_arrays is not None:
             arrays[TRAJECTORY_ARRAYS] = profile_arrays     # (taken out again: save_trajectory)
+    if getattr(flags, "geometry_diagnostics", False):
+        geometry_keys, geometry_arrays = _geometry_report(kernel_results, trace, k, spec, flags, dev, split.mean)
+        keys.update(geometry_keys)
+        if geometry_arrays is not None:
+            arrays[GEOMETRY_ARRAYS] = geometry_arrays      # (taken out again: save_geometry)
     keys["diagnostics_time_sec"] = time.time() - clock
     return keys, arrays
 
@@ -467,6 +472,161 @@ def _trajectory_report(kernel_results, trace, spec, flags, dev, pooled_sd):
     return keys, arrays
 
 
+GEOMETRY_ARRAYS = "geometry/"        # where _convergence_report leaves the arrays of <base>_geometry.npz
+GEOMETRY_CHUNK_BYTES = 256 << 20     # a chunk's transformed [n, D] rows and their [n, 2 D] companion stay below this
+GEOMETRY_KEYS = ("geometry_rows", "geometry_rows_left_out", "geometry_chains", "geometry_elements_left_out",
+                 "geometry_condition_number", "geometry_condition_number_step_scaled", "geometry_condition_number_centred",
+                 "geometry_max_abs_correlation", "geometry_max_correlation_pair", "geometry_max_scale_coupling",
+                 "geometry_max_scale_coupling_pair")
+GEOMETRY_KERNEL_KEYS = tuple(key for key in GEOMETRY_KEYS if key not in (
+    "geometry_rows", "geometry_rows_left_out", "geometry_chains", "geometry_condition_number_centred"))
+
+
+def element_names(spec):
+    """One name per element of the flat state, in trace order: `tau` for a scalar part, `m[17]`, `z[2,3]` otherwise."""
+    names = []
+    for name, shape in zip(spec.part_names, spec.part_shapes):
+        if not len(shape):
+            names.append(name)
+        else:
+            names.extend("%s[%s]" % (name, ",".join(str(int(i)) for i in idx)) for idx in np.ndindex(*shape))
+    return names
+
+
+def geometry_chunk_steps(S, k, D, budget=GEOMETRY_CHUNK_BYTES):
+    """Whole recorded steps per chunk of the geometry report: k chains of D floats each, three times over (the
+    transformed rows and their [n, 2 D] companion), within `budget` bytes; at least one."""
+    return int(max(1, min(max(int(S), 1), budget // max(1, 12 * int(k) * int(D)))))
+
+
+def _geometry_summary(g, K, names):
+    """The per-kernel JSON keys of one diagnostics.Geometry and its coupling matrix K (None: not computed)."""
+    pair = [names[i] for i in g.max_correlation_pair] if g.max_correlation_pair[0] >= 0 else None
+    worst_k, pair_k = None, None
+    if K is not None and K.size:
+        i, j = np.unravel_index(int(np.abs(K).argmax()), K.shape)
+        worst_k, pair_k = _finite_or_none(abs(K[i, j])), [names[i], names[j]]      # the driving element first
+    return OrderedDict([
+        ("geometry_elements_left_out", int(len(g.left_out))),
+        ("geometry_condition_number", _finite_or_none(g.condition_number)),
+        ("geometry_condition_number_step_scaled", _finite_or_none(g.step_scaled_condition_number)),
+        ("geometry_max_abs_correlation", _finite_or_none(g.max_abs_correlation)),
+        ("geometry_max_correlation_pair", pair),
+        ("geometry_max_scale_coupling", worst_k), ("geometry_max_scale_coupling_pair", pair_k)])
+
+
+def _full(matrix, kept, D):
+    """A [k, k] matrix over the kept elements as [D, D], NaN at the elements left out."""
+    out = np.full((D, D), np.nan)
+    out[np.ix_(kept, kept)] = matrix
+    return out
+
+
+def _geometry_report(kernel_results, trace, k, spec, flags, dev, pooled_mean):
+    """--geometry_diagnostics: WHY does this parameterisation mix the way it does?  The cross moments of the recorded draws
+    (diagnostics.gram_sums: arp_gram_sums on the matrix cores) over the leading `k` chains of the device trace -- the
+    chains split R-hat covers -- in two coordinate systems: centred, the trace as it is, and the sampler's own, through
+    the engine's transform, for every inner kernel of the run (--method=i has two).  From them the correlation matrix, its
+    condition number, the stiff and the soft direction, the condition number of the covariance scaled by the run's own
+    base steps, and -- a second pass with the first's mean and sd -- the scale coupling K (diagnostics.scale_coupling:
+    the funnel detector).  The rows are taken in chunks of whole recorded steps (GEOMETRY_CHUNK_BYTES).  `pooled_mean`:
+    the all-reduced pooled centred mean [D]; its transform is the shift of pass 1, identical on every rank, so the sums
+    add: each pass ends in one all-reduce and a sharded job reports real numbers.  A second-order summary pooled over
+    chains, not a local metric; unconverged chains inflate it.  No warning threshold is applied: none can be derived.
+    Returns (JSON keys, arrays of <base>_geometry.npz or None).  (A collective when ws > 1: every rank calls it.)"""
+    import torch
+    ctx = getattr(kernel_results, "probe", None)
+    if ctx is None:
+        return {}, None
+    clock = time.time()
+    eng, D = ctx.engine, int(spec.D)
+    S = int(trace.shape[0])
+    k = int(k) if S > 0 else 0
+    kernels = list(ctx.kernels)
+    nk = len(kernels)
+    device = trace.device
+    null = OrderedDict((key, None) for key in GEOMETRY_KEYS)
+    if D > diagnostics.GRAM_MAX_D:
+        util.print_("    posterior geometry: not computed for more than {} elements".format(diagnostics.GRAM_MAX_D))
+        null["geometry_time_sec"] = time.time() - clock
+        return null, None
+    couple = 2 * D <= diagnostics.GRAM_MAX_D
+    centre = np.nan_to_num(np.asarray(pooled_mean, np.float64).reshape(D), nan=0.0, posinf=0.0, neginf=0.0).astype(np.float32)
+    shift_c = torch.as_tensor(centre, device=device)
+    # one row through the engine's transform: the shift of every kernel's coordinates (a finite guess is all it has to be)
+    shifts = [eng.transform(shift_c[None, :], which=kn.which, to_centered=False)[0].contiguous() for kn in kernels]
+    shifts = [torch.where(torch.isfinite(s), s, torch.zeros_like(s)) for s in shifts]
+    steps = geometry_chunk_steps(S, k, D)
+
+    def chunks():
+        for s0 in range(0, S if k > 0 else 0, steps):
+            yield trace[s0:s0 + steps, :k]
+
+    # pass 1: the cross moments, centred and in every kernel's coordinates
+    total = [torch.zeros(D + 2, D, dtype=torch.float64, device=device) for _ in range(1 + nk)]
+    for chunk in chunks():
+        total[0] += diagnostics.gram_sums(chunk, shift_c)
+        rows = chunk.reshape(-1, D)
+        for j, kn in enumerate(kernels):
+            total[1 + j] += diagnostics.gram_sums(eng.transform(rows, which=kn.which, to_centered=False), shifts[j])
+    flat = np.concatenate([t.cpu().numpy().ravel() for t in total] + [[float(k)]])
+    flat = parallel.all_reduce_sum(flat, dev).cpu().numpy()
+    n_chains = int(round(flat[-1]))
+    sums = flat[:-1].reshape(1 + nk, D + 2, D)
+    if sums[0][D + 1, 0] < 1:                      # no chain with a device trace anywhere in the job
+        null["geometry_time_sec"] = time.time() - clock
+        return null, None
+    centred = diagnostics.geometry_from_sums(sums[0], shift=centre)
+    geo = [diagnostics.geometry_from_sums(sums[1 + j], eps0=kn.eps0, shift=shifts[j]) for j, kn in enumerate(kernels)]
+
+    # pass 2: the scale coupling in every kernel's coordinates, with pass 1's mean and sd
+    Ks = [None] * nk
+    if couple:
+        total2 = [torch.zeros(2 * D + 2, 2 * D, dtype=torch.float64, device=device) for _ in range(nk)]
+        for chunk in chunks():
+            rows = chunk.reshape(-1, D)
+            for j, kn in enumerate(kernels):
+                x = eng.transform(rows, which=kn.which, to_centered=False)
+                total2[j] += diagnostics.scale_coupling(x, geo[j].mean, geo[j].sd)
+        flat2 = parallel.all_reduce_sum(np.concatenate([t.cpu().numpy().ravel() for t in total2]), dev).cpu().numpy()
+        Ks = [diagnostics.coupling_from_sums(s) for s in flat2.reshape(nk, 2 * D + 2, 2 * D)]
+
+    names = element_names(spec)
+    summaries = [_geometry_summary(g, K, names) for g, K in zip(geo, Ks)]
+    left = sums[0][D + 1, 1] if D > 1 else float(S) * n_chains - sums[0][D + 1, 0]
+    keys = OrderedDict([("geometry_rows", int(round(sums[0][D + 1, 0]))), ("geometry_rows_left_out", int(round(left))),
+                        ("geometry_chains", n_chains)])
+    keys.update(summaries[0])
+    keys["geometry_condition_number_centred"] = _finite_or_none(centred.condition_number)
+    if nk > 1:
+        keys["geometry_by_kernel"] = summaries
+    fmt = lambda v: "n/a" if v is None else "{:.4g}".format(v)
+    for j, d in enumerate(summaries):
+        util.print_("    posterior geometry{} over {} draws of {} chains: condition number of the correlation matrix {} in the "
+                    "sampler's coordinates ({} scaled by its steps), {} centred; largest |correlation| {} ({}); largest scale "
+                    "coupling {} ({})".format(
+                        "" if nk == 1 else " of kernel %d" % j, keys["geometry_rows"], n_chains,
+                        fmt(d["geometry_condition_number"]), fmt(d["geometry_condition_number_step_scaled"]),
+                        fmt(keys["geometry_condition_number_centred"]), fmt(d["geometry_max_abs_correlation"]),
+                        " ~ ".join(d["geometry_max_correlation_pair"] or ["n/a"]), fmt(d["geometry_max_scale_coupling"]),
+                        " -> ".join(d["geometry_max_scale_coupling_pair"] or ["n/a"])))
+    arrays = OrderedDict(elements=np.asarray(names))
+    arrays["correlation_centred"] = _full(centred.correlation, centred.kept, D)
+    arrays["eigenvalues_centred"] = centred.eigenvalues
+    for j, (g, K) in enumerate(zip(geo, Ks)):
+        tag = "" if j == 0 else "_%d" % j
+        arrays["mean" + tag], arrays["sd" + tag] = g.mean, g.sd
+        arrays["correlation" + tag] = _full(g.correlation, g.kept, D)
+        arrays["eigenvalues" + tag] = g.eigenvalues
+        arrays["step_scaled_eigenvalues" + tag] = g.step_scaled_eigenvalues
+        arrays["scale_coupling" + tag] = np.full((D, D), np.nan) if K is None else K
+        for key, flat_d in (("stiffest_direction", g.stiffest_direction), ("softest_direction", g.softest_direction)):
+            for name, part in zip(spec.part_names, spec.unpack(flat_d)):
+                arrays["%s%s/%s" % (key, tag, name)] = part
+    keys["geometry_time_sec"] = time.time() - clock
+    return keys, arrays
+
+
 def _rank_fit_chains(trace, k):
     """The largest of k, k/2, k/4, ... leading chains whose z-score trace and workspace fit the free device memory."""
     import torch
@@ -642,14 +802,27 @@ def save_trajectory(file_path_base, arrays):
     np.savez(file_path_base + "_trajectory.npz", **arrays)
 
 
+def save_geometry(file_path_base, arrays):
+    """`<base>_geometry.npz` (build-specific, --geometry_diagnostics): `elements`, one name per element; in the sampler's
+    coordinates `mean`, `sd` [D], `correlation` [D, D] (NaN at the elements left out), `eigenvalues` (ascending, of the
+    correlation matrix over the elements kept), `step_scaled_eigenvalues` (of the covariance scaled by the run's base steps),
+    `scale_coupling` [D, D] (K[i][j]: how strongly element i drives the scale of element j) and per latent part
+    `stiffest_direction/<part>`, `softest_direction/<part>`; centred, `correlation_centred` and `eigenvalues_centred`.  The
+    second inner kernel of --method=i: the same names with the suffix `_1` (`correlation_1`, `stiffest_direction_1/<part>`)."""
+    np.savez(file_path_base + "_geometry.npz", **arrays)
+
+
 def _save_diagnostics(file_path_base, arrays):
-    """The side files of the convergence report: <base>_rhat.npz and, where the probes ran, <base>_energy.npz and
-    <base>_trajectory.npz."""
+    """The side files of the convergence report: <base>_rhat.npz and, where the probes ran, <base>_energy.npz,
+    <base>_trajectory.npz and <base>_geometry.npz."""
     if arrays is None:
         return
     energy = arrays.pop(ENERGY_ARRAYS, None)
     trajectory = arrays.pop(TRAJECTORY_ARRAYS, None)
+    geometry = arrays.pop(GEOMETRY_ARRAYS, None)
     save_rhat(file_path_base, arrays)
+    if geometry is not None:
+        save_geometry(file_path_base, geometry)
     if energy is not None:
         save_energy(file_path_base, energy)
     if trajectory is not None:

@@ -436,6 +436,35 @@ int64_t arp_nested_step_workspace_bytes(int64_t n_samples, int64_t n_chains, int
 int arp_nested_step_sums(const float* trace, int64_t n_samples, int64_t n_chains, int32_t D, int64_t row_stride,
                          int64_t group, double* sums, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* Cross moments of a trace on the matrix cores (build-specific; csrc/gram.hip): what the posterior geometry report takes a
+ * covariance from.  Addressing as arp_rank_normalize: element d of draw s of chain c is x[s * row_stride + c * D + d],
+ * row_stride >= n_chains * D (a block of chains of a wider trace is read in place; a plain [n][D] matrix is n_samples = n,
+ * n_chains = 1); nothing past x[(n_samples - 1) * row_stride + n_chains * D - 1] is read.  shift: a device [D] array, NULL
+ * for zeros (bitwise the result of explicit zeros).  For every row r, u_r = x_r - shift in float32 with one rounding; a row
+ * with a non-finite element (of x, hence of u) is left out whole and counted.  sums is a DEVICE double [D + 2][D]:
+ *   rows 0 ... D - 1: G[i][j] = sum_r u_ri u_rj over the rows that count -- the full matrix, the lower triangle a bitwise
+ *                     mirror of the upper;
+ *   row D:            sum_r u_rd;
+ *   row D + 1:        [0] = rows that counted, [1] = rows left out (D = 1 has no room for it: n_samples * n_chains - [0]),
+ *                     the rest 0.
+ * All of it is additive over rows, hence over calls and ranks that use one shift.  The products and their accumulation
+ * run on v_mfma_f32_32x32x2_f32 (exact f32, bit for bit a k-ordered fmaf chain; k is the row axis), upper-triangle blocks
+ * only, an accumulator over a window of at most 256 rows (kGramWindow) that is then added into float64:
+ *   |G_dev - G_f64|[i][j] <= (kGramWindow + 1) * 2^-24 * sum_r |u_ri u_rj|
+ * where G_f64 is the float64 sum of the float32 u; row D is exact to float64 rounding and the counts are exact.
+ * Select rule: padding columns, missing rows and rows left out enter the MFMA as 0 by select, never by a multiplication
+ * (0 * inf is NaN), and a row's mask is complete before any of its blocks is multiplied.
+ * Reproducibility rule: the workgroups' float64 partials are merged by a second launch in an order that depends on
+ * (n_samples * n_chains, D) alone -- no atomics; two calls give bitwise equal sums, and a block of chains taken in place
+ * gives bitwise the sums of its contiguous copy, at any alignment and stride.
+ * 1 <= D <= 512.  The workspace (arp_gram_workspace_bytes: the partials; 0 for a shape that is refused) is always needed
+ * and 256-byte aligned.  Returns 1 (arp_last_error) before any launch on a NULL x or sums, D < 1 or D > 512,
+ * n_samples < 1 or n_chains < 1, n_samples * n_chains >= 2^31, row_stride < n_chains * D, or a workspace that is missing,
+ * too small or misaligned. */
+int64_t arp_gram_workspace_bytes(int64_t n_samples, int64_t n_chains, int32_t D);
+int arp_gram_sums(const float* x, int64_t n_samples, int64_t n_chains, int32_t D, int64_t row_stride,
+                  const float* shift, double* sums, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* Test hook: the step-size adaptation recurrence of the chain kernels on SCRIPTED log acceptance ratios
  * (tfp.mcmc.DualAveragingStepSizeAdaptation / SimpleStepSizeAdaptation as wired at inference.py:224-226, 288-306;
  * SURVEY.md 8c known answer (7)).  For each of `n` independent rows, applies the update after transitions
