@@ -268,15 +268,26 @@ int arp_transform(arp_model* m, int which, int dir, const float* in, int n_chain
   return 0;
 }
 
+// What both probes ask before a launch: a handle, x, eps0 and the output, `which` in 0 / 1, n_rows >= 1 and few enough for
+// one launch (the instantiation is chosen as arp_logp_grad chooses it; the chain count it decides by is an int), and
+// 1 <= n_leapfrog <= max_leapfrog (0: no upper limit).  Returns the instantiation, or nullptr with the error set; `fn` is
+// the entry point the refusal names.
+static const LaneOps* probe_ops(const char* fn, arp_model* m, int which, const float* x, int64_t n_rows, int n_leapfrog,
+                                int max_leapfrog, const float* eps0, const float* out, int lanes_per_chain) {
+  if (!m || which < 0 || which > 1 || !x || !eps0 || !out || n_rows < 1 || n_leapfrog < 1 ||
+      (max_leapfrog > 0 && n_leapfrog > max_leapfrog)) {
+    set_error(std::string(fn) + ": bad argument (a handle, x, eps0, the output, which in 0 / 1, n_rows >= 1 and a leapfrog "
+              "count of at least 1" + (max_leapfrog > 0 ? " and at most " + std::to_string(max_leapfrog) : "") + " are required)");
+    return nullptr;
+  }
+  if (n_rows > 0x7fffffffLL / 16) { set_error(std::string(fn) + ": n_rows is too large for one launch"); return nullptr; }
+  return select_ops(m, lanes_per_chain, (int)n_rows);
+}
+
 int arp_energy_probe(arp_model* m, int which, const float* x, int64_t n_rows, int n_leapfrog, const float* eps0,
                      const float* kappa, uint64_t seed, int64_t row_offset, float* out4, float* p_out, float* q_out,
                      int lanes_per_chain, void* stream) {
-  if (!m || which < 0 || which > 1 || !x || !eps0 || !out4 || n_rows < 1 || n_leapfrog < 1) {
-    set_error("arp_energy_probe: bad argument"); return 1;
-  }
-  // (the instantiation is chosen as arp_logp_grad chooses it; the chain count it decides by is an int)
-  if (n_rows > 0x7fffffffLL / 16) { set_error("arp_energy_probe: n_rows is too large for one launch"); return 1; }
-  const LaneOps* o = select_ops(m, lanes_per_chain, (int)n_rows);
+  const LaneOps* o = probe_ops("arp_energy_probe", m, which, x, n_rows, n_leapfrog, 0, eps0, out4, lanes_per_chain);
   if (!o) return 1;
   o->probe(m->args, m->dev_ab[which], m->dev_ab[which] + m->D, {x, n_rows, m->D, eps0, kappa, seed, row_offset}, n_leapfrog,
            out4, p_out, q_out, (hipStream_t)stream);
@@ -287,13 +298,7 @@ int arp_energy_probe(arp_model* m, int which, const float* x, int64_t n_rows, in
 int arp_trajectory_probe(arp_model* m, int which, const float* x, int64_t n_rows, int n_leapfrog_max, const float* eps0,
                          const float* kappa, uint64_t seed, int64_t row_offset, float* energy_out, float* path_out,
                          int path_centred, float* p_out, int lanes_per_chain, void* stream) {
-  if (!m || which < 0 || which > 1 || !x || !eps0 || !energy_out || n_rows < 1 || n_leapfrog_max < 1 || n_leapfrog_max > 256) {
-    set_error("arp_trajectory_probe: bad argument (a handle, x, eps0, energy_out, which in 0 / 1, n_rows >= 1 and "
-              "n_leapfrog_max in 1 ... 256 are required)");
-    return 1;
-  }
-  if (n_rows > 0x7fffffffLL / 16) { set_error("arp_trajectory_probe: n_rows is too large for one launch"); return 1; }
-  const LaneOps* o = select_ops(m, lanes_per_chain, (int)n_rows);
+  const LaneOps* o = probe_ops("arp_trajectory_probe", m, which, x, n_rows, n_leapfrog_max, 256, eps0, energy_out, lanes_per_chain);
   if (!o) return 1;
   o->profile(m->args, m->dev_ab[which], m->dev_ab[which] + m->D, {x, n_rows, m->D, eps0, kappa, seed, row_offset},
              n_leapfrog_max, energy_out, path_out, path_centred, p_out, (hipStream_t)stream);

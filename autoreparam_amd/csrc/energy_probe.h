@@ -12,7 +12,7 @@ namespace arp {
 // Thread-to-(row, slot) mapping, dead-lane shadowing and prologue of logp_grad_kernel; integrator of hmc_transition
 // (half kick, drift, L - 1 x kick-drift, gradient, closing half kick) in the general (a, b) form, without the LDS parking.
 // out[r] = {lp0, ke0, lp1, ke1} as computed (NaN and +-inf are results); p_out / q_out (or null): the drawn momentum and
-// the end state, [N][D].
+// the end state, [N][D].  (trajectory_probe_kernel restates the lines from load_row to ke0: an edit here goes there too.)
 template <class Lane>
 __global__ __launch_bounds__(kBlock, Lane::MINW) void energy_probe_kernel(
     typename Lane::Args A, const float* __restrict__ av, const float* __restrict__ bv, const float* __restrict__ x,

@@ -88,16 +88,16 @@ struct Launch {
     hipLaunchKernelGGL(transform_kernel<Lane>, dim3(blocks(C)), dim3(kBlock), 0, s,
                        *(const typename Lane::Args*)args, a, b, dir, in, C, D, out);
   }
+  // the probes' grid: K lanes per row of a ProbeRows, whose row count is a long long (arp_api.hip keeps it inside a launch)
+  static dim3 probe_grid(const ProbeRows& r) { return dim3((unsigned)((r.N * Lane::K + kBlock - 1) / kBlock)); }
   static void probe(const void* args, const float* a, const float* b, const ProbeRows& r, int L, float* out4, float* p_out,
                     float* q_out, hipStream_t s) {
-    const long long nb = (r.N * Lane::K + kBlock - 1) / kBlock;
-    hipLaunchKernelGGL(energy_probe_kernel<Lane>, dim3((unsigned)nb), dim3(kBlock), 0, s, *(const typename Lane::Args*)args,
+    hipLaunchKernelGGL(energy_probe_kernel<Lane>, probe_grid(r), dim3(kBlock), 0, s, *(const typename Lane::Args*)args,
                        a, b, r.x, r.N, r.D, L, r.eps0, r.kappa, r.seed, r.row_offset, out4, p_out, q_out);
   }
   static void profile(const void* args, const float* a, const float* b, const ProbeRows& r, int Lmax, float* energy_out,
                       float* path_out, int path_centred, float* p_out, hipStream_t s) {
-    const long long nb = (r.N * Lane::K + kBlock - 1) / kBlock;
-    hipLaunchKernelGGL(trajectory_probe_kernel<Lane>, dim3((unsigned)nb), dim3(kBlock), 0, s, *(const typename Lane::Args*)args,
+    hipLaunchKernelGGL(trajectory_probe_kernel<Lane>, probe_grid(r), dim3(kBlock), 0, s, *(const typename Lane::Args*)args,
                        a, b, r.x, r.N, r.D, Lmax, r.eps0, r.kappa, r.seed, r.row_offset, energy_out, path_out, path_centred, p_out);
   }
   template <int MODE>

@@ -13,7 +13,10 @@
 namespace arp {
 
 // Thread-to-(row, slot) mapping, dead-lane shadowing, step-size load and momentum draw of energy_probe_kernel, the same
-// stream key (seed, row_offset + row, slot, K): with equal seed, offset and lanes p_out is that kernel's bit for bit.
+// stream key (seed, row_offset + row, slot, K): with equal seed, offset and lanes p_out and ke0 are that kernel's bit for bit.
+// (The lines from load_row to ke0 are that kernel's, restated: an edit to one goes into the other.  A shared function was
+// tried and compiles to other schedules in a quarter of the instantiations, NOTES_r07.md; what holds the two together is
+// tests/test_gpu_trajectory.py::test_same_stream_as_the_energy_probe, on every family and lane shape.)
 // Integrator: half kick, drift, then per step gradient (with the log density: the fused kick_drift of the radon and
 // election lanes returns none), full kick, drift.  The half kick that would close a trajectory of l steps goes into a
 // temporary, for the kinetic energy only: the trajectory itself runs on undisturbed.

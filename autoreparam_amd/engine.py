@@ -11,14 +11,6 @@ import torch
 from . import _lib
 
 
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
 class ChainState(object):
     """Per-chain persistent state of a run (the reference's kernel_results)."""
 
@@ -116,15 +108,15 @@ class Engine(object):
         logp = torch.empty(n, dtype=torch.float32, device=self.device)
         grad = torch.empty_like(x)
         with torch.cuda.device(self.device):
-            _lib.check(self._L.arp_logp_grad(self._h, which, _ptr(x), n, _ptr(logp), _ptr(grad), lanes, _stream()))
+            _lib.check(self._L.arp_logp_grad(self._h, which, _lib.ptr(x), n, _lib.ptr(logp), _lib.ptr(grad), lanes, _lib.stream()))
         return logp, grad
 
     def transform(self, x, which=0, to_centered=True):
         x = self._dev(x)
         out = torch.empty_like(x)
         with torch.cuda.device(self.device):
-            _lib.check(self._L.arp_transform(self._h, which, 0 if to_centered else 1, _ptr(x), x.shape[0],
-                                             _ptr(out), _stream()))
+            _lib.check(self._L.arp_transform(self._h, which, 0 if to_centered else 1, _lib.ptr(x), x.shape[0],
+                                             _lib.ptr(out), _lib.stream()))
         return out
 
     def energy_probe(self, x, eps0, n_leapfrog, which=0, kappa=None, seed=0, row_offset=0, lanes=0, want_p=False,
@@ -133,19 +125,15 @@ class Engine(object):
         eps0[d] * kappa[row] and `n_leapfrog` leapfrog steps (arp_energy_probe): returns out [N, 4] float32 =
         (logp, kinetic energy) at the start and at the end, then the drawn momenta (want_p) and the end states (want_q),
         [N, D] each.  Not a replay of a transition the sampler took; `x` is not changed.  The momenta depend on `lanes`."""
-        x = self._dev(x)
+        x, eps, kap = self._probe_args(x, eps0, kappa)
         n = x.shape[0]
-        eps = eps0.to(self.device, torch.float32).contiguous() if torch.is_tensor(eps0) else self._dev(np.asarray(eps0, np.float32))
-        assert x.dim() == 2 and x.shape[1] == self.D and eps.shape == (self.D,)
-        kap = None if kappa is None else self._dev(kappa)
-        assert kap is None or kap.shape == (n,)
         out = torch.empty(n, 4, dtype=torch.float32, device=self.device)
         p = torch.empty_like(x) if want_p else None
         q = torch.empty_like(x) if want_q else None
         with torch.cuda.device(self.device):
-            _lib.check(self._L.arp_energy_probe(self._h, int(which), _ptr(x), n, int(n_leapfrog), _ptr(eps), _ptr(kap),
-                                                int(seed) & 0xFFFFFFFFFFFFFFFF, int(row_offset), _ptr(out), _ptr(p), _ptr(q),
-                                                int(lanes), _stream()))
+            _lib.check(self._L.arp_energy_probe(self._h, int(which), _lib.ptr(x), n, int(n_leapfrog), _lib.ptr(eps), _lib.ptr(kap),
+                                                int(seed) & 0xFFFFFFFFFFFFFFFF, int(row_offset), _lib.ptr(out), _lib.ptr(p), _lib.ptr(q),
+                                                int(lanes), _lib.stream()))
         extra = tuple(t for t in (p, q) if t is not None)
         return (out,) + extra if extra else out
 
@@ -171,9 +159,9 @@ class Engine(object):
         path = torch.empty(max(Lmax, 0), n, self.D, dtype=torch.float32, device=self.device) if want_path else None
         p = torch.empty_like(x) if want_p else None
         with torch.cuda.device(self.device):
-            _lib.check(self._L.arp_trajectory_probe(self._h, int(which), _ptr(x), n, Lmax, _ptr(eps), _ptr(kap),
-                                                    int(seed) & 0xFFFFFFFFFFFFFFFF, int(row_offset), _ptr(energy), _ptr(path),
-                                                    1 if path_centred else 0, _ptr(p), int(lanes), _stream()))
+            _lib.check(self._L.arp_trajectory_probe(self._h, int(which), _lib.ptr(x), n, Lmax, _lib.ptr(eps), _lib.ptr(kap),
+                                                    int(seed) & 0xFFFFFFFFFFFFFFFF, int(row_offset), _lib.ptr(energy), _lib.ptr(path),
+                                                    1 if path_centred else 0, _lib.ptr(p), int(lanes), _lib.stream()))
         extra = tuple(t for t in (path, p) if t is not None)
         return (energy,) + extra if extra else energy
 
@@ -204,8 +192,8 @@ class Engine(object):
             with torch.cuda.device(self.device):
                 need = int(self._L.arp_jump_workspace_bytes(hi - lo, D, Lmax))
                 ws = torch.empty(need, dtype=torch.uint8, device=self.device) if need > 0 else None
-                _lib.check(self._L.arp_jump_sums(_ptr(x0), _ptr(path), _ptr(e), hi - lo, D, Lmax, _ptr(part), _ptr(ws), need,
-                                                 _stream()))
+                _lib.check(self._L.arp_jump_sums(_lib.ptr(x0), _lib.ptr(path), _lib.ptr(e), hi - lo, D, Lmax, _lib.ptr(part),
+                                                 _lib.ptr(ws), need, _lib.stream()))
             sums += part
             del ws, path
         return sums, energy
@@ -225,14 +213,14 @@ class Engine(object):
         cfg = _hmc_config(state, n_leapfrog, n_steps, seed, chain_offset, adapt_kind, n_adapt, adapt_target, adapt_rate, n_burnin,
                           thin, trace, trace_accept, trace_centered, lanes, stats_batch, n_samples, trace_chains)
         io = _lib.HmcIO()
-        io.q, io.grad, io.logp = _ptr(state.q), _ptr(state.grad), _ptr(state.logp)
-        io.adapt, io.rng, io.accept_count = _ptr(state.adapt), _ptr(state.rng), _ptr(state.accept_count)
+        io.q, io.grad, io.logp = _lib.ptr(state.q), _lib.ptr(state.grad), _lib.ptr(state.logp)
+        io.adapt, io.rng, io.accept_count = _lib.ptr(state.adapt), _lib.ptr(state.rng), _lib.ptr(state.accept_count)
         self._eps0 = eps0 if torch.is_tensor(eps0) else self._dev_cached("eps0", eps0)
-        io.eps0 = _ptr(self._eps0)
-        io.trace, io.trace_accept, io.stats = _ptr(trace), _ptr(trace_accept), _ptr(stats)
-        io.rec_accept_count = _ptr(rec_accept)
+        io.eps0 = _lib.ptr(self._eps0)
+        io.trace, io.trace_accept, io.stats = _lib.ptr(trace), _lib.ptr(trace_accept), _lib.ptr(stats)
+        io.rec_accept_count = _lib.ptr(rec_accept)
         with torch.cuda.device(self.device):
-            _lib.check(self._L.arp_hmc_run(self._h, which, C.byref(cfg), C.byref(io), _stream()))
+            _lib.check(self._L.arp_hmc_run(self._h, which, C.byref(cfg), C.byref(io), _lib.stream()))
         state.step += int(n_steps)
         return state
 
@@ -247,19 +235,19 @@ class Engine(object):
         cfg = _hmc_config(state, n_leapfrog_0, n_steps, seed, chain_offset, adapt_kind, n_adapt, adapt_target, adapt_rate, n_burnin,
                           thin, trace, trace_accept0, trace_centered, lanes, stats_batch, n_samples, trace_chains)
         io = _lib.InterleavedIO()
-        io.k0.q = _ptr(state.q)
-        io.k0.grad, io.k0.logp = _ptr(state.grad), _ptr(state.logp)   # carried gradient / log density
-        io.k0.adapt, io.k0.rng, io.k0.accept_count = _ptr(state.adapt), _ptr(state.rng), _ptr(state.accept_count)
+        io.k0.q = _lib.ptr(state.q)
+        io.k0.grad, io.k0.logp = _lib.ptr(state.grad), _lib.ptr(state.logp)   # carried gradient / log density
+        io.k0.adapt, io.k0.rng, io.k0.accept_count = _lib.ptr(state.adapt), _lib.ptr(state.rng), _lib.ptr(state.accept_count)
         self._eps0 = eps0_0 if torch.is_tensor(eps0_0) else self._dev_cached("eps0", eps0_0)
         self._eps1 = eps0_1 if torch.is_tensor(eps0_1) else self._dev_cached("eps1", eps0_1)
-        io.k0.eps0 = _ptr(self._eps0)
-        io.k0.trace, io.k0.trace_accept = _ptr(trace), _ptr(trace_accept0)
-        io.k0.stats, io.k0.rec_accept_count, io.rec_accept_count1 = _ptr(stats), _ptr(rec_accept0), _ptr(rec_accept1)
-        io.adapt1, io.accept_count1 = _ptr(state.adapt1), _ptr(state.accept_count1)
-        io.eps0_1 = _ptr(self._eps1)
-        io.trace_accept1 = _ptr(trace_accept1)
+        io.k0.eps0 = _lib.ptr(self._eps0)
+        io.k0.trace, io.k0.trace_accept = _lib.ptr(trace), _lib.ptr(trace_accept0)
+        io.k0.stats, io.k0.rec_accept_count, io.rec_accept_count1 = _lib.ptr(stats), _lib.ptr(rec_accept0), _lib.ptr(rec_accept1)
+        io.adapt1, io.accept_count1 = _lib.ptr(state.adapt1), _lib.ptr(state.accept_count1)
+        io.eps0_1 = _lib.ptr(self._eps1)
+        io.trace_accept1 = _lib.ptr(trace_accept1)
         with torch.cuda.device(self.device):
-            _lib.check(self._L.arp_interleaved_run(self._h, C.byref(cfg), int(n_leapfrog_1), C.byref(io), _stream()))
+            _lib.check(self._L.arp_interleaved_run(self._h, C.byref(cfg), int(n_leapfrog_1), C.byref(io), _lib.stream()))
         state.step += int(n_steps)
         return state
 
@@ -284,15 +272,15 @@ class Engine(object):
         cfg.a_prior = 1 if a_prior else 0   # --discrete_prior on the learnable parameters
         cfg.seed = int(seed)
         io = _lib.ViIO()
-        io.lr, io.loc, io.rho, io.w, io.elbo = _ptr(lr_t), _ptr(loc), _ptr(rho), _ptr(w), _ptr(elbo)
-        io.wb = _ptr(wb)
+        io.lr, io.loc, io.rho, io.w, io.elbo = _lib.ptr(lr_t), _lib.ptr(loc), _lib.ptr(rho), _lib.ptr(w), _lib.ptr(elbo)
+        io.wb = _lib.ptr(wb)
         prior = torch.zeros(n_lr, int(n_steps), dtype=torch.float32, device=self.device) if return_prior else None
-        io.prior = _ptr(prior)
+        io.prior = _lib.ptr(prior)
         ag = torch.as_tensor(np.asarray(a_group, np.int32), device=self.device) if a_group is not None else None
         bg = torch.as_tensor(np.asarray(b_group, np.int32), device=self.device) if b_group is not None else None
-        io.a_group, io.b_group = _ptr(ag), _ptr(bg)
+        io.a_group, io.b_group = _lib.ptr(ag), _lib.ptr(bg)
         with torch.cuda.device(self.device):
-            _lib.check(self._L.arp_vi_run(self._h, which, C.byref(cfg), C.byref(io), _stream()))
+            _lib.check(self._L.arp_vi_run(self._h, which, C.byref(cfg), C.byref(io), _lib.stream()))
         return (elbo, prior) if return_prior else elbo
 
 
@@ -347,7 +335,7 @@ class Engine(object):
         cfg.adapt_kind, cfg.n_adapt = int(kind), int(n_adapt)
         cfg.adapt_target, cfg.adapt_rate = float(target), float(rate)
         with torch.cuda.device(self.device):
-            _lib.check(self._L.arp_adapt_probe(C.byref(cfg), _ptr(la), n, _ptr(adapt), _ptr(out), _stream()))
+            _lib.check(self._L.arp_adapt_probe(C.byref(cfg), _lib.ptr(la), n, _lib.ptr(adapt), _lib.ptr(out), _lib.stream()))
         return out
 
 
@@ -359,7 +347,7 @@ def clock_probe(device, ms=10.0):
     out = torch.zeros(3, dtype=torch.int64, device=dev)
     iters = max(1, int(ms * 1e-3 / (64 * 2 * 4.43 / 2.4e9)))       # 64 packed FMAs per iteration, two waves per SIMD
     with torch.cuda.device(dev):
-        _lib.check(_lib.lib().arp_clock_probe(iters, C.c_void_p(out.data_ptr()), _stream()))
+        _lib.check(_lib.lib().arp_clock_probe(iters, C.c_void_p(out.data_ptr()), _lib.stream()))
         torch.cuda.synchronize(dev)
     cyc, ticks = int(out[0].item()), int(out[1].item())
     return (cyc / ticks) * 0.1 if ticks > 0 else None

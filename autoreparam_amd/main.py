@@ -270,22 +270,19 @@ def _convergence_report(kernel_results, model_config, flags, dev):
         keys.update(_bulk_tail_report(trace, k, spec, arrays, by_part))
     if int(getattr(flags, "superchain_size", 0) or 0) >= 2:
         keys.update(_nested_report(trace, moments, int(flags.superchain_size), dev, arrays, by_part))
-    if getattr(flags, "energy_diagnostics", False):
-        energy_keys, energy_arrays = _energy_report(kernel_results, trace, spec, flags, dev)
-        keys.update(energy_keys)
-        if energy_arrays is not None:
-            arrays[ENERGY_ARRAYS] = energy_arrays          # (run_hmc / run_interleaved_hmc take it out again: save_energy)
-    if int(getattr(flags, "trajectory_profile", 0) or 0) != 0:
-        pooled_sd = whole.sd if streaming else split.sd     # (already all-reduced)
-        profile_keys, profile_arrays = _trajectory_report(kernel_results, trace, spec, flags, dev, pooled_sd)
-        keys.update(profile_keys)
-        if profile_arrays is not None:
-            arrays[TRAJECTORY_ARRAYS] = profile_arrays     # (taken out again: save_trajectory)
-    if getattr(flags, "geometry_diagnostics", False):
-        geometry_keys, geometry_arrays = _geometry_report(kernel_results, trace, k, spec, flags, dev, split.mean)
-        keys.update(geometry_keys)
-        if geometry_arrays is not None:
-            arrays[GEOMETRY_ARRAYS] = geometry_arrays      # (taken out again: save_geometry)
+    # the reports with a side file of their own: the file's arrays wait under a tag (_save_diagnostics takes them out again)
+    for asked, tag, report in (
+            (getattr(flags, "energy_diagnostics", False), ENERGY_ARRAYS,
+             lambda: _energy_report(kernel_results, trace, spec, flags, dev)),
+            (int(getattr(flags, "trajectory_profile", 0) or 0) != 0, TRAJECTORY_ARRAYS,      # (the sd: already all-reduced)
+             lambda: _trajectory_report(kernel_results, trace, spec, flags, dev, whole.sd if streaming else split.sd)),
+            (getattr(flags, "geometry_diagnostics", False), GEOMETRY_ARRAYS,
+             lambda: _geometry_report(kernel_results, trace, k, spec, flags, dev, split.mean))):
+        if asked:
+            side_keys, side_arrays = report()
+            keys.update(side_keys)
+            if side_arrays is not None:
+                arrays[tag] = side_arrays
     keys["diagnostics_time_sec"] = time.time() - clock
     return keys, arrays
 
@@ -300,6 +297,31 @@ def probe_steps(S, R):
     if S <= 0 or R <= 0:
         return []
     return sorted({int(round(v)) for v in np.linspace(0, S - 1, min(S, R))})
+
+
+def _probe_walk(ctx, trace, flags, seed_constant):
+    """The rows both probe reports visit, so that they are the same rows: returns (steps, seed, visits).  `steps` is -1 for
+    the final state of every chain of this rank, then --energy_probe_steps evenly spaced recorded steps of the device trace
+    (the same on every rank); `seed` is derived from --seed and the report's own `seed_constant`.  `visits` yields, for
+    every inner kernel j and every step s = steps[i] that has rows on this rank, (j, kn, i, s, centred, x, n, row_offset):
+    the n rows centred and in kernel kn's coordinates (recorded states are centred and go through the existing transform)
+    and the momentum-stream key of the first, the global chain id + num_chains x step index (the final state counts as
+    step S)."""
+    eng, S = ctx.engine, int(trace.shape[0])
+    steps = [-1] + probe_steps(S, int(getattr(flags, "energy_probe_steps", 8)))
+    seed = (int(flags.seed) * 0x9E3779B97F4A7C15 + seed_constant) & 0xFFFFFFFFFFFFFFFF
+    centred_final = eng.transform(ctx.q, which=0, to_centered=True) if int(ctx.q.shape[0]) > 0 else ctx.q
+
+    def visits():
+        for j, kn in enumerate(ctx.kernels):
+            for i, s in enumerate(steps):
+                centred = centred_final if s < 0 else trace[s].contiguous()
+                n = int(centred.shape[0])
+                if n == 0:
+                    continue
+                x = ctx.q if (s < 0 and kn.which == 0) else eng.transform(centred, which=kn.which, to_centered=False)
+                yield j, kn, i, s, centred, x, n, ctx.chain_offset + int(flags.num_chains) * (S if s < 0 else s)
+    return steps, seed, visits()
 
 
 def _energy_summary(e):
@@ -326,36 +348,24 @@ def _energy_report(kernel_results, trace, spec, flags, dev):
         return {}, None
     clock = time.time()
     eng, D = ctx.engine, int(spec.D)
-    S = int(trace.shape[0])
-    C_local = int(ctx.q.shape[0])
-    steps = [-1] + probe_steps(S, int(getattr(flags, "energy_probe_steps", 8)))     # (the same on every rank)
-    seed = (int(flags.seed) * 0x9E3779B97F4A7C15 + 0x454E5247) & 0xFFFFFFFFFFFFFFFF
-    centred_final = eng.transform(ctx.q, which=0, to_centered=True) if C_local > 0 else ctx.q
-    sums, errors, where = [], [], []
-    for j, kn in enumerate(ctx.kernels):
-        total = torch.zeros(9, dtype=torch.float64, device=ctx.q.device)
-        err = np.full((len(steps), C_local), np.nan, np.float32)
-        for i, s in enumerate(steps):
-            centred = centred_final if s < 0 else trace[s].contiguous()
-            n = int(centred.shape[0])
-            if n == 0:
-                continue
-            x = ctx.q if (s < 0 and kn.which == 0) else eng.transform(centred, which=kn.which, to_centered=False)
-            out = eng.energy_probe(x, kn.eps0, kn.n_leapfrog, which=kn.which, kappa=kn.kappa[:n], seed=seed + j,
-                                   row_offset=ctx.chain_offset + int(flags.num_chains) * (S if s < 0 else s),
-                                   lanes=flags.lanes_per_chain)
-            total += diagnostics.energy_sums(out)
-            o = out.to(torch.float64)
-            dh = (o[:, 0] - o[:, 2]) + (o[:, 3] - o[:, 1])
-            err[i, :n] = dh.to(torch.float32).cpu().numpy()
-            bad = torch.nonzero(~torch.isfinite(dh) | (dh > diagnostics.DIVERGENCE_THRESHOLD)).reshape(-1)[:ENERGY_WHERE_MAX]
-            if bad.numel():
-                rows = torch.cat([centred[bad].to(torch.float64), (bad + ctx.chain_offset).to(torch.float64)[:, None],
-                                  torch.full((bad.numel(), 1), float(s), dtype=torch.float64, device=bad.device),
-                                  torch.full((bad.numel(), 1), float(j), dtype=torch.float64, device=bad.device)], dim=1)
-                where.append(rows.cpu().numpy())
-        sums.append(total.cpu().numpy())
-        errors.append(err)
+    steps, seed, visits = _probe_walk(ctx, trace, flags, 0x454E5247)
+    totals = [torch.zeros(9, dtype=torch.float64, device=ctx.q.device) for _ in ctx.kernels]
+    errors = [np.full((len(steps), int(ctx.q.shape[0])), np.nan, np.float32) for _ in ctx.kernels]
+    where = []
+    for j, kn, i, s, centred, x, n, row_offset in visits:
+        out = eng.energy_probe(x, kn.eps0, kn.n_leapfrog, which=kn.which, kappa=kn.kappa[:n], seed=seed + j,
+                               row_offset=row_offset, lanes=flags.lanes_per_chain)
+        totals[j] += diagnostics.energy_sums(out)
+        o = out.to(torch.float64)
+        dh = (o[:, 0] - o[:, 2]) + (o[:, 3] - o[:, 1])
+        errors[j][i, :n] = dh.to(torch.float32).cpu().numpy()
+        bad = torch.nonzero(~torch.isfinite(dh) | (dh > diagnostics.DIVERGENCE_THRESHOLD)).reshape(-1)[:ENERGY_WHERE_MAX]
+        if bad.numel():
+            rows = torch.cat([centred[bad].to(torch.float64), (bad + ctx.chain_offset).to(torch.float64)[:, None],
+                              torch.full((bad.numel(), 1), float(s), dtype=torch.float64, device=bad.device),
+                              torch.full((bad.numel(), 1), float(j), dtype=torch.float64, device=bad.device)], dim=1)
+            where.append(rows.cpu().numpy())
+    sums = [total.cpu().numpy() for total in totals]
     t = parallel.all_reduce_sum(np.concatenate(sums), dev).cpu().numpy().reshape(len(ctx.kernels), 9)
     by_kernel = [diagnostics.energy_from_sums(row, D) for row in t]
     pooled = diagnostics.energy_from_sums(t.sum(axis=0), D)
@@ -408,9 +418,9 @@ def _trajectory_summary(p, run_leapfrogs):
 
 def _trajectory_report(kernel_results, trace, spec, flags, dev, pooled_sd):
     """--trajectory_profile=LMAX: did the run use the right number of leapfrog steps?  From the rows the energy report
-    probes -- the final state of every chain of this rank and --energy_probe_steps recorded steps of the device trace, the
-    same row offsets, a seed constant of its own -- one fresh-momentum trajectory of LMAX steps with the run's own base
-    steps and per-chain multipliers, every step recorded (Engine.trajectory_sums): the Metropolis-weighted expected
+    probes (both walk _probe_walk) -- the final state of every chain of this rank and --energy_probe_steps recorded steps of
+    the device trace, the same row offsets, a seed constant of its own -- one fresh-momentum trajectory of LMAX steps with
+    the run's own base steps and per-chain multipliers, every step recorded (Engine.trajectory_sums): the Metropolis-weighted expected
     squared jump distance of every element, in units of the run's pooled posterior variance, for every leapfrog count
     1 ... LMAX at once, the worst element's per gradient, and the count that maximises it.  NOT a replay of the sampler's
     transitions; the step sizes are those the run adapted for its own leapfrog count (a run at another count would adapt
@@ -425,25 +435,13 @@ def _trajectory_report(kernel_results, trace, spec, flags, dev, pooled_sd):
         return {}, None
     clock = time.time()
     eng, D = ctx.engine, int(spec.D)
-    S = int(trace.shape[0])
-    C_local = int(ctx.q.shape[0])
-    steps = [-1] + probe_steps(S, int(getattr(flags, "energy_probe_steps", 8)))     # (the same on every rank)
-    seed = (int(flags.seed) * 0x9E3779B97F4A7C15 + 0x54524A50) & 0xFFFFFFFFFFFFFFFF
-    centred_final = eng.transform(ctx.q, which=0, to_centered=True) if C_local > 0 else ctx.q
-    sums = []
-    for j, kn in enumerate(ctx.kernels):
-        total = torch.zeros(Lmax, 5 + D, dtype=torch.float64, device=ctx.q.device)
-        for s in steps:
-            centred = centred_final if s < 0 else trace[s].contiguous()
-            n = int(centred.shape[0])
-            if n == 0:
-                continue
-            x = ctx.q if (s < 0 and kn.which == 0) else eng.transform(centred, which=kn.which, to_centered=False)
-            part, _ = eng.trajectory_sums(x, kn.eps0, Lmax, which=kn.which, kappa=kn.kappa[:n], seed=seed + j,
-                                          row_offset=ctx.chain_offset + int(flags.num_chains) * (S if s < 0 else s),
-                                          lanes=flags.lanes_per_chain)
-            total += part.to(total.device)
-        sums.append(total.cpu().numpy().ravel())
+    _, seed, visits = _probe_walk(ctx, trace, flags, 0x54524A50)
+    totals = [torch.zeros(Lmax, 5 + D, dtype=torch.float64, device=ctx.q.device) for _ in ctx.kernels]
+    for j, kn, _, _, _, x, n, row_offset in visits:
+        part, _ = eng.trajectory_sums(x, kn.eps0, Lmax, which=kn.which, kappa=kn.kappa[:n], seed=seed + j,
+                                      row_offset=row_offset, lanes=flags.lanes_per_chain)
+        totals[j] += part.to(totals[j].device)
+    sums = [total.cpu().numpy().ravel() for total in totals]
     t = parallel.all_reduce_sum(np.concatenate(sums), dev).cpu().numpy().reshape(len(ctx.kernels), Lmax, 5 + D)
     var = np.asarray(pooled_sd, np.float64) ** 2
     profiles = [diagnostics.profile_from_sums(row, var) for row in t]
@@ -817,16 +815,13 @@ def _save_diagnostics(file_path_base, arrays):
     <base>_trajectory.npz and <base>_geometry.npz."""
     if arrays is None:
         return
-    energy = arrays.pop(ENERGY_ARRAYS, None)
-    trajectory = arrays.pop(TRAJECTORY_ARRAYS, None)
-    geometry = arrays.pop(GEOMETRY_ARRAYS, None)
+    # (tag _convergence_report left a side file's arrays under, its saver), in the order the files are written after _rhat.npz
+    side = [(arrays.pop(tag, None), save) for tag, save in (
+        (GEOMETRY_ARRAYS, save_geometry), (ENERGY_ARRAYS, save_energy), (TRAJECTORY_ARRAYS, save_trajectory))]
     save_rhat(file_path_base, arrays)
-    if geometry is not None:
-        save_geometry(file_path_base, geometry)
-    if energy is not None:
-        save_energy(file_path_base, energy)
-    if trajectory is not None:
-        save_trajectory(file_path_base, trajectory)
+    for side_arrays, save in side:
+        if side_arrays is not None:
+            save(file_path_base, side_arrays)
 
 
 def save_rhat(file_path_base, arrays):

@@ -145,7 +145,21 @@ class _FakeEngine(object):
         return torch.as_tensor(s), torch.zeros(n_leapfrog_max + 1, n, 2)
 
 
-def _report(monkeypatch, kernels, Lmax, S=6, Cn=4, run_leapfrogs=3):
+class _BothProbesEngine(_FakeEngine):
+    """_FakeEngine with an energy probe that records its call and reports trajectories without an energy error."""
+
+    def __init__(self, D):
+        super(_BothProbesEngine, self).__init__(D)
+        self.energy_calls = []
+
+    def energy_probe(self, x, eps0, n_leapfrog, which=0, kappa=None, seed=0, row_offset=0, lanes=0, want_p=False, want_q=False):
+        n = int(x.shape[0])
+        assert kappa is not None and tuple(kappa.shape) == (n,)
+        self.energy_calls.append((which, int(n_leapfrog), int(row_offset), int(seed), n))
+        return torch.zeros(n, 4)
+
+
+def _report(monkeypatch, kernels, Lmax, S=6, Cn=4, run_leapfrogs=3, energy=False, engine=_FakeEngine):
     from autoreparam_amd import diagnostics, inference, main as cli, models, parallel
     from autoreparam_amd.flags import FlagValues
     cfg = models.get_model_by_name("8schools", "")
@@ -169,16 +183,30 @@ def _report(monkeypatch, kernels, Lmax, S=6, Cn=4, run_leapfrogs=3):
     monkeypatch.setattr(diagnostics, "split_moments", moments)
     monkeypatch.setattr(diagnostics, "fold", fold)
     monkeypatch.setattr(parallel, "all_reduce_sum", all_reduce_sum)
-    eng = _FakeEngine(D)
+    eng = engine(D)
     kappa = torch.ones(Cn)
     ctx = inference.ProbeContext(eng, torch.as_tensor(x[-1]), 0, tuple(
         inference.ProbeKernel(j, np.full(D, 0.1, np.float32), run_leapfrogs + 5 * j, kappa) for j in range(kernels)))
     base = inference.KernelResults(inference.HmcInnerResults(None), 1.0, S, None, None, torch.as_tensor(x))
     kr = inference._with_probe(base, ctx)
     f = FlagValues()
-    f.num_chains, f.seed, f.energy_probe_steps, f.trajectory_profile = Cn, 4, 3, Lmax
+    f.num_chains, f.seed, f.energy_probe_steps, f.trajectory_profile, f.energy_diagnostics = Cn, 4, 3, Lmax, energy
     keys, arrays = cli._convergence_report(kr, cfg, f, None)
     return keys, arrays, eng, cfg, (S, Cn, D), reduces
+
+
+@pytest.mark.parametrize("kernels", [1, 2])
+def test_both_probes_visit_the_same_rows(monkeypatch, kernels):
+    """With --energy_diagnostics and --trajectory_profile both on, Engine.energy_probe and Engine.trajectory_sums see the
+    same sequence of (which, row_offset, rows) -- the trajectory report's "the rows the energy report probes" -- and at every
+    visit their seeds differ by the difference of the two reports' seed constants (so by the same amount within a kernel)."""
+    keys, arrays, eng, _, (S, Cn, D), _ = _report(monkeypatch, kernels, 4, energy=True, engine=_BothProbesEngine)
+    rows = lambda calls: [(c[0], c[2], c[4]) for c in calls]
+    assert rows(eng.energy_calls) == rows(eng.calls)
+    assert rows(eng.calls) == [(j, Cn * (S if s < 0 else s), Cn) for j in range(kernels) for s in (-1, 0, 2, 5)]
+    apart = [(t[3] - e[3]) % (1 << 64) for e, t in zip(eng.energy_calls, eng.calls)]
+    assert apart == [0x54524A50 - 0x454E5247] * len(eng.calls)
+    assert keys["energy_probe_trajectories"] == keys["trajectory_probe_trajectories"] == kernels * 4 * Cn
 
 
 @pytest.mark.parametrize("kernels", [1, 2])
