@@ -112,15 +112,20 @@ struct TimeSeriesLane {
   }
 
   // Forward block scan: centred (alpha_t, mu_t) of this lane's steps; eA/eM = Sa^-b, Sm^-b' per step.
+  // GRAD: the gradient needs Sa^-b and takes c = Sa^(1-b) from it with one multiplication.  The converters (!GRAD) take
+  // the power itself, c = exp((1 - b) log Sa), and get it back in eA/eM: it is exactly 1 at b = 1 and carries the
+  // rounding of (1 - b) log Sa only, where Sa exp(-b log Sa) carries that of b log Sa and misses 1 by a few ulps, which
+  // the cancellation in m + c (at - a m) then multiplies (tests/test_gpu_converters.py: three times the error at CP).
+  template <bool GRAD = true>
   ARP_DEV void forward(const float (&q)[ND], const Scales& S, float (&al)[B], float (&mu)[B], float (&eA)[B],
                        float (&eM)[B]) const {
     // pass 1: zero input, compose the block map (alpha, mu)_out = [[p11, p12], [0, p22]] in + (da, dm)
     float p11 = 1.0f, p12 = 0.0f, p22 = 1.0f, da = 0.0f, dm = 0.0f;
 #pragma unroll
     for (int tl = 0; tl < B; ++tl) {
-      eA[tl] = fast_exp(-bA[tl] * S.lSa);
-      eM[tl] = fast_exp(-bM[tl] * S.lSm);
-      const float cA = S.Sa * eA[tl], cM = S.Sm * eM[tl];
+      eA[tl] = GRAD ? fast_exp(-bA[tl] * S.lSa) : fast_exp((1.0f - bA[tl]) * S.lSa);
+      eM[tl] = GRAD ? fast_exp(-bM[tl] * S.lSm) : fast_exp((1.0f - bM[tl]) * S.lSm);
+      const float cA = GRAD ? S.Sa * eA[tl] : eA[tl], cM = GRAD ? S.Sm * eM[tl] : eM[tl];
       const float fA = fmaf(-aA[tl], cA, 1.0f), fM = fmaf(-aM[tl], cM, 1.0f);
       p12 = fA * (p12 + p22); p11 = fA * p11; p22 = fM * p22;
       da = fmaf(fA, da + dm, cA * q[NG + 2 * tl]);
@@ -137,7 +142,7 @@ struct TimeSeriesLane {
     // pass 2: the block with its real input
 #pragma unroll
     for (int tl = 0; tl < B; ++tl) {
-      const float cA = S.Sa * eA[tl], cM = S.Sm * eM[tl];
+      const float cA = GRAD ? S.Sa * eA[tl] : eA[tl], cM = GRAD ? S.Sm * eM[tl] : eM[tl];
       const float mA = ap + mp;
       al[tl] = fmaf(cA, fmaf(-aA[tl], mA, q[NG + 2 * tl]), mA);
       mu[tl] = fmaf(cM, fmaf(-aM[tl], mp, q[NG + 2 * tl + 1]), mp);
@@ -471,8 +476,8 @@ struct TimeSeriesLane {
 
   ARP_DEV void to_centered(const float (&q)[ND], float (&x)[ND]) const {
     const Scales S = scales(q[0], q[1]);
-    float al[B], mu[B], eA[B], eM[B];
-    forward(q, S, al, mu, eA, eM);
+    float al[B], mu[B], cA[B], cM[B];
+    forward<false>(q, S, al, mu, cA, cM);
     x[0] = q[0]; x[1] = q[1]; x[2] = q[2];
 #pragma unroll
     for (int tl = 0; tl < B; ++tl) { x[NG + 2 * tl] = al[tl]; x[NG + 2 * tl + 1] = mu[tl]; }
