@@ -1,6 +1,7 @@
 """Pretty-printer for the result files main.py writes (reference analyze.py:30-185):
 
-    python -m autoreparam_amd.analyze --results_dir=. --model=radon_MN --elbos --ess --rhat --energy --trajectory --geometry --reparams
+    python -m autoreparam_amd.analyze --results_dir=. --model=radon_MN --elbos --ess --rhat --energy --trajectory --geometry --loo --reparams
+    python -m autoreparam_amd.analyze --loo_compare=radon_MN/CP_tied_loo.npz,radon_stddvs_MN/CP_tied_loo.npz
 
 The reference's method list is stale (`cVIP_exp_tied`, analyze.py:19-26) and it expects a
 `num_leapfrog_steps` key that main.py only writes for interleaved runs; here every
@@ -224,13 +225,55 @@ def report_geometry(results, results_dir=None, model_name=None):
     return lines
 
 
+def report_loo(results):
+    """Build-specific: the predictive report of every sampling run that recorded one (--predictive_diagnostics; the last
+    run of each file): elpd_loo and elpd_waic with their standard errors, the effective numbers of parameters, and the
+    worst Pareto k-hat against its threshold.  No r_eff correction, no moment matching, no K-fold."""
+    lines = []
+    fmt = lambda v: "n/a" if v is None else "{:.4g}".format(v)
+    for m, r in results.items():
+        if "loo_observations" not in r:
+            continue
+        last = {k: r[k][-1] for k in r if k in ("elpd_loo", "elpd_loo_se", "p_loo", "elpd_waic", "elpd_waic_se", "p_waic",
+                                                "loo_time_sec") or k.startswith(("loo_", "pareto_k_"))}
+        if last["loo_observations"] is None:
+            lines.append("{}: PSIS-LOO / WAIC not computed".format(m))
+            continue
+        lines.append("{}: elpd_loo {} +/- {}, p_loo {}; elpd_waic {} +/- {}, p_waic {}; worst Pareto k-hat {} (observation {}; "
+                     "{} above {}); {} observations, {} draws of {} chains, {} left out, {} observation(s) not finite; {}".format(
+                         m, fmt(last["elpd_loo"]), fmt(last["elpd_loo_se"]), fmt(last["p_loo"]), fmt(last["elpd_waic"]),
+                         fmt(last["elpd_waic_se"]), fmt(last["p_waic"]), fmt(last["pareto_k_max"]),
+                         last["pareto_k_max_observation"], last["pareto_k_above_threshold"], fmt(last["pareto_k_threshold"]),
+                         last["loo_observations"], last["loo_draws"], last["loo_chains"], last["loo_draws_left_out"],
+                         last["loo_nonfinite_observations"],
+                         "n/a" if last.get("loo_time_sec") is None else "{:.3f}s".format(last["loo_time_sec"])))
+    return lines
+
+
+def report_loo_compare(path_a, path_b):
+    """Build-specific: the paired difference in elpd_loo of two models fitted to the same observations, from their
+    <method>_loo.npz files (diagnostics.loo_compare): positive favours the first.  Refused unless y agrees."""
+    from . import diagnostics
+    with np.load(path_a) as a, np.load(path_b) as b:
+        diff, se = diagnostics.loo_compare(a, b)
+        return ["elpd_loo({}) - elpd_loo({}) = {:.4g} +/- {:.4g} over {} observations".format(
+            str(a["model"]), str(b["model"]), diff, se, int(np.asarray(a["y"]).size))]
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
-    for f in ("elbos", "ess", "reparams", "normalize_times", "rhat", "energy", "trajectory", "geometry"):
+    for f in ("elbos", "ess", "reparams", "normalize_times", "rhat", "energy", "trajectory", "geometry", "loo"):
         ap.add_argument("--" + f, action="store_true")
+    ap.add_argument("--loo_compare", default="", help="A_loo.npz,B_loo.npz: the paired elpd_loo difference of two models")
     ap.add_argument("--model", default="all")
     ap.add_argument("--results_dir", default="")
     args = ap.parse_args(argv)
+    if args.loo_compare:
+        paths = [p for p in args.loo_compare.split(",") if p]
+        if len(paths) != 2:
+            ap.error("--loo_compare takes two files: A_loo.npz,B_loo.npz")
+        print("\n".join(report_loo_compare(*paths)) + "\n")
+        return
     root = args.results_dir or "."
     names = sorted(d for d in os.listdir(root) if os.path.isdir(os.path.join(root, d))) if args.model == "all" \
         else [args.model]
@@ -253,6 +296,8 @@ def main(argv=None):
             print("\n".join(report_trajectory(results, root, name)) + "\n")
         if args.geometry:
             print("\n".join(report_geometry(results, root, name)) + "\n")
+        if args.loo:
+            print("\n".join(report_loo(results)) + "\n")
 
 
 if __name__ == "__main__":

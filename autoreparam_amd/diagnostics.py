@@ -11,7 +11,9 @@ trajectory-length profile (`profile_from_sums` on Engine.trajectory_sums' output
 distance per gradient for every leapfrog count up to Lmax, from fresh-momentum trajectories with every step recorded);
 and the posterior geometry report (`gram_sums` on `arp_gram_sums`, the cross moments of a trace on the matrix cores;
 `geometry_from_sums`: correlation matrix, its condition number, the stiff and the soft direction, the step-scaled
-condition number; `scale_coupling`, `coupling_from_sums`: the funnel detector).
+condition number; `scale_coupling`, `coupling_from_sums`: the funnel detector); and, the one report that judges the model
+and not the sampler, PSIS-LOO and WAIC (`pointwise_loglik` on `arp_pointwise_loglik`, `psis_loo` on `arp_psis_loo`;
+`loo_summary`, `loo_compare`, `pareto_k_threshold`: the host float64 folds).
 
 Build-specific (the reference runs 100 chains and reports the within-chain ESS only).  The per-chain moments come from
 one pass over a trace that is already on the device (`arp_split_moments`) or from the in-kernel statistics of a
@@ -547,3 +549,144 @@ def coupling_from_sums(sums):
     K = np.where(np.outer(ok[:D], ok[D:]) & np.isfinite(K), K, 0.0)
     np.fill_diagonal(K, 0.0)
     return K
+
+
+# ---- predictive diagnostics: pointwise log-likelihood, PSIS-LOO and WAIC (csrc/loglik.hip, csrc/psis.hip) ----
+# An observation table (models.ObservationTable) in device memory: kind, T and N as ints; idx [N, T] int32, w [N, T]
+# float32, y, log_scale [N] float32 and scale_idx [N] int32 as contiguous device tensors; y_host: y as numpy float32.
+DeviceTable = collections.namedtuple("DeviceTable", ["kind", "T", "N", "idx", "w", "y", "scale_idx", "log_scale", "y_host"])
+# Totals of the report (loo_summary), floats: elpd_loo = sum_n elpd_loo_n with se = sqrt(N var_n), p_loo =
+# sum_n (lppd_n - elpd_loo_n); elpd_waic_n = lppd_n - p_waic_n likewise, p_waic = sum_n p_waic_n.
+LooSummary = collections.namedtuple("LooSummary", ["elpd_loo", "elpd_loo_se", "p_loo", "elpd_waic", "elpd_waic_se", "p_waic"])
+PSIS_COLUMNS = ("elpd_loo", "pareto_k", "lppd", "p_waic", "tail_len", "cutoff", "gpd_sigma", "draws_used")
+PSIS_MAX_DRAWS = 1 << 24          # the most draws per observation arp_psis_loo takes (csrc/psis.hip: kPsMaxR)
+LOGLIK_MAX_D = 255                # the widest state arp_pointwise_loglik takes (csrc/loglik.hip: kLlMaxD)
+PARETO_K_CAP = 0.7                # the k-hat above which PSIS is unreliable at any sample size (Vehtari et al. 2024)
+
+
+def upload_table(table, D, device):
+    """models.ObservationTable -> DeviceTable on `device`, checked against a state of D elements: every idx in [0, D),
+    every scale_idx in [-1, D) -- the kernel addresses its LDS tile with them."""
+    idx = np.ascontiguousarray(table.idx, np.int32)
+    w = np.ascontiguousarray(table.w, np.float32)
+    if idx.ndim != 2 or idx.shape != w.shape or idx.shape[1] < 1:
+        raise ValueError("observation table: idx and w of one [N, T] shape, T >= 1, are required")
+    N, T = idx.shape
+    y, ls = (np.ascontiguousarray(v, np.float32).reshape(-1) for v in (table.y, table.log_scale))
+    si = np.ascontiguousarray(table.scale_idx, np.int32).reshape(-1)
+    if not (y.size == N and ls.size == N and si.size == N):
+        raise ValueError("observation table: y, scale_idx and log_scale must have one entry per observation")
+    if N and (idx.min() < 0 or idx.max() >= D or si.min() < -1 or si.max() >= D):
+        raise ValueError("observation table: an index lies outside the state's %d elements" % D)
+    if int(table.kind) not in (0, 1):
+        raise ValueError("observation table: kind must be 0 (Normal) or 1 (Bernoulli-logit)")
+    dev = lambda a: torch.as_tensor(a, device=device)
+    return DeviceTable(int(table.kind), int(T), int(N), dev(idx), dev(w), dev(y), dev(si), dev(ls), y)
+
+
+def pointwise_loglik(trace, table, n0=0, n1=None, out=None):
+    """(ll, mask, n_masked) of `arp_pointwise_loglik` for a recorded CENTRED [S, C, D] float32 trace on the GPU and the
+    observations [n0, n1) of a DeviceTable: ll [n1 - n0, S C] float32, ll[n - n0, s C + c] the log-likelihood of
+    observation n at draw (s, c); mask [S C] uint8, 1 for a draw with a non-finite element (its ll entries are 0 and not
+    to be read); n_masked: their count, an int64 device scalar.  A leading or inner block of chains of a wider trace is
+    read in place, as gram_sums reads it.  out: an optional float32 device matrix of at least n1 - n0 rows whose rows are
+    at least S C apart, written in place (ll is then a view of it)."""
+    from . import _lib
+    x, S, Cn, D, row_stride = _lib.trace_view(trace, "pointwise_loglik")
+    n1 = table.N if n1 is None else int(n1)
+    n0 = int(n0)
+    if not 0 <= n0 < n1 <= table.N:
+        raise ValueError("pointwise_loglik: 0 <= n0 < n1 <= %d observations is required" % table.N)
+    R = S * Cn
+    if R == 0 or D == 0:
+        raise ValueError("pointwise_loglik: an empty trace")
+    if out is None:
+        out = torch.empty(n1 - n0, R, dtype=torch.float32, device=x.device)
+    if not (torch.is_tensor(out) and out.is_cuda and out.dtype == torch.float32 and out.dim() == 2 and out.shape[0] >= n1 - n0
+            and out.shape[1] >= R and out.stride(1) == 1 and (out.stride(0) >= R or out.shape[0] == 1)):
+        raise ValueError("pointwise_loglik: out must be a float32 [>= n1 - n0, >= S C] matrix on the GPU with unit column stride")
+    ll_stride = int(out.stride(0)) if out.shape[0] > 1 else max(R, int(out.shape[1]))
+    mask = torch.empty(R, dtype=torch.uint8, device=x.device)
+    n_masked = torch.zeros((), dtype=torch.int64, device=x.device)
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.lib().arp_pointwise_loglik(
+            _lib.ptr(x), S, Cn, D, row_stride, table.kind, _lib.ptr(table.idx), _lib.ptr(table.w), table.T, _lib.ptr(table.y),
+            _lib.ptr(table.scale_idx), _lib.ptr(table.log_scale), n0, n1, _lib.ptr(out), ll_stride, _lib.ptr(mask),
+            _lib.ptr(n_masked), _lib.stream()))
+    return out[:n1 - n0, :R], mask, n_masked
+
+
+def psis_workspace_bytes(N, R):
+    """Bytes of device workspace `psis_loo` takes for N observations of R draws; raises on a shape that is refused."""
+    from . import _lib
+    need = int(_lib.lib().arp_psis_workspace_bytes(int(N), int(R)))
+    if need <= 0:
+        raise ValueError("psis_loo: 1 <= N < 2^31 observations of 1 ... 2^24 draws are required")
+    return need
+
+
+def psis_loo(ll, mask=None):
+    """out [N, 8] float64 device tensor of `arp_psis_loo` for ll [N, R] float32 on the GPU (rows may be further apart
+    than R), columns PSIS_COLUMNS: per observation elpd_loo, the Pareto k-hat of its importance ratios, lppd, p_waic, the
+    tail length M, the cut-off (the largest shifted log ratio not in the tail), the fitted GPD's sigma and the draws
+    used.  mask: an optional [R] uint8 device tensor, draws with a non-zero entry are left out (pointwise_loglik's).
+    k-hat = +inf where no tail was fitted (M < 5, a constant tail, a non-finite ll).  The workspace is owned here."""
+    from . import _lib
+    if not (torch.is_tensor(ll) and ll.is_cuda and ll.dtype == torch.float32 and ll.dim() == 2):
+        raise ValueError("psis_loo: a float32 [N, R] matrix on the GPU is required (there is no CPU fallback)")
+    N, R = (int(v) for v in ll.shape)
+    if N == 0 or R == 0:
+        raise ValueError("psis_loo: an empty matrix")
+    if not (ll.stride(1) == 1 and (N == 1 or ll.stride(0) >= R)):
+        ll = ll.contiguous()
+    stride = int(ll.stride(0)) if N > 1 else R
+    if mask is not None and not (torch.is_tensor(mask) and mask.is_cuda and mask.dtype == torch.uint8 and mask.is_contiguous()
+                                 and tuple(mask.shape) == (R,)):
+        raise ValueError("psis_loo: mask must be a contiguous uint8 [R] tensor on the GPU")
+    out = torch.empty(N, 8, dtype=torch.float64, device=ll.device)
+    with torch.cuda.device(ll.device):
+        need = psis_workspace_bytes(N, R)
+        ws = torch.empty(need, dtype=torch.uint8, device=ll.device)
+        _lib.check(_lib.lib().arp_psis_loo(_lib.ptr(ll), N, R, stride, _lib.ptr(mask), _lib.ptr(out), _lib.ptr(ws), need,
+                                           _lib.stream()))
+        del ws
+    return out
+
+
+def pareto_k_threshold(R):
+    """min(1 - 1 / log10(R), 0.7): the k-hat up to which PSIS with R draws is reliable (Vehtari et al. 2024); NaN for R < 2."""
+    R = float(R)
+    return min(1.0 - 1.0 / np.log10(R), PARETO_K_CAP) if R > 1 else float("nan")
+
+
+def _se_of_sum(v):
+    """sqrt(N var_n(v)), the standard error of sum_n v_n over N observations (var with divisor N - 1); NaN for N < 2."""
+    v = np.asarray(v, np.float64).reshape(-1)
+    with np.errstate(invalid="ignore"):
+        return float(np.sqrt(v.size * np.var(v, ddof=1))) if v.size > 1 else float("nan")
+
+
+def loo_summary(elpd_loo_i, lppd_i, p_waic_i):
+    """The totals of the per-observation columns of `psis_loo` -> LooSummary; float64 numpy.  A non-finite column entry
+    carries through (a -inf elpd_loo_i makes elpd_loo -inf and its se NaN): nothing is skipped silently."""
+    e, l, p = (np.asarray(v.cpu() if torch.is_tensor(v) else v, np.float64).reshape(-1) for v in (elpd_loo_i, lppd_i, p_waic_i))
+    if not (e.size == l.size == p.size):
+        raise ValueError("loo_summary: columns of one length are required")
+    with np.errstate(invalid="ignore"):
+        w = l - p
+        return LooSummary(float(e.sum()), _se_of_sum(e), float((l - e).sum()), float(w.sum()), _se_of_sum(w), float(p.sum()))
+
+
+def loo_compare(a, b):
+    """(diff, se_diff) of two models' pointwise elpd over the SAME observations: diff = sum_n (a_n - b_n), se_diff =
+    sqrt(N var_n(a_n - b_n)) -- the paired comparison of Vehtari, Gelman, Gabry 2017.  a, b: dicts (or npz files) with
+    `elpd_loo_i` and `y`; refused unless N and the observed y agree, since the pairing is what the se rests on."""
+    ea, eb = (np.asarray(m["elpd_loo_i"], np.float64).reshape(-1) for m in (a, b))
+    ya, yb = (np.asarray(m["y"], np.float64).reshape(-1) for m in (a, b))
+    if ea.size != eb.size or ya.size != yb.size or ea.size != ya.size:
+        raise ValueError("loo_compare: the two models have different numbers of observations")
+    if not np.array_equal(ya, yb):
+        raise ValueError("loo_compare: the two models were not fitted to the same observations (y differs)")
+    with np.errstate(invalid="ignore"):
+        d = ea - eb
+        return float(d.sum()), _se_of_sum(d)

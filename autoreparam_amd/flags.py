@@ -87,6 +87,19 @@ _DEFS = [
                                           "coupling of every pair, which sees the funnels that linear correlation does not "
                                           "(geometry_* JSON keys, <base>_geometry.npz).  A second-order summary pooled over "
                                           "chains, not a local metric; unconverged chains inflate it.  Sharded jobs included."),
+    ("predictive_diagnostics", bool, False, "Sampling runs, with --convergence_diagnostics: judge the MODEL, not the sampler. "
+                                            "The pointwise log-likelihood of every observation at --loo_draws draws of the "
+                                            "chains split R-hat covers (arp_pointwise_loglik), then Pareto-smoothed "
+                                            "importance-sampling leave-one-out cross-validation and WAIC per observation "
+                                            "(arp_psis_loo; Vehtari, Gelman, Gabry 2017; Vehtari et al. 2024): elpd_loo, "
+                                            "p_loo, elpd_waic, p_waic with standard errors and the Pareto k-hat of every "
+                                            "observation (loo_*, elpd_*, pareto_k_* JSON keys, <base>_loo.npz; two models of "
+                                            "the same data are compared by analyze --loo_compare).  No r_eff correction, no "
+                                            "moment matching or refits for high k-hat, no K-fold.  One process only: a "
+                                            "sharded job writes null.  Refused for neals_funnel, which has no observations."),
+    ("loo_draws", int, 65536, "With --predictive_diagnostics: the draws per observation, taken as loo_draws // chains evenly "
+                              "spaced recorded steps of the device trace (at least one, at most all; the last step among "
+                              "them)."),
     ("lanes_per_chain", int, 0, "Lanes of a wave64 a chain is spread over (0 = automatic)."),
 ]
 

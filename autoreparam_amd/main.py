@@ -219,6 +219,8 @@ def _convergence_report(kernel_results, model_config, flags, dev):
     (A collective when ws > 1: every rank calls it.)"""
     trace = getattr(kernel_results, "trace", None)
     if not getattr(flags, "convergence_diagnostics", True) or trace is None:
+        if getattr(flags, "convergence_diagnostics", True) and getattr(flags, "predictive_diagnostics", False):
+            return _loo_null("no chain has its trace on the device"), None
         return {}, None
     clock = time.time()
     spec = model_config.model
@@ -277,7 +279,9 @@ def _convergence_report(kernel_results, model_config, flags, dev):
             (int(getattr(flags, "trajectory_profile", 0) or 0) != 0, TRAJECTORY_ARRAYS,      # (the sd: already all-reduced)
              lambda: _trajectory_report(kernel_results, trace, spec, flags, dev, whole.sd if streaming else split.sd)),
             (getattr(flags, "geometry_diagnostics", False), GEOMETRY_ARRAYS,
-             lambda: _geometry_report(kernel_results, trace, k, spec, flags, dev, split.mean))):
+             lambda: _geometry_report(kernel_results, trace, k, spec, flags, dev, split.mean)),
+            (getattr(flags, "predictive_diagnostics", False), LOO_ARRAYS,
+             lambda: _loo_report(kernel_results, trace, k, spec, flags))):
         if asked:
             side_keys, side_arrays = report()
             keys.update(side_keys)
@@ -625,6 +629,125 @@ def _geometry_report(kernel_results, trace, k, spec, flags, dev, pooled_mean):
     return keys, arrays
 
 
+LOO_ARRAYS = "loo/"                  # where _convergence_report leaves the arrays of <base>_loo.npz
+LOO_CHUNK_BYTES = 256 << 20          # a tile's [observations, draws] float32 log-likelihoods stay below this
+LOO_KEYS = ("loo_draws", "loo_draws_left_out", "loo_chains", "loo_steps", "loo_observations", "elpd_loo", "elpd_loo_se",
+            "p_loo", "elpd_waic", "elpd_waic_se", "p_waic", "pareto_k_max", "pareto_k_max_observation",
+            "pareto_k_threshold", "pareto_k_above_threshold", "loo_nonfinite_observations", "loo_time_sec")
+
+
+def check_predictive(flags):
+    """--predictive_diagnostics against the job, before anything runs: raises ValueError for a model without
+    observations (neals_funnel), whose pointwise log-likelihood does not exist."""
+    if getattr(flags, "predictive_diagnostics", False) and flags.model == "neals_funnel":
+        raise ValueError("--predictive_diagnostics: neals_funnel has no observations, so there is no pointwise "
+                         "log-likelihood to cross-validate")
+
+
+def loo_steps(S, k, draws):
+    """The recorded steps the predictive report takes its draws from: clamp(draws // k, 1, S) evenly spaced of S, the last
+    one among them (probe_steps, the rule of --energy_probe_steps, counted from the end: a single step is the last), and
+    no more than arp_psis_loo takes draws of."""
+    k, S = max(int(k), 1), int(S)
+    want = max(1, min(S, int(draws) // k))
+    return sorted(S - 1 - s for s in probe_steps(S, min(want, diagnostics.PSIS_MAX_DRAWS // k)))
+
+
+def loo_tile_rows(N, R, budget=None):
+    """Observations per tile of the predictive report: rows of R float32 within `budget` bytes (LOO_CHUNK_BYTES); at
+    least one."""
+    budget = LOO_CHUNK_BYTES if budget is None else int(budget)
+    return int(max(1, min(max(int(N), 1), budget // max(1, 4 * int(R)))))
+
+
+def _loo_null(why):
+    """Every key of the predictive report as null, with the one message that says why."""
+    util.print_("    PSIS-LOO / WAIC: not computed, {}".format(why))
+    return OrderedDict((key, None) for key in LOO_KEYS)
+
+
+def loo_keys(columns, R, left_out, n_chains, n_steps):
+    """The JSON keys of the predictive report from the [N, 8] per-observation columns of diagnostics.psis_loo (host
+    float64), the draws taken `R` and how many of them were left out; pure numpy."""
+    c = np.asarray(columns, np.float64).reshape(-1, 8)
+    used = int(R) - int(left_out)
+    total = diagnostics.loo_summary(c[:, 0], c[:, 2], c[:, 3])
+    threshold = diagnostics.pareto_k_threshold(used)
+    k_max, at = _nan_max(c[:, 1])
+    with np.errstate(invalid="ignore"):
+        above = int(np.sum(c[:, 1] > threshold)) if np.isfinite(threshold) else int(np.sum(~np.isfinite(c[:, 1])))
+    return OrderedDict([
+        ("loo_draws", used), ("loo_draws_left_out", int(left_out)), ("loo_chains", int(n_chains)), ("loo_steps", int(n_steps)),
+        ("loo_observations", int(c.shape[0])),
+        ("elpd_loo", _finite_or_none(total.elpd_loo)), ("elpd_loo_se", _finite_or_none(total.elpd_loo_se)),
+        ("p_loo", _finite_or_none(total.p_loo)), ("elpd_waic", _finite_or_none(total.elpd_waic)),
+        ("elpd_waic_se", _finite_or_none(total.elpd_waic_se)), ("p_waic", _finite_or_none(total.p_waic)),
+        ("pareto_k_max", _finite_or_none(k_max)), ("pareto_k_max_observation", at if at >= 0 else None),
+        ("pareto_k_threshold", _finite_or_none(threshold)), ("pareto_k_above_threshold", above),
+        ("loo_nonfinite_observations", int(np.sum(~np.isfinite(c[:, 0]))))])
+
+
+def _loo_report(kernel_results, trace, k, spec, flags):
+    """--predictive_diagnostics: how well does this MODEL predict an observation it has not seen?  Over the leading `k`
+    chains of the device trace -- the chains split R-hat covers -- and clamp(--loo_draws // k, 1, S) evenly spaced recorded
+    steps (loo_steps): the pointwise log-likelihood of every observation at every draw (diagnostics.pointwise_loglik, from
+    the model's observation table; the trace is centred, so one table serves every method), then PSIS-LOO and WAIC per
+    observation (diagnostics.psis_loo), in tiles of observations whose log-likelihoods stay within LOO_CHUNK_BYTES; the
+    per-observation columns are folded on the host (loo_keys).  A tail fit needs all draws of an observation in one place:
+    a sharded job (world size > 1) writes null, says so once, and enters no collective -- the rule of the rank reports.
+    No r_eff correction of the Monte-Carlo error, no moment matching or refits for high k-hat, no K-fold.
+    Returns (JSON keys, arrays of <base>_loo.npz or None)."""
+    import torch
+    if parallel.world()[1] > 1:
+        return _loo_null("the chains of a sharded job are on several devices (a tail fit needs all draws of an "
+                         "observation on one)"), None
+    clock = time.time()
+    S, _, D = (int(v) for v in trace.shape)
+    k = int(k) if S > 0 else 0
+    if k <= 0:
+        return _loo_null("no chain has its trace on the device"), None
+    if D > diagnostics.LOGLIK_MAX_D:
+        return _loo_null("the model has more than {} elements".format(diagnostics.LOGLIK_MAX_D)), None
+    steps = loo_steps(S, k, getattr(flags, "loo_draws", 65536))
+    if not steps:
+        return _loo_null("more than {} chains".format(diagnostics.PSIS_MAX_DRAWS)), None
+    table = diagnostics.upload_table(spec.observation_table(), D, trace.device)
+    draws = trace[torch.as_tensor(steps, device=trace.device), :k].contiguous()      # [len(steps), k, D]: a copy, D floats a draw
+    R, N = len(steps) * k, table.N
+    rows = loo_tile_rows(N, R)
+    ll_buffer = torch.empty(rows, R, dtype=torch.float32, device=trace.device)
+    columns, left_out = [], 0
+    for n0 in range(0, N, rows):
+        n1 = min(N, n0 + rows)
+        ll, mask, n_masked = diagnostics.pointwise_loglik(draws, table, n0, n1, out=ll_buffer)
+        columns.append(diagnostics.psis_loo(ll, mask).cpu().numpy())
+        left_out = int(n_masked.item())                                   # (the same draws for every tile)
+    del ll_buffer
+    c = np.concatenate(columns, axis=0)
+    keys = loo_keys(c, R, left_out, k, len(steps))
+    fmt = lambda v: "n/a" if v is None else "{:.4g}".format(v)
+    util.print_("    PSIS-LOO over {} observations, {} draws ({} step(s) of {} chains, {} left out): elpd_loo {} +/- {}, "
+                "p_loo {}; elpd_waic {} +/- {}; worst Pareto k-hat {} (observation {})".format(
+                    N, keys["loo_draws"], len(steps), k, left_out, fmt(keys["elpd_loo"]), fmt(keys["elpd_loo_se"]),
+                    fmt(keys["p_loo"]), fmt(keys["elpd_waic"]), fmt(keys["elpd_waic_se"]), fmt(keys["pareto_k_max"]),
+                    keys["pareto_k_max_observation"]))
+    if keys["pareto_k_above_threshold"]:
+        util.print_("    WARNING: Pareto k-hat above {} for {} of {} observations (not fitted ones included): their "
+                    "leave-one-out estimates are unreliable, the posterior hangs on them (which: <base>_loo.npz)".format(
+                        fmt(keys["pareto_k_threshold"]), keys["pareto_k_above_threshold"], N))
+    arrays = OrderedDict([("elpd_loo_i", c[:, 0]), ("pareto_k", c[:, 1]), ("lppd_i", c[:, 2]), ("p_waic_i", c[:, 3]),
+                          ("y", np.asarray(table.y_host, np.float32)), ("model", np.asarray(spec.name))])
+    keys["loo_time_sec"] = time.time() - clock
+    return keys, arrays
+
+
+def save_loo(file_path_base, arrays):
+    """`<base>_loo.npz` (build-specific, --predictive_diagnostics): per observation `elpd_loo_i`, `pareto_k` (+inf where no
+    tail was fitted), `lppd_i` and `p_waic_i` [N] float64; `y` [N], the observations themselves -- what
+    diagnostics.loo_compare pairs two models by -- and `model`, the model's name."""
+    np.savez(file_path_base + "_loo.npz", **arrays)
+
+
 def _rank_fit_chains(trace, k):
     """The largest of k, k/2, k/4, ... leading chains whose z-score trace and workspace fit the free device memory."""
     import torch
@@ -812,12 +935,13 @@ def save_geometry(file_path_base, arrays):
 
 def _save_diagnostics(file_path_base, arrays):
     """The side files of the convergence report: <base>_rhat.npz and, where the probes ran, <base>_energy.npz,
-    <base>_trajectory.npz and <base>_geometry.npz."""
+    <base>_trajectory.npz, <base>_geometry.npz and <base>_loo.npz."""
     if arrays is None:
         return
     # (tag _convergence_report left a side file's arrays under, its saver), in the order the files are written after _rhat.npz
     side = [(arrays.pop(tag, None), save) for tag, save in (
-        (GEOMETRY_ARRAYS, save_geometry), (ENERGY_ARRAYS, save_energy), (TRAJECTORY_ARRAYS, save_trajectory))]
+        (GEOMETRY_ARRAYS, save_geometry), (ENERGY_ARRAYS, save_energy), (TRAJECTORY_ARRAYS, save_trajectory),
+        (LOO_ARRAYS, save_loo))]
     save_rhat(file_path_base, arrays)
     for side_arrays, save in side:
         if side_arrays is not None:
@@ -1106,6 +1230,7 @@ def main(argv=None, flags=FLAGS, out=None):
         # util.make_variational_model_special (reference util.py:334-391) is outside the hot path this build covers;
         # accepting the flag silently would write a *_reparam_variational*.json that holds ordinary mean-field results
         raise NotImplementedError("--reparameterise_variational is not supported by this build (SURVEY.md section 2)")
+    check_predictive(flags)
     ws = int(os.environ.get("WORLD_SIZE", "1"))
     if ws > 1:
         # launched by torch.distributed.run: one rank per GPU, RCCL for the statistics exchange

@@ -22,6 +22,11 @@ ModelConfig = collections.namedtuple(
                     "make_to_partially_noncentered", "bijectors_fn"))
 
 
+# ModelSpec.observation_table: the likelihood of every observation as arp_pointwise_loglik reads it
+ObservationTable = collections.namedtuple("ObservationTable", ("kind", "idx", "w", "y", "scale_idx", "log_scale"))
+OBS_NORMAL, OBS_BERNOULLI = 0, 1     # include/autoreparam.h: ARP_OBS_NORMAL, ARP_OBS_BERNOULLI
+
+
 class ModelSpec(object):
     """Joint density of one model: id, latent parts in trace order, raw inputs."""
 
@@ -107,6 +112,70 @@ class ModelSpec(object):
         k = self.part_names.index(name)
         shared = name in (self.scalar_loc if which == "a" else self.scalar_scale)
         return () if shared else self.part_shapes[k]
+
+    def observation_table(self):
+        """One row per observation for `arp_pointwise_loglik` -> ObservationTable, or None for a model without data
+        (neals_funnel).  Every likelihood here is Normal or Bernoulli-logit over a linear predictor of the CENTRED latents,
+        eta_n = sum_t w[n][t] x[idx[n][t]], with the log-scale s_n = log_scale[n] + (x[scale_idx[n]] if scale_idx[n] >= 0):
+        kind (OBS_NORMAL / OBS_BERNOULLI), idx [N, T] int32, w [N, T] float32 (T the model's largest term count; padding
+        terms have w = 0, idx = 0), y [N] float32, scale_idx [N] int32, log_scale [N] float32.  A function of the data
+        alone: one table serves every parameterisation, since the trace is centred.  The reference's one-hot quirks are
+        restated as csrc/arp_build.hip restates them for the sufficient statistics: an index outside [0, depth) is an
+        all-zero one-hot row -- a term of weight 0 and, for electric's grade, scale_idx = -1 with log_scale = 0; radon_stddvs
+        refuses such a county as its builder does (the observation's scale would be 0)."""
+        r, off = self.raw, dict(zip(self.part_names, (int(o) for o in self.offsets[:-1])))
+        mid = self.model_id
+        if mid == _lib.MODEL_NEALS_FUNNEL:
+            return None
+
+        def term(base, index, depth, weight):
+            """(idx, w) columns of a one-hot term: x[base + index] * weight where 0 <= index < depth, weight 0 elsewhere."""
+            index = np.asarray(index).astype(np.int64).reshape(-1)
+            ok = (index >= 0) & (index < depth)
+            weight = np.broadcast_to(np.asarray(weight, np.float32), index.shape)
+            return np.where(ok, base + index, 0), np.where(ok, weight, np.float32(0.0))
+
+        y = np.asarray(r["y"], np.float32).reshape(-1)
+        N = y.size
+        kind, scale_idx, log_scale = OBS_NORMAL, np.full(N, -1), np.zeros(N, np.float32)
+        if mid == _lib.MODEL_EIGHT_SCHOOLS:
+            terms = [(off["theta"] + np.arange(N), np.ones(N, np.float32))]
+            log_scale = np.log(np.asarray(r["sigma"], np.float64))
+        elif mid in (_lib.MODEL_RADON, _lib.MODEL_RADON_STDDVS):
+            J = len(r["u"])
+            county = np.asarray(r["county"]).astype(np.int64).reshape(-1)
+            terms = [term(off["m"], county, J, 1.0), (np.full(N, off["b2"]), np.asarray(r["x"], np.float32))]
+            if mid == _lib.MODEL_RADON_STDDVS:
+                if np.any((county < 0) | (county >= J)):
+                    raise ValueError("radon_stddvs: county index out of range")
+                scale_idx = off["log_m_stddv"] + county
+        elif mid == _lib.MODEL_GERMAN_CREDIT:
+            kind = OBS_BERNOULLI
+            X = np.asarray(r["X"], np.float32)
+            F = X.shape[1]
+            terms = [(np.full(N, off["beta"] + f), X[:, f]) for f in range(F)]
+        elif mid == _lib.MODEL_ELECTION:
+            kind = OBS_BERNOULLI
+            terms = [term(off["a"], r["state"], int(r["n_state"]), 1.0),
+                     (np.full(N, off["b2"]), np.asarray(r["female"], np.float32)),
+                     (np.full(N, off["b1"]), np.asarray(r["black"], np.float32))]
+        elif mid == _lib.MODEL_ELECTRIC:
+            G = int(r["n_grade"])
+            grade = np.asarray(r["grade"]).astype(np.int64).reshape(-1)
+            terms = [term(off["a"], r["pair"], int(r["n_pair"]), 1.0),
+                     term(off["b"], grade, G, np.asarray(r["treatment"], np.float32))]
+            scale_idx = np.where((grade >= 0) & (grade < G), off["sigma_y"] + grade, -1)
+        elif mid == _lib.MODEL_TIME_SERIES:
+            terms = [(np.asarray([off["alpha%d" % t] for t in range(N)]), np.ones(N, np.float32)),
+                     (np.full(N, off["beta"]), np.asarray(r["x"], np.float32))]
+            log_scale = np.full(N, np.log(0.12))
+        else:
+            raise ValueError("unknown model id")
+        idx = np.ascontiguousarray(np.stack([np.asarray(i) for i, _ in terms], axis=1).astype(np.int32))
+        w = np.ascontiguousarray(np.stack([np.asarray(v, np.float32) for _, v in terms], axis=1).astype(np.float32))
+        idx[w == 0] = 0          # (a term of weight 0 reads element 0: padding and zero one-hot rows alike)
+        return ObservationTable(kind, idx, w, y, np.ascontiguousarray(scale_idx, dtype=np.int32),
+                                np.ascontiguousarray(log_scale, dtype=np.float32))
 
     def dataset(self):
         """(ctypes Dataset, keep-alive list) for arp_model_create."""

@@ -465,6 +465,44 @@ int64_t arp_gram_workspace_bytes(int64_t n_samples, int64_t n_chains, int32_t D)
 int arp_gram_sums(const float* x, int64_t n_samples, int64_t n_chains, int32_t D, int64_t row_stride,
                   const float* shift, double* sums, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* Pointwise log-likelihood of recorded draws (csrc/loglik.hip; needs no model handle): for a block of recorded steps of
+ * the CENTRED trace x [n_samples][n_chains][D] (rows `row_stride` floats apart, read in place, as arp_gram_sums reads it)
+ * and the observations [n0, n1) of an observation table in device memory,
+ *   eta_n = sum_t w[n * T + t] * x[idx[n * T + t]],   s_n = log_scale[n] + (scale_idx[n] >= 0 ? x[scale_idx[n]] : 0)
+ *   kind ARP_OBS_NORMAL:     ll = -0.5 * ((y[n] - eta_n) * exp(-s_n))^2 - s_n - 0.5 * log(2 pi)
+ *   kind ARP_OBS_BERNOULLI:  ll = y[n] * eta_n - (max(eta_n, 0) + log1p(exp(-|eta_n|)))
+ * it writes ll[(n - n0) * ll_stride + r] for draw r = step * n_chains + chain, mask[r] = 1 for a draw with a non-finite
+ * element among its D (0 otherwise; [n_samples * n_chains] bytes) and their count into *n_masked (device memory).  The ll
+ * entries of a masked draw are written as 0 by select and are not to be read.  float32, contraction off, the T terms in
+ * their order: with u = 2^-24, A = sum_t |w_t x_t|, z = (y - eta) exp(-s), to first order
+ *   |eta_dev - eta| <= T u A
+ *   Normal:     |ll_dev - ll| <= u (T A exp(-s) |z| + z^2 (5 + |s|) + 3 |s| + |ll|)
+ *   Bernoulli:  |ll_dev - ll| <= u (T A (|y| + 1) + |y eta| + 3 + softplus(eta) + |ll|)
+ * Nothing is read past the last element of the trace block; idx and scale_idx are clamped into [0, D).  Asynchronous.
+ * Refused before any launch: a NULL pointer, D < 1 or D > 255, a trace shape the other diagnostics refuse,
+ * row_stride < n_chains * D, an unknown kind, T < 1 or T > 4096, n0 < 0 or n1 <= n0, ll_stride < n_samples * n_chains. */
+enum { ARP_OBS_NORMAL = 0, ARP_OBS_BERNOULLI = 1 };
+int arp_pointwise_loglik(const float* x, int64_t n_samples, int64_t n_chains, int32_t D, int64_t row_stride,
+                         int32_t kind, const int32_t* idx, const float* w, int32_t T, const float* y,
+                         const int32_t* scale_idx, const float* log_scale, int64_t n0, int64_t n1, float* ll,
+                         int64_t ll_stride, uint8_t* mask, int64_t* n_masked, void* stream);
+
+/* PSIS-LOO and WAIC per observation (csrc/psis.hip; Vehtari, Gelman, Gabry 2017; Vehtari et al. 2024): from
+ * ll [n_obs][n_draws] (rows ll_stride floats apart) over the draws with mask[r] == 0 (mask NULL: all of them),
+ *   out[n][8] = {elpd_loo, pareto_k, lppd, p_waic, tail_len, cutoff, gpd_sigma, draws_used}      (float64)
+ * One workgroup per observation; everything after the float32 load is float64.  The tail is the
+ * M = min(floor(R' / 5), m), m^2 >= 9 R', largest log ratios -ll of the R' kept draws, found exactly by a radix select
+ * (ties across the cut-off are handled by count); M < 5, or a fit that is not finite, gives pareto_k = +inf and raw
+ * weights; a non-finite ll among the kept draws gives pareto_k = +inf and elpd_loo = -inf (NaN for a NaN).  No float
+ * atomics, fixed reduction orders: two calls give bitwise equal results.  tail_len, cutoff and draws_used are exact;
+ * |lppd - ref| <= (R' + 32) 2^-53 + 4 2^-53 max|ll|,  |p_waic - ref| <= (R' + 8) 2^-52 p_waic + R' (2^-52 max|ll|)^2.
+ * The workspace (arp_psis_workspace_bytes; 0 for a shape that is refused) is the caller's, 256-byte aligned.
+ * Asynchronous; device pointers.  Refused before any launch: a NULL ll or out, n_obs < 1, n_draws < 1 or above 2^24,
+ * ll_stride < n_draws, a workspace that is missing, too small or misaligned. */
+int64_t arp_psis_workspace_bytes(int64_t n_obs, int64_t n_draws);
+int arp_psis_loo(const float* ll, int64_t n_obs, int64_t n_draws, int64_t ll_stride, const uint8_t* mask, double* out,
+                 void* workspace, int64_t workspace_bytes, void* stream);
+
 /* Test hook: the step-size adaptation recurrence of the chain kernels on SCRIPTED log acceptance ratios
  * (tfp.mcmc.DualAveragingStepSizeAdaptation / SimpleStepSizeAdaptation as wired at inference.py:224-226, 288-306;
  * SURVEY.md 8c known answer (7)).  For each of `n` independent rows, applies the update after transitions
