@@ -196,6 +196,36 @@ def stream():
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
+def host64(x):
+    """A tensor (wherever it lives) or anything numpy reads, as float64 numpy."""
+    import numpy as np
+    import torch
+    return np.asarray(x.cpu() if torch.is_tensor(x) else x, np.float64)
+
+
+def call(device, fn, *args, workspace=None):
+    """check(fn(*args, stream())) with `device` current.  workspace=need, for an entry point that ends in (workspace,
+    workspace_bytes, stream): a uint8 tensor of `need` bytes on `device` is passed and lives until the call returns when
+    need > 0, (NULL, 0) otherwise.  Launches only: nothing here waits for the device or copies."""
+    import torch
+    with torch.cuda.device(device):
+        if workspace is not None:
+            need = int(workspace)
+            ws = torch.empty(need, dtype=torch.uint8, device=device) if need > 0 else None
+            args += (ptr(ws), need)
+        check(fn(*args, stream()))
+
+
+def device_operand(t, dtype, shape, who, name, dims):
+    """`t`, an optional device operand of `who`: None, or a contiguous `dtype` tensor of `shape` on the GPU (`dims`: the
+    shape as the message spells it); raises ValueError otherwise."""
+    import torch
+    if t is not None and not (torch.is_tensor(t) and t.is_cuda and t.dtype == dtype and t.is_contiguous()
+                              and tuple(t.shape) == tuple(shape)):
+        raise ValueError("%s: %s must be a contiguous %s [%s] tensor on the GPU" % (who, name, str(dtype)[len("torch."):], dims))
+    return t
+
+
 def trace_view(trace, who):
     """(x, S, C, D, row_stride) of a float32 [S, C, D] device trace as the diagnostics kernels read it: rows of C * D
     adjacent floats, `row_stride` floats apart.  A contiguous trace and a leading or inner block of chains of a wider one

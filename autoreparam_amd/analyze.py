@@ -16,6 +16,18 @@ import os
 import numpy as np
 
 
+def _fmt(v, spec="{:.4g}"):
+    return "n/a" if v is None else spec.format(v)
+
+
+def _secs(t):
+    return _fmt(t, "{:.3f}s")
+
+
+def _last(r, prefixes):
+    return {k: v[-1] for k, v in r.items() if k.startswith(prefixes)}
+
+
 def load(results_dir, model_name):
     out = {}
     for path in sorted(glob.glob(os.path.join(results_dir, model_name, "*.json"))):
@@ -86,31 +98,31 @@ def report_rhat(results, results_dir=None, model_name=None, threshold=1.01):
     for m, r in results.items():
         if "split_rhat_max" not in r:
             continue
-        fmt = lambda v: "n/a" if v is None else "{:.4f}".format(v)
+        fmt = lambda v: _fmt(v, "{:.4f}")
         ranked = "rank_rhat_max" in r                      # (--rank_normalized_rhat runs only)
         worst = max((v for v in (r["split_rhat_max"][-1], r["rhat_max_all_chains"][-1],
                                  r["rank_rhat_max"][-1] if ranked else None) if v is not None), default=None)
         rank_cols = "" if not ranked else " rank-normalised max {} (bulk {}, tail {}) over {} chains, {};".format(
             fmt(r["rank_rhat_max"][-1]), fmt(r["rank_rhat_bulk_max"][-1]), fmt(r["rank_rhat_tail_max"][-1]),
             r["rank_rhat_chains"][-1],
-            "n/a" if r["rank_rhat_time_sec"][-1] is None else "{:.3f}s".format(r["rank_rhat_time_sec"][-1]))
+            _secs(r["rank_rhat_time_sec"][-1]))
         line = "split R-hat max {} over {} chains; all chains (un-split) {};{} {:.3f}s : {}{}".format(
             fmt(r["split_rhat_max"][-1]), r["split_rhat_chains"][-1], fmt(r["rhat_max_all_chains"][-1]), rank_cols,
             r["diagnostics_time_sec"][-1], m, "" if worst is None or worst <= threshold else "   <-- NOT CONVERGED")
         lines.append(line)
         if "ess_bulk_min" in r:                            # (--bulk_tail_ess runs only)
-            num = lambda v: "n/a" if v is None else "{:.1f}".format(v)
+            num = lambda v: _fmt(v, "{:.1f}")
             lines.append("      multi-chain ESS min: bulk {}, tail {}, mean {}; largest MCSE of a mean {} sd; over {} chains, {}".format(
                 num(r["ess_bulk_min"][-1]), num(r["ess_tail_min"][-1]), num(r["ess_mean_min"][-1]),
                 fmt(r["mcse_mean_over_sd_max"][-1]), r["bulk_tail_ess_chains"][-1],
-                "n/a" if r["bulk_tail_ess_time_sec"][-1] is None else "{:.3f}s".format(r["bulk_tail_ess_time_sec"][-1])))
+                _secs(r["bulk_tail_ess_time_sec"][-1])))
         if "nested_rhat_max" in r:                         # (--superchain_size runs only)
             lines.append("      nested R-hat max {} over {} superchains of {} ({} chains, {} left out; stationary floor {}); "
                          "by step: first {}, last {}; {}".format(
                 fmt(r["nested_rhat_max"][-1]), r["nested_rhat_superchains"][-1], r["nested_rhat_superchain_size"][-1],
                 r["nested_rhat_chains"][-1], r["nested_rhat_left_out"][-1], fmt(r["nested_rhat_floor"][-1]),
                 fmt(r["nested_rhat_first_step_max"][-1]), fmt(r["nested_rhat_last_step_max"][-1]),
-                "n/a" if r["nested_rhat_time_sec"][-1] is None else "{:.3f}s".format(r["nested_rhat_time_sec"][-1])))
+                _secs(r["nested_rhat_time_sec"][-1])))
         path = os.path.join(results_dir or ".", model_name or "", m + "_rhat.npz")
         if os.path.exists(path):
             z = np.load(path)
@@ -129,18 +141,17 @@ def report_energy(results, results_dir=None, model_name=None):
     file): fresh-momentum trajectories from the run's final and recorded states, not a replay of the transitions the
     sampler took -- and, where <method>_energy.npz is at hand, where the divergent ones started."""
     lines = []
-    fmt = lambda v: "n/a" if v is None else "{:.4g}".format(v)
 
     def row(d):
         return ("{} of {} trajectories divergent (rate {}, {} not finite); energy error {} +/- {}; expected acceptance {}; "
                 "kinetic share of the energy variance {}").format(
-                    d["divergent_trajectories"], d["energy_probe_trajectories"], fmt(d["divergence_rate"]), d["energy_nonfinite"],
-                    fmt(d["energy_error_mean"]), fmt(d["energy_error_sd"]), fmt(d["energy_accept_prob"]),
-                    fmt(d["energy_kinetic_share"]))
+                    d["divergent_trajectories"], d["energy_probe_trajectories"], _fmt(d["divergence_rate"]), d["energy_nonfinite"],
+                    _fmt(d["energy_error_mean"]), _fmt(d["energy_error_sd"]), _fmt(d["energy_accept_prob"]),
+                    _fmt(d["energy_kinetic_share"]))
     for m, r in results.items():
         if "divergence_rate" not in r:
             continue
-        last = {k: v[-1] for k, v in r.items() if k.startswith(("divergen", "energy_"))}
+        last = _last(r, ("divergen", "energy_"))
         lines.append("{}; {:.3f}s : {}{}".format(row(last), last["energy_time_sec"], m,
                                                  "   <-- DIVERGENT" if last["divergent_trajectories"] else ""))
         for j, d in enumerate(last.get("energy_by_kernel") or []):
@@ -163,26 +174,25 @@ def report_trajectory(results, results_dir=None, model_name=None):
     trajectories with the step sizes the run adapted for its own count, not a replay of the sampler's transitions; a
     one-transition criterion, not an ESS."""
     lines = []
-    fmt = lambda v: "n/a" if v is None else "{:.4g}".format(v)
     for m, r in results.items():
         if "trajectory_leapfrogs_max" not in r:
             continue
-        last = {k: v[-1] for k, v in r.items() if k.startswith("trajectory_")}
+        last = _last(r, "trajectory_")
         kernels = last.get("trajectory_by_kernel") or [last]
         for j, d in enumerate(kernels):
             lines.append("{}{}: trajectory profile over {} trajectories, {:.3f}s: best {} leapfrog step(s), the run took {} "
                          "(efficiency against the best {})".format(
                              m, "" if len(kernels) == 1 else " kernel %d" % j, last["trajectory_probe_trajectories"],
-                             last["trajectory_time_sec"], fmt(d["trajectory_best_leapfrogs"]), d["trajectory_run_leapfrogs"],
-                             fmt(d["trajectory_efficiency_vs_best"])))
+                             last["trajectory_time_sec"], _fmt(d["trajectory_best_leapfrogs"]), d["trajectory_run_leapfrogs"],
+                             _fmt(d["trajectory_efficiency_vs_best"])))
             lines.append("    leapfrogs  accept  divergent  esjd_min (element)  per gradient")
             for l in range(last["trajectory_leapfrogs_max"]):
                 mark = "  <-- best" if d["trajectory_best_leapfrogs"] == l + 1 else ""
                 mark += "  <-- this run" if d["trajectory_run_leapfrogs"] == l + 1 else ""
                 lines.append("    {:9d}  {:>6}  {:>9}  {:>8} ({:d})  {:>12}{}".format(
-                    l + 1, fmt(d["trajectory_accept_prob"][l]), fmt(d["trajectory_divergence_rate"][l]),
-                    fmt(d["trajectory_esjd_min"][l]), d["trajectory_esjd_min_element"][l],
-                    fmt(d["trajectory_esjd_min_per_gradient"][l]), mark))
+                    l + 1, _fmt(d["trajectory_accept_prob"][l]), _fmt(d["trajectory_divergence_rate"][l]),
+                    _fmt(d["trajectory_esjd_min"][l]), d["trajectory_esjd_min_element"][l],
+                    _fmt(d["trajectory_esjd_min_per_gradient"][l]), mark))
     return lines
 
 
@@ -192,21 +202,20 @@ def report_geometry(results, results_dir=None, model_name=None):
     strongest scale coupling -- and, where <method>_geometry.npz is at hand, the elements that carry the stiff direction.
     A second-order summary pooled over chains, not a local metric; unconverged chains inflate it."""
     lines = []
-    fmt = lambda v: "n/a" if v is None else "{:.4g}".format(v)
     for m, r in results.items():
         if "geometry_rows" not in r:
             continue
-        last = {k: v[-1] for k, v in r.items() if k.startswith("geometry_")}
+        last = _last(r, "geometry_")
         kernels = last.get("geometry_by_kernel") or [last]
         for j, d in enumerate(kernels):
             lines.append("{}{}: condition number {} in the sampler's coordinates ({} scaled by its steps), {} centred; largest "
                          "|correlation| {} ({}); largest scale coupling {} ({}); {} draws of {} chains, {} left out; {}".format(
-                             m, "" if len(kernels) == 1 else " kernel %d" % j, fmt(d["geometry_condition_number"]),
-                             fmt(d["geometry_condition_number_step_scaled"]), fmt(last["geometry_condition_number_centred"]),
-                             fmt(d["geometry_max_abs_correlation"]), " ~ ".join(d["geometry_max_correlation_pair"] or ["n/a"]),
-                             fmt(d["geometry_max_scale_coupling"]), " -> ".join(d["geometry_max_scale_coupling_pair"] or ["n/a"]),
+                             m, "" if len(kernels) == 1 else " kernel %d" % j, _fmt(d["geometry_condition_number"]),
+                             _fmt(d["geometry_condition_number_step_scaled"]), _fmt(last["geometry_condition_number_centred"]),
+                             _fmt(d["geometry_max_abs_correlation"]), " ~ ".join(d["geometry_max_correlation_pair"] or ["n/a"]),
+                             _fmt(d["geometry_max_scale_coupling"]), " -> ".join(d["geometry_max_scale_coupling_pair"] or ["n/a"]),
                              last["geometry_rows"], last["geometry_chains"], last["geometry_rows_left_out"],
-                             "n/a" if last.get("geometry_time_sec") is None else "{:.3f}s".format(last["geometry_time_sec"])))
+                             _secs(last.get("geometry_time_sec"))))
         path = os.path.join(results_dir or ".", model_name or "", m + "_geometry.npz")
         if os.path.exists(path):
             z = np.load(path)
@@ -230,23 +239,21 @@ def report_loo(results):
     run of each file): elpd_loo and elpd_waic with their standard errors, the effective numbers of parameters, and the
     worst Pareto k-hat against its threshold.  No r_eff correction, no moment matching, no K-fold."""
     lines = []
-    fmt = lambda v: "n/a" if v is None else "{:.4g}".format(v)
     for m, r in results.items():
         if "loo_observations" not in r:
             continue
-        last = {k: r[k][-1] for k in r if k in ("elpd_loo", "elpd_loo_se", "p_loo", "elpd_waic", "elpd_waic_se", "p_waic",
-                                                "loo_time_sec") or k.startswith(("loo_", "pareto_k_"))}
+        last = _last(r, ("elpd_", "p_loo", "p_waic", "loo_", "pareto_k_"))
         if last["loo_observations"] is None:
             lines.append("{}: PSIS-LOO / WAIC not computed".format(m))
             continue
         lines.append("{}: elpd_loo {} +/- {}, p_loo {}; elpd_waic {} +/- {}, p_waic {}; worst Pareto k-hat {} (observation {}; "
                      "{} above {}); {} observations, {} draws of {} chains, {} left out, {} observation(s) not finite; {}".format(
-                         m, fmt(last["elpd_loo"]), fmt(last["elpd_loo_se"]), fmt(last["p_loo"]), fmt(last["elpd_waic"]),
-                         fmt(last["elpd_waic_se"]), fmt(last["p_waic"]), fmt(last["pareto_k_max"]),
-                         last["pareto_k_max_observation"], last["pareto_k_above_threshold"], fmt(last["pareto_k_threshold"]),
+                         m, _fmt(last["elpd_loo"]), _fmt(last["elpd_loo_se"]), _fmt(last["p_loo"]), _fmt(last["elpd_waic"]),
+                         _fmt(last["elpd_waic_se"]), _fmt(last["p_waic"]), _fmt(last["pareto_k_max"]),
+                         last["pareto_k_max_observation"], last["pareto_k_above_threshold"], _fmt(last["pareto_k_threshold"]),
                          last["loo_observations"], last["loo_draws"], last["loo_chains"], last["loo_draws_left_out"],
                          last["loo_nonfinite_observations"],
-                         "n/a" if last.get("loo_time_sec") is None else "{:.3f}s".format(last["loo_time_sec"])))
+                         _secs(last.get("loo_time_sec"))))
     return lines
 
 
@@ -282,22 +289,14 @@ def main(argv=None):
         if not results:
             continue
         print(" ******  {}  ****** ".format(name))
-        if args.elbos:
-            print("\n".join(report_elbos(results)) + "\n")
-        if args.reparams:
-            print("\n".join(report_reparams(results)) + "\n")
-        if args.ess:
-            print("\n".join(report_ess(results, args.normalize_times)) + "\n")
-        if args.rhat:
-            print("\n".join(report_rhat(results, root, name)) + "\n")
-        if args.energy:
-            print("\n".join(report_energy(results, root, name)) + "\n")
-        if args.trajectory:
-            print("\n".join(report_trajectory(results, root, name)) + "\n")
-        if args.geometry:
-            print("\n".join(report_geometry(results, root, name)) + "\n")
-        if args.loo:
-            print("\n".join(report_loo(results)) + "\n")
+        for flag, lines in (("elbos", lambda: report_elbos(results)), ("reparams", lambda: report_reparams(results)),
+                            ("ess", lambda: report_ess(results, args.normalize_times)),
+                            ("rhat", lambda: report_rhat(results, root, name)),
+                            ("energy", lambda: report_energy(results, root, name)),
+                            ("trajectory", lambda: report_trajectory(results, root, name)),
+                            ("geometry", lambda: report_geometry(results, root, name)), ("loo", lambda: report_loo(results))):
+            if getattr(args, flag):
+                print("\n".join(lines()) + "\n")
 
 
 if __name__ == "__main__":

@@ -29,6 +29,8 @@ import ctypes as C
 import numpy as np
 import torch
 
+from . import _lib
+
 # rhat, mean, sd: [D] float64 (NaN where W = 0 or fewer than two rows have a finite variance); rows = m, the number of
 # rows with a finite variance; constant_rows = how many of them never moved (variance exactly 0)
 Rhat = collections.namedtuple("Rhat", ["rhat", "mean", "sd", "rows", "constant_rows"])
@@ -82,7 +84,6 @@ def split_moments(trace, split=True):
     """(mean, var) [P, C, D] float32 device tensors of a recorded [S, C, D] float32 trace on the GPU: P = 2 halves of
     S // 2 draws (split) or P = 1.  A leading or inner block of chains of a wider trace is taken in place, as
     util.effective_sample_size does; the workspace of the long-trace route is owned here."""
-    from . import _lib
     x, S, Cn, D, row_stride = _lib.trace_view(trace, "split_moments")
     P = 2 if split else 1
     mean = torch.empty(P, Cn, D, dtype=torch.float32, device=trace.device)
@@ -92,35 +93,33 @@ def split_moments(trace, split=True):
     if S == 0:
         return mean.fill_(float("nan")), var.fill_(float("nan"))
     L = _lib.lib()
-    with torch.cuda.device(x.device):
-        need = int(L.arp_moments_workspace_bytes(S, Cn * D, int(bool(split))))
-        ws = torch.empty(need, dtype=torch.uint8, device=x.device) if need > 0 else None
-        _lib.check(L.arp_split_moments(_lib.ptr(x), S, Cn * D, row_stride, int(bool(split)), _lib.ptr(mean), _lib.ptr(var),
-                                       _lib.ptr(ws), need, _lib.stream()))
-        del ws
+    _lib.call(x.device, L.arp_split_moments, _lib.ptr(x), S, Cn * D, row_stride, int(bool(split)), _lib.ptr(mean),
+              _lib.ptr(var), workspace=L.arp_moments_workspace_bytes(S, Cn * D, int(bool(split))))
     return mean, var
+
+
+def _rows(moments):
+    """[..., D] moments as the contiguous float32 [rows, D] matrix the fold kernels read."""
+    return moments.reshape(-1, int(moments.shape[-1])).to(torch.float32).contiguous()
 
 
 def fold(mean, var):
     """The [5, D] float64 device tensor of `arp_moments_fold` over every leading axis of `mean`, `var` ([..., D] float32
     on the GPU): count, sum of mean, sum of mean^2, sum of var over the rows with a finite var, and how many have var == 0."""
-    from . import _lib
     if not (mean.is_cuda and mean.shape == var.shape):
         raise ValueError("fold: mean and var of one shape on the GPU are required (there is no CPU fallback)")
-    D = int(mean.shape[-1])
-    m = mean.reshape(-1, D).to(torch.float32).contiguous()
-    v = var.reshape(-1, D).to(torch.float32).contiguous()
+    m, v = _rows(mean), _rows(var)
+    D = int(m.shape[1])
     sums = torch.empty(5, D, dtype=torch.float64, device=mean.device)
     if D == 0:
         return sums
-    with torch.cuda.device(mean.device):
-        _lib.check(_lib.lib().arp_moments_fold(_lib.ptr(m), _lib.ptr(v), m.shape[0], D, _lib.ptr(sums), _lib.stream()))
+    _lib.call(mean.device, _lib.lib().arp_moments_fold, _lib.ptr(m), _lib.ptr(v), m.shape[0], D, _lib.ptr(sums))
     return sums
 
 
 def rhat_from_sums(sums, n):
     """The statistic from the (all-reduced) [5, D] sums of `fold` over rows of `n` draws each -> Rhat."""
-    s = np.asarray(sums.cpu() if torch.is_tensor(sums) else sums, np.float64)
+    s = _lib.host64(sums)
     n = float(n)
     with np.errstate(divide="ignore", invalid="ignore"):
         m = s[0]
@@ -141,7 +140,6 @@ def from_stats(mean, var):
 
 def _workspace_bytes(symbol, S, Cn, D, flag):
     """What the library's sizing function `symbol` asks for a [S, Cn, D] trace: 0 for an empty one, raises on a refusal."""
-    from . import _lib
     if S <= 0 or Cn <= 0 or D <= 0:
         return 0
     need = int(getattr(_lib.lib(), symbol)(S, Cn, D, int(bool(flag))))
@@ -163,26 +161,18 @@ def rank_normalize(trace, fold=False, probs=None, rank2=None):
     pooled draws, x_(k) with k = ceil(p N).  rank2: an optional contiguous [S, C, D] int32 device tensor that receives
     2 r - 1 as unsigned 32-bit words.  A leading or inner block of chains of a wider trace is taken in place, as
     split_moments takes it; the workspace is owned here."""
-    from . import _lib
     x, S, Cn, D, row_stride = _lib.trace_view(trace, "rank_normalize")
     probs = None if probs is None else [float(p) for p in probs]
     z = torch.empty(S, Cn, D, dtype=torch.float32, device=trace.device)
     median = torch.full((D,), float("nan"), dtype=torch.float32, device=trace.device)
     quantiles = None if probs is None else torch.full((len(probs), D), float("nan"), dtype=torch.float32, device=trace.device)
-    if rank2 is not None and not (rank2.is_cuda and rank2.dtype == torch.int32 and rank2.is_contiguous()
-                                  and tuple(rank2.shape) == (S, Cn, D)):
-        raise ValueError("rank_normalize: rank2 must be a contiguous int32 [S, C, D] tensor on the GPU")
+    _lib.device_operand(rank2, torch.int32, (S, Cn, D), "rank_normalize", "rank2", "S, C, D")
     if S == 0 or Cn == 0 or D == 0:
         return z, median, quantiles
-    L = _lib.lib()
-    with torch.cuda.device(x.device):
-        need = rank_workspace_bytes(S, Cn, D, fold)
-        ws = torch.empty(need, dtype=torch.uint8, device=x.device) if need > 0 else None
-        pr = (C.c_double * len(probs))(*probs) if probs else None
-        _lib.check(L.arp_rank_normalize(_lib.ptr(x), S, Cn, D, row_stride, int(bool(fold)), _lib.ptr(z), _lib.ptr(rank2),
-                                        _lib.ptr(median), pr, len(probs) if probs else 0,
-                                        _lib.ptr(quantiles if probs else None), _lib.ptr(ws), need, _lib.stream()))
-        del ws
+    pr = (C.c_double * len(probs))(*probs) if probs else None
+    _lib.call(x.device, _lib.lib().arp_rank_normalize, _lib.ptr(x), S, Cn, D, row_stride, int(bool(fold)), _lib.ptr(z),
+              _lib.ptr(rank2), _lib.ptr(median), pr, len(probs) if probs else 0, _lib.ptr(quantiles if probs else None),
+              workspace=rank_workspace_bytes(S, Cn, D, fold))
     return z, median, quantiles
 
 
@@ -199,25 +189,17 @@ def ess_multichain(trace, split=True, threshold=None, n_rho=0):
     threshold: an optional [D] float32 device tensor; the statistic is then that of the indicator x <= threshold[d],
     which is never written out.  A leading or inner block of chains of a wider trace is taken in place, as rank_normalize
     takes it; the workspace is owned here."""
-    from . import _lib
     x, S, Cn, D, row_stride = _lib.trace_view(trace, "ess_multichain")
     n_rho = int(n_rho)
-    if threshold is not None and not (threshold.is_cuda and threshold.dtype == torch.float32 and threshold.is_contiguous()
-                                      and tuple(threshold.shape) == (D,)):
-        raise ValueError("ess_multichain: threshold must be a contiguous float32 [D] tensor on the GPU")
+    _lib.device_operand(threshold, torch.float32, (D,), "ess_multichain", "threshold", "D")
     ess = torch.full((D,), float("nan"), dtype=torch.float32, device=trace.device)
     max_t = torch.zeros(D, dtype=torch.int32, device=trace.device)
     rho = torch.full((n_rho, D), float("nan"), dtype=torch.float32, device=trace.device) if n_rho > 0 else None
     if S == 0 or Cn == 0 or D == 0:
         return ess, max_t, rho
-    L = _lib.lib()
-    with torch.cuda.device(x.device):
-        need = ess_multichain_workspace_bytes(S, Cn, D, split)
-        ws = torch.empty(need, dtype=torch.uint8, device=x.device) if need > 0 else None
-        _lib.check(L.arp_ess_multichain(_lib.ptr(x), S, Cn, D, row_stride, int(bool(split)), _lib.ptr(threshold),
-                                        _lib.ptr(ess), _lib.ptr(max_t), _lib.ptr(rho), n_rho, _lib.ptr(ws), need,
-                                        _lib.stream()))
-        del ws
+    _lib.call(x.device, _lib.lib().arp_ess_multichain, _lib.ptr(x), S, Cn, D, row_stride, int(bool(split)),
+              _lib.ptr(threshold), _lib.ptr(ess), _lib.ptr(max_t), _lib.ptr(rho), n_rho,
+              workspace=ess_multichain_workspace_bytes(S, Cn, D, split))
     return ess, max_t, rho
 
 
@@ -235,12 +217,9 @@ def bulk_tail_ess(trace):
     hi = ess_multichain(trace, True, threshold=q[1].contiguous())[0]
     mean = ess_multichain(trace, True)[0]
     sd = rhat_from_sums(fold(*split_moments(trace, True)), S // 2).sd
-
-    def f64(t):
-        return t.cpu().numpy().astype(np.float64)
-    lo, hi, mean = f64(lo), f64(hi), f64(mean)
+    lo, hi, mean = _lib.host64(lo), _lib.host64(hi), _lib.host64(mean)
     with np.errstate(divide="ignore", invalid="ignore"):
-        return BulkTailEss(f64(bulk), np.minimum(lo, hi), mean, sd / np.sqrt(mean), sd)
+        return BulkTailEss(_lib.host64(bulk), np.minimum(lo, hi), mean, sd / np.sqrt(mean), sd)
 
 
 def rank_rhat(trace):
@@ -255,9 +234,9 @@ def rank_rhat(trace):
     z, _, _ = rank_normalize(trace, fold=True)
     tail = rhat_from_sums(fold(*split_moments(z, True)), S // 2)
     del z
-    q = q.cpu().numpy().astype(np.float64)
-    return RankRhat(bulk.rhat, tail.rhat, np.fmax(bulk.rhat, tail.rhat), median.cpu().numpy().astype(np.float64), q[0], q[1],
-                    bulk.rows, bulk.constant_rows)
+    q = _lib.host64(q)
+    return RankRhat(bulk.rhat, tail.rhat, np.fmax(bulk.rhat, tail.rhat), _lib.host64(median), q[0], q[1], bulk.rows,
+                    bulk.constant_rows)
 
 
 def nested_fold(mean, var, M):
@@ -265,18 +244,14 @@ def nested_fold(mean, var, M):
     GPU; leading axes are flattened): superchains of M adjacent chains.  Rows: the superchains that count (all M chains
     finite), sum of g, sum of g^2, sum of b, sum of w, superchains left out.  var = None: one draw per chain, every
     within-chain variance is 0."""
-    from . import _lib
     if not (mean.is_cuda and (var is None or (var.is_cuda and var.shape == mean.shape))):
         raise ValueError("nested_fold: mean (and var, of the same shape) on the GPU are required (there is no CPU fallback)")
-    D = int(mean.shape[-1])
-    m = mean.reshape(-1, D).to(torch.float32).contiguous()
-    v = None if var is None else var.reshape(-1, D).to(torch.float32).contiguous()
+    m, v = _rows(mean), None if var is None else _rows(var)
+    D = int(m.shape[1])
     sums = torch.empty(6, D, dtype=torch.float64, device=mean.device)
     if D == 0:
         return sums
-    with torch.cuda.device(mean.device):
-        _lib.check(_lib.lib().arp_moments_fold_nested(_lib.ptr(m), _lib.ptr(v), m.shape[0], D, int(M), _lib.ptr(sums),
-                                                      _lib.stream()))
+    _lib.call(mean.device, _lib.lib().arp_moments_fold_nested, _lib.ptr(m), _lib.ptr(v), m.shape[0], D, int(M), _lib.ptr(sums))
     return sums
 
 
@@ -292,14 +267,13 @@ def _nested(k, sg, sgg, sb, sw):
 
 def nested_rhat_from_sums(sums):
     """The statistic from the (all-reduced) [6, D] sums of `nested_fold` -> NestedRhat."""
-    s = np.asarray(sums.cpu() if torch.is_tensor(sums) else sums, np.float64)
+    s = _lib.host64(sums)
     rhat, excess, between, within = _nested(s[0], s[1], s[2], s[3], s[4])
     return NestedRhat(rhat, excess, between, within, s[0], s[5])
 
 
 def nested_step_workspace_bytes(S, Cn, D, M):
     """Bytes of device workspace `nested_step_sums` takes for a [S, Cn, D] trace (0: none)."""
-    from . import _lib
     return int(_lib.lib().arp_nested_step_workspace_bytes(S, Cn, D, int(M)))
 
 
@@ -308,24 +282,18 @@ def nested_step_sums(trace, M):
     every row s the one-draw-per-chain sums over superchains of M adjacent chains -- the superchains that count, sum of g,
     sum of g^2, sum of b.  A leading or inner block of chains of a wider trace is taken in place, as split_moments takes
     it; the workspace is owned here."""
-    from . import _lib
     x, S, Cn, D, row_stride = _lib.trace_view(trace, "nested_step_sums")
     sums = torch.zeros(4, S, D, dtype=torch.float64, device=trace.device)
     if S == 0 or Cn == 0 or D == 0:
         return sums
-    L = _lib.lib()
-    with torch.cuda.device(x.device):
-        need = nested_step_workspace_bytes(S, Cn, D, M)
-        ws = torch.empty(need, dtype=torch.uint8, device=x.device) if need > 0 else None
-        _lib.check(L.arp_nested_step_sums(_lib.ptr(x), S, Cn, D, row_stride, int(M), _lib.ptr(sums), _lib.ptr(ws), need,
-                                          _lib.stream()))
-        del ws
+    _lib.call(x.device, _lib.lib().arp_nested_step_sums, _lib.ptr(x), S, Cn, D, row_stride, int(M), _lib.ptr(sums),
+              workspace=nested_step_workspace_bytes(S, Cn, D, M))
     return sums
 
 
 def nested_rhat_by_step(sums4):
     """[S, D] float64 nested R-hat of every row from the (all-reduced) [4, S, D] sums of `nested_step_sums`."""
-    s = np.asarray(sums4.cpu() if torch.is_tensor(sums4) else sums4, np.float64)
+    s = _lib.host64(sums4)
     return _nested(s[0], s[1], s[2], s[3], np.zeros_like(s[3]))[0]
 
 
@@ -360,7 +328,7 @@ def energy_from_sums(sums, D):
     well-mixed chain: its numerator is the mean squared change of E between two transitions, which for an accurate
     integrator is that of a momentum resampling, E[(K' - K)^2] = 2 Var(K) = D, twice the numerator here.  Stan's customary
     threshold (0.3) is therefore not this figure's, and none is applied."""
-    s = np.asarray(sums.cpu() if torch.is_tensor(sums) else sums, np.float64).reshape(9)
+    s = _lib.host64(sums).reshape(9)
     rows, divergent, nonfinite = int(round(s[0])), int(round(s[1])), int(round(s[2]))
     good = rows - divergent
     nan = float("nan")
@@ -379,8 +347,7 @@ def profile_from_sums(sums, var):
     the min-ESS-per-gradient figure a set of tuning runs is compared by, not an ESS.  The trajectories behind the sums start
     from fresh momenta (no replay of the sampler's transitions) and use the step sizes the run adapted for its own leapfrog
     count; a run at another count would adapt others.  An empty or degenerate input gives NaN, never an exception."""
-    s = np.asarray(sums.cpu() if torch.is_tensor(sums) else sums, np.float64)
-    v = np.asarray(var.cpu() if torch.is_tensor(var) else var, np.float64).reshape(-1)
+    s, v = _lib.host64(sums), _lib.host64(var).reshape(-1)
     if s.ndim != 2 or s.shape[1] < JUMP_HEAD:
         s = np.zeros((0, JUMP_HEAD + v.size))
     Lmax, D = s.shape[0], s.shape[1] - JUMP_HEAD
@@ -414,7 +381,6 @@ def gram_sums(trace_or_matrix, shift=None):
     out.  shift: a [D] float32 device tensor or None (zeros).  Additive over rows, hence over calls and ranks that use
     one shift.  A leading or inner block of chains of a wider trace, and a matrix whose rows are further apart than D, are
     read in place; the workspace is owned here.  An empty input gives zeros."""
-    from . import _lib
     x = trace_or_matrix
     if torch.is_tensor(x) and x.dim() == 2:
         if not (x.is_cuda and x.dtype == torch.float32):
@@ -425,25 +391,19 @@ def gram_sums(trace_or_matrix, shift=None):
         S, Cn, row_stride = n, 1, (int(x.stride(0)) if n > 1 else D)
     else:
         x, S, Cn, D, row_stride = _lib.trace_view(x, "gram_sums")
-    if shift is not None and not (torch.is_tensor(shift) and shift.is_cuda and shift.dtype == torch.float32
-                                  and shift.is_contiguous() and tuple(shift.shape) == (D,)):
-        raise ValueError("gram_sums: shift must be a contiguous float32 [D] tensor on the GPU")
+    _lib.device_operand(shift, torch.float32, (D,), "gram_sums", "shift", "D")
     sums = torch.zeros(D + 2, D, dtype=torch.float64, device=x.device)
     if S == 0 or Cn == 0 or D == 0:
         return sums
     L = _lib.lib()
-    with torch.cuda.device(x.device):
-        need = int(L.arp_gram_workspace_bytes(S, Cn, D))
-        ws = torch.empty(need, dtype=torch.uint8, device=x.device) if need > 0 else None
-        _lib.check(L.arp_gram_sums(_lib.ptr(x), S, Cn, D, row_stride, _lib.ptr(shift), _lib.ptr(sums), _lib.ptr(ws), need,
-                                   _lib.stream()))
-        del ws
+    _lib.call(x.device, L.arp_gram_sums, _lib.ptr(x), S, Cn, D, row_stride, _lib.ptr(shift), _lib.ptr(sums),
+              workspace=L.arp_gram_workspace_bytes(S, Cn, D))
     return sums
 
 
 def _moments_from_sums(sums):
     """(n, left out, m = mean of u, cov) in float64 from [D + 2, D] sums; cov is NaN throughout for n < 2."""
-    s = np.asarray(sums.cpu() if torch.is_tensor(sums) else sums, np.float64)
+    s = _lib.host64(sums)
     if s.ndim != 2 or s.shape[0] != s.shape[1] + 2:
         raise ValueError("a [D + 2, D] array of sums is required")
     D = s.shape[1]
@@ -472,7 +432,7 @@ def geometry_from_sums(sums, eps0=None, shift=None):
     NaN and empty matrices, never an exception."""
     n, left, m, cov = _moments_from_sums(sums)
     D = m.size
-    sh = np.zeros(D) if shift is None else np.asarray(shift.cpu() if torch.is_tensor(shift) else shift, np.float64).reshape(D)
+    sh = np.zeros(D) if shift is None else _lib.host64(shift).reshape(D)
     var = np.diag(cov).copy()
     ok = np.isfinite(var) & (var > 0)
     kept, out = np.flatnonzero(ok), np.flatnonzero(~ok)
@@ -499,7 +459,7 @@ def geometry_from_sums(sums, eps0=None, shift=None):
         worst, pair = float(off[i, j]), (int(kept[min(i, j)]), int(kept[max(i, j)]))
     scaled, scaled_cond = None, float("nan")
     if eps0 is not None:
-        e = np.asarray(eps0.cpu() if torch.is_tensor(eps0) else eps0, np.float64).reshape(D)[kept]
+        e = _lib.host64(eps0).reshape(D)[kept]
         with np.errstate(divide="ignore", invalid="ignore"):
             a = c / np.outer(e, e)
         scaled = np.linalg.eigvalsh(a) if k and np.all(np.isfinite(a)) else np.full(k, np.nan)
@@ -520,7 +480,7 @@ def scale_coupling(rows, mean, sd):
     if 2 * D > GRAM_MAX_D:
         raise ValueError("scale_coupling: at most %d elements" % (GRAM_MAX_D // 2))
     x = rows.reshape(-1, D)
-    vec = lambda a: torch.as_tensor(np.asarray(a.cpu() if torch.is_tensor(a) else a, np.float64).reshape(D)).to(x.device)
+    vec = lambda a: torch.as_tensor(_lib.host64(a).reshape(D)).to(x.device)
     mean64, sd64 = vec(mean), vec(sd)
     ok = torch.isfinite(sd64) & (sd64 > 0) & torch.isfinite(mean64)
     m32 = torch.where(ok, mean64, torch.zeros_like(mean64)).to(torch.float32)
@@ -591,7 +551,6 @@ def pointwise_loglik(trace, table, n0=0, n1=None, out=None):
     to be read); n_masked: their count, an int64 device scalar.  A leading or inner block of chains of a wider trace is
     read in place, as gram_sums reads it.  out: an optional float32 device matrix of at least n1 - n0 rows whose rows are
     at least S C apart, written in place (ll is then a view of it)."""
-    from . import _lib
     x, S, Cn, D, row_stride = _lib.trace_view(trace, "pointwise_loglik")
     n1 = table.N if n1 is None else int(n1)
     n0 = int(n0)
@@ -608,17 +567,14 @@ def pointwise_loglik(trace, table, n0=0, n1=None, out=None):
     ll_stride = int(out.stride(0)) if out.shape[0] > 1 else max(R, int(out.shape[1]))
     mask = torch.empty(R, dtype=torch.uint8, device=x.device)
     n_masked = torch.zeros((), dtype=torch.int64, device=x.device)
-    with torch.cuda.device(x.device):
-        _lib.check(_lib.lib().arp_pointwise_loglik(
-            _lib.ptr(x), S, Cn, D, row_stride, table.kind, _lib.ptr(table.idx), _lib.ptr(table.w), table.T, _lib.ptr(table.y),
-            _lib.ptr(table.scale_idx), _lib.ptr(table.log_scale), n0, n1, _lib.ptr(out), ll_stride, _lib.ptr(mask),
-            _lib.ptr(n_masked), _lib.stream()))
+    _lib.call(x.device, _lib.lib().arp_pointwise_loglik, _lib.ptr(x), S, Cn, D, row_stride, table.kind, _lib.ptr(table.idx),
+              _lib.ptr(table.w), table.T, _lib.ptr(table.y), _lib.ptr(table.scale_idx), _lib.ptr(table.log_scale), n0, n1,
+              _lib.ptr(out), ll_stride, _lib.ptr(mask), _lib.ptr(n_masked))
     return out[:n1 - n0, :R], mask, n_masked
 
 
 def psis_workspace_bytes(N, R):
     """Bytes of device workspace `psis_loo` takes for N observations of R draws; raises on a shape that is refused."""
-    from . import _lib
     need = int(_lib.lib().arp_psis_workspace_bytes(int(N), int(R)))
     if need <= 0:
         raise ValueError("psis_loo: 1 <= N < 2^31 observations of 1 ... 2^24 draws are required")
@@ -631,7 +587,6 @@ def psis_loo(ll, mask=None):
     tail length M, the cut-off (the largest shifted log ratio not in the tail), the fitted GPD's sigma and the draws
     used.  mask: an optional [R] uint8 device tensor, draws with a non-zero entry are left out (pointwise_loglik's).
     k-hat = +inf where no tail was fitted (M < 5, a constant tail, a non-finite ll).  The workspace is owned here."""
-    from . import _lib
     if not (torch.is_tensor(ll) and ll.is_cuda and ll.dtype == torch.float32 and ll.dim() == 2):
         raise ValueError("psis_loo: a float32 [N, R] matrix on the GPU is required (there is no CPU fallback)")
     N, R = (int(v) for v in ll.shape)
@@ -640,16 +595,10 @@ def psis_loo(ll, mask=None):
     if not (ll.stride(1) == 1 and (N == 1 or ll.stride(0) >= R)):
         ll = ll.contiguous()
     stride = int(ll.stride(0)) if N > 1 else R
-    if mask is not None and not (torch.is_tensor(mask) and mask.is_cuda and mask.dtype == torch.uint8 and mask.is_contiguous()
-                                 and tuple(mask.shape) == (R,)):
-        raise ValueError("psis_loo: mask must be a contiguous uint8 [R] tensor on the GPU")
+    _lib.device_operand(mask, torch.uint8, (R,), "psis_loo", "mask", "R")
     out = torch.empty(N, 8, dtype=torch.float64, device=ll.device)
-    with torch.cuda.device(ll.device):
-        need = psis_workspace_bytes(N, R)
-        ws = torch.empty(need, dtype=torch.uint8, device=ll.device)
-        _lib.check(_lib.lib().arp_psis_loo(_lib.ptr(ll), N, R, stride, _lib.ptr(mask), _lib.ptr(out), _lib.ptr(ws), need,
-                                           _lib.stream()))
-        del ws
+    _lib.call(ll.device, _lib.lib().arp_psis_loo, _lib.ptr(ll), N, R, stride, _lib.ptr(mask), _lib.ptr(out),
+              workspace=psis_workspace_bytes(N, R))
     return out
 
 
@@ -669,7 +618,7 @@ def _se_of_sum(v):
 def loo_summary(elpd_loo_i, lppd_i, p_waic_i):
     """The totals of the per-observation columns of `psis_loo` -> LooSummary; float64 numpy.  A non-finite column entry
     carries through (a -inf elpd_loo_i makes elpd_loo -inf and its se NaN): nothing is skipped silently."""
-    e, l, p = (np.asarray(v.cpu() if torch.is_tensor(v) else v, np.float64).reshape(-1) for v in (elpd_loo_i, lppd_i, p_waic_i))
+    e, l, p = (_lib.host64(v).reshape(-1) for v in (elpd_loo_i, lppd_i, p_waic_i))
     if not (e.size == l.size == p.size):
         raise ValueError("loo_summary: columns of one length are required")
     with np.errstate(invalid="ignore"):

@@ -107,16 +107,14 @@ class Engine(object):
         n = x.shape[0]
         logp = torch.empty(n, dtype=torch.float32, device=self.device)
         grad = torch.empty_like(x)
-        with torch.cuda.device(self.device):
-            _lib.check(self._L.arp_logp_grad(self._h, which, _lib.ptr(x), n, _lib.ptr(logp), _lib.ptr(grad), lanes, _lib.stream()))
+        _lib.call(self.device, self._L.arp_logp_grad, self._h, which, _lib.ptr(x), n, _lib.ptr(logp), _lib.ptr(grad), lanes)
         return logp, grad
 
     def transform(self, x, which=0, to_centered=True):
         x = self._dev(x)
         out = torch.empty_like(x)
-        with torch.cuda.device(self.device):
-            _lib.check(self._L.arp_transform(self._h, which, 0 if to_centered else 1, _lib.ptr(x), x.shape[0],
-                                             _lib.ptr(out), _lib.stream()))
+        _lib.call(self.device, self._L.arp_transform, self._h, which, 0 if to_centered else 1, _lib.ptr(x), x.shape[0],
+                  _lib.ptr(out))
         return out
 
     def energy_probe(self, x, eps0, n_leapfrog, which=0, kappa=None, seed=0, row_offset=0, lanes=0, want_p=False,
@@ -130,10 +128,9 @@ class Engine(object):
         out = torch.empty(n, 4, dtype=torch.float32, device=self.device)
         p = torch.empty_like(x) if want_p else None
         q = torch.empty_like(x) if want_q else None
-        with torch.cuda.device(self.device):
-            _lib.check(self._L.arp_energy_probe(self._h, int(which), _lib.ptr(x), n, int(n_leapfrog), _lib.ptr(eps), _lib.ptr(kap),
-                                                int(seed) & 0xFFFFFFFFFFFFFFFF, int(row_offset), _lib.ptr(out), _lib.ptr(p), _lib.ptr(q),
-                                                int(lanes), _lib.stream()))
+        _lib.call(self.device, self._L.arp_energy_probe, self._h, int(which), _lib.ptr(x), n, int(n_leapfrog), _lib.ptr(eps),
+                  _lib.ptr(kap), int(seed) & 0xFFFFFFFFFFFFFFFF, int(row_offset), _lib.ptr(out), _lib.ptr(p), _lib.ptr(q),
+                  int(lanes))
         extra = tuple(t for t in (p, q) if t is not None)
         return (out,) + extra if extra else out
 
@@ -158,10 +155,9 @@ class Engine(object):
         energy = torch.empty(max(Lmax, 0) + 1, n, 2, dtype=torch.float32, device=self.device)
         path = torch.empty(max(Lmax, 0), n, self.D, dtype=torch.float32, device=self.device) if want_path else None
         p = torch.empty_like(x) if want_p else None
-        with torch.cuda.device(self.device):
-            _lib.check(self._L.arp_trajectory_probe(self._h, int(which), _lib.ptr(x), n, Lmax, _lib.ptr(eps), _lib.ptr(kap),
-                                                    int(seed) & 0xFFFFFFFFFFFFFFFF, int(row_offset), _lib.ptr(energy), _lib.ptr(path),
-                                                    1 if path_centred else 0, _lib.ptr(p), int(lanes), _lib.stream()))
+        _lib.call(self.device, self._L.arp_trajectory_probe, self._h, int(which), _lib.ptr(x), n, Lmax, _lib.ptr(eps),
+                  _lib.ptr(kap), int(seed) & 0xFFFFFFFFFFFFFFFF, int(row_offset), _lib.ptr(energy), _lib.ptr(path),
+                  1 if path_centred else 0, _lib.ptr(p), int(lanes))
         extra = tuple(t for t in (path, p) if t is not None)
         return (energy,) + extra if extra else energy
 
@@ -189,13 +185,10 @@ class Engine(object):
                                             row_offset=int(row_offset) + lo, lanes=lanes, want_path=True, path_centred=True)
             energy[:, lo:hi] = e
             part = torch.empty_like(sums)
-            with torch.cuda.device(self.device):
-                need = int(self._L.arp_jump_workspace_bytes(hi - lo, D, Lmax))
-                ws = torch.empty(need, dtype=torch.uint8, device=self.device) if need > 0 else None
-                _lib.check(self._L.arp_jump_sums(_lib.ptr(x0), _lib.ptr(path), _lib.ptr(e), hi - lo, D, Lmax, _lib.ptr(part),
-                                                 _lib.ptr(ws), need, _lib.stream()))
+            _lib.call(self.device, self._L.arp_jump_sums, _lib.ptr(x0), _lib.ptr(path), _lib.ptr(e), hi - lo, D, Lmax,
+                      _lib.ptr(part), workspace=self._L.arp_jump_workspace_bytes(hi - lo, D, Lmax))
             sums += part
-            del ws, path
+            del path
         return sums, energy
 
     # -- HMC ----------------------------------------------------------------
@@ -219,8 +212,7 @@ class Engine(object):
         io.eps0 = _lib.ptr(self._eps0)
         io.trace, io.trace_accept, io.stats = _lib.ptr(trace), _lib.ptr(trace_accept), _lib.ptr(stats)
         io.rec_accept_count = _lib.ptr(rec_accept)
-        with torch.cuda.device(self.device):
-            _lib.check(self._L.arp_hmc_run(self._h, which, C.byref(cfg), C.byref(io), _lib.stream()))
+        _lib.call(self.device, self._L.arp_hmc_run, self._h, which, C.byref(cfg), C.byref(io))
         state.step += int(n_steps)
         return state
 
@@ -246,8 +238,7 @@ class Engine(object):
         io.adapt1, io.accept_count1 = _lib.ptr(state.adapt1), _lib.ptr(state.accept_count1)
         io.eps0_1 = _lib.ptr(self._eps1)
         io.trace_accept1 = _lib.ptr(trace_accept1)
-        with torch.cuda.device(self.device):
-            _lib.check(self._L.arp_interleaved_run(self._h, C.byref(cfg), int(n_leapfrog_1), C.byref(io), _lib.stream()))
+        _lib.call(self.device, self._L.arp_interleaved_run, self._h, C.byref(cfg), int(n_leapfrog_1), C.byref(io))
         state.step += int(n_steps)
         return state
 
@@ -279,8 +270,7 @@ class Engine(object):
         ag = torch.as_tensor(np.asarray(a_group, np.int32), device=self.device) if a_group is not None else None
         bg = torch.as_tensor(np.asarray(b_group, np.int32), device=self.device) if b_group is not None else None
         io.a_group, io.b_group = _lib.ptr(ag), _lib.ptr(bg)
-        with torch.cuda.device(self.device):
-            _lib.check(self._L.arp_vi_run(self._h, which, C.byref(cfg), C.byref(io), _lib.stream()))
+        _lib.call(self.device, self._L.arp_vi_run, self._h, which, C.byref(cfg), C.byref(io))
         return (elbo, prior) if return_prior else elbo
 
 
@@ -334,8 +324,7 @@ class Engine(object):
         cfg.n_steps, cfg.step_base = int(n_steps), int(step_base)
         cfg.adapt_kind, cfg.n_adapt = int(kind), int(n_adapt)
         cfg.adapt_target, cfg.adapt_rate = float(target), float(rate)
-        with torch.cuda.device(self.device):
-            _lib.check(self._L.arp_adapt_probe(C.byref(cfg), _lib.ptr(la), n, _lib.ptr(adapt), _lib.ptr(out), _lib.stream()))
+        _lib.call(self.device, self._L.arp_adapt_probe, C.byref(cfg), _lib.ptr(la), n, _lib.ptr(adapt), _lib.ptr(out))
         return out
 
 
@@ -346,9 +335,8 @@ def clock_probe(device, ms=10.0):
     dev = torch.device(device)
     out = torch.zeros(3, dtype=torch.int64, device=dev)
     iters = max(1, int(ms * 1e-3 / (64 * 2 * 4.43 / 2.4e9)))       # 64 packed FMAs per iteration, two waves per SIMD
-    with torch.cuda.device(dev):
-        _lib.check(_lib.lib().arp_clock_probe(iters, C.c_void_p(out.data_ptr()), _lib.stream()))
-        torch.cuda.synchronize(dev)
+    _lib.call(dev, _lib.lib().arp_clock_probe, iters, _lib.ptr(out))
+    torch.cuda.synchronize(dev)
     cyc, ticks = int(out[0].item()), int(out[1].item())
     return (cyc / ticks) * 0.1 if ticks > 0 else None
 

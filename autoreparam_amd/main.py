@@ -19,7 +19,7 @@ from collections import OrderedDict
 
 import numpy as np
 
-from . import diagnostics, graphs, inference, models, parallel, util
+from . import _lib, diagnostics, graphs, inference, models, parallel, util
 from .flags import FLAGS
 
 
@@ -209,6 +209,25 @@ def _nan_max(x):
     return float(x[at]), at
 
 
+def _reduced(blocks, dev):
+    """The `blocks` (arrays, tensors or scalars), summed over the ranks of the job in ONE all-reduce of their ravelled
+    concatenation, as float64 numpy arrays of their own shapes."""
+    local = [_lib.host64(b) for b in blocks]
+    t = parallel.all_reduce_sum(np.concatenate([b.ravel() for b in local]), dev).cpu().numpy()
+    return [part.reshape(b.shape) for part, b in zip(np.split(t, np.cumsum([b.size for b in local])[:-1]), local)]
+
+
+def _by_part(spec, arrays, rows):
+    """arrays["<key>/<part>"] = that latent part of the flat [..., D] array, for every (key, flat) of `rows`."""
+    for key, flat in rows:
+        for name, part in zip(spec.part_names, spec.unpack(flat)):
+            arrays["%s/%s" % (key, name)] = part
+
+
+def _fmt(v):
+    return "n/a" if v is None else "{:.4g}".format(v)
+
+
 def _convergence_report(kernel_results, model_config, flags, dev):
     """Build-specific (--convergence_diagnostics): do the chains of this run agree with each other?  Split R-hat of every
     element over the chains whose trace is on the device (all of them in a whole-trace run; the --ess_chains subset of a
@@ -234,13 +253,10 @@ def _convergence_report(kernel_results, model_config, flags, dev):
 
     def reduced(sums, count):
         # the five [D] vectors and the chain count in ONE all-reduce per statistic
-        t = parallel.all_reduce_sum(np.concatenate([sums.cpu().numpy().ravel(), [float(count)]]), dev).cpu().numpy()
-        return t[:-1].reshape(5, D), int(round(t[-1]))
+        sums, count = _reduced([sums, float(count)], dev)
+        return sums, int(round(float(count)))
 
-    def by_part(arrays, rows):
-        for key, flat in rows:
-            for name, part in zip(spec.part_names, spec.unpack(flat)):
-                arrays["%s/%s" % (key, name)] = part
+    by_part = lambda arrays, rows: _by_part(spec, arrays, rows)
 
     none = trace.new_empty(0, D)
     local = diagnostics.fold(*diagnostics.split_moments(trace[:, :k], split=True)) if k > 0 else diagnostics.fold(none, none)
@@ -369,10 +385,9 @@ def _energy_report(kernel_results, trace, spec, flags, dev):
                               torch.full((bad.numel(), 1), float(s), dtype=torch.float64, device=bad.device),
                               torch.full((bad.numel(), 1), float(j), dtype=torch.float64, device=bad.device)], dim=1)
             where.append(rows.cpu().numpy())
-    sums = [total.cpu().numpy() for total in totals]
-    t = parallel.all_reduce_sum(np.concatenate(sums), dev).cpu().numpy().reshape(len(ctx.kernels), 9)
+    t = _reduced(totals, dev)
     by_kernel = [diagnostics.energy_from_sums(row, D) for row in t]
-    pooled = diagnostics.energy_from_sums(t.sum(axis=0), D)
+    pooled = diagnostics.energy_from_sums(np.sum(t, axis=0), D)
     keys = _energy_summary(pooled)
     if len(by_kernel) > 1:
         keys["energy_by_kernel"] = [_energy_summary(e) for e in by_kernel]
@@ -392,8 +407,7 @@ def _energy_report(kernel_results, trace, spec, flags, dev):
     for j, err in enumerate(errors):
         whole = parallel.all_gather_chains(np.ascontiguousarray(err.T), int(flags.num_chains), dev).cpu().numpy().T
         arrays["energy_error" if j == 0 else "energy_error_%d" % j] = np.ascontiguousarray(whole)
-    for name, part in zip(spec.part_names, spec.unpack(all_where[:, :D].astype(np.float32))):
-        arrays["divergent_where/%s" % name] = part
+    _by_part(spec, arrays, (("divergent_where", all_where[:, :D].astype(np.float32)),))
     arrays["divergent_chain"] = all_where[:, D].astype(np.int64)
     arrays["divergent_step"] = all_where[:, D + 1].astype(np.int64)
     arrays["divergent_kernel"] = all_where[:, D + 2].astype(np.int64)
@@ -445,10 +459,8 @@ def _trajectory_report(kernel_results, trace, spec, flags, dev, pooled_sd):
         part, _ = eng.trajectory_sums(x, kn.eps0, Lmax, which=kn.which, kappa=kn.kappa[:n], seed=seed + j,
                                       row_offset=row_offset, lanes=flags.lanes_per_chain)
         totals[j] += part.to(totals[j].device)
-    sums = [total.cpu().numpy().ravel() for total in totals]
-    t = parallel.all_reduce_sum(np.concatenate(sums), dev).cpu().numpy().reshape(len(ctx.kernels), Lmax, 5 + D)
     var = np.asarray(pooled_sd, np.float64) ** 2
-    profiles = [diagnostics.profile_from_sums(row, var) for row in t]
+    profiles = [diagnostics.profile_from_sums(row, var) for row in _reduced(totals, dev)]
     summaries = [_trajectory_summary(p, kn.n_leapfrog) for p, kn in zip(profiles, ctx.kernels)]
     keys = OrderedDict([("trajectory_leapfrogs_max", Lmax),
                         ("trajectory_probe_trajectories", int(round(sum(float(p.rows[0]) for p in profiles))))])
@@ -466,8 +478,7 @@ def _trajectory_report(kernel_results, trace, spec, flags, dev, pooled_sd):
     arrays = OrderedDict(leapfrogs=np.arange(1, Lmax + 1, dtype=np.int64))
     for j, p in enumerate(profiles):
         tag = "" if j == 0 else "_%d" % j
-        for name, part in zip(spec.part_names, spec.unpack(np.ascontiguousarray(p.esjd))):
-            arrays["esjd%s/%s" % (tag, name)] = part
+        _by_part(spec, arrays, (("esjd" + tag, np.ascontiguousarray(p.esjd)),))
         arrays["accept_prob" + tag] = np.asarray(p.accept_prob, np.float64)
         arrays["divergence_rate" + tag] = np.asarray(p.divergence_rate, np.float64)
     keys["trajectory_time_sec"] = time.time() - clock
@@ -571,10 +582,8 @@ def _geometry_report(kernel_results, trace, k, spec, flags, dev, pooled_mean):
         rows = chunk.reshape(-1, D)
         for j, kn in enumerate(kernels):
             total[1 + j] += diagnostics.gram_sums(eng.transform(rows, which=kn.which, to_centered=False), shifts[j])
-    flat = np.concatenate([t.cpu().numpy().ravel() for t in total] + [[float(k)]])
-    flat = parallel.all_reduce_sum(flat, dev).cpu().numpy()
-    n_chains = int(round(flat[-1]))
-    sums = flat[:-1].reshape(1 + nk, D + 2, D)
+    sums = _reduced(total + [float(k)], dev)
+    n_chains = int(round(float(sums.pop())))
     if sums[0][D + 1, 0] < 1:                      # no chain with a device trace anywhere in the job
         null["geometry_time_sec"] = time.time() - clock
         return null, None
@@ -590,8 +599,7 @@ def _geometry_report(kernel_results, trace, k, spec, flags, dev, pooled_mean):
             for j, kn in enumerate(kernels):
                 x = eng.transform(rows, which=kn.which, to_centered=False)
                 total2[j] += diagnostics.scale_coupling(x, geo[j].mean, geo[j].sd)
-        flat2 = parallel.all_reduce_sum(np.concatenate([t.cpu().numpy().ravel() for t in total2]), dev).cpu().numpy()
-        Ks = [diagnostics.coupling_from_sums(s) for s in flat2.reshape(nk, 2 * D + 2, 2 * D)]
+        Ks = [diagnostics.coupling_from_sums(s) for s in _reduced(total2, dev)]
 
     names = element_names(spec)
     summaries = [_geometry_summary(g, K, names) for g, K in zip(geo, Ks)]
@@ -602,15 +610,14 @@ def _geometry_report(kernel_results, trace, k, spec, flags, dev, pooled_mean):
     keys["geometry_condition_number_centred"] = _finite_or_none(centred.condition_number)
     if nk > 1:
         keys["geometry_by_kernel"] = summaries
-    fmt = lambda v: "n/a" if v is None else "{:.4g}".format(v)
     for j, d in enumerate(summaries):
         util.print_("    posterior geometry{} over {} draws of {} chains: condition number of the correlation matrix {} in the "
                     "sampler's coordinates ({} scaled by its steps), {} centred; largest |correlation| {} ({}); largest scale "
                     "coupling {} ({})".format(
                         "" if nk == 1 else " of kernel %d" % j, keys["geometry_rows"], n_chains,
-                        fmt(d["geometry_condition_number"]), fmt(d["geometry_condition_number_step_scaled"]),
-                        fmt(keys["geometry_condition_number_centred"]), fmt(d["geometry_max_abs_correlation"]),
-                        " ~ ".join(d["geometry_max_correlation_pair"] or ["n/a"]), fmt(d["geometry_max_scale_coupling"]),
+                        _fmt(d["geometry_condition_number"]), _fmt(d["geometry_condition_number_step_scaled"]),
+                        _fmt(keys["geometry_condition_number_centred"]), _fmt(d["geometry_max_abs_correlation"]),
+                        " ~ ".join(d["geometry_max_correlation_pair"] or ["n/a"]), _fmt(d["geometry_max_scale_coupling"]),
                         " -> ".join(d["geometry_max_scale_coupling_pair"] or ["n/a"])))
     arrays = OrderedDict(elements=np.asarray(names))
     arrays["correlation_centred"] = _full(centred.correlation, centred.kept, D)
@@ -622,9 +629,7 @@ def _geometry_report(kernel_results, trace, k, spec, flags, dev, pooled_mean):
         arrays["eigenvalues" + tag] = g.eigenvalues
         arrays["step_scaled_eigenvalues" + tag] = g.step_scaled_eigenvalues
         arrays["scale_coupling" + tag] = np.full((D, D), np.nan) if K is None else K
-        for key, flat_d in (("stiffest_direction", g.stiffest_direction), ("softest_direction", g.softest_direction)):
-            for name, part in zip(spec.part_names, spec.unpack(flat_d)):
-                arrays["%s%s/%s" % (key, tag, name)] = part
+        _by_part(spec, arrays, (("stiffest_direction" + tag, g.stiffest_direction), ("softest_direction" + tag, g.softest_direction)))
     keys["geometry_time_sec"] = time.time() - clock
     return keys, arrays
 
@@ -725,16 +730,15 @@ def _loo_report(kernel_results, trace, k, spec, flags):
     del ll_buffer
     c = np.concatenate(columns, axis=0)
     keys = loo_keys(c, R, left_out, k, len(steps))
-    fmt = lambda v: "n/a" if v is None else "{:.4g}".format(v)
     util.print_("    PSIS-LOO over {} observations, {} draws ({} step(s) of {} chains, {} left out): elpd_loo {} +/- {}, "
                 "p_loo {}; elpd_waic {} +/- {}; worst Pareto k-hat {} (observation {})".format(
-                    N, keys["loo_draws"], len(steps), k, left_out, fmt(keys["elpd_loo"]), fmt(keys["elpd_loo_se"]),
-                    fmt(keys["p_loo"]), fmt(keys["elpd_waic"]), fmt(keys["elpd_waic_se"]), fmt(keys["pareto_k_max"]),
+                    N, keys["loo_draws"], len(steps), k, left_out, _fmt(keys["elpd_loo"]), _fmt(keys["elpd_loo_se"]),
+                    _fmt(keys["p_loo"]), _fmt(keys["elpd_waic"]), _fmt(keys["elpd_waic_se"]), _fmt(keys["pareto_k_max"]),
                     keys["pareto_k_max_observation"]))
     if keys["pareto_k_above_threshold"]:
         util.print_("    WARNING: Pareto k-hat above {} for {} of {} observations (not fitted ones included): their "
                     "leave-one-out estimates are unreliable, the posterior hangs on them (which: <base>_loo.npz)".format(
-                        fmt(keys["pareto_k_threshold"]), keys["pareto_k_above_threshold"], N))
+                        _fmt(keys["pareto_k_threshold"]), keys["pareto_k_above_threshold"], N))
     arrays = OrderedDict([("elpd_loo_i", c[:, 0]), ("pareto_k", c[:, 1]), ("lppd_i", c[:, 2]), ("p_waic_i", c[:, 3]),
                           ("y", np.asarray(table.y_host, np.float32)), ("model", np.asarray(spec.name))])
     keys["loo_time_sec"] = time.time() - clock
@@ -748,14 +752,20 @@ def save_loo(file_path_base, arrays):
     np.savez(file_path_base + "_loo.npz", **arrays)
 
 
-def _rank_fit_chains(trace, k):
-    """The largest of k, k/2, k/4, ... leading chains whose z-score trace and workspace fit the free device memory."""
+def _fit_chains(trace, k, workspace_bytes):
+    """The largest of k, k/2, k/4, ... leading chains whose z-score trace and the `workspace_bytes(S, k, D)` next to it
+    fit the free device memory."""
     import torch
     S, _, D = (int(v) for v in trace.shape)
     free = torch.cuda.mem_get_info(trace.device)[0]
-    while k > 0 and S * k * D * 4 + diagnostics.rank_workspace_bytes(S, k, D, True) > free:
+    while k > 0 and S * k * D * 4 + workspace_bytes(S, k, D) > free:
         k //= 2
     return k
+
+
+def _rank_fit_chains(trace, k):
+    """_fit_chains for the rank report: the z-score trace and the rank workspace."""
+    return _fit_chains(trace, k, lambda S, k, D: diagnostics.rank_workspace_bytes(S, k, D, True))
 
 
 def _rank_report(trace, k, spec, arrays, by_part):
@@ -813,9 +823,8 @@ def _nested_report(trace, moments, M, dev, arrays, by_part):
         mean, var = (m[0] for m in diagnostics.split_moments(trace, split=False))
     n_local = int(mean.shape[0])
     local = diagnostics.nested_fold(mean, None if S == 1 else var, M)
-    t = parallel.all_reduce_sum(np.concatenate([local.cpu().numpy().ravel(), [float(n_local)]]), dev).cpu().numpy()
-    whole = diagnostics.nested_rhat_from_sums(t[:-1].reshape(6, D))
-    n_chains = int(round(t[-1]))
+    sums, n_chains = _reduced([local, float(n_local)], dev)
+    whole, n_chains = diagnostics.nested_rhat_from_sums(sums), int(round(float(n_chains)))
     top, at = _nan_max(whole.rhat)
     by_part(arrays, (("nested_rhat", whole.rhat),))
     counted = int(whole.superchains.min()) if D else 0
@@ -828,18 +837,18 @@ def _nested_report(trace, moments, M, dev, arrays, by_part):
 
     # the profile: one draw per chain at every recorded step, over the leading whole superchains of the device trace
     kk = (C_local // M) * M
-    local4 = diagnostics.nested_step_sums(trace[:, :kk], M).cpu().numpy() if kk > 0 else np.zeros((4, S, D))
-    t = parallel.all_reduce_sum(np.concatenate([local4.ravel(), [float(kk // M)]]), dev).cpu().numpy()
+    sums4, n_super = _reduced([diagnostics.nested_step_sums(trace[:, :kk], M) if kk > 0 else np.zeros((4, S, D)),
+                               float(kk // M)], dev)
+    n_super = int(round(float(n_super)))
     first = last = float("nan")
-    if int(round(t[-1])) >= 2 and S > 0:
-        sums4 = t[:-1].reshape(4, S, D)
+    if n_super >= 2 and S > 0:
         by_step = diagnostics.nested_rhat_by_step(sums4)                       # [S, D]: not saved (tens of MB for a kept trace)
         ok = np.isfinite(by_step)
         arrays["nested_rhat_by_step_element"] = np.where(ok.any(axis=1), np.where(ok, by_step, -np.inf).argmax(axis=1), -1)
         arrays["nested_rhat_by_step"] = np.where(ok.any(axis=1), np.where(ok, by_step, -np.inf).max(axis=1), np.nan)
         first, last = float(arrays["nested_rhat_by_step"][0]), float(arrays["nested_rhat_by_step"][-1])
         util.print_("    nested R-hat by step over {} superchains (one draw per chain): first {:.4f}, last {:.4f}".format(
-            int(round(t[-1])), first, last))
+            n_super, first, last))
         with np.errstate(invalid="ignore"):
             alarm = alarm or bool(np.any(by_step[0] ** 2 - 1.0 > nested_warn_level(sums4[0, 0], M)))
     else:
@@ -858,15 +867,10 @@ ESS_PER_CHAIN_WARN = 100    # Stan's rule: bulk- and tail-ESS of at least 100 pe
 
 
 def _bulk_tail_fit_chains(trace, k):
-    """The largest of k, k/2, k/4, ... leading chains whose z-score trace and workspaces fit the free device memory (the
-    rank workspace and the ESS workspace are not alive together: the larger counts)."""
-    import torch
-    S, _, D = (int(v) for v in trace.shape)
-    free = torch.cuda.mem_get_info(trace.device)[0]
-    while k > 0 and S * k * D * 4 + max(diagnostics.rank_workspace_bytes(S, k, D, False),
-                                        diagnostics.ess_multichain_workspace_bytes(S, k, D, True)) > free:
-        k //= 2
-    return k
+    """_fit_chains for the bulk / tail report: the z-score trace and the larger of the rank workspace and the ESS
+    workspace (they are not alive together)."""
+    return _fit_chains(trace, k, lambda S, k, D: max(diagnostics.rank_workspace_bytes(S, k, D, False),
+                                                     diagnostics.ess_multichain_workspace_bytes(S, k, D, True)))
 
 
 def _bulk_tail_report(trace, k, spec, arrays, by_part):
