@@ -81,6 +81,7 @@ SYMBOLS = ["arp_version", "arp_last_error", "arp_model_create", "arp_model_destr
            "arp_moments_fold_nested", "arp_nested_step_workspace_bytes", "arp_nested_step_sums",
            "arp_gram_workspace_bytes", "arp_gram_sums",
            "arp_pointwise_loglik", "arp_psis_workspace_bytes", "arp_psis_loo",
+           "arp_predictive_workspace_bytes", "arp_predictive_check",
            "arp_adapt_probe", "arp_clock_probe", "arp_energy_probe",
            "arp_trajectory_probe", "arp_jump_workspace_bytes", "arp_jump_sums"]
 
@@ -174,6 +175,13 @@ def lib():
     L.arp_psis_loo.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
                                C.c_void_p]
     L.arp_psis_loo.restype = C.c_int
+    L.arp_predictive_workspace_bytes.argtypes = [C.c_int64, C.c_int64]
+    L.arp_predictive_workspace_bytes.restype = C.c_int64
+    L.arp_predictive_check.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int64, C.c_int32, C.c_void_p,
+                                       C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64,
+                                       C.c_uint64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                       C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+    L.arp_predictive_check.restype = C.c_int
     L.arp_clock_probe.argtypes = [C.c_int, C.c_void_p, C.c_void_p]
     L.arp_adapt_probe.argtypes = [C.POINTER(HmcConfig), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     _lib = L

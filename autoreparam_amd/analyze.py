@@ -1,6 +1,6 @@
 """Pretty-printer for the result files main.py writes (reference analyze.py:30-185):
 
-    python -m autoreparam_amd.analyze --results_dir=. --model=radon_MN --elbos --ess --rhat --energy --trajectory --geometry --loo --reparams
+    python -m autoreparam_amd.analyze --results_dir=. --model=radon_MN --elbos --ess --rhat --energy --trajectory --geometry --loo --ppc --reparams
     python -m autoreparam_amd.analyze --loo_compare=radon_MN/CP_tied_loo.npz,radon_stddvs_MN/CP_tied_loo.npz
 
 The reference's method list is stale (`cVIP_exp_tied`, analyze.py:19-26) and it expects a
@@ -257,6 +257,31 @@ def report_loo(results):
     return lines
 
 
+def report_ppc(results):
+    """Build-specific: the posterior predictive checks of every sampling run that recorded them (--predictive_checks; the
+    last run of each file): the predictive p-values of mean, sd, min, max and deviance, the replicated against the
+    observed mean and sd, and the calibration of the PIT values.  The posterior PIT, not LOO-PIT; an extreme p-value is
+    marked by the customary reading (outside [0.01, 0.99]), not by a derived threshold."""
+    lines = []
+    for m, r in results.items():
+        if "ppc_observations" not in r:
+            continue
+        last = _last(r, "ppc_")
+        if last["ppc_observations"] is None:
+            lines.append("{}: posterior predictive checks not computed".format(m))
+            continue
+        stats = ("mean", "sd", "min", "max", "deviance")
+        extreme = [s for s in stats if last["ppc_p_" + s] is not None and not 0.01 <= last["ppc_p_" + s] <= 0.99]
+        lines.append("{}: predictive p-values {}; replicated mean {} (observed {}), sd {} (observed {}); PIT Kolmogorov "
+                     "distance {}, 90 % coverage {}; {} observations, {} draws of {} chains, {} left out; {}{}".format(
+                         m, ", ".join("{} {}".format(s, _fmt(last["ppc_p_" + s])) for s in stats), _fmt(last["ppc_rep_mean"]),
+                         _fmt(last["ppc_obs_mean"]), _fmt(last["ppc_rep_sd"]), _fmt(last["ppc_obs_sd"]), _fmt(last["ppc_pit_ks"]),
+                         _fmt(last["ppc_coverage_90"]), last["ppc_observations"], last["ppc_draws"], last["ppc_chains"],
+                         last["ppc_draws_left_out"], _secs(last.get("ppc_time_sec")),
+                         "   <-- EXTREME: " + ", ".join(extreme) if extreme else ""))
+    return lines
+
+
 def report_loo_compare(path_a, path_b):
     """Build-specific: the paired difference in elpd_loo of two models fitted to the same observations, from their
     <method>_loo.npz files (diagnostics.loo_compare): positive favours the first.  Refused unless y agrees."""
@@ -269,7 +294,7 @@ def report_loo_compare(path_a, path_b):
 
 def main(argv=None):
     ap = argparse.ArgumentParser()
-    for f in ("elbos", "ess", "reparams", "normalize_times", "rhat", "energy", "trajectory", "geometry", "loo"):
+    for f in ("elbos", "ess", "reparams", "normalize_times", "rhat", "energy", "trajectory", "geometry", "loo", "ppc"):
         ap.add_argument("--" + f, action="store_true")
     ap.add_argument("--loo_compare", default="", help="A_loo.npz,B_loo.npz: the paired elpd_loo difference of two models")
     ap.add_argument("--model", default="all")
@@ -294,7 +319,8 @@ def main(argv=None):
                             ("rhat", lambda: report_rhat(results, root, name)),
                             ("energy", lambda: report_energy(results, root, name)),
                             ("trajectory", lambda: report_trajectory(results, root, name)),
-                            ("geometry", lambda: report_geometry(results, root, name)), ("loo", lambda: report_loo(results))):
+                            ("geometry", lambda: report_geometry(results, root, name)), ("loo", lambda: report_loo(results)),
+                            ("ppc", lambda: report_ppc(results))):
             if getattr(args, flag):
                 print("\n".join(lines()) + "\n")
 

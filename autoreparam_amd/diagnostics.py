@@ -13,7 +13,9 @@ and the posterior geometry report (`gram_sums` on `arp_gram_sums`, the cross mom
 `geometry_from_sums`: correlation matrix, its condition number, the stiff and the soft direction, the step-scaled
 condition number; `scale_coupling`, `coupling_from_sums`: the funnel detector); and, the one report that judges the model
 and not the sampler, PSIS-LOO and WAIC (`pointwise_loglik` on `arp_pointwise_loglik`, `psis_loo` on `arp_psis_loo`;
-`loo_summary`, `loo_compare`, `pareto_k_threshold`: the host float64 folds).
+`loo_summary`, `loo_compare`, `pareto_k_threshold`: the host float64 folds) and the posterior predictive check
+(`predictive_check` on `arp_predictive_check`: replicated observations folded on the device; `combine_draw_stats`,
+`ppc_summary`: the test statistics, their p-values, the per-observation predictive moments and the PIT calibration).
 
 Build-specific (the reference runs 100 chains and reports the within-chain ESS only).  The per-chain moments come from
 one pass over a trace that is already on the device (`arp_split_moments`) or from the in-kernel statistics of a
@@ -639,3 +641,160 @@ def loo_compare(a, b):
     with np.errstate(invalid="ignore"):
         d = ea - eb
         return float(d.sum()), _se_of_sum(d)
+
+
+# ---- posterior predictive check: replicated observations folded on the device (csrc/ppc.hip) ----
+PPC_DRAW_COLUMNS = ("sum_y_rep", "sum_y_rep_sq", "min_y_rep", "max_y_rep", "deviance_rep", "deviance_obs", "sum_mu", "observations")
+PPC_OBS_COLUMNS = ("sum_mu", "sum_second_moment", "sum_pit", "count_rep_le_obs")
+PPC_STATISTICS = ("mean", "sd", "min", "max", "deviance")
+# what ppc_counts returns, in order: draws used, draws left out, then per statistic of PPC_STATISTICS #{T_rep >= T_obs} and
+# the sum of T_rep over the draws used, then the sum of the observed deviance -- all additive over draws, hence over ranks
+PPC_COUNTS = 2 + 2 * len(PPC_STATISTICS) + 1
+# The report (ppc_from_counts).  draws_used, draws_left_out, observations: ints.  p, rep, obs: dicts over PPC_STATISTICS --
+# the posterior predictive p-value #{T_rep >= T_obs} / draws_used, the mean of T_rep over the draws used, and T_obs (of y
+# itself; for the deviance, a realised discrepancy, the mean over draws of the observed deviance); None where it is not
+# defined (no draw used; sd, min and max of Bernoulli data, which are functions of the mean or trivial).
+# predictive_mean, predictive_sd, pit, rep_le_obs: [N] float64 per observation (NaN without draws).  pit_ks: the
+# Kolmogorov distance of the pit values from uniform; coverage_90: the share of observations with pit in [0.05, 0.95];
+# both None for Bernoulli data.
+PpcSummary = collections.namedtuple("PpcSummary", ["draws_used", "draws_left_out", "observations", "p", "rep", "obs",
+                                                   "predictive_mean", "predictive_sd", "pit", "rep_le_obs", "pit_ks",
+                                                   "coverage_90"])
+
+
+def predictive_workspace_bytes(N, R):
+    """Bytes of device workspace `predictive_check` takes for N observations of R draws; raises on a shape that is refused."""
+    need = int(_lib.lib().arp_predictive_workspace_bytes(int(N), int(R)))
+    if need <= 0:
+        raise ValueError("predictive_check: 1 <= N < 2^31 observations of 1 ... 2^31 - 1 draws are required")
+    return need
+
+
+def predictive_check(trace, table, n0=0, n1=None, seed=0, draw_offset=0, want_y_rep=False):
+    """(draw_stats, obs_sums, y_rep, mask, n_masked) of `arp_predictive_check` for a recorded CENTRED [S, C, D] float32
+    trace on the GPU and the observations [n0, n1) of a DeviceTable, all device tensors: draw_stats [S C, 8] float64
+    (PPC_DRAW_COLUMNS, per draw over these observations; two ranges combine through `combine_draw_stats`), obs_sums
+    [n1 - n0, 4] float64 (PPC_OBS_COLUMNS, per observation over the draws not left out), y_rep [n1 - n0, S C] float32
+    with want_y_rep (None otherwise), mask and n_masked as pointwise_loglik's.  The replicated value of (observation n,
+    draw r) is a function of (seed, n, draw_offset + r) alone: `draw_offset` is the global number of this trace's first
+    draw when the draws of a job are spread over calls or ranks.  A block of chains of a wider trace is read in place;
+    the workspace is owned here."""
+    x, S, Cn, D, row_stride = _lib.trace_view(trace, "predictive_check")
+    n1 = table.N if n1 is None else int(n1)
+    n0 = int(n0)
+    if not 0 <= n0 < n1 <= table.N:
+        raise ValueError("predictive_check: 0 <= n0 < n1 <= %d observations is required" % table.N)
+    R = S * Cn
+    if R == 0 or D == 0:
+        raise ValueError("predictive_check: an empty trace")
+    if int(draw_offset) < 0:
+        raise ValueError("predictive_check: draw_offset >= 0 is required")
+    draw_stats = torch.empty(R, len(PPC_DRAW_COLUMNS), dtype=torch.float64, device=x.device)
+    obs_sums = torch.empty(n1 - n0, len(PPC_OBS_COLUMNS), dtype=torch.float64, device=x.device)
+    y_rep = torch.empty(n1 - n0, R, dtype=torch.float32, device=x.device) if want_y_rep else None
+    mask = torch.empty(R, dtype=torch.uint8, device=x.device)
+    n_masked = torch.zeros((), dtype=torch.int64, device=x.device)
+    _lib.call(x.device, _lib.lib().arp_predictive_check, _lib.ptr(x), S, Cn, D, row_stride, table.kind, _lib.ptr(table.idx),
+              _lib.ptr(table.w), table.T, _lib.ptr(table.y), _lib.ptr(table.scale_idx), _lib.ptr(table.log_scale), n0, n1,
+              int(seed) & 0xFFFFFFFFFFFFFFFF, int(draw_offset), _lib.ptr(draw_stats), _lib.ptr(obs_sums), _lib.ptr(y_rep), R,
+              _lib.ptr(mask), _lib.ptr(n_masked), workspace=predictive_workspace_bytes(n1 - n0, R))
+    return draw_stats, obs_sums, y_rep, mask, n_masked
+
+
+def combine_draw_stats(a, b):
+    """The [R, 8] draw statistics of two observation ranges over the same draws as those of their union: columns combine
+    by +, +, min, max, +, +, +, +.  Tensors (on one device) or numpy arrays; the result is of the same kind."""
+    if tuple(a.shape) != tuple(b.shape) or len(a.shape) != 2 or a.shape[1] != len(PPC_DRAW_COLUMNS):
+        raise ValueError("combine_draw_stats: two [R, 8] arrays of one shape are required")
+    out = a + b
+    if torch.is_tensor(out):
+        out[:, 2], out[:, 3] = torch.minimum(a[:, 2], b[:, 2]), torch.maximum(a[:, 3], b[:, 3])
+    else:
+        out[:, 2], out[:, 3] = np.minimum(a[:, 2], b[:, 2]), np.maximum(a[:, 3], b[:, 3])
+    return out
+
+
+def _ppc_observed(y):
+    """T_obs of the first four statistics from y itself, float64 (sd with divisor N - 1, NaN for N < 2)."""
+    y = np.asarray(y, np.float64).reshape(-1)
+    sd = float(np.std(y, ddof=1)) if y.size > 1 else float("nan")
+    return float(y.mean()), sd, float(y.min()), float(y.max())
+
+
+def ppc_counts(draw_stats, y, mask=None):
+    """The [PPC_COUNTS] float64 vector behind the p-values, from the [R, 8] draw statistics of ALL N observations and the
+    observed y [N]: additive over draws, so a job whose draws are spread over ranks adds its ranks' vectors.  mask: [R],
+    non-zero for a draw that is left out.  The replicated statistics of draw r: mean = c0 / N, sd^2 = (c1 - c0^2 / N) /
+    (N - 1), min = c2, max = c3, deviance = c4, against mean, sd, min, max of y and the draw's own observed deviance c5;
+    a tie counts as T_rep >= T_obs.  The kind of data does not enter: ppc_from_counts leaves out what Bernoulli data do
+    not define."""
+    c = _lib.host64(draw_stats).reshape(-1, len(PPC_DRAW_COLUMNS))
+    y = np.asarray(_lib.host64(y), np.float64).reshape(-1)
+    N = y.size
+    if N < 1:
+        raise ValueError("ppc_counts: at least one observation is required")
+    used = np.ones(c.shape[0], bool) if mask is None else (_lib.host64(mask).reshape(-1) == 0)
+    if used.size != c.shape[0]:
+        raise ValueError("ppc_counts: mask must have one entry per draw")
+    c = c[used]
+    if c.size and not np.all(c[:, 7] == N):
+        raise ValueError("ppc_counts: the draw statistics must cover all %d observations" % N)
+    out = np.zeros(PPC_COUNTS)
+    out[0], out[1] = c.shape[0], used.size - c.shape[0]
+    obs_mean, obs_sd, obs_min, obs_max = _ppc_observed(y)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        rep_sd = np.sqrt(np.maximum(c[:, 1] - c[:, 0] * c[:, 0] / N, 0.0) / (N - 1)) if N > 1 else np.full(c.shape[0], np.nan)
+        pairs = ((c[:, 0] / N, obs_mean), (rep_sd, obs_sd), (c[:, 2], obs_min), (c[:, 3], obs_max), (c[:, 4], c[:, 5]))
+        for j, (rep, obs) in enumerate(pairs):
+            out[2 + j] = np.sum(rep >= obs)
+            out[2 + len(pairs) + j] = np.sum(rep)
+    out[2 + 2 * len(PPC_STATISTICS)] = np.sum(c[:, 5])
+    return out
+
+
+def ppc_from_counts(counts, obs_sums, y, kind):
+    """The report from the (all-reduced) vector of `ppc_counts`, the (all-reduced) [N, 4] obs_sums and y -> PpcSummary;
+    pure numpy float64.  Never raises on a job without a usable draw: everything is then None or NaN."""
+    t = np.asarray(counts, np.float64).reshape(PPC_COUNTS)
+    o = _lib.host64(obs_sums).reshape(-1, len(PPC_OBS_COLUMNS))
+    y = np.asarray(_lib.host64(y), np.float64).reshape(-1)
+    if o.shape[0] != y.size:
+        raise ValueError("ppc_from_counts: obs_sums must have one row per observation")
+    used, left = int(round(t[0])), int(round(t[1]))
+    normal = int(kind) == 0
+    defined = {"mean": True, "sd": normal and y.size > 1, "min": normal, "max": normal, "deviance": True}
+    obs_first = dict(zip(PPC_STATISTICS[:4], _ppc_observed(y))) if y.size else {}
+    k = len(PPC_STATISTICS)
+    p, rep, obs = {}, {}, {}
+    for j, name in enumerate(PPC_STATISTICS):
+        ok = defined[name] and used > 0
+        p[name] = float(t[2 + j] / used) if ok else None
+        rep[name] = float(t[2 + k + j] / used) if ok else None
+        obs[name] = (float(t[2 + 2 * k] / used) if ok else None) if name == "deviance" else \
+            (obs_first.get(name) if defined[name] else None)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        nan = np.full(y.size, np.nan)
+        mean = o[:, 0] / used if used else nan
+        sd = np.sqrt(np.maximum(o[:, 1] / used - mean * mean, 0.0)) if used else nan
+        pit = o[:, 2] / used if used else nan
+        le = o[:, 3] / used if used else nan
+    ks = coverage = None
+    if normal and used and y.size:
+        s = np.sort(pit)
+        i = np.arange(1, s.size + 1, dtype=np.float64)
+        ks = float(max(np.max(i / s.size - s), np.max(s - (i - 1.0) / s.size)))
+        coverage = float(np.mean((pit >= 0.05) & (pit <= 0.95)))
+    return PpcSummary(used, left, int(y.size), p, rep, obs, mean, sd, pit, le, ks, coverage)
+
+
+def ppc_summary(draw_stats, obs_sums, y, kind, mask=None):
+    """The posterior predictive check of one process, the single place where its statistics are defined -> PpcSummary;
+    pure numpy float64.  draw_stats [R, 8] over ALL N observations (PPC_DRAW_COLUMNS), obs_sums [N, 4]
+    (PPC_OBS_COLUMNS), y [N], kind 0 (Normal) or 1 (Bernoulli-logit), mask [R] (non-zero: the draw is left out of R_used).
+    Test statistics T in PPC_STATISTICS: T_obs of mean, sd (divisor N - 1), min and max from y itself; the observed
+    deviance is per draw (a realised discrepancy); p_T = #{r used: T_rep,r >= T_obs(,r)} / R_used, a tie counting as >=.
+    For Bernoulli data sd, min and max are functions of the mean or trivial: None.  Per observation: the predictive mean,
+    the predictive sd sqrt(E[mu^2 + var] - mean^2), the posterior PIT (NOT the leave-one-out PIT) and its empirical
+    counterpart #{y_rep <= y} / R_used.  Calibration, Normal data only: pit_ks and coverage_90.  = ppc_from_counts of
+    ppc_counts: a job whose draws are spread over ranks adds the counts and obs_sums of its ranks first."""
+    return ppc_from_counts(ppc_counts(draw_stats, y, mask), obs_sums, y, kind)

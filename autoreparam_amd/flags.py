@@ -100,6 +100,16 @@ _DEFS = [
     ("loo_draws", int, 65536, "With --predictive_diagnostics: the draws per observation, taken as loo_draws // chains evenly "
                               "spaced recorded steps of the device trace (at least one, at most all; the last step among "
                               "them)."),
+    ("predictive_checks", bool, False, "Sampling runs, with --convergence_diagnostics: posterior predictive checks -- does "
+                                       "data simulated from the fitted model look like the data?  For every draw the "
+                                       "--predictive_diagnostics report would take (--loo_draws of the chains split R-hat "
+                                       "covers) one replicated data set at the observed covariates (arp_predictive_check; "
+                                       "Gelman, Meng, Stern 1996), folded on the device: posterior predictive p-values of "
+                                       "the mean, sd, min, max and deviance, the predictive mean and sd of every observation "
+                                       "and its PIT value with their calibration (ppc_* JSON keys, <base>_ppc.npz).  The "
+                                       "posterior PIT, not LOO-PIT; no group-level statistics, no user-defined statistic.  "
+                                       "Every quantity is a sum over draws: sharded jobs included.  Refused for "
+                                       "neals_funnel, which has no observations."),
     ("lanes_per_chain", int, 0, "Lanes of a wave64 a chain is spread over (0 = automatic)."),
 ]
 

@@ -238,6 +238,11 @@ def _convergence_report(kernel_results, model_config, flags, dev):
     (A collective when ws > 1: every rank calls it.)"""
     trace = getattr(kernel_results, "trace", None)
     if not getattr(flags, "convergence_diagnostics", True) or trace is None:
+        if getattr(flags, "convergence_diagnostics", True) and getattr(flags, "predictive_checks", False):
+            keys = _loo_null("no chain has its trace on the device") if getattr(flags, "predictive_diagnostics", False) \
+                else OrderedDict()
+            keys.update(_ppc_null("no chain has its trace on the device"))
+            return keys, None
         if getattr(flags, "convergence_diagnostics", True) and getattr(flags, "predictive_diagnostics", False):
             return _loo_null("no chain has its trace on the device"), None
         return {}, None
@@ -297,7 +302,9 @@ def _convergence_report(kernel_results, model_config, flags, dev):
             (getattr(flags, "geometry_diagnostics", False), GEOMETRY_ARRAYS,
              lambda: _geometry_report(kernel_results, trace, k, spec, flags, dev, split.mean)),
             (getattr(flags, "predictive_diagnostics", False), LOO_ARRAYS,
-             lambda: _loo_report(kernel_results, trace, k, spec, flags))):
+             lambda: _loo_report(kernel_results, trace, k, spec, flags)),
+            (getattr(flags, "predictive_checks", False), PPC_ARRAYS,               # (n_split: already all-reduced)
+             lambda: _ppc_report(kernel_results, trace, k, n_split, spec, flags, dev))):
         if asked:
             side_keys, side_arrays = report()
             keys.update(side_keys)
@@ -752,6 +759,125 @@ def save_loo(file_path_base, arrays):
     np.savez(file_path_base + "_loo.npz", **arrays)
 
 
+PPC_ARRAYS = "ppc/"                  # where _convergence_report leaves the arrays of <base>_ppc.npz
+PPC_SEED = 0x50504331                # the report's own seed constant (the probes have theirs)
+PPC_EXTREME = (0.01, 0.99)           # the customary reading of an extreme predictive p-value, not a derived threshold
+PPC_KEYS = ("ppc_draws", "ppc_draws_left_out", "ppc_chains", "ppc_steps", "ppc_observations", "ppc_p_mean", "ppc_p_sd",
+            "ppc_p_min", "ppc_p_max", "ppc_p_deviance", "ppc_rep_mean", "ppc_rep_sd", "ppc_obs_mean", "ppc_obs_sd",
+            "ppc_pit_ks", "ppc_coverage_90", "ppc_time_sec")
+
+
+def check_predictive_checks(flags):
+    """--predictive_checks against the job, before anything runs: check_predictive's rule for the other predictive
+    report -- raises ValueError for a model without observations (neals_funnel), which has nothing to replicate."""
+    if getattr(flags, "predictive_checks", False) and flags.model == "neals_funnel":
+        raise ValueError("--predictive_checks: neals_funnel has no observations, so there is no data to replicate")
+
+
+def ppc_tile_rows(N, R, workspace_bytes, budget=None):
+    """Observations per tile of the predictive checks: loo_tile_rows, halved until `workspace_bytes(rows, R)` -- the
+    kernel's partial sums, the only [observations, draws]-sized memory this report takes -- is within the budget too; at
+    least one."""
+    budget = LOO_CHUNK_BYTES if budget is None else int(budget)
+    rows = loo_tile_rows(N, R, budget)
+    while rows > 1 and workspace_bytes(rows, R) > budget:
+        rows = (rows + 1) // 2
+    return rows
+
+
+def _ppc_null(why):
+    """Every key of the predictive checks as null, with the one message that says why."""
+    util.print_("    posterior predictive checks: not computed, {}".format(why))
+    return OrderedDict((key, None) for key in PPC_KEYS)
+
+
+def ppc_keys(summary, n_chains, n_steps):
+    """The JSON keys of the predictive checks (all but ppc_time_sec) from a diagnostics.PpcSummary; pure Python."""
+    num = lambda v: None if v is None else _finite_or_none(v)
+    keys = OrderedDict([("ppc_draws", int(summary.draws_used)), ("ppc_draws_left_out", int(summary.draws_left_out)),
+                        ("ppc_chains", int(n_chains)), ("ppc_steps", int(n_steps)),
+                        ("ppc_observations", int(summary.observations))])
+    for name in diagnostics.PPC_STATISTICS:
+        keys["ppc_p_" + name] = num(summary.p[name])
+    keys.update([("ppc_rep_mean", num(summary.rep["mean"])), ("ppc_rep_sd", num(summary.rep["sd"])),
+                 ("ppc_obs_mean", num(summary.obs["mean"])), ("ppc_obs_sd", num(summary.obs["sd"])),
+                 ("ppc_pit_ks", num(summary.pit_ks)), ("ppc_coverage_90", num(summary.coverage_90))])
+    return keys
+
+
+def _ppc_report(kernel_results, trace, k, k_total, spec, flags, dev):
+    """--predictive_checks: does data simulated from the fitted MODEL look like the data?  Over the draws the predictive
+    report takes -- the leading `k` chains of this rank's device trace, the chains split R-hat covers (`k_total` of them in
+    the whole job, already all-reduced), at clamp(--loo_draws // k_total, 1, S) evenly spaced recorded steps (loo_steps) --
+    one replicated data set per draw at the observed covariates (diagnostics.predictive_check, from the model's
+    observation table), folded on the device into per-draw test statistics and per-observation predictive sums, in tiles
+    of observations (ppc_tile_rows) combined on the device.  The random numbers are keyed by (seed, observation, global
+    draw number), the seed derived from --seed and PPC_SEED; a rank's first global draw number is its chain offset times
+    the number of steps.  Every quantity is a sum over draws: the counts behind the p-values and the per-observation sums go
+    through ONE all-reduce, and a sharded job reports real numbers (rank 0 writes them; <base>_ppc.npz then holds the
+    draw statistics of rank 0's draws).  The posterior PIT, not LOO-PIT; no group-level statistics; no user-defined
+    statistic.  Returns (JSON keys, arrays of <base>_ppc.npz or None).  (A collective when ws > 1: every rank calls it.)"""
+    import torch
+    clock = time.time()
+    S, _, D = (int(v) for v in trace.shape)
+    k = int(k) if S > 0 else 0
+    if int(k_total) <= 0 or S <= 0:
+        return _ppc_null("no chain has its trace on the device"), None
+    if D > diagnostics.LOGLIK_MAX_D:
+        return _ppc_null("the model has more than {} elements".format(diagnostics.LOGLIK_MAX_D)), None
+    steps = loo_steps(S, k_total, getattr(flags, "loo_draws", 65536))
+    if not steps:
+        return _ppc_null("more than {} chains".format(diagnostics.PSIS_MAX_DRAWS)), None
+    host_table = spec.observation_table()
+    N, kind = int(np.asarray(host_table.y).size), int(host_table.kind)
+    y = np.asarray(host_table.y, np.float32).reshape(-1)
+    seed = (int(flags.seed) * 0x9E3779B97F4A7C15 + PPC_SEED) & 0xFFFFFFFFFFFFFFFF
+    ctx = getattr(kernel_results, "probe", None)
+    draw_offset = (int(ctx.chain_offset) if ctx is not None else 0) * len(steps)
+    counts, obs_sums, stats_host = np.zeros(diagnostics.PPC_COUNTS), np.zeros((N, len(diagnostics.PPC_OBS_COLUMNS))), None
+    if k > 0:
+        table = diagnostics.upload_table(host_table, D, trace.device)
+        draws = trace[torch.as_tensor(steps, device=trace.device), :k].contiguous()      # [len(steps), k, D]: a copy, D floats a draw
+        R = len(steps) * k
+        rows = ppc_tile_rows(N, R, diagnostics.predictive_workspace_bytes)
+        stats, sums, mask = None, [], None
+        for n0 in range(0, N, rows):
+            part, obs, _, mask, _ = diagnostics.predictive_check(draws, table, n0, min(N, n0 + rows), seed=seed,
+                                                                 draw_offset=draw_offset)
+            stats = part if stats is None else diagnostics.combine_draw_stats(stats, part)
+            sums.append(obs)
+        stats_host, obs_sums = _lib.host64(stats), _lib.host64(torch.cat(sums, dim=0))
+        counts = diagnostics.ppc_counts(stats_host, y, mask)                             # (the same draws for every tile)
+    counts, obs_sums = _reduced([counts, obs_sums], dev)
+    summary = diagnostics.ppc_from_counts(counts, obs_sums, y, kind)
+    keys = ppc_keys(summary, k_total, len(steps))
+    p = OrderedDict((name, keys["ppc_p_" + name]) for name in diagnostics.PPC_STATISTICS)
+    util.print_("    posterior predictive checks over {} observations, {} draws ({} step(s) of {} chains, {} left out): "
+                "p-values mean {}, sd {}, min {}, max {}, deviance {}; replicated mean {} against {} observed; PIT "
+                "Kolmogorov distance {}, 90 % coverage {}".format(
+                    N, keys["ppc_draws"], len(steps), int(k_total), keys["ppc_draws_left_out"], _fmt(p["mean"]), _fmt(p["sd"]),
+                    _fmt(p["min"]), _fmt(p["max"]), _fmt(p["deviance"]), _fmt(keys["ppc_rep_mean"]), _fmt(keys["ppc_obs_mean"]),
+                    _fmt(keys["ppc_pit_ks"]), _fmt(keys["ppc_coverage_90"])))
+    extreme = [name for name, v in p.items() if v is not None and not PPC_EXTREME[0] <= v <= PPC_EXTREME[1]]
+    if extreme:
+        util.print_("    WARNING: posterior predictive p-value outside [{}, {}] for: {} -- replicated data sets (almost) never "
+                    "or (almost) always exceed the observed statistic; customarily read as a misfit of the model in that "
+                    "respect (a convention, not a derived threshold)".format(PPC_EXTREME[0], PPC_EXTREME[1], ", ".join(extreme)))
+    arrays = OrderedDict([("predictive_mean", summary.predictive_mean), ("predictive_sd", summary.predictive_sd),
+                          ("pit", summary.pit), ("y", y),
+                          ("draw_stats", stats_host if stats_host is not None else np.zeros((0, len(diagnostics.PPC_DRAW_COLUMNS)))),
+                          ("model", np.asarray(spec.name))])
+    keys["ppc_time_sec"] = time.time() - clock
+    return keys, arrays
+
+
+def save_ppc(file_path_base, arrays):
+    """`<base>_ppc.npz` (build-specific, --predictive_checks): per observation `predictive_mean`, `predictive_sd` and `pit`
+    [N] float64 and `y` [N], the observations themselves; `draw_stats` [R, 8] float64, the per-draw sums of
+    diagnostics.PPC_DRAW_COLUMNS (zeros for a draw left out); `model`, the model's name."""
+    np.savez(file_path_base + "_ppc.npz", **arrays)
+
+
 def _fit_chains(trace, k, workspace_bytes):
     """The largest of k, k/2, k/4, ... leading chains whose z-score trace and the `workspace_bytes(S, k, D)` next to it
     fit the free device memory."""
@@ -939,13 +1065,13 @@ def save_geometry(file_path_base, arrays):
 
 def _save_diagnostics(file_path_base, arrays):
     """The side files of the convergence report: <base>_rhat.npz and, where the probes ran, <base>_energy.npz,
-    <base>_trajectory.npz, <base>_geometry.npz and <base>_loo.npz."""
+    <base>_trajectory.npz, <base>_geometry.npz, <base>_loo.npz and <base>_ppc.npz."""
     if arrays is None:
         return
     # (tag _convergence_report left a side file's arrays under, its saver), in the order the files are written after _rhat.npz
     side = [(arrays.pop(tag, None), save) for tag, save in (
         (GEOMETRY_ARRAYS, save_geometry), (ENERGY_ARRAYS, save_energy), (TRAJECTORY_ARRAYS, save_trajectory),
-        (LOO_ARRAYS, save_loo))]
+        (LOO_ARRAYS, save_loo), (PPC_ARRAYS, save_ppc))]
     save_rhat(file_path_base, arrays)
     for side_arrays, save in side:
         if side_arrays is not None:
@@ -1235,6 +1361,7 @@ def main(argv=None, flags=FLAGS, out=None):
         # accepting the flag silently would write a *_reparam_variational*.json that holds ordinary mean-field results
         raise NotImplementedError("--reparameterise_variational is not supported by this build (SURVEY.md section 2)")
     check_predictive(flags)
+    check_predictive_checks(flags)
     ws = int(os.environ.get("WORLD_SIZE", "1"))
     if ws > 1:
         # launched by torch.distributed.run: one rank per GPU, RCCL for the statistics exchange

@@ -503,6 +503,44 @@ int64_t arp_psis_workspace_bytes(int64_t n_obs, int64_t n_draws);
 int arp_psis_loo(const float* ll, int64_t n_obs, int64_t n_draws, int64_t ll_stride, const uint8_t* mask, double* out,
                  void* workspace, int64_t workspace_bytes, void* stream);
 
+/* Posterior predictive check (csrc/ppc.hip; Gelman, Meng, Stern 1996; BDA3 ch. 6): replicated observations of recorded
+ * draws, folded on the device.  The trace x, the table and the observation range [n0, n1) are those of
+ * arp_pointwise_loglik (same addressing, same row_stride rule, 1 <= D <= 255, 1 <= T <= 4096), and eta_n, s_n are its
+ * float32 chain, operation for operation.  For observation n (its GLOBAL index in the table) and draw
+ * r = step * n_chains + chain, with mu and var the mean and the variance of y_rep given the draw:
+ *   kind ARP_OBS_NORMAL:     mu = eta, var = exp(s)^2;  y_rep = eta + exp(s) * z;  z_obs = (y - eta) * exp(-s);
+ *                            pit = Phi(z_obs) = 0.5 * erfc(-z_obs / sqrt 2);  dev(v) = ((v - eta) * exp(-s))^2 + 2 s + log(2 pi)
+ *   kind ARP_OBS_BERNOULLI:  p = sigmoid(eta) = (eta >= 0 ? 1 : e) / (1 + e), e = exp(-|eta|);  mu = p, var = p * (1 - p);
+ *                            y_rep = (u < p) ? 1 : 0;  pit = P(y_rep < y) + P(y_rep = y) / 2 (y > 0.5: 1 - p / 2; else (1 - p) / 2);
+ *                            dev(v) = -2 * (v * eta - (max(eta, 0) + log1p(e)))
+ * dev is -2 log-likelihood.  Random numbers: ONE call philox4x32_10(counter = (n, lo32(g), hi32(g), 0), key = (lo32(seed),
+ * hi32(seed))) per (n, r), g = draw_offset + r; words 0 and 1 are used.  Bernoulli: u = (w0 >> 8) * 2^-24 in [0, 1).
+ * Normal: z = sqrt(-2 log(u')) * cospi(2 a), u' = fma((float)w0, 2^-32, 2^-33) in (0, 1], a = the float in [1, 2) whose
+ * mantissa is the low 23 bits of w1 (the sampler's normal_pair, through logf, sqrtf, cospif).  A result therefore never
+ * depends on the tiling, on [n0, n1) or on which rank holds a draw.  Outputs (device memory):
+ *   draw_stats [n_samples * n_chains][8] double, per draw over the observations of this call:
+ *     {sum y_rep, sum y_rep^2, min y_rep, max y_rep, sum dev(y_rep), sum dev(y), sum mu, observations counted};
+ *     two observation ranges combine by +, +, min, max, +, +, +, +.
+ *   obs_sums [n1 - n0][4] double, per observation over the draws not left out:
+ *     {sum mu, sum (mu^2 + var), sum pit, #{y_rep <= y}}.
+ *   y_rep: NULL, or float [n1 - n0][y_rep_stride], y_rep[(n - n0) * y_rep_stride + r]; NULL leaves every other output
+ *     bitwise as it is.
+ *   mask [n_samples * n_chains] bytes and *n_masked as arp_pointwise_loglik's: a draw with a non-finite element is left
+ *     out; its draw_stats row and its y_rep entries are written as 0 by select and it enters no obs_sums.
+ * The per-(n, r) values are float32; every sum is accumulated in float64 in a fixed order, no float atomics: two calls give
+ * bitwise equal outputs.  Error bounds of the per-(n, r) values: the header of csrc/ppc.hip.
+ * The workspace (arp_predictive_workspace_bytes(n1 - n0, n_samples * n_chains): the per-tile partial sums of obs_sums,
+ * (n_draws / 64) * n_obs * 32 bytes, and the per-group partials of draw_stats; <= 0 for a shape that is refused) is the
+ * caller's, 256-byte aligned.  Asynchronous.  Refused before any launch: what arp_pointwise_loglik refuses (a NULL
+ * pointer other than y_rep, D, the trace shape, row_stride, kind, T, n0 and n1; y_rep_stride < n_samples * n_chains with
+ * a y_rep), a workspace that is missing, too small or misaligned. */
+int64_t arp_predictive_workspace_bytes(int64_t n_obs, int64_t n_draws);
+int arp_predictive_check(const float* x, int64_t n_samples, int64_t n_chains, int32_t D, int64_t row_stride, int32_t kind,
+                         const int32_t* idx, const float* w, int32_t T, const float* y, const int32_t* scale_idx,
+                         const float* log_scale, int64_t n0, int64_t n1, uint64_t seed, int64_t draw_offset,
+                         double* draw_stats, double* obs_sums, float* y_rep, int64_t y_rep_stride, uint8_t* mask,
+                         int64_t* n_masked, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* Test hook: the step-size adaptation recurrence of the chain kernels on SCRIPTED log acceptance ratios
  * (tfp.mcmc.DualAveragingStepSizeAdaptation / SimpleStepSizeAdaptation as wired at inference.py:224-226, 288-306;
  * SURVEY.md 8c known answer (7)).  For each of `n` independent rows, applies the update after transitions
