@@ -81,6 +81,8 @@ SYMBOLS = ["arp_version", "arp_last_error", "arp_model_create", "arp_model_destr
            "arp_moments_fold_nested", "arp_nested_step_workspace_bytes", "arp_nested_step_sums",
            "arp_gram_workspace_bytes", "arp_gram_sums",
            "arp_pointwise_loglik", "arp_psis_workspace_bytes", "arp_psis_loo",
+           "arp_psis_weights_workspace_bytes", "arp_psis_weights",
+           "arp_vi_draws", "arp_vi_fold_workspace_bytes", "arp_vi_fold",
            "arp_predictive_workspace_bytes", "arp_predictive_check",
            "arp_adapt_probe", "arp_clock_probe", "arp_energy_probe",
            "arp_trajectory_probe", "arp_jump_workspace_bytes", "arp_jump_sums"]
@@ -182,6 +184,19 @@ def lib():
                                        C.c_uint64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
     L.arp_predictive_check.restype = C.c_int
+    L.arp_psis_weights_workspace_bytes.argtypes = [C.c_int64, C.c_int64]
+    L.arp_psis_weights_workspace_bytes.restype = C.c_int64
+    L.arp_psis_weights.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                   C.c_void_p, C.c_int64, C.c_void_p]
+    L.arp_psis_weights.restype = C.c_int
+    L.arp_vi_draws.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_uint64, C.c_int64, C.c_void_p, C.c_void_p,
+                               C.c_int64, C.c_void_p, C.c_void_p]
+    L.arp_vi_draws.restype = C.c_int
+    L.arp_vi_fold_workspace_bytes.argtypes = [C.c_int64, C.c_int32]
+    L.arp_vi_fold_workspace_bytes.restype = C.c_int64
+    L.arp_vi_fold.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                              C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+    L.arp_vi_fold.restype = C.c_int
     L.arp_clock_probe.argtypes = [C.c_int, C.c_void_p, C.c_void_p]
     L.arp_adapt_probe.argtypes = [C.POINTER(HmcConfig), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     _lib = L

@@ -1,6 +1,6 @@
 """Pretty-printer for the result files main.py writes (reference analyze.py:30-185):
 
-    python -m autoreparam_amd.analyze --results_dir=. --model=radon_MN --elbos --ess --rhat --energy --trajectory --geometry --loo --ppc --reparams
+    python -m autoreparam_amd.analyze --results_dir=. --model=radon_MN --elbos --ess --rhat --energy --trajectory --geometry --loo --ppc --vi --reparams
     python -m autoreparam_amd.analyze --loo_compare=radon_MN/CP_tied_loo.npz,radon_stddvs_MN/CP_tied_loo.npz
 
 The reference's method list is stale (`cVIP_exp_tied`, analyze.py:19-26) and it expects a
@@ -282,6 +282,34 @@ def report_ppc(results):
     return lines
 
 
+def report_vi(results):
+    """Build-specific: the fit check of every VI result file that holds one (--vi_diagnostics): the Pareto k-hat of the
+    importance ratios p / q against its threshold, the ELBO of the final parameters next to the optimiser's own figure, the
+    evidence and KL estimates, the largest ELBO gradients and the spread of the importance-corrected sd.  k-hat is the only
+    figure with a threshold; above it the importance-corrected figures are marked unreliable."""
+    lines = []
+    for m, r in results.items():
+        if "vi_check_draws" not in r:
+            continue
+        k, cap = r["vi_pareto_k"], r["vi_pareto_k_threshold"]
+        far = k is None or cap is None or k > cap
+        lines.append("{}: Pareto k-hat {} (threshold {}); ELBO of the final parameters {} +/- {} (optimiser: {} +/- {}); log "
+                     "evidence {} +/- {}, KL(q || p) {} +/- {}; largest ELBO gradient along loc {} +/- {} ({}), along log scale "
+                     "{} +/- {} ({}); largest score gap {} ({}), loc shift {} sd ({}); sd ratio {} ({}) ... {} ({}); {} draws, "
+                     "{} left out; {}{}".format(
+                         m, _fmt(k), _fmt(cap), _fmt(r["vi_elbo_final"], "{:.4f}"), _fmt(r["vi_elbo_final_se"]),
+                         _fmt(r.get("elbo"), "{:.4f}"), _fmt(r.get("estimated_elbo_std")), _fmt(r["vi_log_evidence"], "{:.4f}"),
+                         _fmt(r["vi_log_evidence_se"]), _fmt(r["vi_kl_estimate"]), _fmt(r["vi_kl_estimate_se"]),
+                         _fmt(r["vi_elbo_grad_loc_max"]), _fmt(r["vi_elbo_grad_loc_max_se"]), r["vi_elbo_grad_loc_max_element"],
+                         _fmt(r["vi_elbo_grad_scale_max"]), _fmt(r["vi_elbo_grad_scale_max_se"]),
+                         r["vi_elbo_grad_scale_max_element"], _fmt(r["vi_score_gap_max"]), r["vi_score_gap_max_element"],
+                         _fmt(r["vi_loc_shift_max"]), r["vi_loc_shift_max_element"], _fmt(r["vi_sd_ratio_min"]),
+                         r["vi_sd_ratio_min_element"], _fmt(r["vi_sd_ratio_max"]), r["vi_sd_ratio_max_element"],
+                         r["vi_check_draws"], r["vi_check_draws_left_out"], _secs(r.get("vi_check_time_sec")),
+                         "   <-- q IS FAR FROM THE POSTERIOR: the importance-corrected figures are unreliable" if far else ""))
+    return lines
+
+
 def report_loo_compare(path_a, path_b):
     """Build-specific: the paired difference in elpd_loo of two models fitted to the same observations, from their
     <method>_loo.npz files (diagnostics.loo_compare): positive favours the first.  Refused unless y agrees."""
@@ -294,7 +322,7 @@ def report_loo_compare(path_a, path_b):
 
 def main(argv=None):
     ap = argparse.ArgumentParser()
-    for f in ("elbos", "ess", "reparams", "normalize_times", "rhat", "energy", "trajectory", "geometry", "loo", "ppc"):
+    for f in ("elbos", "ess", "reparams", "normalize_times", "rhat", "energy", "trajectory", "geometry", "loo", "ppc", "vi"):
         ap.add_argument("--" + f, action="store_true")
     ap.add_argument("--loo_compare", default="", help="A_loo.npz,B_loo.npz: the paired elpd_loo difference of two models")
     ap.add_argument("--model", default="all")
@@ -320,7 +348,7 @@ def main(argv=None):
                             ("energy", lambda: report_energy(results, root, name)),
                             ("trajectory", lambda: report_trajectory(results, root, name)),
                             ("geometry", lambda: report_geometry(results, root, name)), ("loo", lambda: report_loo(results)),
-                            ("ppc", lambda: report_ppc(results))):
+                            ("ppc", lambda: report_ppc(results)), ("vi", lambda: report_vi(results))):
             if getattr(args, flag):
                 print("\n".join(lines()) + "\n")
 

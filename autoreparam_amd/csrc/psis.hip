@@ -342,6 +342,13 @@ bool psis_shape_ok(int64_t n_obs, int64_t n_draws) {
 long long ws_stride_of(int64_t n_draws) { return (tail_length(n_draws) + 31) / 32 * 32; }
 
 }  // namespace
+
+// psis_weights.hip: the second launch of arp_psis_weights (kept out of this file so that psis_kernel's code object is
+// the one arp_psis_loo has always launched, instruction for instruction: tools/listing_diff.py)
+int psis_weights_launch(const float* ll, long long n_obs, long long R, long long stride, const unsigned char* mask,
+                        const double* out, const double* ws, unsigned long long* members, long long ws_stride, double* lw,
+                        long long lw_stride, hipStream_t stream);
+
 }  // namespace arp
 
 extern "C" int64_t arp_psis_workspace_bytes(int64_t n_obs, int64_t n_draws) {
@@ -369,4 +376,41 @@ extern "C" int arp_psis_loo(const float* ll, int64_t n_obs, int64_t n_draws, int
                      (long long)ll_stride, (const unsigned char*)mask, out, (double*)workspace, ws_stride_of(n_draws));
   ARP_HIP_OK(hipGetLastError());
   return 0;
+}
+
+extern "C" int64_t arp_psis_weights_workspace_bytes(int64_t n_obs, int64_t n_draws) {
+  using namespace arp;
+  if (!psis_shape_ok(n_obs, n_draws)) return 0;
+  Carve c;
+  c.take(arp_psis_workspace_bytes(n_obs, n_draws));
+  c.take(n_obs * ws_stride_of(n_draws) * 8);
+  return c.bytes();
+}
+
+extern "C" int arp_psis_weights(const float* ll, int64_t n_obs, int64_t n_draws, int64_t ll_stride, const uint8_t* mask,
+                                double* out, double* lw, int64_t lw_stride, void* workspace, int64_t workspace_bytes,
+                                void* stream) {
+  using namespace arp;
+  const char* who = "arp_psis_weights";
+  if (!ll || !out || !lw) { set_error(std::string(who) + ": ll, out and lw are required"); return 1; }
+  if (n_obs < 1 || n_obs >= (1ll << 31) || n_draws < 1) {
+    set_error(std::string(who) + ": 1 <= n_obs < 2^31 and n_draws >= 1 are required");
+    return 1;
+  }
+  if (n_draws > kPsMaxR) { set_error(std::string(who) + ": at most 2^24 draws per observation"); return 1; }
+  if (ll_stride < n_draws) { set_error(std::string(who) + ": ll_stride >= n_draws is required"); return 1; }
+  if (lw_stride < n_draws) { set_error(std::string(who) + ": lw_stride >= n_draws is required"); return 1; }
+  const int64_t need = arp_psis_weights_workspace_bytes(n_obs, n_draws);
+  if (!workspace_size_ok(workspace && workspace_bytes >= need, who, "see arp_psis_weights_workspace_bytes")) return 1;
+  if (!workspace_aligned(workspace, who)) return 1;
+  Carve c;
+  double* xs = (double*)((char*)workspace + c.take(arp_psis_workspace_bytes(n_obs, n_draws)));
+  unsigned long long* members = (unsigned long long*)((char*)workspace + c.take(n_obs * ws_stride_of(n_draws) * 8));
+  // the launch of arp_psis_loo, argument for argument: out is its out
+  const size_t lds = (size_t)std::max<long long>(1, tail_length(n_draws)) * sizeof(float);
+  hipLaunchKernelGGL(psis_kernel, dim3((unsigned)n_obs), dim3(kPsThreads), lds, (hipStream_t)stream, ll, (long long)n_draws,
+                     (long long)ll_stride, (const unsigned char*)mask, out, xs, ws_stride_of(n_draws));
+  ARP_HIP_OK(hipGetLastError());
+  return psis_weights_launch(ll, (long long)n_obs, (long long)n_draws, (long long)ll_stride, (const unsigned char*)mask, out, xs,
+                             members, ws_stride_of(n_draws), lw, (long long)lw_stride, (hipStream_t)stream);
 }

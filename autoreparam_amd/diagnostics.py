@@ -15,7 +15,10 @@ condition number; `scale_coupling`, `coupling_from_sums`: the funnel detector); 
 and not the sampler, PSIS-LOO and WAIC (`pointwise_loglik` on `arp_pointwise_loglik`, `psis_loo` on `arp_psis_loo`;
 `loo_summary`, `loo_compare`, `pareto_k_threshold`: the host float64 folds) and the posterior predictive check
 (`predictive_check` on `arp_predictive_check`: replicated observations folded on the device; `combine_draw_stats`,
-`ppc_summary`: the test statistics, their p-values, the per-observation predictive moments and the PIT calibration).
+`ppc_summary`: the test statistics, their p-values, the per-observation predictive moments and the PIT calibration); and
+the one report that judges the variational fit the sampler inherits its steps and its start from (`vi_check` on
+`arp_vi_draws`, `arp_psis_weights` and `arp_vi_fold`; `vi_check_summary`: the Pareto k-hat of the importance ratios p / q,
+the ELBO and its gradient at the final parameters, the importance-corrected loc and scale; Yao et al. 2018).
 
 Build-specific (the reference runs 100 chains and reports the within-chain ESS only).  The per-chain moments come from
 one pass over a trace that is already on the device (`arp_split_moments`) or from the in-kernel statistics of a
@@ -798,3 +801,192 @@ def ppc_summary(draw_stats, obs_sums, y, kind, mask=None):
     counterpart #{y_rep <= y} / R_used.  Calibration, Normal data only: pit_ks and coverage_90.  = ppc_from_counts of
     ppc_counts: a job whose draws are spread over ranks adds the counts and obs_sums of its ranks first."""
     return ppc_from_counts(ppc_counts(draw_stats, y, mask), obs_sums, y, kind)
+
+
+# ---- check of a mean-field fit: draws from q, Pareto-smoothed importance ratios, one fold (csrc/vicheck.hip, psis.hip) ----
+VI_ELEM_COLUMNS = ("sum_u", "sum_u_sq", "sum_uz", "sum_uz_sq", "sum_u_plus_z_sq", "sum_wz", "sum_wz_sq", "sum_wc", "sum_wc_sq")
+VI_TOT_COLUMNS = ("kept", "sum_w", "sum_w_sq", "sum_ll", "min_ll")
+VI_MAX_DRAWS = 1 << 24            # the most draws arp_vi_draws and arp_vi_fold take
+# What vi_check leaves on the host: elem [D, 9] and tot [5] float64 (arp_vi_fold), out8 [8] float64 (PSIS_COLUMNS of the one
+# row of log ratios), e0 [D] float64 (the centred image of loc), logp_const (the density's additive constant), left_out
+# (draws with a non-finite logp, gradient or centred element), log_ratio [R] float32 (log p - log q without the constant;
+# NaN or +-inf where the draw was left out), log_weight [R] float64 (arp_psis_weights' lw; -inf where left out).
+ViCheck = collections.namedtuple("ViCheck", ["elem", "tot", "out8", "e0", "logp_const", "left_out", "log_ratio", "log_weight"])
+# The report (vi_check_summary).  Floats, None where not defined: draws, elbo_final, elbo_final_se, pareto_k,
+# pareto_k_threshold, tail_length, is_ess, log_evidence, log_evidence_se, kl_estimate, kl_estimate_se; [D] float64:
+# elbo_grad_loc, elbo_grad_loc_se, elbo_grad_scale, elbo_grad_scale_se, score_gap, loc_shift, sd_ratio, is_mean, is_sd.
+ViCheckSummary = collections.namedtuple("ViCheckSummary", [
+    "draws", "elbo_final", "elbo_final_se", "pareto_k", "pareto_k_threshold", "tail_length", "is_ess", "log_evidence",
+    "log_evidence_se", "kl_estimate", "kl_estimate_se", "elbo_grad_loc", "elbo_grad_loc_se", "elbo_grad_scale",
+    "elbo_grad_scale_se", "score_gap", "loc_shift", "sd_ratio", "is_mean", "is_sd"])
+
+
+def _rows_out(t, R, D, who, name):
+    """`t`, an optional float32 [R, >= D] device matrix with unit column stride that `who` writes in place -> (t, stride)."""
+    if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.dim() == 2 and t.shape[0] == R
+            and t.shape[1] >= D and t.stride(1) == 1 and (R == 1 or t.stride(0) >= t.shape[1])):
+        raise ValueError("%s: %s must be a float32 [n_draws, >= D] matrix on the GPU with unit column stride" % (who, name))
+    return t, (int(t.stride(0)) if R > 1 else int(t.shape[1]))
+
+
+def vi_draws(loc, scale, draws, seed=0, draw_offset=0, device=None, out=None):
+    """(x, z, logq) of `arp_vi_draws`: `draws` draws x = loc + scale z from the mean-field normal, z [draws, D] float32 the
+    standard normals behind them and logq [draws] float64 = log q(x), device tensors.  loc, scale: [D], anything numpy
+    reads; a scale that is not finite and positive is refused here, before upload.  Draw r is a function of (seed,
+    draw_offset + r) alone.  out: an optional pair (x, z) of float32 [draws, >= D] device matrices of one row stride,
+    written in place in their first D columns (the others are not touched)."""
+    loc32 = np.ascontiguousarray(_lib.host64(loc).reshape(-1), np.float32)
+    scale32 = np.ascontiguousarray(_lib.host64(scale).reshape(-1), np.float32)
+    D, R = int(loc32.size), int(draws)
+    if D < 1 or scale32.size != D:
+        raise ValueError("vi_draws: loc and scale of one length D >= 1 are required")
+    if not (np.all(np.isfinite(scale32)) and np.all(scale32 > 0)):
+        raise ValueError("vi_draws: every scale must be finite and positive")
+    if not 1 <= R <= VI_MAX_DRAWS:
+        raise ValueError("vi_draws: 1 <= draws <= 2^24 is required")
+    if int(draw_offset) < 0:
+        raise ValueError("vi_draws: draw_offset >= 0 is required")
+    if out is None:
+        if device is None or torch.device(device).type != "cuda":
+            raise ValueError("vi_draws: a GPU device is required (there is no CPU fallback)")
+        dev = torch.device(device)
+        x, z = (torch.empty(R, D, dtype=torch.float32, device=dev) for _ in range(2))
+        stride = D
+    else:
+        (x, stride), (z, zs) = _rows_out(out[0], R, D, "vi_draws", "x"), _rows_out(out[1], R, D, "vi_draws", "z")
+        if zs != stride or z.device != x.device:
+            raise ValueError("vi_draws: x and z must have one row stride and one device")
+        dev = x.device
+    logq = torch.empty(R, dtype=torch.float64, device=dev)
+    loc_d, scale_d = torch.as_tensor(loc32, device=dev), torch.as_tensor(scale32, device=dev)
+    _lib.call(dev, _lib.lib().arp_vi_draws, _lib.ptr(loc_d), _lib.ptr(scale_d), D, R, int(seed) & 0xFFFFFFFFFFFFFFFF,
+              int(draw_offset), _lib.ptr(x), _lib.ptr(z), stride, _lib.ptr(logq))
+    return x, z, logq
+
+
+def psis_weights(ll, mask=None):
+    """(out, lw) of `arp_psis_weights` for ll [N, R] float32 on the GPU: out [N, 8] float64 is psis_loo's bit for bit, lw
+    [N, R] float64 the max-shifted, Pareto-smoothed log weight of every draw (raw where the row was not fitted, -inf for a
+    masked draw, NaN throughout the kept draws of a row with a non-finite kept ll).  The workspace is owned here."""
+    if not (torch.is_tensor(ll) and ll.is_cuda and ll.dtype == torch.float32 and ll.dim() == 2):
+        raise ValueError("psis_weights: a float32 [N, R] matrix on the GPU is required (there is no CPU fallback)")
+    N, R = (int(v) for v in ll.shape)
+    if N == 0 or R == 0:
+        raise ValueError("psis_weights: an empty matrix")
+    if not (ll.stride(1) == 1 and (N == 1 or ll.stride(0) >= R)):
+        ll = ll.contiguous()
+    stride = int(ll.stride(0)) if N > 1 else R
+    _lib.device_operand(mask, torch.uint8, (R,), "psis_weights", "mask", "R")
+    need = int(_lib.lib().arp_psis_weights_workspace_bytes(N, R))
+    if need <= 0:
+        raise ValueError("psis_weights: 1 <= N < 2^31 observations of 1 ... 2^24 draws are required")
+    out = torch.empty(N, 8, dtype=torch.float64, device=ll.device)
+    lw = torch.empty(N, R, dtype=torch.float64, device=ll.device)
+    _lib.call(ll.device, _lib.lib().arp_psis_weights, _lib.ptr(ll), N, R, stride, _lib.ptr(mask), _lib.ptr(out), _lib.ptr(lw), R,
+              workspace=need)
+    return out, lw
+
+
+def vi_fold(z, grad, e, ll, lw, scale, e0):
+    """(elem [D, 9], tot [5]) float64 device tensors of `arp_vi_fold` (VI_ELEM_COLUMNS, VI_TOT_COLUMNS): z, grad, e contiguous
+    float32 [R, D] on the GPU, ll [R] float32, lw [R] float64, scale and e0 [D] float32.  The workspace is owned here."""
+    if not (torch.is_tensor(z) and z.is_cuda and z.dtype == torch.float32 and z.dim() == 2 and z.is_contiguous()):
+        raise ValueError("vi_fold: z must be a contiguous float32 [R, D] matrix on the GPU (there is no CPU fallback)")
+    R, D = (int(v) for v in z.shape)
+    if R == 0 or D == 0:
+        raise ValueError("vi_fold: an empty matrix")
+    for name, t, dtype, shape, dims in (("grad", grad, torch.float32, (R, D), "R, D"), ("e", e, torch.float32, (R, D), "R, D"),
+                                        ("ll", ll, torch.float32, (R,), "R"), ("lw", lw, torch.float64, (R,), "R"),
+                                        ("scale", scale, torch.float32, (D,), "D"), ("e0", e0, torch.float32, (D,), "D")):
+        if t is None:
+            raise ValueError("vi_fold: %s is required" % name)
+        _lib.device_operand(t, dtype, shape, "vi_fold", name, dims)
+    need = int(_lib.lib().arp_vi_fold_workspace_bytes(R, D))
+    if need <= 0:
+        raise ValueError("vi_fold: 1 <= R <= 2^24 draws of 1 <= D <= 2^24 elements are required")
+    elem = torch.empty(D, len(VI_ELEM_COLUMNS), dtype=torch.float64, device=z.device)
+    tot = torch.empty(len(VI_TOT_COLUMNS), dtype=torch.float64, device=z.device)
+    _lib.call(z.device, _lib.lib().arp_vi_fold, _lib.ptr(z), _lib.ptr(grad), _lib.ptr(e), D, _lib.ptr(ll), _lib.ptr(lw),
+              _lib.ptr(scale), _lib.ptr(e0), R, D, _lib.ptr(elem), _lib.ptr(tot), workspace=need)
+    return elem, tot
+
+
+def vi_check(eng, loc, scale, which=0, draws=65536, seed=0):
+    """The device half of the check of a mean-field normal fit q = N(loc, diag(scale^2)) against the density of
+    parameterisation `which` of the engine `eng`, in that parameterisation's coordinates -> ViCheck (host arrays):
+    1. x, z, logq of vi_draws; logp and its gradient at x (Engine.logp_grad), the centred image of x and of loc
+       (Engine.transform);
+    2. ll = float32(logq - float64(logp)), the negated log importance ratio (without the density's constant);
+    3. the mask: a draw whose logp, any gradient element or any centred element is not finite is left out and counted;
+    4. psis_weights of the one row ll: the Pareto fit of the ratios' tail and every draw's smoothed weight;
+    5. vi_fold.
+    What the numbers mean is vi_check_summary's business."""
+    dev = eng.device
+    x, z, logq = vi_draws(loc, scale, draws, seed=seed, device=dev)
+    D = int(x.shape[1])
+    if D != int(eng.D):
+        raise ValueError("vi_check: loc and scale must have the engine's %d elements" % int(eng.D))
+    logp, grad = eng.logp_grad(x, which=which)
+    e = eng.transform(x, which=which, to_centered=True)
+    loc32 = np.ascontiguousarray(_lib.host64(loc).reshape(1, D), np.float32)
+    e0 = eng.transform(loc32, which=which, to_centered=True).reshape(D)
+    ll = (logq - logp.to(torch.float64)).to(torch.float32)
+    bad = ~(torch.isfinite(logp) & torch.isfinite(grad).all(dim=1) & torch.isfinite(e).all(dim=1))
+    out8, lw = psis_weights(ll.reshape(1, -1), bad.to(torch.uint8))
+    scale_d = torch.as_tensor(np.ascontiguousarray(_lib.host64(scale).reshape(D), np.float32), device=dev)
+    elem, tot = vi_fold(z, grad, e, ll, lw.reshape(-1), scale_d, e0.contiguous())
+    return ViCheck(_lib.host64(elem), _lib.host64(tot), _lib.host64(out8).reshape(8), _lib.host64(e0),
+                   float(eng.logp_const(which)), int(bad.sum().item()), (-ll).cpu().numpy(), _lib.host64(lw).reshape(-1))
+
+
+def vi_check_summary(elem, tot, out8, loc, scale, e0, logp_const):
+    """The check of a mean-field fit, the single place where its statistics are defined -> ViCheckSummary; pure numpy
+    float64.  elem [D, 9], tot [5] (arp_vi_fold: VI_ELEM_COLUMNS, VI_TOT_COLUMNS), out8 [8] (PSIS_COLUMNS of the one row of
+    negated log ratios ll = log q - log p), loc, scale [D] (q), e0 [D] (the centred image of loc), logp_const (what the
+    density leaves out of log p).  With R' = tot[0] kept draws, u = scale_d dlogp/dx_d, w the smoothed importance weights:
+      elbo_final = -sum ll / R' + const, the ELBO OF THE FINAL PARAMETERS (not the optimiser's running figure), with
+        elbo_final_se = sqrt(var(ll) / R'), var(ll) = out8[3] the two-pass variance;
+      pareto_k = out8[1] (None: no tail was fitted) against pareto_k_threshold(R'); tail_length = out8[4];
+      is_ess = (sum w)^2 / sum w^2;
+      log_evidence = -min ll + log sum w - log R' + const, the importance-sampling estimate of log Z, with
+        log_evidence_se = sqrt(1 / is_ess - 1 / R') (the delta method on the self-normalised weights);
+      kl_estimate = log_evidence - elbo_final = KL(q || p), kl_estimate_se the root sum of squares of the two se -- both are
+        functions of the same draws and their covariance is IGNORED;
+      elbo_grad_loc[d] = sum u / R' = scale_d dELBO/dloc_d, elbo_grad_scale[d] = sum u z / R' + 1 = dELBO/dlog scale_d, with
+        standard errors from the squared sums: both 0 at a stationary point whatever the posterior is;
+      score_gap[d] = sqrt(sum (u + z)^2 / R'): 0 where q's score equals the posterior's along d;
+      loc_shift[d] = sum w z / sum w (in units of q's sd), sd_ratio[d] = sqrt(sum w z^2 / sum w - loc_shift^2): the
+        importance-corrected mean and sd of z; is_mean, is_sd: the same two of the centred coordinates (e0 + ...).
+    Never raises on a check without a usable draw: everything is then None or NaN."""
+    el = np.asarray(_lib.host64(elem), np.float64)
+    t = np.asarray(_lib.host64(tot), np.float64).reshape(len(VI_TOT_COLUMNS))
+    o = np.asarray(_lib.host64(out8), np.float64).reshape(8)
+    D = int(np.asarray(loc).size)
+    el = el.reshape(D, len(VI_ELEM_COLUMNS))
+    e0 = np.asarray(_lib.host64(e0), np.float64).reshape(D)
+    if int(np.asarray(scale).size) != D:
+        raise ValueError("vi_check_summary: loc, scale and e0 of one length are required")
+    n = float(t[0])
+    num = lambda v: float(v) if np.isfinite(v) else None
+    nanv = np.full(D, np.nan)
+    if not n >= 1:
+        return ViCheckSummary(0, None, None, None, None, 0, None, None, None, None, None, *([nanv] * 9))
+    const = float(logp_const)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        elbo = -t[3] / n + const
+        elbo_se = np.sqrt(o[3] / n)
+        ess = t[1] * t[1] / t[2]
+        evidence = -t[4] + np.log(t[1]) - np.log(n) + const
+        evidence_se = np.sqrt(max(1.0 / ess - 1.0 / n, 0.0)) if np.isfinite(ess) and ess > 0 else np.nan
+        se_of_mean = lambda s1, s2: np.sqrt(np.maximum(s2 - s1 * s1 / n, 0.0) / (n - 1.0) / n) if n > 1 else nanv
+        g_loc, g_loc_se = el[:, 0] / n, se_of_mean(el[:, 0], el[:, 1])
+        g_scale, g_scale_se = el[:, 2] / n + 1.0, se_of_mean(el[:, 2], el[:, 3])
+        gap = np.sqrt(el[:, 4] / n)
+        shift = el[:, 5] / t[1]
+        ratio = np.sqrt(np.maximum(el[:, 6] / t[1] - shift * shift, 0.0))
+        cm = el[:, 7] / t[1]
+        is_sd = np.sqrt(np.maximum(el[:, 8] / t[1] - cm * cm, 0.0))
+    return ViCheckSummary(int(round(n)), num(elbo), num(elbo_se), num(o[1]), num(pareto_k_threshold(n)), int(round(o[4])),
+                          num(ess), num(evidence), num(evidence_se), num(evidence - elbo),
+                          num(np.sqrt(evidence_se * evidence_se + elbo_se * elbo_se)), g_loc, g_loc_se, g_scale, g_scale_se,
+                          gap, shift, ratio, e0 + cm, is_sd)

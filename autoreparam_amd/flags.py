@@ -110,6 +110,18 @@ _DEFS = [
                                        "posterior PIT, not LOO-PIT; no group-level statistics, no user-defined statistic.  "
                                        "Every quantity is a sum over draws: sharded jobs included.  Refused for "
                                        "neals_funnel, which has no observations."),
+    ("vi_diagnostics", bool, False, "--inference=VI: judge the mean-field FIT the sampler takes its step sizes, its initial "
+                                    "population and (cVIP, dVIP) its parameterisation from.  After the fit's clock has "
+                                    "stopped, --vi_check_draws draws from the fitted q in the coordinates of the "
+                                    "parameterisation the fit ended in (arp_vi_draws), their log importance ratios "
+                                    "log p - log q, the Pareto k-hat of the ratios' tail (arp_psis_weights; Yao, Vehtari, "
+                                    "Simpson, Gelman 2018) and one fold (arp_vi_fold): had the optimiser converged (the "
+                                    "ELBO's gradient at the final parameters), is q close to the posterior (k-hat, the "
+                                    "evidence, KL), and if so how far off are loc and scale (vi_* JSON keys, "
+                                    "<base>_vicheck.npz).  A check of the final iterate of the best learning rate only; it "
+                                    "changes no step size and no initial state.  A result file written without the flag "
+                                    "is checked from its stored fit, without refitting."),
+    ("vi_check_draws", int, 65536, "With --vi_diagnostics: the draws from q, 1024 ... 2^20."),
     ("lanes_per_chain", int, 0, "Lanes of a wave64 a chain is spread over (0 = automatic)."),
 ]
 
@@ -169,6 +181,17 @@ class FlagValues(object):
             else:
                 setattr(self, name, val)
         return rest
+
+
+VI_CHECK_DRAWS_MIN, VI_CHECK_DRAWS_MAX = 1024, 1 << 20      # the range of --vi_check_draws
+
+
+def check_vi_check_draws(value):
+    """--vi_check_draws as an int in VI_CHECK_DRAWS_MIN ... VI_CHECK_DRAWS_MAX; raises ValueError outside."""
+    value = int(value)
+    if not VI_CHECK_DRAWS_MIN <= value <= VI_CHECK_DRAWS_MAX:
+        raise ValueError("--vi_check_draws must lie in %d ... %d, not %d" % (VI_CHECK_DRAWS_MIN, VI_CHECK_DRAWS_MAX, value))
+    return value
 
 
 TRAJECTORY_PROFILE_MAX = 256      # the largest --trajectory_profile (arp_trajectory_probe's n_leapfrog_max)

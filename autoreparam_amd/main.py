@@ -20,7 +20,8 @@ from collections import OrderedDict
 import numpy as np
 
 from . import _lib, diagnostics, graphs, inference, models, parallel, util
-from .flags import FLAGS
+from . import engine as _engine
+from .flags import FLAGS, check_vi_check_draws
 
 
 def _vip_suffix(flags):
@@ -103,10 +104,137 @@ def _clean_dict(d):
                         for k in d.keys()])
 
 
+VI_CHECK_SEED = 0x56494348           # the check's own seed constant (the probes and the predictive checks have theirs)
+VI_CHECK_FAMILIES = ("elbo_grad_loc", "elbo_grad_loc_se", "elbo_grad_scale", "elbo_grad_scale_se", "score_gap", "loc_shift",
+                     "sd_ratio", "is_mean", "is_sd")
+VI_CHECK_KEYS = ("vi_check_draws", "vi_check_draws_left_out", "vi_pareto_k", "vi_pareto_k_threshold", "vi_tail_length",
+                 "vi_is_ess", "vi_elbo_final", "vi_elbo_final_se", "vi_log_evidence", "vi_log_evidence_se", "vi_kl_estimate",
+                 "vi_kl_estimate_se", "vi_elbo_grad_loc_max", "vi_elbo_grad_loc_max_se", "vi_elbo_grad_loc_max_element",
+                 "vi_elbo_grad_scale_max", "vi_elbo_grad_scale_max_se", "vi_elbo_grad_scale_max_element", "vi_score_gap_max",
+                 "vi_score_gap_max_element", "vi_loc_shift_max", "vi_loc_shift_max_element", "vi_sd_ratio_min",
+                 "vi_sd_ratio_min_element", "vi_sd_ratio_max", "vi_sd_ratio_max_element", "vi_check_time_sec")
+
+
+def check_vi_diagnostics(flags):
+    """--vi_diagnostics against the job, before anything runs: raises ValueError for --vi_check_draws outside its range."""
+    if getattr(flags, "vi_diagnostics", False):
+        check_vi_check_draws(getattr(flags, "vi_check_draws", 65536))
+
+
+def vi_check_keys(summary, draws, left_out, names):
+    """The JSON keys of the fit check (all but vi_check_time_sec) from a diagnostics.ViCheckSummary; pure Python.  Of every
+    per-element family the entry that stands out, with the element's name: the largest |gradient| (with its own value,
+    signed, and its standard error), the largest score gap and |loc shift|, the smallest and the largest sd ratio."""
+    s = summary
+    keys = OrderedDict([("vi_check_draws", int(draws)), ("vi_check_draws_left_out", int(left_out)),
+                        ("vi_pareto_k", s.pareto_k), ("vi_pareto_k_threshold", s.pareto_k_threshold),
+                        ("vi_tail_length", int(s.tail_length)), ("vi_is_ess", s.is_ess), ("vi_elbo_final", s.elbo_final),
+                        ("vi_elbo_final_se", s.elbo_final_se), ("vi_log_evidence", s.log_evidence),
+                        ("vi_log_evidence_se", s.log_evidence_se), ("vi_kl_estimate", s.kl_estimate),
+                        ("vi_kl_estimate_se", s.kl_estimate_se)])
+
+    def stands_out(key, values, rank, extra=()):
+        _, at = _nan_max(rank)
+        keys[key] = _finite_or_none(values[at]) if at >= 0 else None
+        for suffix, other in extra:
+            keys[key + suffix] = _finite_or_none(other[at]) if at >= 0 else None
+        keys[key + "_element"] = names[at] if at >= 0 else None
+    stands_out("vi_elbo_grad_loc_max", s.elbo_grad_loc, np.abs(s.elbo_grad_loc), (("_se", s.elbo_grad_loc_se),))
+    stands_out("vi_elbo_grad_scale_max", s.elbo_grad_scale, np.abs(s.elbo_grad_scale), (("_se", s.elbo_grad_scale_se),))
+    stands_out("vi_score_gap_max", s.score_gap, s.score_gap)
+    stands_out("vi_loc_shift_max", s.loc_shift, np.abs(s.loc_shift))
+    stands_out("vi_sd_ratio_min", s.sd_ratio, -np.asarray(s.sd_ratio))
+    stands_out("vi_sd_ratio_max", s.sd_ratio, s.sd_ratio)
+    return keys
+
+
+def vi_check_warning(keys):
+    """The one warning of the fit check, or None: k-hat above its threshold, or no tail fitted.  No threshold is tied to
+    the gradient figures: none can be derived (the rule of the trajectory and geometry reports)."""
+    k, cap = keys["vi_pareto_k"], keys["vi_pareto_k_threshold"]
+    if k is not None and cap is not None and k <= cap:
+        return None
+    return ("    WARNING: Pareto k-hat of the importance ratios p / q is {} (reliable up to {}): q is far from the posterior "
+            "in this parameterisation.  The importance-corrected figures (vi_loc_shift_*, vi_sd_ratio_*, is_mean, is_sd) and "
+            "vi_log_evidence / vi_kl_estimate are then unreliable (they are still written); try another --method.".format(
+                "not fitted" if k is None else _fmt(k), _fmt(cap)))
+
+
+def _fixed(v):
+    return "n/a" if v is None else "{:.4f}".format(v)
+
+
+def _fitted_q(spec, fit):
+    """(loc, scale) float32 [D] of the stored `learned_variational_params`."""
+    p = fit["learned_variational_params"]
+    flat = lambda suffix: np.concatenate([np.asarray(p[name + suffix], np.float32).reshape(-1) for name in spec.part_names])
+    return flat("_loc"), flat("_scale")
+
+
+def _vi_check_report(model_config, fit, actual_reparam, file_path, flags):
+    """--vi_diagnostics: is the mean-field fit `fit` (the keys run_vi writes) any good?  Draws from the fitted q in the
+    coordinates of the parameterisation the fit ended in -- the method's (a, b) for CP, NCP and dVIP, the learned a with b
+    as arp_vi_run read it for cVIP --, their importance ratios against that density on the device (diagnostics.vi_check)
+    and the statistics of diagnostics.vi_check_summary.  The seed is derived from --seed and VI_CHECK_SEED.  Reads nothing
+    but the stored fit, so a result file from a run without the flag gives the bits of a run with it (JSON round-trips
+    float32 exactly).  Returns the JSON keys; writes <base>_vicheck.npz."""
+    clock = time.time()
+    spec = model_config.model
+    reparam = fit.get("learned_reparam") if fit.get("learned_reparam") is not None else actual_reparam
+    a, b = spec.ab_from_reparam(reparam)
+    loc, scale = _fitted_q(spec, fit)
+    import torch
+    eng = _engine.engine_for(spec, torch.device(flags.device))
+    eng.set_param(0, (a, b))
+    draws = check_vi_check_draws(flags.vi_check_draws)
+    seed = (int(flags.seed) * 0x9E3779B97F4A7C15 + VI_CHECK_SEED) & 0xFFFFFFFFFFFFFFFF
+    chk = diagnostics.vi_check(eng, loc, scale, which=0, draws=draws, seed=seed)
+    summary = diagnostics.vi_check_summary(chk.elem, chk.tot, chk.out8, loc, scale, chk.e0, chk.logp_const)
+    keys = vi_check_keys(summary, draws, chk.left_out, element_names(spec))
+    util.print_("    fit check over {} draws from q ({} left out): Pareto k-hat {} (threshold {}), ELBO of the final parameters "
+                "{} +- {}, log evidence {} +- {}, KL(q || p) {} +- {}; largest ELBO gradient along loc {} ({}), along log scale "
+                "{} ({}); largest score gap {} ({}); importance-corrected sd / q's sd in {} ... {}".format(
+                    draws, chk.left_out, _fmt(keys["vi_pareto_k"]), _fmt(keys["vi_pareto_k_threshold"]), _fixed(keys["vi_elbo_final"]),
+                    _fmt(keys["vi_elbo_final_se"]), _fixed(keys["vi_log_evidence"]), _fmt(keys["vi_log_evidence_se"]),
+                    _fmt(keys["vi_kl_estimate"]), _fmt(keys["vi_kl_estimate_se"]), _fmt(keys["vi_elbo_grad_loc_max"]),
+                    keys["vi_elbo_grad_loc_max_element"], _fmt(keys["vi_elbo_grad_scale_max"]),
+                    keys["vi_elbo_grad_scale_max_element"], _fmt(keys["vi_score_gap_max"]), keys["vi_score_gap_max_element"],
+                    _fmt(keys["vi_sd_ratio_min"]), _fmt(keys["vi_sd_ratio_max"])))
+    warning = vi_check_warning(keys)
+    if warning:
+        util.print_(warning)
+    arrays = OrderedDict()
+    _by_part(spec, arrays, [(family, getattr(summary, family)) for family in VI_CHECK_FAMILIES])
+    arrays.update([("log_ratio", np.asarray(chk.log_ratio, np.float32)), ("log_weight", np.asarray(chk.log_weight, np.float64)),
+                   ("left_out", np.asarray(chk.left_out, np.int64))])
+    save_vicheck(file_path[:-5], arrays)
+    keys["vi_check_time_sec"] = time.time() - clock
+    return keys
+
+
+def save_vicheck(file_path_base, arrays):
+    """`<base>_vicheck.npz` (build-specific, --vi_diagnostics): per latent part `elbo_grad_loc/`, `elbo_grad_loc_se/`,
+    `elbo_grad_scale/`, `elbo_grad_scale_se/`, `score_gap/`, `loc_shift/`, `sd_ratio/`, `is_mean/`, `is_sd/`; `log_ratio` [R]
+    float32 (log p - log q of every draw, without the density's constant), `log_weight` [R] (its Pareto-smoothed,
+    max-shifted log weight; -inf for a draw left out) and `left_out`."""
+    np.savez(file_path_base + "_vicheck.npz", **arrays)
+
+
 def run_vi(model_config, results_dir, file_path, flags=FLAGS):
-    """reference main.py:234-290"""
+    """reference main.py:234-290; with --vi_diagnostics the fit check after the fit's clock has stopped, or, for a result
+    file that lacks it, from the stored fit."""
     target, model, elbo, vp, lp, actual_reparam = create_target_graph(model_config, results_dir, flags)
+    want_check = getattr(flags, "vi_diagnostics", False)
     if os.path.exists(file_path):
+        if want_check:
+            with open(file_path, "r") as f:
+                stored = json.load(f)
+            if "vi_check_draws" not in stored:
+                util.print_("fit check of the stored {}-{} fit of model {} with dataset {} (no refit)".format(
+                    flags.inference, flags.method, flags.model, flags.dataset))
+                stored.update(_vi_check_report(model_config, stored, actual_reparam, file_path, flags))
+                _write_json_atomic(file_path, stored)
+                return stored
         util.print_("Already ran experiment {}-{} on model {} with dataset {}. Skipping".format(
             flags.inference, flags.method, flags.model, flags.dataset))
         return
@@ -132,6 +260,8 @@ def run_vi(model_config, results_dir, file_path, flags=FLAGS):
         "learned_reparam": _clean_dict(learned_reparam),
         "learned_variational_params": _clean_dict(learned_variational_params),
     }
+    if want_check:
+        results.update(_vi_check_report(model_config, results, actual_reparam, file_path, flags))
     _write_json_atomic(file_path, results)
     return results
 
@@ -1362,6 +1492,7 @@ def main(argv=None, flags=FLAGS, out=None):
         raise NotImplementedError("--reparameterise_variational is not supported by this build (SURVEY.md section 2)")
     check_predictive(flags)
     check_predictive_checks(flags)
+    check_vi_diagnostics(flags)
     ws = int(os.environ.get("WORLD_SIZE", "1"))
     if ws > 1:
         # launched by torch.distributed.run: one rank per GPU, RCCL for the statistics exchange

@@ -503,6 +503,23 @@ int64_t arp_psis_workspace_bytes(int64_t n_obs, int64_t n_draws);
 int arp_psis_loo(const float* ll, int64_t n_obs, int64_t n_draws, int64_t ll_stride, const uint8_t* mask, double* out,
                  void* workspace, int64_t workspace_bytes, void* stream);
 
+/* arp_psis_loo, and the Pareto-smoothed log weight of every draw with it (csrc/psis.hip; the second launch is
+ * csrc/psis_weights.hip): ll, mask and out are arp_psis_loo's and out[n][8] is that function's on the same input BIT FOR
+ * BIT (the same kernel, launched the same way).
+ * lw [n_obs][lw_stride] double receives the max-shifted, smoothed log weights as tests/psis_ref.py: psis_row forms `lws`:
+ * a draw outside the tail takes its raw weight llmin - ll (llmin: the smallest kept ll of the row); the draw at position
+ * i < M of the ascending-ll order -- ties in ascending draw index, a stable sort -- takes the (M - 1 - i)-th smallest
+ * smoothed tail weight, truncated at 0; a row that is not fitted (M < 5, or a fit that is not finite) keeps raw weights
+ * throughout; a masked draw takes -inf; every kept draw of a row with a non-finite kept ll takes NaN.  Raw positions are
+ * exact (one float64 subtraction of two float32 values); smoothed ones carry the error of the fit (csrc/psis.hip).  The
+ * tail's members find their rank by counting among themselves (at most 12 288), integers only; no float atomics: two
+ * calls give bitwise equal out and lw.  The workspace (arp_psis_weights_workspace_bytes: arp_psis_loo's and one 64-bit
+ * word per tail member; 0 for a shape that is refused) is the caller's, 256-byte aligned.  Asynchronous; device pointers.
+ * Refused before any launch: what arp_psis_loo refuses, a NULL lw, lw_stride < n_draws. */
+int64_t arp_psis_weights_workspace_bytes(int64_t n_obs, int64_t n_draws);
+int arp_psis_weights(const float* ll, int64_t n_obs, int64_t n_draws, int64_t ll_stride, const uint8_t* mask, double* out,
+                     double* lw, int64_t lw_stride, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* Posterior predictive check (csrc/ppc.hip; Gelman, Meng, Stern 1996; BDA3 ch. 6): replicated observations of recorded
  * draws, folded on the device.  The trace x, the table and the observation range [n0, n1) are those of
  * arp_pointwise_loglik (same addressing, same row_stride rule, 1 <= D <= 255, 1 <= T <= 4096), and eta_n, s_n are its
@@ -540,6 +557,38 @@ int arp_predictive_check(const float* x, int64_t n_samples, int64_t n_chains, in
                          const float* log_scale, int64_t n0, int64_t n1, uint64_t seed, int64_t draw_offset,
                          double* draw_stats, double* obs_sums, float* y_rep, int64_t y_rep_stride, uint8_t* mask,
                          int64_t* n_masked, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* Check of a mean-field normal fit (csrc/vicheck.hip; Yao, Vehtari, Simpson, Gelman 2018, "Yes, but did it work?"): draws
+ * from q = N(loc, diag(scale^2)) in the coordinates the fit was made in.  For draw r, g = draw_offset + r, and element
+ * d = 4 e + i: ONE call philox4x32_10(counter = (e, lo32(g), hi32(g), 0), key = (lo32(seed), hi32(seed))) per (r, e); words
+ * (0, 1) give z[4 e] = rho * cospi(2 a) and z[4 e + 1] = rho * sinpi(2 a), words (2, 3) give z[4 e + 2] and z[4 e + 3] the
+ * same way, rho = sqrt(-2 log(u')), with u' and a formed from their two words exactly as arp_predictive_check forms them,
+ * through logf, sqrtf, cospif and sinpif:  |z_dev - z| <= 18 * 2^-24 |z| to first order (csrc/ppc.hip's derivation; sinpi
+ * has cospi's ulp figure).  Outputs (device memory): z and x [n_draws][row_stride] float, x = fmaf(scale[d], z, loc[d]),
+ * columns d >= D are not touched;  logq [n_draws] double = -sum_d (z_d^2 / 2 + log(scale_d)) - (D / 2) log(2 pi), in
+ * float64 from the float32 z, in ascending d.  No result depends on the launch shape: rows [0, n) at draw_offset k equal
+ * rows [k, k + n) at offset 0, bit for bit.  Asynchronous.  Refused before any launch: a NULL pointer, D < 1, n_draws < 1
+ * or above 2^24, row_stride < D, more than 2^35 values, draw_offset < 0.  The scale is not checked here (a scale that is
+ * not finite and positive gives NaN): the Python wrapper refuses it before upload. */
+int arp_vi_draws(const float* loc, const float* scale, int32_t D, int64_t n_draws, uint64_t seed, int64_t draw_offset,
+                 float* x, float* z, int64_t row_stride, double* logq, void* stream);
+
+/* Fold of a fit check (csrc/vicheck.hip): ONE pass over z (arp_vi_draws), grad (arp_logp_grad at x) and e (the centred
+ * image of x, arp_transform), all [n_draws][row_stride] float, with ll [n_draws] float (the negated log ratio
+ * log q - log p), lw [n_draws] double (arp_psis_weights), scale [D] and e0 [D] (the centred image of loc).  Every sum is
+ * over the draws with lw > -inf (a draw the caller left out has lw = -inf; NaN does not count either), in float64.  With
+ * u = scale_d * grad[r][d], c = e[r][d] - e0[d], w = exp(lw[r]):
+ *   elem [D][9] = {sum u, sum u^2, sum u z, sum (u z)^2, sum (u + z)^2, sum w z, sum w z^2, sum w c, sum w c^2}
+ *   tot [5]     = {kept draws, sum w, sum w^2, sum ll, min ll}
+ * The rows are tiled and a second launch adds the tiles' partials in ascending order: fixed order, no float atomics, two
+ * calls give bitwise equal output; tot[0] and tot[4] are exact.  The workspace (arp_vi_fold_workspace_bytes: the tiles'
+ * partials; 0 for a shape that is refused) is the caller's, 256-byte aligned.  Asynchronous; device pointers.  Refused
+ * before any launch: a NULL pointer, D < 1 or above 2^24, n_draws < 1 or above 2^24, row_stride < D, a workspace that is
+ * missing, too small or misaligned. */
+int64_t arp_vi_fold_workspace_bytes(int64_t n_draws, int32_t D);
+int arp_vi_fold(const float* z, const float* grad, const float* e, int64_t row_stride, const float* ll, const double* lw,
+                const float* scale, const float* e0, int64_t n_draws, int32_t D, double* elem, double* tot, void* workspace,
+                int64_t workspace_bytes, void* stream);
 
 /* Test hook: the step-size adaptation recurrence of the chain kernels on SCRIPTED log acceptance ratios
  * (tfp.mcmc.DualAveragingStepSizeAdaptation / SimpleStepSizeAdaptation as wired at inference.py:224-226, 288-306;
