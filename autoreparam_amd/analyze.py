@@ -237,7 +237,9 @@ def report_geometry(results, results_dir=None, model_name=None):
 def report_loo(results):
     """Build-specific: the predictive report of every sampling run that recorded one (--predictive_diagnostics; the last
     run of each file): elpd_loo and elpd_waic with their standard errors, the effective numbers of parameters, and the
-    worst Pareto k-hat against its threshold.  No r_eff correction, no moment matching, no K-fold."""
+    worst Pareto k-hat against its threshold.  No r_eff correction, no moment matching, no K-fold.  A run with
+    --loo_predictive gets a second line: the calibration of the LOO-PIT (with the posterior PIT's of --predictive_checks
+    next to it where recorded), RMSE and R^2 or Brier score and accuracy, and the smallest importance-sampling ESS."""
     lines = []
     for m, r in results.items():
         if "loo_observations" not in r:
@@ -254,6 +256,23 @@ def report_loo(results):
                          last["loo_observations"], last["loo_draws"], last["loo_chains"], last["loo_draws_left_out"],
                          last["loo_nonfinite_observations"],
                          _secs(last.get("loo_time_sec"))))
+        if last.get("loo_pred_observations") is not None:
+            # the leave-one-out predictive report (--loo_predictive); next to the posterior figures of --predictive_checks
+            # where the run recorded them: a posterior PIT that looks better calibrated than the LOO-PIT is the optimism
+            # of checking an observation against a posterior that has seen it
+            post = _last(r, "ppc_")
+            beside = lambda key: " (posterior {})".format(_fmt(post[key])) if post.get(key) is not None else ""
+            shown = [("LOO-PIT Kolmogorov distance", "loo_pit_ks", beside("ppc_pit_ks")),
+                     ("90 % coverage", "loo_coverage_90", beside("ppc_coverage_90")), ("RMSE", "loo_rmse", ""),
+                     ("R^2", "loo_r2", ""), ("Brier score", "loo_brier", ""), ("accuracy", "loo_accuracy", ""),
+                     ("balanced accuracy", "loo_balanced_accuracy", "")]
+            lines.append("      LOO predictive: {}; {} observations, {} left out; smallest importance-sampling ESS {} "
+                         "(observation {}); {}".format(
+                             ", ".join("{} {}{}".format(name, _fmt(last[key]), more) for name, key, more in shown
+                                       if last.get(key) is not None) or "no figure is defined",
+                             last["loo_pred_observations"], last.get("loo_pred_observations_left_out"),
+                             _fmt(last.get("loo_is_ess_min")), last.get("loo_is_ess_min_observation"),
+                             _secs(last.get("loo_pred_time_sec"))))
     return lines
 
 

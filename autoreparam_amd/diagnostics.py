@@ -15,7 +15,9 @@ condition number; `scale_coupling`, `coupling_from_sums`: the funnel detector); 
 and not the sampler, PSIS-LOO and WAIC (`pointwise_loglik` on `arp_pointwise_loglik`, `psis_loo` on `arp_psis_loo`;
 `loo_summary`, `loo_compare`, `pareto_k_threshold`: the host float64 folds) and the posterior predictive check
 (`predictive_check` on `arp_predictive_check`: replicated observations folded on the device; `combine_draw_stats`,
-`ppc_summary`: the test statistics, their p-values, the per-observation predictive moments and the PIT calibration); and
+`ppc_summary`: the test statistics, their p-values, the per-observation predictive moments and the PIT calibration) with
+its leave-one-out counterpart (`loo_predictive` on `arp_loo_predictive`: the same predictive quantities folded with the
+smoothed weights of `psis_weights`; `loo_predictive_summary`: the LOO predictive mean and sd, the LOO-PIT); and
 the one report that judges the variational fit the sampler inherits its steps and its start from (`vi_check` on
 `arp_vi_draws`, `arp_psis_weights` and `arp_vi_fold`; `vi_check_summary`: the Pareto k-hat of the importance ratios p / q,
 the ELBO and its gradient at the final parameters, the importance-corrected loc and scale; Yao et al. 2018).
@@ -755,6 +757,16 @@ def ppc_counts(draw_stats, y, mask=None):
     return out
 
 
+def _pit_calibration(pit):
+    """(pit_ks, coverage_90) of a non-empty vector of PIT values: the Kolmogorov distance of their empirical distribution
+    from the uniform, and the share of them in [0.05, 0.95].  One definition for the posterior PIT (ppc_from_counts) and
+    the leave-one-out PIT (loo_predictive_summary)."""
+    s = np.sort(pit)
+    i = np.arange(1, s.size + 1, dtype=np.float64)
+    ks = float(max(np.max(i / s.size - s), np.max(s - (i - 1.0) / s.size)))
+    return ks, float(np.mean((pit >= 0.05) & (pit <= 0.95)))
+
+
 def ppc_from_counts(counts, obs_sums, y, kind):
     """The report from the (all-reduced) vector of `ppc_counts`, the (all-reduced) [N, 4] obs_sums and y -> PpcSummary;
     pure numpy float64.  Never raises on a job without a usable draw: everything is then None or NaN."""
@@ -781,12 +793,7 @@ def ppc_from_counts(counts, obs_sums, y, kind):
         sd = np.sqrt(np.maximum(o[:, 1] / used - mean * mean, 0.0)) if used else nan
         pit = o[:, 2] / used if used else nan
         le = o[:, 3] / used if used else nan
-    ks = coverage = None
-    if normal and used and y.size:
-        s = np.sort(pit)
-        i = np.arange(1, s.size + 1, dtype=np.float64)
-        ks = float(max(np.max(i / s.size - s), np.max(s - (i - 1.0) / s.size)))
-        coverage = float(np.mean((pit >= 0.05) & (pit <= 0.95)))
+    ks, coverage = _pit_calibration(pit) if normal and used and y.size else (None, None)
     return PpcSummary(used, left, int(y.size), p, rep, obs, mean, sd, pit, le, ks, coverage)
 
 
@@ -797,10 +804,102 @@ def ppc_summary(draw_stats, obs_sums, y, kind, mask=None):
     Test statistics T in PPC_STATISTICS: T_obs of mean, sd (divisor N - 1), min and max from y itself; the observed
     deviance is per draw (a realised discrepancy); p_T = #{r used: T_rep,r >= T_obs(,r)} / R_used, a tie counting as >=.
     For Bernoulli data sd, min and max are functions of the mean or trivial: None.  Per observation: the predictive mean,
-    the predictive sd sqrt(E[mu^2 + var] - mean^2), the posterior PIT (NOT the leave-one-out PIT) and its empirical
+    the predictive sd sqrt(E[mu^2 + var] - mean^2), the posterior PIT (the leave-one-out PIT: loo_predictive) and its empirical
     counterpart #{y_rep <= y} / R_used.  Calibration, Normal data only: pit_ks and coverage_90.  = ppc_from_counts of
     ppc_counts: a job whose draws are spread over ranks adds the counts and obs_sums of its ranks first."""
     return ppc_from_counts(ppc_counts(draw_stats, y, mask), obs_sums, y, kind)
+
+
+# ---- leave-one-out predictive report: the predictive quantities folded with the PSIS weights (csrc/loopred.hip) ----
+LOO_PRED_COLUMNS = ("sum_w", "sum_w_sq", "sum_w_mu", "sum_w_second_moment", "sum_w_pit", "draws_counted")
+# The report (loo_predictive_summary).  observations: those whose four figures are finite; left_out: the others.  loo_mean,
+# loo_sd, loo_pit, is_ess: [N] float64 per observation (NaN where there is nothing to divide by).  Floats, None where not
+# defined for the data kind or the data: pit_ks, coverage_90, rmse, r2 (Normal); brier, accuracy, balanced_accuracy
+# (Bernoulli); is_ess_min and is_ess_min_observation (-1: none) for both.
+LooPredSummary = collections.namedtuple("LooPredSummary", ["observations", "left_out", "loo_mean", "loo_sd", "loo_pit", "is_ess",
+                                                           "pit_ks", "coverage_90", "rmse", "r2", "brier", "accuracy",
+                                                           "balanced_accuracy", "is_ess_min", "is_ess_min_observation"])
+
+
+def loo_predictive_workspace_bytes(N, R):
+    """Bytes of device workspace `loo_predictive` takes for N observations of R draws; raises on a shape that is refused."""
+    need = int(_lib.lib().arp_loo_predictive_workspace_bytes(int(N), int(R)))
+    if need <= 0:
+        raise ValueError("loo_predictive: 1 <= N < 2^31 observations of 1 ... 2^31 - 1 draws are required")
+    return need
+
+
+def loo_predictive(trace, table, lw, n0=0, n1=None):
+    """obs_sums [n1 - n0, 6] float64 device tensor of `arp_loo_predictive` (LOO_PRED_COLUMNS) for a recorded CENTRED
+    [S, C, D] float32 trace on the GPU, the observations [n0, n1) of a DeviceTable and lw, a float64 [>= n1 - n0, >= S C]
+    device matrix with unit column stride: lw[n - n0, s C + c] is the log weight of draw (s, c) for observation n
+    (psis_weights' lw of pointwise_loglik's ll over the same draws and the same range).  Per observation, over the draws
+    with lw != -inf and W = exp(lw): sum W, sum W^2, sum W mu, sum W (mu^2 + var), sum W pit and the draws counted, mu, var
+    and pit as predictive_check defines them.  A block of chains of a wider trace is read in place; the workspace is
+    owned here."""
+    x, S, Cn, D, row_stride = _lib.trace_view(trace, "loo_predictive")
+    n1 = table.N if n1 is None else int(n1)
+    n0 = int(n0)
+    if not 0 <= n0 < n1 <= table.N:
+        raise ValueError("loo_predictive: 0 <= n0 < n1 <= %d observations is required" % table.N)
+    R = S * Cn
+    if R == 0 or D == 0:
+        raise ValueError("loo_predictive: an empty trace")
+    if not (torch.is_tensor(lw) and lw.is_cuda and lw.dtype == torch.float64 and lw.dim() == 2 and lw.shape[0] >= n1 - n0
+            and lw.shape[1] >= R and lw.stride(1) == 1 and (lw.stride(0) >= R or lw.shape[0] == 1)):
+        raise ValueError("loo_predictive: lw must be a float64 [>= n1 - n0, >= S C] matrix on the GPU with unit column stride")
+    lw_stride = int(lw.stride(0)) if lw.shape[0] > 1 else max(R, int(lw.shape[1]))
+    obs_sums = torch.empty(n1 - n0, len(LOO_PRED_COLUMNS), dtype=torch.float64, device=x.device)
+    _lib.call(x.device, _lib.lib().arp_loo_predictive, _lib.ptr(x), S, Cn, D, row_stride, table.kind, _lib.ptr(table.idx),
+              _lib.ptr(table.w), table.T, _lib.ptr(table.y), _lib.ptr(table.scale_idx), _lib.ptr(table.log_scale), n0, n1,
+              _lib.ptr(lw), lw_stride, _lib.ptr(obs_sums), workspace=loo_predictive_workspace_bytes(n1 - n0, R))
+    return obs_sums
+
+
+def loo_predictive_summary(obs_sums, y, kind):
+    """The leave-one-out predictive report, the single place where its statistics are defined -> LooPredSummary; pure
+    numpy float64.  obs_sums [N, 6] (LOO_PRED_COLUMNS: S0 ... S5), y [N], kind 0 (Normal) or 1 (Bernoulli-logit).  Per
+    observation, the self-normalised importance-sampling estimates under the weights behind the sums (Vehtari, Gelman,
+    Gabry 2017): loo_mean = S2 / S0, loo_sd = sqrt(max(S3 / S0 - loo_mean^2, 0)), loo_pit = S4 / S0, is_ess = S0^2 / S1.
+    An observation counts when all four are finite; the others are counted as left out and enter no total.  Normal data:
+    pit_ks and coverage_90 of the LOO-PIT values (ppc_summary's definition on another input), rmse = sqrt(mean (y -
+    loo_mean)^2), r2 = 1 - sum (y - loo_mean)^2 / sum (y - mean y)^2 (None for fewer than two observations or constant y).
+    Bernoulli data: brier = mean (y - loo_mean)^2, accuracy = the share with (loo_mean > 0.5) == (y > 0.5),
+    balanced_accuracy = the mean of the two per-class shares (None when a class is absent); the mid-p PIT of a binary
+    outcome says nothing, so pit_ks and coverage_90 are None, ppc_summary's rule.  Both: is_ess_min and its observation.
+    No r_eff, no quantiles, no moment matching; the figures of an observation with a high Pareto k-hat are as unreliable
+    as its elpd_loo.  Never raises on degenerate sums: everything is then None or NaN."""
+    o = _lib.host64(obs_sums).reshape(-1, len(LOO_PRED_COLUMNS))
+    y = np.asarray(_lib.host64(y), np.float64).reshape(-1)
+    if o.shape[0] != y.size:
+        raise ValueError("loo_predictive_summary: obs_sums must have one row per observation")
+    normal = int(kind) == 0
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        mean = o[:, 2] / o[:, 0]
+        sd = np.sqrt(np.maximum(o[:, 3] / o[:, 0] - mean * mean, 0.0))
+        pit = o[:, 4] / o[:, 0]
+        ess = o[:, 0] * o[:, 0] / o[:, 1]
+    ok = np.isfinite(mean) & np.isfinite(sd) & np.isfinite(pit) & np.isfinite(ess)
+    n = int(ok.sum())
+    ks = coverage = rmse = r2 = brier = accuracy = balanced = ess_min = None
+    at = -1
+    if n:
+        yk, mk = y[ok], mean[ok]
+        sq = (yk - mk) ** 2
+        at = int(np.flatnonzero(ok)[np.argmin(ess[ok])])
+        ess_min = float(ess[at])
+        if normal:
+            ks, coverage = _pit_calibration(pit[ok])
+            rmse = float(np.sqrt(np.mean(sq)))
+            total = float(np.sum((yk - np.mean(yk)) ** 2))
+            r2 = float(1.0 - np.sum(sq) / total) if n >= 2 and total > 0 else None
+        else:
+            brier = float(np.mean(sq))
+            hit = (mk > 0.5) == (yk > 0.5)
+            accuracy = float(np.mean(hit))
+            pos = yk > 0.5
+            balanced = float(0.5 * (np.mean(hit[pos]) + np.mean(hit[~pos]))) if pos.any() and (~pos).any() else None
+    return LooPredSummary(n, int(y.size) - n, mean, sd, pit, ess, ks, coverage, rmse, r2, brier, accuracy, balanced, ess_min, at)
 
 
 # ---- check of a mean-field fit: draws from q, Pareto-smoothed importance ratios, one fold (csrc/vicheck.hip, psis.hip) ----

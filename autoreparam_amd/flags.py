@@ -107,9 +107,21 @@ _DEFS = [
                                        "Gelman, Meng, Stern 1996), folded on the device: posterior predictive p-values of "
                                        "the mean, sd, min, max and deviance, the predictive mean and sd of every observation "
                                        "and its PIT value with their calibration (ppc_* JSON keys, <base>_ppc.npz).  The "
-                                       "posterior PIT, not LOO-PIT; no group-level statistics, no user-defined statistic.  "
+                                       "posterior PIT (the leave-one-out PIT: --loo_predictive); no group-level statistics, "
+                                       "no user-defined statistic.  "
                                        "Every quantity is a sum over draws: sharded jobs included.  Refused for "
                                        "neals_funnel, which has no observations."),
+    ("loo_predictive", bool, False, "With --predictive_diagnostics only: the leave-one-out predictive report.  The predictive "
+                                    "mean, variance and PIT value of every observation at every draw, folded with the "
+                                    "Pareto-smoothed weights of its own leave-one-out posterior (arp_psis_weights, "
+                                    "arp_loo_predictive; Vehtari, Gelman, Gabry 2017): the LOO predictive mean and sd and the "
+                                    "LOO-PIT of every observation -- the honest counterpart of the posterior PIT of "
+                                    "--predictive_checks -- with their calibration, RMSE and R^2 (Normal data) or Brier "
+                                    "score and accuracy (Bernoulli data) (loo_pred_*, loo_pit_*, loo_* JSON keys, "
+                                    "<base>_loopred.npz).  No r_eff, no predictive quantiles or intervals, no moment "
+                                    "matching; an observation with a high Pareto k-hat is as unreliable here as its "
+                                    "elpd_loo.  Every other output of --predictive_diagnostics is bit for bit unchanged.  "
+                                    "One process only: a sharded job writes null."),
     ("vi_diagnostics", bool, False, "--inference=VI: judge the mean-field FIT the sampler takes its step sizes, its initial "
                                     "population and (cVIP, dVIP) its parameterisation from.  After the fit's clock has "
                                     "stopped, --vi_check_draws draws from the fitted q in the coordinates of the "

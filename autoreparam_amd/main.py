@@ -369,12 +369,12 @@ def _convergence_report(kernel_results, model_config, flags, dev):
     trace = getattr(kernel_results, "trace", None)
     if not getattr(flags, "convergence_diagnostics", True) or trace is None:
         if getattr(flags, "convergence_diagnostics", True) and getattr(flags, "predictive_checks", False):
-            keys = _loo_null("no chain has its trace on the device") if getattr(flags, "predictive_diagnostics", False) \
+            keys = _loo_null("no chain has its trace on the device", flags) if getattr(flags, "predictive_diagnostics", False) \
                 else OrderedDict()
             keys.update(_ppc_null("no chain has its trace on the device"))
             return keys, None
         if getattr(flags, "convergence_diagnostics", True) and getattr(flags, "predictive_diagnostics", False):
-            return _loo_null("no chain has its trace on the device"), None
+            return _loo_null("no chain has its trace on the device", flags), None
         return {}, None
     clock = time.time()
     spec = model_config.model
@@ -432,7 +432,7 @@ def _convergence_report(kernel_results, model_config, flags, dev):
             (getattr(flags, "geometry_diagnostics", False), GEOMETRY_ARRAYS,
              lambda: _geometry_report(kernel_results, trace, k, spec, flags, dev, split.mean)),
             (getattr(flags, "predictive_diagnostics", False), LOO_ARRAYS,
-             lambda: _loo_report(kernel_results, trace, k, spec, flags)),
+             lambda: _loo_report(kernel_results, trace, k, spec, flags, arrays)),     # (--loo_predictive: a second tag)
             (getattr(flags, "predictive_checks", False), PPC_ARRAYS,               # (n_split: already all-reduced)
              lambda: _ppc_report(kernel_results, trace, k, n_split, spec, flags, dev))):
         if asked:
@@ -776,11 +776,19 @@ LOO_CHUNK_BYTES = 256 << 20          # a tile's [observations, draws] float32 lo
 LOO_KEYS = ("loo_draws", "loo_draws_left_out", "loo_chains", "loo_steps", "loo_observations", "elpd_loo", "elpd_loo_se",
             "p_loo", "elpd_waic", "elpd_waic_se", "p_waic", "pareto_k_max", "pareto_k_max_observation",
             "pareto_k_threshold", "pareto_k_above_threshold", "loo_nonfinite_observations", "loo_time_sec")
+LOO_PRED_ARRAYS = "loopred/"         # where _loo_report leaves the arrays of <base>_loopred.npz (--loo_predictive)
+LOO_PRED_KEYS = ("loo_pred_observations", "loo_pred_observations_left_out", "loo_pit_ks", "loo_coverage_90", "loo_rmse",
+                 "loo_r2", "loo_brier", "loo_accuracy", "loo_balanced_accuracy", "loo_is_ess_min",
+                 "loo_is_ess_min_observation", "loo_pred_time_sec")
 
 
 def check_predictive(flags):
-    """--predictive_diagnostics against the job, before anything runs: raises ValueError for a model without
-    observations (neals_funnel), whose pointwise log-likelihood does not exist."""
+    """--predictive_diagnostics and --loo_predictive against the job, before anything runs: raises ValueError for a model
+    without observations (neals_funnel), whose pointwise log-likelihood does not exist, and for --loo_predictive without
+    the report it extends."""
+    if getattr(flags, "loo_predictive", False) and not getattr(flags, "predictive_diagnostics", False):
+        raise ValueError("--loo_predictive: --predictive_diagnostics is required (the report folds the predictive "
+                         "quantities with the weights of its Pareto fits)")
     if getattr(flags, "predictive_diagnostics", False) and flags.model == "neals_funnel":
         raise ValueError("--predictive_diagnostics: neals_funnel has no observations, so there is no pointwise "
                          "log-likelihood to cross-validate")
@@ -802,10 +810,24 @@ def loo_tile_rows(N, R, budget=None):
     return int(max(1, min(max(int(N), 1), budget // max(1, 4 * int(R)))))
 
 
-def _loo_null(why):
-    """Every key of the predictive report as null, with the one message that says why."""
+def _loo_null(why, flags=None):
+    """Every key of the predictive report as null, with the one message that says why; with --loo_predictive those of the
+    leave-one-out predictive report too (no message of their own)."""
     util.print_("    PSIS-LOO / WAIC: not computed, {}".format(why))
-    return OrderedDict((key, None) for key in LOO_KEYS)
+    return OrderedDict((key, None) for key in LOO_KEYS + (LOO_PRED_KEYS if getattr(flags, "loo_predictive", False) else ()))
+
+
+def loo_pred_keys(summary):
+    """The JSON keys of the leave-one-out predictive report (all but loo_pred_time_sec) from a
+    diagnostics.LooPredSummary; pure Python."""
+    num = lambda v: None if v is None else _finite_or_none(v)
+    at = int(summary.is_ess_min_observation)
+    return OrderedDict([
+        ("loo_pred_observations", int(summary.observations)), ("loo_pred_observations_left_out", int(summary.left_out)),
+        ("loo_pit_ks", num(summary.pit_ks)), ("loo_coverage_90", num(summary.coverage_90)), ("loo_rmse", num(summary.rmse)),
+        ("loo_r2", num(summary.r2)), ("loo_brier", num(summary.brier)), ("loo_accuracy", num(summary.accuracy)),
+        ("loo_balanced_accuracy", num(summary.balanced_accuracy)), ("loo_is_ess_min", num(summary.is_ess_min)),
+        ("loo_is_ess_min_observation", at if at >= 0 else None)])
 
 
 def loo_keys(columns, R, left_out, n_chains, n_steps):
@@ -829,7 +851,7 @@ def loo_keys(columns, R, left_out, n_chains, n_steps):
         ("loo_nonfinite_observations", int(np.sum(~np.isfinite(c[:, 0]))))])
 
 
-def _loo_report(kernel_results, trace, k, spec, flags):
+def _loo_report(kernel_results, trace, k, spec, flags, side=None):
     """--predictive_diagnostics: how well does this MODEL predict an observation it has not seen?  Over the leading `k`
     chains of the device trace -- the chains split R-hat covers -- and clamp(--loo_draws // k, 1, S) evenly spaced recorded
     steps (loo_steps): the pointwise log-likelihood of every observation at every draw (diagnostics.pointwise_loglik, from
@@ -838,31 +860,47 @@ def _loo_report(kernel_results, trace, k, spec, flags):
     per-observation columns are folded on the host (loo_keys).  A tail fit needs all draws of an observation in one place:
     a sharded job (world size > 1) writes null, says so once, and enters no collective -- the rule of the rank reports.
     No r_eff correction of the Monte-Carlo error, no moment matching or refits for high k-hat, no K-fold.
+    --loo_predictive: the leave-one-out predictive report on the same draws.  A tile then holds the float64 log weights
+    next to its log-likelihoods (a third of the rows, the two together within LOO_CHUNK_BYTES); diagnostics.psis_weights
+    takes psis_loo's place -- the same columns bit for bit, and no column depends on the tiling, so every LOO_KEYS value
+    and every array of <base>_loo.npz is the unflagged run's -- and diagnostics.loo_predictive folds mu, mu^2 + var and the
+    PIT of every (observation, draw) with those weights; the per-observation sums are turned into the report on the host
+    (diagnostics.loo_predictive_summary -> LOO_PRED_KEYS; no threshold can be derived for them, so no warning) and the
+    arrays of <base>_loopred.npz are left in `side` under LOO_PRED_ARRAYS.  The keys are null whenever the report is.
     Returns (JSON keys, arrays of <base>_loo.npz or None)."""
     import torch
+    pred = bool(getattr(flags, "loo_predictive", False))
     if parallel.world()[1] > 1:
         return _loo_null("the chains of a sharded job are on several devices (a tail fit needs all draws of an "
-                         "observation on one)"), None
+                         "observation on one)", flags), None
     clock = time.time()
     S, _, D = (int(v) for v in trace.shape)
     k = int(k) if S > 0 else 0
     if k <= 0:
-        return _loo_null("no chain has its trace on the device"), None
+        return _loo_null("no chain has its trace on the device", flags), None
     if D > diagnostics.LOGLIK_MAX_D:
-        return _loo_null("the model has more than {} elements".format(diagnostics.LOGLIK_MAX_D)), None
+        return _loo_null("the model has more than {} elements".format(diagnostics.LOGLIK_MAX_D), flags), None
     steps = loo_steps(S, k, getattr(flags, "loo_draws", 65536))
     if not steps:
-        return _loo_null("more than {} chains".format(diagnostics.PSIS_MAX_DRAWS)), None
+        return _loo_null("more than {} chains".format(diagnostics.PSIS_MAX_DRAWS), flags), None
     table = diagnostics.upload_table(spec.observation_table(), D, trace.device)
     draws = trace[torch.as_tensor(steps, device=trace.device), :k].contiguous()      # [len(steps), k, D]: a copy, D floats a draw
     R, N = len(steps) * k, table.N
-    rows = loo_tile_rows(N, R)
+    rows = loo_tile_rows(N, R, LOO_CHUNK_BYTES // 3) if pred else loo_tile_rows(N, R)
     ll_buffer = torch.empty(rows, R, dtype=torch.float32, device=trace.device)
-    columns, left_out = [], 0
+    columns, sums, left_out, pred_time = [], [], 0, 0.0
     for n0 in range(0, N, rows):
         n1 = min(N, n0 + rows)
         ll, mask, n_masked = diagnostics.pointwise_loglik(draws, table, n0, n1, out=ll_buffer)
-        columns.append(diagnostics.psis_loo(ll, mask).cpu().numpy())
+        if pred:
+            out8, lw = diagnostics.psis_weights(ll, mask)
+            columns.append(out8.cpu().numpy())
+            pred_clock = time.time()                                      # (the copy above waited for the fits)
+            sums.append(diagnostics.loo_predictive(draws, table, lw, n0, n1).cpu().numpy())
+            pred_time += time.time() - pred_clock
+            del lw
+        else:
+            columns.append(diagnostics.psis_loo(ll, mask).cpu().numpy())
         left_out = int(n_masked.item())                                   # (the same draws for every tile)
     del ll_buffer
     c = np.concatenate(columns, axis=0)
@@ -878,6 +916,24 @@ def _loo_report(kernel_results, trace, k, spec, flags):
                         _fmt(keys["pareto_k_threshold"]), keys["pareto_k_above_threshold"], N))
     arrays = OrderedDict([("elpd_loo_i", c[:, 0]), ("pareto_k", c[:, 1]), ("lppd_i", c[:, 2]), ("p_waic_i", c[:, 3]),
                           ("y", np.asarray(table.y_host, np.float32)), ("model", np.asarray(spec.name))])
+    if pred:
+        pred_clock = time.time()
+        summary = diagnostics.loo_predictive_summary(np.concatenate(sums, axis=0), table.y_host, table.kind)
+        more = loo_pred_keys(summary)
+        shown = (("LOO-PIT Kolmogorov distance", "loo_pit_ks"), ("90 % coverage", "loo_coverage_90"), ("RMSE", "loo_rmse"),
+                 ("R^2", "loo_r2")) if table.kind == 0 else \
+            (("Brier score", "loo_brier"), ("accuracy", "loo_accuracy"), ("balanced accuracy", "loo_balanced_accuracy"))
+        util.print_("    LOO predictive report over {} observations ({} left out, not finite): {}; smallest importance-sampling "
+                    "ESS {} (observation {})".format(
+                        more["loo_pred_observations"], more["loo_pred_observations_left_out"],
+                        ", ".join("{} {}".format(name, _fmt(more[key])) for name, key in shown), _fmt(more["loo_is_ess_min"]),
+                        more["loo_is_ess_min_observation"]))
+        if side is not None:
+            side[LOO_PRED_ARRAYS] = OrderedDict([
+                ("loo_mean", summary.loo_mean), ("loo_sd", summary.loo_sd), ("loo_pit", summary.loo_pit),
+                ("loo_is_ess", summary.is_ess), ("y", np.asarray(table.y_host, np.float32)), ("model", np.asarray(spec.name))])
+        keys.update(more)
+        keys["loo_pred_time_sec"] = pred_time + (time.time() - pred_clock)
     keys["loo_time_sec"] = time.time() - clock
     return keys, arrays
 
@@ -887,6 +943,14 @@ def save_loo(file_path_base, arrays):
     tail was fitted), `lppd_i` and `p_waic_i` [N] float64; `y` [N], the observations themselves -- what
     diagnostics.loo_compare pairs two models by -- and `model`, the model's name."""
     np.savez(file_path_base + "_loo.npz", **arrays)
+
+
+def save_loo_pred(file_path_base, arrays):
+    """`<base>_loopred.npz` (build-specific, --loo_predictive): per observation `loo_mean`, `loo_sd`, `loo_pit` and
+    `loo_is_ess` [N] float64 (NaN where the weights leave nothing to divide by); `y` [N], the observations themselves;
+    `model`, the model's name.  The rows of observations with a high `pareto_k` in <base>_loo.npz are as unreliable as
+    their `elpd_loo_i`."""
+    np.savez(file_path_base + "_loopred.npz", **arrays)
 
 
 PPC_ARRAYS = "ppc/"                  # where _convergence_report leaves the arrays of <base>_ppc.npz
@@ -945,7 +1009,7 @@ def _ppc_report(kernel_results, trace, k, k_total, spec, flags, dev):
     draw number), the seed derived from --seed and PPC_SEED; a rank's first global draw number is its chain offset times
     the number of steps.  Every quantity is a sum over draws: the counts behind the p-values and the per-observation sums go
     through ONE all-reduce, and a sharded job reports real numbers (rank 0 writes them; <base>_ppc.npz then holds the
-    draw statistics of rank 0's draws).  The posterior PIT, not LOO-PIT; no group-level statistics; no user-defined
+    draw statistics of rank 0's draws).  The posterior PIT (the LOO-PIT: --loo_predictive); no group-level statistics; no user-defined
     statistic.  Returns (JSON keys, arrays of <base>_ppc.npz or None).  (A collective when ws > 1: every rank calls it.)"""
     import torch
     clock = time.time()
@@ -1195,13 +1259,13 @@ def save_geometry(file_path_base, arrays):
 
 def _save_diagnostics(file_path_base, arrays):
     """The side files of the convergence report: <base>_rhat.npz and, where the probes ran, <base>_energy.npz,
-    <base>_trajectory.npz, <base>_geometry.npz, <base>_loo.npz and <base>_ppc.npz."""
+    <base>_trajectory.npz, <base>_geometry.npz, <base>_loo.npz, <base>_loopred.npz and <base>_ppc.npz."""
     if arrays is None:
         return
     # (tag _convergence_report left a side file's arrays under, its saver), in the order the files are written after _rhat.npz
     side = [(arrays.pop(tag, None), save) for tag, save in (
         (GEOMETRY_ARRAYS, save_geometry), (ENERGY_ARRAYS, save_energy), (TRAJECTORY_ARRAYS, save_trajectory),
-        (LOO_ARRAYS, save_loo), (PPC_ARRAYS, save_ppc))]
+        (LOO_ARRAYS, save_loo), (LOO_PRED_ARRAYS, save_loo_pred), (PPC_ARRAYS, save_ppc))]
     save_rhat(file_path_base, arrays)
     for side_arrays, save in side:
         if side_arrays is not None:

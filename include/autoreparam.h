@@ -558,6 +558,33 @@ int arp_predictive_check(const float* x, int64_t n_samples, int64_t n_chains, in
                          double* draw_stats, double* obs_sums, float* y_rep, int64_t y_rep_stride, uint8_t* mask,
                          int64_t* n_masked, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* Leave-one-out predictive sums (csrc/loopred.hip; Vehtari, Gelman, Gabry 2017 section 2; loo::E_loo, loo::loo_pit): the
+ * per-(observation, draw) predictive quantities of arp_predictive_check folded over the draws with importance weights.
+ * The trace x, the table and the observation range [n0, n1) are those of arp_pointwise_loglik (same addressing, same
+ * row_stride rule, 1 <= D <= 255, 1 <= T <= 4096); eta_n, s_n are its float32 chain and mu, var, pit are
+ * arp_predictive_check's definitions, operation for operation, through the same device-library functions:
+ *   kind ARP_OBS_NORMAL:     mu = eta, var = exp(s)^2, pit = 0.5 * erfc(-(y - eta) * exp(-s) / sqrt 2)
+ *   kind ARP_OBS_BERNOULLI:  mu = p = sigmoid(eta), var = p * (1 - p), pit = the mid-p value (y > 0.5: 1 - p / 2; else (1 - p) / 2)
+ * lw[(n - n0) * lw_stride + r] (double, device memory) is the log weight of draw r = step * n_chains + chain for
+ * observation n, as arp_psis_weights writes it; where it came from does not matter.  With W = exp(lw), one float64 exp:
+ *   obs_sums [n1 - n0][6] double = {sum W, sum W^2, sum W * mu, sum W * (mu^2 + var), sum W * pit, draws counted}
+ * over the draws with lw != -inf.  A draw with lw = -inf enters nothing, by select (its state may be non-finite); a NaN
+ * lw enters, is counted and carries through to the observation's five float columns; the count is exact.  The per-(n, r)
+ * values are float32 with the first-order bounds of csrc/ppc.hip's header (restated in csrc/loopred.hip); the products
+ * with W and every sum are float64 in a fixed order (an xor butterfly over a tile of 64 draws, then the tiles in ascending
+ * order), no float atomics: two calls give bitwise equal output, and the row of observation n does not depend on
+ * [n0, n1).  Nothing is read past the last element of the trace block or of lw's rows; idx and scale_idx are clamped
+ * into [0, D).  The workspace (arp_loo_predictive_workspace_bytes(n1 - n0, n_samples * n_chains): the per-tile partial
+ * sums, ceil(n_draws / 64) * n_obs * 48 bytes; <= 0 for a shape that is refused) is the caller's, 256-byte aligned.
+ * Asynchronous.  Refused before any launch: what arp_pointwise_loglik refuses (a NULL x or table pointer, D, the trace
+ * shape, row_stride, kind, T, n0 and n1), a NULL lw or obs_sums, lw_stride < n_samples * n_chains, a workspace that is
+ * missing, too small or misaligned. */
+int64_t arp_loo_predictive_workspace_bytes(int64_t n_obs, int64_t n_draws);
+int arp_loo_predictive(const float* x, int64_t n_samples, int64_t n_chains, int32_t D, int64_t row_stride, int32_t kind,
+                       const int32_t* idx, const float* w, int32_t T, const float* y, const int32_t* scale_idx,
+                       const float* log_scale, int64_t n0, int64_t n1, const double* lw, int64_t lw_stride,
+                       double* obs_sums, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* Check of a mean-field normal fit (csrc/vicheck.hip; Yao, Vehtari, Simpson, Gelman 2018, "Yes, but did it work?"): draws
  * from q = N(loc, diag(scale^2)) in the coordinates the fit was made in.  For draw r, g = draw_offset + r, and element
  * d = 4 e + i: ONE call philox4x32_10(counter = (e, lo32(g), hi32(g), 0), key = (lo32(seed), hi32(seed))) per (r, e); words

@@ -1,0 +1,275 @@
+"""GPU: arp_loo_predictive (csrc/loopred.hip) through diagnostics.loo_predictive against the float64 definition of
+tests/loopred_ref.py.
+
+Parity, per column, at the shapes of tests/test_gpu_ppc.py with synthetic log weights (so that a misplaced weight cannot
+hide): |got - ref| <= 2 sum W b_h + 4 2^-52 (terms + 1) sum W |h|, b_h the first-order bound of mu, m2 or pit from the
+ppc.hip header evaluated per element from float64 quantities (test_gpu_ppc.normal_bounds / bernoulli_bounds), the factor 2
+the project's standing allowance for second-order terms, the second part the float64 association and the one exp; sum W
+and sum W^2 carry the second part only; the count is exact.  Nothing is fitted to the device's output.
+
+The real pipeline once (pointwise_loglik -> psis_weights -> loo_predictive) against the reference on the device's own lw,
+and that lw against the reference's draw-order weights within the tolerance of tests/test_gpu_vicheck.py; the structural
+properties; a statistical tie with a closed form; the refusals.
+
+The tie (test_closed_form_of_a_normal_mean): N = 20, R = 8 192, RandomState(1).  Checked on the CPU from the reference
+alone when the test was written: the worst of the 60 ratios lies 0.99 se from the closed form (bound here: 4 se; a change
+of N, R or the seed is to be re-checked to stay under 3 se the same way)."""
+import ctypes as C
+import math
+
+import numpy as np
+import pytest
+import torch
+
+import loopred_ref as lr
+import ppc_ref as pp
+from test_gpu_ppc import DIMS, F64, FACTOR, SHAPES, Table, bernoulli_bounds, bits, make_case, make_table, normal_bounds
+from test_gpu_vicheck import FACTOR as LW_FACTOR, LW_MEASURED
+
+pytestmark = pytest.mark.gpu
+
+
+def make_lw(N, R, seed):
+    """lw [N, R] = -|N(0, 3^2)| per (n, r); about a tenth of every row -inf, one of them in the ragged last tile where R
+    allows; where N >= 3, row 1 entirely -inf."""
+    rs = np.random.RandomState(seed)
+    lw = -np.abs(3.0 * rs.randn(N, R))
+    lw[rs.rand(N, R) < 0.1] = -np.inf
+    if R % 64 and R >= 2:
+        lw[:, R - 1] = -np.inf
+    if N >= 3:
+        lw[1] = -np.inf
+    return lw
+
+
+def run(gpu, x3, table, lw, n0=0, n1=None, pad=0):
+    """obs_sums [n, 6] on the host; lw [n1 - n0, R] (numpy or a device tensor), `pad` columns of NaN behind its rows."""
+    from autoreparam_amd import diagnostics
+    xd = x3 if torch.is_tensor(x3) else torch.as_tensor(np.ascontiguousarray(x3, np.float32), device=gpu)
+    dt = diagnostics.upload_table(table, int(xd.shape[2]), gpu)
+    if not torch.is_tensor(lw):
+        n, R = lw.shape
+        buf = torch.full((n, R + pad), float("nan"), dtype=torch.float64, device=gpu)
+        buf[:, :R] = torch.as_tensor(np.ascontiguousarray(lw, np.float64), device=gpu)
+        lw = buf[:, :R] if pad else buf
+    return diagnostics.loo_predictive(xd, dt, lw, n0, n1).cpu().numpy()
+
+
+def allowances(table, c, n0, n1):
+    """[n, 5] allowance of the five float columns from loopred_ref.Columns `c`."""
+    T = table.idx.shape[1]
+    y = table.y[n0:n1].astype(np.float64)
+    if table.kind == pp.NORMAL:
+        _, b_pit, _, _, b_mu, b_m2, _ = normal_bounds(T, c.r, y)
+    else:
+        b_mu, b_pit, b_m2, _ = bernoulli_bounds(T, c.r, y)
+    first = np.stack([np.zeros(y.size), np.zeros(y.size)] + [(c.W * b).sum(1) for b in (b_mu, b_m2, b_pit)], axis=1)
+    return FACTOR * first + 4.0 * F64 * (c.terms[:, None] + 1.0) * c.absw
+
+
+def check(gpu, table, x3, lw, n0=0, n1=None, what="", got=None):
+    S, Cn, D = x3.shape
+    N = table.idx.shape[0]
+    n1 = N if n1 is None else n1
+    x = np.asarray(x3, np.float32).reshape(S * Cn, D)
+    c = lr.columns(table, x, lw, n0, n1)
+    got = run(gpu, x3, table, lw, n0, n1) if got is None else got
+    assert got.shape == (n1 - n0, 6), what
+    assert np.array_equal(got[:, 5], c.sums[:, 5]), what                                  # the count: exact
+    allow = allowances(table, c, n0, n1)
+    gap = np.abs(got[:, :5] - c.sums[:, :5])
+    assert np.isfinite(got).all() and np.all(gap <= allow), (what, [float(np.max(gap[:, j] / np.maximum(allow[:, j], 1e-300))) for j in range(5)])
+    empty = c.terms == 0
+    assert np.all(got[empty] == 0.0), what                                                # a row without a draw: zeros
+    return c, got
+
+
+@pytest.mark.parametrize("kind", (pp.NORMAL, pp.BERNOULLI))
+@pytest.mark.parametrize("D", DIMS)
+def test_parity_at_the_shape_edges(gpu, D, kind):
+    for shape in SHAPES:
+        table, x3, seed = make_case(kind, D, shape)
+        T, N, S, Cn = shape
+        lw = make_lw(N, S * Cn, seed + 1)
+        c, got = check(gpu, table, x3, lw, what=(kind, D, shape))
+        if N >= 3:
+            assert c.terms[1] == 0 and np.all(got[1] == 0.0)
+    # a ragged observation range and the last observation alone
+    table, x3, seed = make_case(kind, D, SHAPES[3])
+    lw = make_lw(130, 65, seed + 2)
+    check(gpu, table, x3, lw[3:127], 3, 127, what=(kind, D, "ragged"))
+    check(gpu, table, x3, lw[129:130], 129, 130, what=(kind, D, "last"))
+
+
+@pytest.mark.parametrize("kind", (pp.NORMAL, pp.BERNOULLI))
+def test_the_real_pipeline_once(gpu, kind):
+    """pointwise_loglik -> psis_weights -> loo_predictive at R = 2 000 (M = 135: every row's tail goes to the fit): the fold
+    against the reference on the device's OWN lw, and that lw against the reference's draw-order weights."""
+    from autoreparam_amd import diagnostics
+    T, N, S, Cn, D = 5, 5, 40, 50, 9
+    table, x3, seed = make_case(kind, D, (T, N, S, Cn))
+    xd = torch.as_tensor(x3, device=gpu)
+    dt = diagnostics.upload_table(table, D, gpu)
+    ll, mask, count = diagnostics.pointwise_loglik(xd, dt)
+    out8, lw = diagnostics.psis_weights(ll, mask)
+    sums = diagnostics.loo_predictive(xd, dt, lw).cpu().numpy()
+    out8, lw_host, ll_host = out8.cpu().numpy(), lw.cpu().numpy(), ll.cpu().numpy()
+    # (a row whose fit does not come out finite keeps raw weights, on the device and in the reference alike)
+    assert int(count.item()) == 0 and np.all(out8[:, 4] == 135.0) and np.isfinite(out8[:, 1]).any() and np.isfinite(lw_host).all()
+    check(gpu, table, x3, lw_host, what=("pipeline", kind), got=sums)
+    assert np.all(sums[:, 5] == 2000.0)
+    ref = lr.psis_log_weights(ll_host)
+    dev = np.abs(lw_host - ref) / np.maximum(np.abs(ref), 1.0)
+    print("largest |lw_dev - lw_ref| / max(|lw_ref|, 1): %.3g of %.3g allowed" % (dev.max(), LW_FACTOR * LW_MEASURED))
+    assert dev.max() <= LW_FACTOR * LW_MEASURED
+    # the report of these sums is the reference's
+    s, want = diagnostics.loo_predictive_summary(sums, table.y, kind), lr.summary(sums, table.y, kind)
+    assert s.observations == N and s.left_out == 0 and np.allclose(s.loo_mean, want["loo_mean"], rtol=1e-13)
+    assert np.all(s.is_ess >= 1.0 - 1e-12) and np.all(s.is_ess <= 2000.0) and np.all((s.loo_pit >= 0) & (s.loo_pit <= 1))
+
+
+@pytest.mark.parametrize("kind", (pp.NORMAL, pp.BERNOULLI))
+def test_structure(gpu, kind):
+    """Two calls; a split observation range; lw_stride > R; a NaN lw; a left-out draw with a non-finite state."""
+    N, T, D, S, Cn = 130, 5, 9, 5, 13
+    R = S * Cn
+    table = make_table(N, T, D, kind, 21 + kind)
+    x3 = (0.5 * np.random.RandomState(22).randn(S, Cn, D)).astype(np.float32)
+    lw = make_lw(N, R, 23)
+    whole = run(gpu, x3, table, lw)
+    assert np.array_equal(bits(whole), bits(run(gpu, x3, table, lw)))
+    for a in (1, 67, 129):
+        lo, hi = run(gpu, x3, table, lw[:a], 0, a), run(gpu, x3, table, lw[a:], a, N)
+        assert np.array_equal(bits(np.concatenate([lo, hi])), bits(whole)), a
+    assert np.array_equal(bits(run(gpu, x3, table, lw, pad=7)), bits(whole))              # rows R + 7 apart, NaN between them
+    assert np.array_equal(bits(run(gpu, x3, table, lw[40:90], 40, 90, pad=1)), bits(whole[40:90]))
+    # one NaN entry: that observation's float columns are NaN, its count stands, every other row keeps its bits
+    poisoned = lw.copy()
+    poisoned[77, np.flatnonzero(np.isfinite(lw[77]))[30]] = np.nan
+    got = run(gpu, x3, table, poisoned)
+    others = np.arange(N) != 77
+    assert np.isnan(got[77, :5]).all() and got[77, 5] == whole[77, 5]
+    assert np.array_equal(bits(got[others]), bits(whole[others]))
+    # a draw that every observation leaves out may hold anything: nothing of it enters, by select
+    out = lw.copy()
+    out[:, 64] = -np.inf                                                    # the one draw of the ragged last tile
+    out[:, 3] = -np.inf
+    clean = run(gpu, x3, table, out)
+    bad = x3.copy().reshape(R, D)
+    bad[64], bad[3, D - 1] = np.nan, np.inf
+    assert np.array_equal(bits(run(gpu, bad.reshape(S, Cn, D), table, out)), bits(clean)) and np.isfinite(clean).all()
+    assert np.all(clean[:, 5] == np.sum(out != -np.inf, axis=1))
+
+
+@pytest.mark.parametrize("kind", (pp.NORMAL, pp.BERNOULLI))
+def test_block_of_chains_read_in_place_is_bitwise_its_copy(gpu, kind):
+    """row_stride > n_chains * D: chains 7 ... 43 of 64."""
+    from autoreparam_amd import _lib
+    lo, hi = 7, 44
+    table = make_table(17, 5, 33, kind, 9)
+    wide = torch.as_tensor((0.5 * np.random.RandomState(11).randn(4, 64, 33)).astype(np.float32), device=gpu)
+    block = wide[:, lo:hi]
+    x, S, Cn, D, stride = _lib.trace_view(block, "test")
+    assert x.data_ptr() == block.data_ptr() and stride == 64 * 33 and stride > Cn * D
+    lw = make_lw(17, 4 * (hi - lo), 12)
+    a = run(gpu, block, table, lw)
+    assert np.array_equal(bits(a), bits(run(gpu, block.contiguous(), table, lw)))
+    check(gpu, table, block.contiguous().cpu().numpy(), lw, what="block", got=a)
+
+
+def tie_case():
+    """The closed-form case: (table, x3 [32, 256, 1], closed [3, 20]) -- the LOO predictive mean, second moment and PIT of
+    y_n ~ N(x, 1) under a flat prior, whose posterior from all 20 observations is N(mean y, 1 / 20), the draws' law."""
+    rs = np.random.RandomState(1)
+    N, S, Cn = 20, 32, 256
+    y = (1.5 * rs.randn(N)).astype(np.float32)
+    y64 = y.astype(np.float64)
+    x3 = (y64.mean() + math.sqrt(1.0 / N) * rs.randn(S, Cn, 1)).astype(np.float32)
+    table = Table(pp.NORMAL, np.zeros((N, 1), np.int32), np.ones((N, 1), np.float32), y, np.full(N, -1, np.int32),
+                  np.zeros(N, np.float32))
+    rest = (y64.sum() - y64) / (N - 1)                                       # the mean of the other 19
+    var = 1.0 + 1.0 / (N - 1)
+    pit = np.array([0.5 * math.erfc(-(a - b) / math.sqrt(2.0 * var)) for a, b in zip(y64, rest)])
+    return table, x3, np.stack([rest, rest * rest + var, pit])
+
+
+def tie_reference(table, x3):
+    """(ratios [3, N], se [3, N]) from the float64 reference alone: its log-likelihoods, its smoothed weights, its sums;
+    se = sqrt(sum W^2 (h - ratio)^2) / sum W, the delta-method standard error of a self-normalised estimate."""
+    x = x3.reshape(-1, x3.shape[2])
+    c = lr.columns(table, x, lr.psis_log_weights(lr.loglik(table, x)))
+    ratios = np.stack([c.sums[:, j] / c.sums[:, 0] for j in (2, 3, 4)])
+    se = np.stack([np.sqrt((c.W ** 2 * (h - r[:, None]) ** 2).sum(1)) / c.sums[:, 0]
+                   for h, r in zip((c.r.mu, c.r.m2, c.r.pit), ratios)])
+    return ratios, se
+
+
+def test_closed_form_of_a_normal_mean(gpu):
+    """A tie that does not rest on the reference's tiling: each of the 60 device ratios within 4 se of the closed form,
+    se from the reference's weights (never the device's output).  From the reference alone, on the CPU, when the test was
+    written: worst 0.99 se."""
+    from autoreparam_amd import diagnostics
+    table, x3, closed = tie_case()
+    ratios, se = tie_reference(table, x3)
+    assert np.all(np.abs(ratios - closed) <= 3.0 * se), float(np.max(np.abs(ratios - closed) / se))
+    xd = torch.as_tensor(x3, device=gpu)
+    dt = diagnostics.upload_table(table, 1, gpu)
+    ll, mask, _ = diagnostics.pointwise_loglik(xd, dt)
+    _, lw = diagnostics.psis_weights(ll, mask)
+    s = diagnostics.loo_predictive(xd, dt, lw).cpu().numpy()
+    assert np.all(s[:, 5] == 8192.0)
+    got = np.stack([s[:, j] / s[:, 0] for j in (2, 3, 4)])
+    worst = float(np.max(np.abs(got - closed) / se))
+    print("worst of the 60 ratios: %.3f se from the closed form (4 allowed)" % worst)
+    assert worst <= 4.0
+    report = diagnostics.loo_predictive_summary(s, table.y, pp.NORMAL)
+    assert np.allclose(report.loo_mean, closed[0], atol=4.0 * se[0].max()) and np.all(np.abs(report.loo_sd ** 2 - (1.0 + 1.0 / 19)) < 0.05)
+
+
+def test_refusals(gpu):
+    from autoreparam_amd import _lib, diagnostics
+    L = _lib.lib()
+    table = make_table(5, 2, 8, pp.NORMAL, 1)
+    dt = diagnostics.upload_table(table, 8, gpu)
+    x = torch.zeros(2, 3, 8, device=gpu)
+    lw = torch.zeros(5, 6, dtype=torch.float64, device=gpu)
+    obs = torch.full((5, 6), -7.0, dtype=torch.float64, device=gpu)
+    need = diagnostics.loo_predictive_workspace_bytes(5, 6)
+    assert need > 0 and need % 256 == 0 and need >= 5 * 6 * 8
+    assert L.arp_loo_predictive_workspace_bytes(0, 6) <= 0 and L.arp_loo_predictive_workspace_bytes(5, 0) <= 0
+    assert L.arp_loo_predictive_workspace_bytes(1 << 31, 6) <= 0 and L.arp_loo_predictive_workspace_bytes(5, 1 << 31) <= 0
+    assert L.arp_loo_predictive_workspace_bytes(1000, 65536) == 1024 * 1000 * 48
+    ws = torch.zeros(need + 256, dtype=torch.uint8, device=gpu)
+    p = _lib.ptr
+
+    def call(x_=x, S=2, Cn=3, D=8, stride=24, kind=0, T=2, n0=0, n1=5, lw_=lw, lws=6, obs_=obs, idx=dt.idx, w_=dt.w, y_=dt.y,
+             si=dt.scale_idx, ls=dt.log_scale, ws_=ws, ws_bytes=need):
+        return L.arp_loo_predictive(p(x_), S, Cn, D, stride, kind, p(idx), p(w_), T, p(y_), p(si), p(ls), n0, n1, p(lw_), lws,
+                                    p(obs_), C.c_void_p(ws_.data_ptr() if ws_ is not None else 0), ws_bytes, C.c_void_p(0))
+    refused = ((dict(x_=None), b"required"), (dict(idx=None), b"required"), (dict(w_=None), b"required"), (dict(y_=None), b"required"),
+               (dict(si=None), b"required"), (dict(ls=None), b"required"), (dict(lw_=None), b"required"),
+               (dict(obs_=None), b"required"), (dict(D=0), b"D"), (dict(D=256), b"D"), (dict(stride=23), b"row_stride"),
+               (dict(kind=2), b"kind"), (dict(kind=-1), b"kind"), (dict(T=0), b"T"), (dict(T=4097), b"T"),
+               (dict(n0=5, n1=5), b"n0"), (dict(n0=3, n1=2), b"n0"), (dict(n0=-1), b"n0"), (dict(n1=1 << 31), b"n0"),
+               (dict(S=0), b"n_samples"), (dict(Cn=0), b"n_samples"), (dict(S=1 << 31), b"2^31"), (dict(lws=5), b"lw_stride"),
+               (dict(ws_bytes=need - 1), b"workspace too small"), (dict(ws_=None), b"workspace too small"),
+               (dict(ws_=ws[8:]), b"256-byte aligned"))
+    for kwargs, word in refused:
+        assert call(**kwargs) == 1, kwargs
+        msg = L.arp_last_error()
+        assert word in msg and b"arp_loo_predictive" in msg, (kwargs, msg)
+    torch.cuda.synchronize()
+    assert bool((obs == -7.0).all())                                     # no launch was made for a refused call
+    assert call() == 0
+    torch.cuda.synchronize()
+    assert bool((obs != -7.0).all()) and bool((obs[:, 5] == 6.0).all()) and bool((obs[:, 0] == 6.0).all())
+    with pytest.raises(ValueError, match="observations is required"):
+        diagnostics.loo_predictive(x, dt, lw, 0, 6)
+    with pytest.raises(ValueError, match="lw must be a float64"):
+        diagnostics.loo_predictive(x, dt, lw.to(torch.float32))
+    with pytest.raises(ValueError, match="lw must be a float64"):
+        diagnostics.loo_predictive(x, dt, lw[:, :5])
+    with pytest.raises(ValueError, match="lw must be a float64"):
+        diagnostics.loo_predictive(x, dt, lw[:4])
+    with pytest.raises(ValueError, match="lw must be a float64"):
+        diagnostics.loo_predictive(x, dt, lw.cpu())
