@@ -6,22 +6,13 @@
 //
 // from which the host forms the LOO predictive mean and sd, the LOO-PIT and the importance-sampling ESS of every
 // observation (diagnostics.loo_predictive_summary; Vehtari, Gelman, Gabry 2017 section 2; loo::E_loo, loo::loo_pit).
-// Model-independent, as loglik.hip and ppc.hip are:
+// Model-independent; the table, the tile of draws, eta_n and s_n, and mu, var and pit of the two kinds of data are
+// obs_table.h's, the very functions ppc.hip calls.
 //
-//   eta_n = sum_t w[n][t] x[idx[n][t]],   s_n = log_scale[n] + (scale_idx[n] >= 0 ? x[scale_idx[n]] : 0)
-//   Normal:     mu = eta, var = exp(s)^2;  z_obs = (y - eta) exp(-s);  pit = 0.5 erfc(-z_obs / sqrt 2)
-//   Bernoulli:  e = exp(-|eta|), p = (eta >= 0 ? 1 : e) / (1 + e);  mu = p, var = p (1 - p);
-//               pit = y > 0.5 ? 1 - p / 2 : (1 - p) / 2 (the mid-p value)
+// Build-specific: the reference has no predictive reports.  The kernel does not care where lw came from.
 //
-// Build-specific: the reference has no predictive reports.  A translation unit of its own: ppc.hip's device code stays
-// what arp_predictive_check has always launched, and the few lines both need (the tile, the chain of eta, the butterfly)
-// are restated here.  The kernel does not care where lw came from.
-//
-// Shape of the work: ppc.hip's "along the draws" direction and nothing else.  Draws lie across the lanes of a wave and
-// the observation is uniform per wave, so idx, w, y and the scale entries are scalar loads (the table pointers are
-// __restrict__ kernel arguments: see loglik.hip); a workgroup of four waves stages one tile of 64 draws x D floats in LDS
-// with an odd row pitch and its waves walk the observations of the workgroup's share (blockIdx.y), wave v taking every
-// fourth.  lw is read coalesced along r, one 8-byte load per (n, r), asked for one observation ahead.  Per (n, tile) an xor butterfly on doubles
+// Shape of the work: obs_table.h's, with ppc.hip's "along the draws" direction and nothing else.  lw is read coalesced
+// along r, one 8-byte load per (n, r), asked for one observation ahead.  Per (n, tile) an xor butterfly on doubles
 // over the 64 lanes (wave_sum below: lane permutations in registers, no LDS; every lane ends with the same bits) gives the
 // tile's five sums, the count is a ballot, lane 0 stores the six to the workspace [tile][n][6], and a second launch adds
 // the tiles in ascending order (loopred_fold: the loads staged through LDS, the additions of one (n, c) a chain).
@@ -32,15 +23,8 @@
 // float64 exp more; five float64 butterflies per (n, tile) instead of three.  Measured, with what each of the three
 // choices above (the load ahead, the butterfly in registers, the staged second launch) was worth: DESIGN.md section 6.
 //
-// Arithmetic.  eta, s, mu, m2 = mu^2 + var and pit are float32, contraction off, ppc.hip's operations in ppc.hip's order
-// through the same device-library functions, so its first-order bounds carry over unchanged (u = 2^-24, A = sum_t |w_t x_t|,
-// phi the standard normal density):
-//
-//   Normal     mu = eta: |eta_dev - eta| <= T u A
-//              |m2_dev - m2|   <= u [ 2 |eta| T A + eta^2 + exp(2 s) (14 + 2 |s|) + m2 ]
-//              |pit_dev - pit| <= u [ phi(z_obs) (T A exp(-s) + |z_obs| (10 + |s|)) + 32 pit ] + 2^-126
-//   Bernoulli  |p_dev - p| <= u [ p (1 - p) (T A + 6) + 2 p ] =: bp,  |m2_dev - m2| <= 3 bp + 4 u,  |pit_dev - pit| <= bp / 2 + u
-//
+// Arithmetic.  eta, s, mu, m2 = mu^2 + var and pit are float32, contraction off, and obs_table.h's: the first-order
+// bounds b_h of h = mu, m2 and pit are those derived in ppc.hip.
 // W = exp(lw) is ONE float64 exp of the float64 input (the device library's, good to about an ulp, 2^-52 relative);
 // W^2 and W h (h the float32 value taken to float64) are one float64 product each, and every sum is a float64 sum in a
 // fixed order: a column sum_r W h is off by at most sum_r W b_h plus a few 2^-52 (terms + 1) sum_r W |h|.
@@ -53,43 +37,17 @@
 //    skipped silently.  A draw whose state is non-finite while its lw is finite carries through the same way.
 //  * Dead lanes of the last ragged tile take part in every shuffle and in the ballot (the butterfly needs all 64) with 0
 //    by select; their lw is never loaded.
-//  * Reads past the end, the table's indices: as loglik.hip (loads for r < R, d < D only; idx and scale_idx clamped into
-//    [0, D)).  lw is read at (n - n0) * lw_stride + r for n0 <= n < n1, r < R only.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-#include <algorithm>
-#include "diag_host.h"
+//  * Reads past the end, the table's indices: obs_table.h.  lw is read at (n - n0) * lw_stride + r for n0 <= n < n1, r < R only.
+#include "obs_table.h"
 
 #pragma clang fp contract(off)
 
 namespace arp {
 namespace {
 
-constexpr int kLpThreads = 256;
-constexpr int kLpWaves = kLpThreads / 64;
-constexpr int kLpDraws = 64;                     // draws per tile: one per lane
-constexpr int kLpMaxD = 255;                     // 64 rows of pitch 255 floats: 65 280 bytes of LDS
-constexpr int kLpMaxT = 4096;
 constexpr int kLpCols = 6;                       // columns of obs_sums
 constexpr int kLpFoldOut = 32;                   // the second launch: (n, c) per workgroup ...
 constexpr int kLpFoldTiles = 64;                 // ... and tiles staged at a time: 16 KB of LDS
-constexpr long long kLpTargetWorkgroups = 2048;
-constexpr float kNegInvSqrt2F = -0.7071067811865476f;
-
-// how the observations [n0, n1) are shared among blockIdx.y: loglik.hip's rule
-struct Split { long long ntiles, groups, per_group; };
-inline Split split_of(long long nobs, long long R) {
-  Split s;
-  s.ntiles = (R + kLpDraws - 1) / kLpDraws;
-  long long groups = std::max<long long>(1, (kLpTargetWorkgroups + s.ntiles - 1) / s.ntiles);
-  groups = std::min<long long>(std::min<long long>(groups, (nobs + kLpWaves - 1) / kLpWaves), 65535);
-  s.per_group = (nobs + groups - 1) / groups;
-  s.groups = (nobs + s.per_group - 1) / s.per_group;
-  return s;
-}
-inline bool loopred_shape_ok(int64_t n_obs, int64_t n_draws) {
-  return n_obs >= 1 && n_obs < (1ll << 31) && n_draws >= 1 && n_draws < (1ll << 31);
-}
 
 // v of the lane this lane is paired with by the data-parallel-primitive control `Ctrl` (a permutation within a row of 16)
 template <int Ctrl>
@@ -121,79 +79,47 @@ __device__ __forceinline__ double wave_sum(double v) {
   return __hiloint2double((int)h32[0], (int)l32[0]) + __hiloint2double((int)h32[1], (int)l32[1]);      // i ^ 32
 }
 
-__global__ __launch_bounds__(kLpThreads) void loopred_kernel(
+__global__ __launch_bounds__(kObsThreads) void loopred_kernel(
     const float* __restrict__ x, long long R, unsigned n_chains, int D, long long stride, int kind, int T,
     const int* __restrict__ idx, const float* __restrict__ w, const float* __restrict__ y,
     const int* __restrict__ scale_idx, const float* __restrict__ log_scale, long long n0, long long n1, long long per_group,
     const double* __restrict__ lw, long long lw_stride, double* __restrict__ part) {
-  extern __shared__ float tile[];                // [64][Dp]
-  const int t = threadIdx.x;
-  const int lane = t & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
-  const int Dp = D | 1;
-  const long long r0 = (long long)blockIdx.x * kLpDraws;
-  const int nrows = (int)min((long long)kLpDraws, R - r0);
-
-  // element e = t + 256 a of the tile is (row e / D, column e % D); a dead row takes 0 without a load
-  const int nelem = kLpDraws * D;
-  for (int e = t; e < nelem; e += kLpThreads) {
-    const int lr = (int)((unsigned)e / (unsigned)D), d = e - lr * D;
-    float v = 0.0f;
-    if (lr < nrows) {
-      const unsigned r = (unsigned)(r0 + lr);
-      const unsigned step = r / n_chains, chain = r - step * n_chains;
-      v = x[(long long)step * stride + (long long)chain * D + d];
-    }
-    tile[lr * Dp + d] = v;
-  }
-  __syncthreads();
+  extern __shared__ float tile[];                // [64][D | 1]
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const long long r0 = (long long)blockIdx.x * kObsDraws;
+  const int nrows = (int)min((long long)kObsDraws, R - r0);
+  stage_tile<false>(x, r0, nrows, n_chains, D, stride, tile, nullptr);
   const bool live = lane < nrows;
   const double ninf = -__longlong_as_double(0x7ff0000000000000ll);
 
-  const float* row = tile + lane * Dp;
+  const float* row = tile + lane * (D | 1);
   const long long nb = n0 + (long long)blockIdx.y * per_group, ne = min(n1, nb + per_group);
   // the log weight of the NEXT observation is asked for before this one's arithmetic: the load's latency (the only
   // per-lane global load of the loop) is then hidden behind a whole iteration and not paid in front of the exp
   double l_next = ninf;
   if (live && nb + wave < ne) l_next = lw[(nb + wave - n0) * lw_stride + r0 + lane];
-  for (long long n = nb + wave; n < ne; n += kLpWaves) {
+  for (long long n = nb + wave; n < ne; n += kObsWaves) {
     const double l = l_next;                     // (a dead lane holds -inf)
     l_next = ninf;
-    if (live && n + kLpWaves < ne) l_next = lw[(n + kLpWaves - n0) * lw_stride + r0 + lane];
-    const int* ip = idx + n * T;
-    const float* wp = w + n * T;
-    float eta = 0.0f;
-#pragma unroll 4
-    for (int k = 0; k < T; ++k) {
-      const int i = min(max(ip[k], 0), D - 1);
-      eta = eta + wp[k] * row[i];
-    }
+    if (live && n + kObsWaves < ne) l_next = lw[(n + kObsWaves - n0) * lw_stride + r0 + lane];
+    const float eta = obs_eta(row, idx, w, n, T, D);
     const float yn = y[n];
-    float pit, mu, m2;
+    PredTerms pt;
     if (kind == 0) {
-      const int si = scale_idx[n];
-      float s = log_scale[n];
-      if (si >= 0) s = s + row[min(si, D - 1)];
-      const float es = expf(s), ems = expf(-s);
-      const float zo = (yn - eta) * ems;
-      pit = 0.5f * erfcf(zo * kNegInvSqrt2F);
-      mu = eta;
-      m2 = eta * eta + es * es;
+      const float s = obs_log_scale(row, scale_idx, log_scale, n, D);
+      pt = normal_terms(eta, yn, expf(s), expf(-s));
     } else {
-      const float e = expf(-fabsf(eta));
-      const float p = (eta >= 0.0f ? 1.0f : e) / (1.0f + e);
-      pit = yn > 0.5f ? 1.0f - 0.5f * p : 0.5f * (1.0f - p);
-      mu = p;
-      m2 = p * p + p * (1.0f - p);
+      pt = bernoulli_terms(eta, yn);
     }
     const bool in = l != ninf;                   // (a NaN enters)
     const double W = exp(l);
     // every lane takes part, one that does not count with 0 by select
     const double s_w = wave_sum(in ? W : 0.0);
     const double s_ww = wave_sum(in ? W * W : 0.0);
-    const double s_mu = wave_sum(in ? W * (double)mu : 0.0);
-    const double s_m2 = wave_sum(in ? W * (double)m2 : 0.0);
-    const double s_pit = wave_sum(in ? W * (double)pit : 0.0);
+    const double s_mu = wave_sum(in ? W * (double)pt.mu : 0.0);
+    const double s_m2 = wave_sum(in ? W * (double)pt.m2 : 0.0);
+    const double s_pit = wave_sum(in ? W * (double)pt.pit : 0.0);
     const unsigned long long counted = __ballot(in);
     if (lane == 0) {
       double* po = part + ((long long)blockIdx.x * (n1 - n0) + (n - n0)) * kLpCols;
@@ -207,7 +133,7 @@ __global__ __launch_bounds__(kLpThreads) void loopred_kernel(
 // with its loads in flight together (rows of 256 contiguous bytes), and thread j < kLpFoldOut then adds column j in order.
 // (One thread per (n, c) walking the tiles by itself, ppc.hip's third launch, waits for memory once per tile: at 1 024 tiles
 // and 2 046 (n, c) that was about 0.19 ms a call whatever the first launch took)
-__global__ __launch_bounds__(kLpThreads) void loopred_fold(const double* __restrict__ part, long long total, long long ntiles,
+__global__ __launch_bounds__(kObsThreads) void loopred_fold(const double* __restrict__ part, long long total, long long ntiles,
                                                            double* __restrict__ obs_sums) {
   __shared__ double stage[kLpFoldTiles][kLpFoldOut];
   const int t = threadIdx.x;
@@ -218,7 +144,7 @@ __global__ __launch_bounds__(kLpThreads) void loopred_fold(const double* __restr
     const int nt = (int)min((long long)kLpFoldTiles, ntiles - t0);
     __syncthreads();                             // (the chunk before this one has been added)
 #pragma unroll
-    for (int r = row0; r < kLpFoldTiles; r += kLpThreads / kLpFoldOut)
+    for (int r = row0; r < kLpFoldTiles; r += kObsThreads / kLpFoldOut)
       if (r < nt && i < total) stage[r][col] = part[(t0 + r) * total + i];
     __syncthreads();
     if (t < kLpFoldOut && i < total) {
@@ -235,7 +161,7 @@ __global__ __launch_bounds__(kLpThreads) void loopred_fold(const double* __restr
 
 extern "C" int64_t arp_loo_predictive_workspace_bytes(int64_t n_obs, int64_t n_draws) {
   using namespace arp;
-  if (!loopred_shape_ok(n_obs, n_draws)) return 0;
+  if (!obs_shape_ok(n_obs, n_draws)) return 0;
   Carve c;
   c.take(split_of(n_obs, n_draws).ntiles * n_obs * kLpCols * (int64_t)sizeof(double));
   return c.bytes();
@@ -252,12 +178,7 @@ extern "C" int arp_loo_predictive(const float* x, int64_t n_samples, int64_t n_c
     set_error(who + ": x, the table (idx, w, y, scale_idx, log_scale), lw and obs_sums are required");
     return 1;
   }
-  if (D < 1 || D > kLpMaxD) { set_error(who + ": 1 <= D <= 255 is required"); return 1; }
-  if (!trace_shape_ok(n_samples, n_chains, D, name)) return 1;
-  if (row_stride < n_chains * D) { set_error(who + ": row_stride >= n_chains * D is required"); return 1; }
-  if (kind != 0 && kind != 1) { set_error(who + ": kind must be ARP_OBS_NORMAL or ARP_OBS_BERNOULLI"); return 1; }
-  if (T < 1 || T > kLpMaxT) { set_error(who + ": 1 <= T <= 4096 is required"); return 1; }
-  if (n0 < 0 || n1 <= n0 || n1 >= (1ll << 31)) { set_error(who + ": 0 <= n0 < n1 < 2^31 is required"); return 1; }
+  if (!table_call_ok(name, n_samples, n_chains, D, row_stride, kind, T, n0, n1)) return 1;
   const long long R = n_samples * n_chains;
   if (lw_stride < R) { set_error(who + ": lw_stride >= n_samples * n_chains is required"); return 1; }
   const long long nobs = n1 - n0;
@@ -267,12 +188,11 @@ extern "C" int arp_loo_predictive(const float* x, int64_t n_samples, int64_t n_c
   const Split sp = split_of(nobs, R);
   double* part = (double*)workspace;
   hipStream_t st = (hipStream_t)stream;
-  const size_t lds = (size_t)kLpDraws * (D | 1) * sizeof(float);
-  hipLaunchKernelGGL(loopred_kernel, dim3((unsigned)sp.ntiles, (unsigned)sp.groups), dim3(kLpThreads), lds, st, x, R, (unsigned)n_chains,
-                     (int)D, (long long)row_stride, (int)kind, (int)T, idx, w, y, scale_idx, log_scale, (long long)n0, (long long)n1,
+  hipLaunchKernelGGL(loopred_kernel, dim3((unsigned)sp.ntiles, (unsigned)sp.groups), dim3(kObsThreads), tile_lds_bytes(D), st, x, R,
+                     (unsigned)n_chains, (int)D, (long long)row_stride, (int)kind, (int)T, idx, w, y, scale_idx, log_scale, (long long)n0, (long long)n1,
                      sp.per_group, lw, (long long)lw_stride, part);
   ARP_HIP_OK(hipGetLastError());
-  hipLaunchKernelGGL(loopred_fold, dim3(blocks_for(nobs * kLpCols, kLpFoldOut)), dim3(kLpThreads), 0, st, (const double*)part,
+  hipLaunchKernelGGL(loopred_fold, dim3(blocks_for(nobs * kLpCols, kLpFoldOut)), dim3(kObsThreads), 0, st, (const double*)part,
                      nobs * kLpCols, sp.ntiles, obs_sums);
   ARP_HIP_OK(hipGetLastError());
   return 0;

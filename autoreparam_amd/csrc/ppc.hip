@@ -1,13 +1,11 @@
 // Posterior predictive check (include/autoreparam.h: arp_predictive_check): replicated observations y_rep[n][r] of
 // observation n at draw r of a centred trace, drawn from the model's observation table (autoreparam_amd/models.py:
 // ModelSpec.observation_table) and folded on the spot into per-draw test statistics and per-observation predictive
-// moments -- does data simulated from the fitted model look like the data?  Model-independent, as loglik.hip is:
+// moments -- does data simulated from the fitted model look like the data?  Model-independent; the table, the tile of
+// draws, eta_n and s_n, and the predictive terms mu, var, z_obs, e, p and pit of the two kinds of data: obs_table.h.
 //
-//   eta_n = sum_t w[n][t] x[idx[n][t]],   s_n = log_scale[n] + (scale_idx[n] >= 0 ? x[scale_idx[n]] : 0)
-//   Normal:     mu = eta, var = exp(s)^2;  y_rep = eta + exp(s) z;  z_obs = (y - eta) exp(-s);  pit = 0.5 erfc(-z_obs / sqrt 2);
-//               dev(v) = ((v - eta) exp(-s))^2 + 2 s + log 2 pi
-//   Bernoulli:  e = exp(-|eta|), p = (eta >= 0 ? 1 : e) / (1 + e);  mu = p, var = p (1 - p);  y_rep = (u < p);
-//               pit = y > 0.5 ? 1 - p / 2 : (1 - p) / 2 (the mid-p value);  dev(v) = -2 (v eta - (max(eta, 0) + log1p(e)))
+//   Normal:     y_rep = eta + exp(s) z;  dev(v) = ((v - eta) exp(-s))^2 + 2 s + log 2 pi
+//   Bernoulli:  y_rep = (u < p);  dev(v) = -2 (v eta - (max(eta, 0) + log1p(e)))
 //
 // Build-specific: the reference has no predictive checks.
 //
@@ -19,11 +17,8 @@
 // cospif: not the hardware approximations, whose error is not stated anywhere -- this is not the sampler's hot path, and a
 // per-element test needs a bound.
 //
-// Shape of the work: loglik.hip's.  Draws lie across the lanes of a wave and the observation is uniform per wave, so idx,
-// w, y and the scale entries are scalar loads; a workgroup of four waves stages one tile of 64 draws in LDS with an odd
-// row pitch (lane l reads x[l][idx]: ds_read_b32 banks by (l Dp + idx) mod 32 within a half-wave, 32 different banks
-// whatever idx is) and its waves walk the observations of the workgroup's share (blockIdx.y), wave v taking every fourth.
-// What is new is the fold, in two directions, all of it in float64 over the float32 per-(n, r) values and in a fixed order:
+// Shape of the work: obs_table.h's, and the fold, in two directions, all of it in float64 over the float32 per-(n, r)
+// values and in a fixed order:
 //  * along the observations, per draw: every lane carries its draw's eight statistics in registers over its wave's
 //    observations (ascending n); the four waves are added through LDS in wave order; the workgroup's row goes to the
 //    workspace [group][R][8], and a second launch combines the groups in ascending order (+, +, min, max, +, +, +, +).
@@ -37,13 +32,14 @@
 // i.e. 40 v_mul_lo / v_mul_hi at quarter rate -- and logf, sqrtf, cospif, two expf and erfcf (Normal) or expf, log1pf
 // and a division (Bernoulli).  Measured next to arp_pointwise_loglik: DESIGN.md section 6.
 //
-// Arithmetic.  float32, contraction off; eta and s are loglik.hip's chain operation for operation, so its bound on eta
-// carries over.  Library functions at the OpenCL full-profile limits (OpenCL C specification, "Relative error as ULPs":
-// log 3, exp 3, sqrt 3, sinpi / cospi 4, erfc 16, log1p 2 ulp; no sharper statement for the ROCm device library was at
-// hand, so these are what the tests use).  With u = 2^-24 (one ulp <= 2 u relative), A = sum_t |w_t x_t|, z_obs = (y - eta)
-// exp(-s), phi the standard normal density, to first order against the exact value of the same float32 inputs:
+// Arithmetic.  float32, contraction off; eta, s and the predictive terms are obs_table.h's functions, which loopred.hip
+// calls too: the bounds on mu, m2 and pit below are derived here once and hold for both.  Library functions at the OpenCL
+// full-profile limits (OpenCL C specification, "Relative error as ULPs": log 3, exp 3, sqrt 3, sinpi / cospi 4, erfc 16,
+// log1p 2 ulp; no sharper statement for the ROCm device library was at hand, so these are what the tests use).  With
+// u = 2^-24 (one ulp <= 2 u relative), A = sum_t |w_t x_t|, z_obs = (y - eta) exp(-s), phi the standard normal density, to
+// first order against the exact value of the same float32 inputs:
 //
-//   |eta_dev - eta| <= T u A
+//   |eta_dev - eta| <= T u A                              (obs_table.h)
 //   Normal
 //     |z_dev - z|         <= 18 u |z|                      (log 6 u halved by the root, sqrt 6 u, cospi 8 u, the product 1)
 //     |y_rep_dev - y_rep| <= u [ T A + exp(s) |z| (26 + |s|) + |y_rep| ]
@@ -66,45 +62,20 @@
 // Things that go wrong quietly here:
 //  * A draw that is left out (a non-finite element among its D): its draw_stats row and its y_rep entries are WRITTEN, as
 //    0 by select -- never a product with a 0 / 1 mask, 0 * inf is NaN -- and it enters no obs_sums, again by select.
-//  * Reads past the end, the table's indices: as loglik.hip (loads for r < R, d < D only; idx and scale_idx clamped).
+//  * Reads past the end, the table's indices: obs_table.h.
 //  * Dead lanes of the last ragged tile take part in every shuffle and ballot (the butterfly needs all 64) with 0 by
 //    select; they store nothing.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-#include <algorithm>
 #include "arp_device.h"
-#include "diag_host.h"
+#include "obs_table.h"
 
 #pragma clang fp contract(off)
 
 namespace arp {
 namespace {
 
-constexpr int kPcThreads = 256;
-constexpr int kPcWaves = kPcThreads / 64;
-constexpr int kPcDraws = 64;                     // draws per tile: one per lane
-constexpr int kPcMaxD = 255;                     // 64 rows of pitch 255 floats: 65 280 bytes of LDS
-constexpr int kPcMaxT = 4096;
 constexpr int kPcCols = 8;                       // columns of draw_stats
 constexpr int kPcObsCols = 4;                    // columns of obs_sums
-constexpr long long kPcTargetWorkgroups = 2048;
 constexpr float kLog2PiF = 1.8378770664093453f;
-constexpr float kNegInvSqrt2F = -0.7071067811865476f;
-
-// how the observations [n0, n1) are shared among blockIdx.y: loglik.hip's rule
-struct Split { long long ntiles, groups, per_group; };
-inline Split split_of(long long nobs, long long R) {
-  Split s;
-  s.ntiles = (R + kPcDraws - 1) / kPcDraws;
-  long long groups = std::max<long long>(1, (kPcTargetWorkgroups + s.ntiles - 1) / s.ntiles);
-  groups = std::min<long long>(std::min<long long>(groups, (nobs + kPcWaves - 1) / kPcWaves), 65535);
-  s.per_group = (nobs + groups - 1) / groups;
-  s.groups = (nobs + s.per_group - 1) / s.per_group;
-  return s;
-}
-inline bool ppc_shape_ok(int64_t n_obs, int64_t n_draws) {
-  return n_obs >= 1 && n_obs < (1ll << 31) && n_draws >= 1 && n_draws < (1ll << 31);
-}
 
 __device__ __forceinline__ double wave_sum(double v) {
 #pragma unroll
@@ -112,95 +83,60 @@ __device__ __forceinline__ double wave_sum(double v) {
   return v;
 }
 
-__global__ __launch_bounds__(kPcThreads) void ppc_kernel(
+__global__ __launch_bounds__(kObsThreads) void ppc_kernel(
     const float* __restrict__ x, long long R, unsigned n_chains, int D, long long stride, int kind, int T,
     const int* __restrict__ idx, const float* __restrict__ w, const float* __restrict__ y,
     const int* __restrict__ scale_idx, const float* __restrict__ log_scale, long long n0, long long n1, long long per_group,
     unsigned key0, unsigned key1, unsigned long long draw_offset, double* __restrict__ part_draw,
     double* __restrict__ part_obs, float* __restrict__ y_rep, long long y_rep_stride, unsigned char* __restrict__ mask,
     unsigned long long* __restrict__ n_masked) {
-  extern __shared__ float tile[];                // [64][Dp]
-  __shared__ int sh_bad[kPcDraws];
-  __shared__ double sh_part[kPcWaves - 1][kPcCols][kPcDraws];
-  const int t = threadIdx.x;
-  const int lane = t & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
-  const int Dp = D | 1;
-  const long long r0 = (long long)blockIdx.x * kPcDraws;
-  const int nrows = (int)min((long long)kPcDraws, R - r0);
-
-  if (t < kPcDraws) sh_bad[t] = 0;
-  __syncthreads();
-  // element e = t + 256 a of the tile is (row e / D, column e % D); a dead row takes 0 without a load
-  const int nelem = kPcDraws * D;
-  for (int e = t; e < nelem; e += kPcThreads) {
-    const int lr = (int)((unsigned)e / (unsigned)D), d = e - lr * D;
-    float v = 0.0f;
-    if (lr < nrows) {
-      const unsigned r = (unsigned)(r0 + lr);
-      const unsigned step = r / n_chains, chain = r - step * n_chains;
-      v = x[(long long)step * stride + (long long)chain * D + d];
-      if (!(v - v == 0.0f)) sh_bad[lr] = 1;
-    }
-    tile[lr * Dp + d] = v;
-  }
-  __syncthreads();
+  extern __shared__ float tile[];                // [64][D | 1]
+  __shared__ int sh_bad[kObsDraws];
+  __shared__ double sh_part[kObsWaves - 1][kPcCols][kObsDraws];
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const long long r0 = (long long)blockIdx.x * kObsDraws;
+  const int nrows = (int)min((long long)kObsDraws, R - r0);
+  stage_tile<true>(x, r0, nrows, n_chains, D, stride, tile, sh_bad);
   const bool live = lane < nrows;
   const bool bad = sh_bad[lane] != 0;
   const bool used = live && !bad;
-  if (blockIdx.y == 0 && wave == 0) {
-    if (live) mask[r0 + lane] = bad ? 1 : 0;
-    const unsigned long long b = __ballot(live && bad);
-    if (lane == 0 && b != 0) atomicAdd(n_masked, (unsigned long long)__popcll(b));      // (an integer count: order-free)
-  }
+  if (blockIdx.y == 0 && wave == 0) write_mask(live, bad, lane, r0, mask, n_masked);
 
   const unsigned long long g = draw_offset + (unsigned long long)(r0 + lane);
   const unsigned g_lo = (unsigned)g, g_hi = (unsigned)(g >> 32);
-  const float* row = tile + lane * Dp;
+  const float* row = tile + lane * (D | 1);
   const long long nb = n0 + (long long)blockIdx.y * per_group, ne = min(n1, nb + per_group);
   double a_y = 0.0, a_yy = 0.0, a_dr = 0.0, a_do = 0.0, a_mu = 0.0, a_n = 0.0;
   float a_min = __builtin_inff(), a_max = -__builtin_inff();
-  for (long long n = nb + wave; n < ne; n += kPcWaves) {
-    const int* ip = idx + n * T;
-    const float* wp = w + n * T;
-    float eta = 0.0f;
-#pragma unroll 4
-    for (int k = 0; k < T; ++k) {
-      const int i = min(max(ip[k], 0), D - 1);
-      eta = eta + wp[k] * row[i];
-    }
+  for (long long n = nb + wave; n < ne; n += kObsWaves) {
+    const float eta = obs_eta(row, idx, w, n, T, D);
     const float yn = y[n];
     uint32_t rnd[4];
     philox4x32_10((uint32_t)n, g_lo, g_hi, 0u, key0, key1, rnd);
-    float yr, pit, dev_r, dev_o, mu, m2;
+    float yr, dev_r, dev_o;
+    PredTerms pt;
     if (kind == 0) {
-      const int si = scale_idx[n];
-      float s = log_scale[n];
-      if (si >= 0) s = s + row[min(si, D - 1)];
+      const float s = obs_log_scale(row, scale_idx, log_scale, n, D);
       const float es = expf(s), ems = expf(-s);
       const float up = fmaf((float)rnd[0], 2.3283064365386963e-10f, 1.1641532182693481e-10f);
       const float z = sqrtf(-2.0f * logf(up)) * cospif(2.0f * angle_rev(rnd[1]));
       yr = eta + es * z;
-      const float zo = (yn - eta) * ems;
-      pit = 0.5f * erfcf(zo * kNegInvSqrt2F);
-      const float zr = (yr - eta) * ems;
+      pt = normal_terms(eta, yn, es, ems);
+      const float zo = pt.aux, zr = (yr - eta) * ems;
       const float two_s = 2.0f * s;
       dev_r = (zr * zr + two_s) + kLog2PiF;
       dev_o = (zo * zo + two_s) + kLog2PiF;
-      mu = eta;
-      m2 = eta * eta + es * es;
     } else {
-      const float e = expf(-fabsf(eta));
-      const float p = (eta >= 0.0f ? 1.0f : e) / (1.0f + e);
+      pt = bernoulli_terms(eta, yn);
+      const float e = pt.aux, p = pt.mu;
       const float u01 = (float)(rnd[0] >> 8) * 5.9604644775390625e-08f;
       yr = u01 < p ? 1.0f : 0.0f;
-      pit = yn > 0.5f ? 1.0f - 0.5f * p : 0.5f * (1.0f - p);
       const float sp = fmaxf(eta, 0.0f) + log1pf(e);
       dev_r = -2.0f * (yr * eta - sp);
       dev_o = -2.0f * (yn * eta - sp);
-      mu = p;
-      m2 = p * p + p * (1.0f - p);
     }
+    const float mu = pt.mu, m2 = pt.m2, pit = pt.pit;
     // along the observations (this lane's draw)
     a_y += (double)yr;
     a_yy += (double)yr * (double)yr;
@@ -224,7 +160,7 @@ __global__ __launch_bounds__(kPcThreads) void ppc_kernel(
 
   // the four waves' rows of this tile, added in wave order
   if (wave > 0) {
-    double (*sp)[kPcDraws] = sh_part[wave - 1];
+    double (*sp)[kObsDraws] = sh_part[wave - 1];
     sp[0][lane] = a_y; sp[1][lane] = a_yy; sp[2][lane] = (double)a_min; sp[3][lane] = (double)a_max;
     sp[4][lane] = a_dr; sp[5][lane] = a_do; sp[6][lane] = a_mu; sp[7][lane] = a_n;
   }
@@ -232,7 +168,7 @@ __global__ __launch_bounds__(kPcThreads) void ppc_kernel(
   if (wave == 0 && live) {
     double lo = (double)a_min, hi = (double)a_max;
 #pragma unroll
-    for (int v = 0; v < kPcWaves - 1; ++v) {
+    for (int v = 0; v < kObsWaves - 1; ++v) {
       a_y += sh_part[v][0][lane]; a_yy += sh_part[v][1][lane];
       lo = fmin(lo, sh_part[v][2][lane]); hi = fmax(hi, sh_part[v][3][lane]);
       a_dr += sh_part[v][4][lane]; a_do += sh_part[v][5][lane]; a_mu += sh_part[v][6][lane]; a_n += sh_part[v][7][lane];
@@ -244,9 +180,9 @@ __global__ __launch_bounds__(kPcThreads) void ppc_kernel(
 }
 
 // draw_stats[r][c] over the groups in ascending order; one thread per (r, c)
-__global__ __launch_bounds__(kPcThreads) void ppc_fold_draws(const double* __restrict__ part_draw, long long R, long long groups,
+__global__ __launch_bounds__(kObsThreads) void ppc_fold_draws(const double* __restrict__ part_draw, long long R, long long groups,
                                                              double* __restrict__ draw_stats) {
-  const long long i = (long long)blockIdx.x * kPcThreads + threadIdx.x;
+  const long long i = (long long)blockIdx.x * kObsThreads + threadIdx.x;
   if (i >= R * kPcCols) return;
   const int c = (int)(i & (kPcCols - 1));
   double v = part_draw[i];
@@ -258,9 +194,9 @@ __global__ __launch_bounds__(kPcThreads) void ppc_fold_draws(const double* __res
 }
 
 // obs_sums[n][c] over the tiles in ascending order; one thread per (n, c)
-__global__ __launch_bounds__(kPcThreads) void ppc_fold_obs(const double* __restrict__ part_obs, long long nobs, long long ntiles,
+__global__ __launch_bounds__(kObsThreads) void ppc_fold_obs(const double* __restrict__ part_obs, long long nobs, long long ntiles,
                                                            double* __restrict__ obs_sums) {
-  const long long i = (long long)blockIdx.x * kPcThreads + threadIdx.x;
+  const long long i = (long long)blockIdx.x * kObsThreads + threadIdx.x;
   if (i >= nobs * kPcObsCols) return;
   double v = part_obs[i];
   for (long long ti = 1; ti < ntiles; ++ti) v += part_obs[ti * nobs * kPcObsCols + i];
@@ -272,7 +208,7 @@ __global__ __launch_bounds__(kPcThreads) void ppc_fold_obs(const double* __restr
 
 extern "C" int64_t arp_predictive_workspace_bytes(int64_t n_obs, int64_t n_draws) {
   using namespace arp;
-  if (!ppc_shape_ok(n_obs, n_draws)) return 0;
+  if (!obs_shape_ok(n_obs, n_draws)) return 0;
   const Split sp = split_of(n_obs, n_draws);
   Carve c;
   c.take(sp.ntiles * n_obs * kPcObsCols * (int64_t)sizeof(double));
@@ -293,12 +229,7 @@ extern "C" int arp_predictive_check(const float* x, int64_t n_samples, int64_t n
     set_error(who + ": x, the table (idx, w, y, scale_idx, log_scale), draw_stats, obs_sums, mask and n_masked are required");
     return 1;
   }
-  if (D < 1 || D > kPcMaxD) { set_error(who + ": 1 <= D <= 255 is required"); return 1; }
-  if (!trace_shape_ok(n_samples, n_chains, D, name)) return 1;
-  if (row_stride < n_chains * D) { set_error(who + ": row_stride >= n_chains * D is required"); return 1; }
-  if (kind != 0 && kind != 1) { set_error(who + ": kind must be ARP_OBS_NORMAL or ARP_OBS_BERNOULLI"); return 1; }
-  if (T < 1 || T > kPcMaxT) { set_error(who + ": 1 <= T <= 4096 is required"); return 1; }
-  if (n0 < 0 || n1 <= n0 || n1 >= (1ll << 31)) { set_error(who + ": 0 <= n0 < n1 < 2^31 is required"); return 1; }
+  if (!table_call_ok(name, n_samples, n_chains, D, row_stride, kind, T, n0, n1)) return 1;
   if (draw_offset < 0) { set_error(who + ": draw_offset >= 0 is required"); return 1; }
   const long long R = n_samples * n_chains;
   if (y_rep && y_rep_stride < R) { set_error(who + ": y_rep_stride >= n_samples * n_chains is required"); return 1; }
@@ -312,16 +243,15 @@ extern "C" int arp_predictive_check(const float* x, int64_t n_samples, int64_t n
   double* part_draw = (double*)((char*)workspace + c.take(sp.groups * R * kPcCols * (int64_t)sizeof(double)));
   hipStream_t st = (hipStream_t)stream;
   ARP_HIP_OK(hipMemsetAsync(n_masked, 0, sizeof(int64_t), st));
-  const size_t lds = (size_t)kPcDraws * (D | 1) * sizeof(float);
-  hipLaunchKernelGGL(ppc_kernel, dim3((unsigned)sp.ntiles, (unsigned)sp.groups), dim3(kPcThreads), lds, st, x, R, (unsigned)n_chains,
-                     (int)D, (long long)row_stride, (int)kind, (int)T, idx, w, y, scale_idx, log_scale, (long long)n0, (long long)n1,
+  hipLaunchKernelGGL(ppc_kernel, dim3((unsigned)sp.ntiles, (unsigned)sp.groups), dim3(kObsThreads), tile_lds_bytes(D), st, x, R,
+                     (unsigned)n_chains, (int)D, (long long)row_stride, (int)kind, (int)T, idx, w, y, scale_idx, log_scale, (long long)n0, (long long)n1,
                      sp.per_group, (unsigned)seed, (unsigned)(seed >> 32), (unsigned long long)draw_offset, part_draw, part_obs,
                      y_rep, (long long)y_rep_stride, (unsigned char*)mask, (unsigned long long*)n_masked);
   ARP_HIP_OK(hipGetLastError());
-  hipLaunchKernelGGL(ppc_fold_draws, dim3(blocks_for(R * kPcCols, kPcThreads)), dim3(kPcThreads), 0, st, (const double*)part_draw, R,
+  hipLaunchKernelGGL(ppc_fold_draws, dim3(blocks_for(R * kPcCols, kObsThreads)), dim3(kObsThreads), 0, st, (const double*)part_draw, R,
                      sp.groups, draw_stats);
   ARP_HIP_OK(hipGetLastError());
-  hipLaunchKernelGGL(ppc_fold_obs, dim3(blocks_for(nobs * kPcObsCols, kPcThreads)), dim3(kPcThreads), 0, st, (const double*)part_obs,
+  hipLaunchKernelGGL(ppc_fold_obs, dim3(blocks_for(nobs * kPcObsCols, kObsThreads)), dim3(kObsThreads), 0, st, (const double*)part_obs,
                      nobs, sp.ntiles, obs_sums);
   ARP_HIP_OK(hipGetLastError());
   return 0;

@@ -527,7 +527,7 @@ DeviceTable = collections.namedtuple("DeviceTable", ["kind", "T", "N", "idx", "w
 LooSummary = collections.namedtuple("LooSummary", ["elpd_loo", "elpd_loo_se", "p_loo", "elpd_waic", "elpd_waic_se", "p_waic"])
 PSIS_COLUMNS = ("elpd_loo", "pareto_k", "lppd", "p_waic", "tail_len", "cutoff", "gpd_sigma", "draws_used")
 PSIS_MAX_DRAWS = 1 << 24          # the most draws per observation arp_psis_loo takes (csrc/psis.hip: kPsMaxR)
-LOGLIK_MAX_D = 255                # the widest state arp_pointwise_loglik takes (csrc/loglik.hip: kLlMaxD)
+LOGLIK_MAX_D = 255                # the widest state arp_pointwise_loglik takes (csrc/obs_table.h: kObsMaxD)
 PARETO_K_CAP = 0.7                # the k-hat above which PSIS is unreliable at any sample size (Vehtari et al. 2024)
 
 
@@ -551,6 +551,44 @@ def upload_table(table, D, device):
     return DeviceTable(int(table.kind), int(T), int(N), dev(idx), dev(w), dev(y), dev(si), dev(ls), y)
 
 
+def _table_call(trace, table, n0, n1, who):
+    """How the wrappers over an observation table open -> (view, n0, n1, R): _lib.trace_view's tuple of the trace, the
+    resolved observation range and R = S C draws; an empty range or trace is refused."""
+    view = _lib.trace_view(trace, who)
+    n1 = table.N if n1 is None else int(n1)
+    n0 = int(n0)
+    if not 0 <= n0 < n1 <= table.N:
+        raise ValueError("%s: 0 <= n0 < n1 <= %d observations is required" % (who, table.N))
+    R = view[1] * view[2]
+    if R == 0 or view[3] == 0:
+        raise ValueError("%s: an empty trace" % who)
+    return view, n0, n1, R
+
+
+def _table_args(view, table, n0, n1):
+    """The leading C arguments of those entry points: the trace, the table, the range."""
+    x, S, Cn, D, row_stride = view
+    return (_lib.ptr(x), S, Cn, D, row_stride, table.kind, _lib.ptr(table.idx), _lib.ptr(table.w), table.T, _lib.ptr(table.y),
+            _lib.ptr(table.scale_idx), _lib.ptr(table.log_scale), n0, n1)
+
+
+def _draw_matrix(t, dtype, rows, R, who, name):
+    """`t`, a `dtype` [>= rows, >= R] device matrix with unit column stride -> (t, row stride)."""
+    if not (torch.is_tensor(t) and t.is_cuda and t.dtype == dtype and t.dim() == 2 and t.shape[0] >= rows and t.shape[1] >= R
+            and t.stride(1) == 1 and (t.stride(0) >= R or t.shape[0] == 1)):
+        raise ValueError("%s: %s must be a %s [>= n1 - n0, >= S C] matrix on the GPU with unit column stride"
+                         % (who, name, str(dtype).replace("torch.", "")))
+    return t, (int(t.stride(0)) if t.shape[0] > 1 else max(R, int(t.shape[1])))
+
+
+def _obs_workspace_bytes(symbol, N, R, who, most_draws):
+    """What the library's sizing function `symbol` asks for N observations of R draws; raises on a shape it refuses."""
+    need = int(getattr(_lib.lib(), symbol)(int(N), int(R)))
+    if need <= 0:
+        raise ValueError("%s: 1 <= N < 2^31 observations of 1 ... %s draws are required" % (who, most_draws))
+    return need
+
+
 def pointwise_loglik(trace, table, n0=0, n1=None, out=None):
     """(ll, mask, n_masked) of `arp_pointwise_loglik` for a recorded CENTRED [S, C, D] float32 trace on the GPU and the
     observations [n0, n1) of a DeviceTable: ll [n1 - n0, S C] float32, ll[n - n0, s C + c] the log-likelihood of
@@ -558,34 +596,35 @@ def pointwise_loglik(trace, table, n0=0, n1=None, out=None):
     to be read); n_masked: their count, an int64 device scalar.  A leading or inner block of chains of a wider trace is
     read in place, as gram_sums reads it.  out: an optional float32 device matrix of at least n1 - n0 rows whose rows are
     at least S C apart, written in place (ll is then a view of it)."""
-    x, S, Cn, D, row_stride = _lib.trace_view(trace, "pointwise_loglik")
-    n1 = table.N if n1 is None else int(n1)
-    n0 = int(n0)
-    if not 0 <= n0 < n1 <= table.N:
-        raise ValueError("pointwise_loglik: 0 <= n0 < n1 <= %d observations is required" % table.N)
-    R = S * Cn
-    if R == 0 or D == 0:
-        raise ValueError("pointwise_loglik: an empty trace")
+    view, n0, n1, R = _table_call(trace, table, n0, n1, "pointwise_loglik")
+    dev = view[0].device
     if out is None:
-        out = torch.empty(n1 - n0, R, dtype=torch.float32, device=x.device)
-    if not (torch.is_tensor(out) and out.is_cuda and out.dtype == torch.float32 and out.dim() == 2 and out.shape[0] >= n1 - n0
-            and out.shape[1] >= R and out.stride(1) == 1 and (out.stride(0) >= R or out.shape[0] == 1)):
-        raise ValueError("pointwise_loglik: out must be a float32 [>= n1 - n0, >= S C] matrix on the GPU with unit column stride")
-    ll_stride = int(out.stride(0)) if out.shape[0] > 1 else max(R, int(out.shape[1]))
-    mask = torch.empty(R, dtype=torch.uint8, device=x.device)
-    n_masked = torch.zeros((), dtype=torch.int64, device=x.device)
-    _lib.call(x.device, _lib.lib().arp_pointwise_loglik, _lib.ptr(x), S, Cn, D, row_stride, table.kind, _lib.ptr(table.idx),
-              _lib.ptr(table.w), table.T, _lib.ptr(table.y), _lib.ptr(table.scale_idx), _lib.ptr(table.log_scale), n0, n1,
-              _lib.ptr(out), ll_stride, _lib.ptr(mask), _lib.ptr(n_masked))
+        out = torch.empty(n1 - n0, R, dtype=torch.float32, device=dev)
+    out, ll_stride = _draw_matrix(out, torch.float32, n1 - n0, R, "pointwise_loglik", "out")
+    mask = torch.empty(R, dtype=torch.uint8, device=dev)
+    n_masked = torch.zeros((), dtype=torch.int64, device=dev)
+    _lib.call(dev, _lib.lib().arp_pointwise_loglik, *_table_args(view, table, n0, n1), _lib.ptr(out), ll_stride, _lib.ptr(mask),
+              _lib.ptr(n_masked))
     return out[:n1 - n0, :R], mask, n_masked
 
 
 def psis_workspace_bytes(N, R):
     """Bytes of device workspace `psis_loo` takes for N observations of R draws; raises on a shape that is refused."""
-    need = int(_lib.lib().arp_psis_workspace_bytes(int(N), int(R)))
-    if need <= 0:
-        raise ValueError("psis_loo: 1 <= N < 2^31 observations of 1 ... 2^24 draws are required")
-    return need
+    return _obs_workspace_bytes("arp_psis_workspace_bytes", N, R, "psis_loo", "2^24")
+
+
+def _ll_matrix(ll, mask, who):
+    """ll [N, R] float32 on the GPU as the PSIS entry points read it -> (ll, N, R, row stride): rows at least R apart, a
+    contiguous copy otherwise; the optional mask [R] uint8 is checked on the way."""
+    if not (torch.is_tensor(ll) and ll.is_cuda and ll.dtype == torch.float32 and ll.dim() == 2):
+        raise ValueError("%s: a float32 [N, R] matrix on the GPU is required (there is no CPU fallback)" % who)
+    N, R = (int(v) for v in ll.shape)
+    if N == 0 or R == 0:
+        raise ValueError("%s: an empty matrix" % who)
+    if not (ll.stride(1) == 1 and (N == 1 or ll.stride(0) >= R)):
+        ll = ll.contiguous()
+    _lib.device_operand(mask, torch.uint8, (R,), who, "mask", "R")
+    return ll, N, R, (int(ll.stride(0)) if N > 1 else R)
 
 
 def psis_loo(ll, mask=None):
@@ -594,15 +633,7 @@ def psis_loo(ll, mask=None):
     tail length M, the cut-off (the largest shifted log ratio not in the tail), the fitted GPD's sigma and the draws
     used.  mask: an optional [R] uint8 device tensor, draws with a non-zero entry are left out (pointwise_loglik's).
     k-hat = +inf where no tail was fitted (M < 5, a constant tail, a non-finite ll).  The workspace is owned here."""
-    if not (torch.is_tensor(ll) and ll.is_cuda and ll.dtype == torch.float32 and ll.dim() == 2):
-        raise ValueError("psis_loo: a float32 [N, R] matrix on the GPU is required (there is no CPU fallback)")
-    N, R = (int(v) for v in ll.shape)
-    if N == 0 or R == 0:
-        raise ValueError("psis_loo: an empty matrix")
-    if not (ll.stride(1) == 1 and (N == 1 or ll.stride(0) >= R)):
-        ll = ll.contiguous()
-    stride = int(ll.stride(0)) if N > 1 else R
-    _lib.device_operand(mask, torch.uint8, (R,), "psis_loo", "mask", "R")
+    ll, N, R, stride = _ll_matrix(ll, mask, "psis_loo")
     out = torch.empty(N, 8, dtype=torch.float64, device=ll.device)
     _lib.call(ll.device, _lib.lib().arp_psis_loo, _lib.ptr(ll), N, R, stride, _lib.ptr(mask), _lib.ptr(out),
               workspace=psis_workspace_bytes(N, R))
@@ -669,10 +700,7 @@ PpcSummary = collections.namedtuple("PpcSummary", ["draws_used", "draws_left_out
 
 def predictive_workspace_bytes(N, R):
     """Bytes of device workspace `predictive_check` takes for N observations of R draws; raises on a shape that is refused."""
-    need = int(_lib.lib().arp_predictive_workspace_bytes(int(N), int(R)))
-    if need <= 0:
-        raise ValueError("predictive_check: 1 <= N < 2^31 observations of 1 ... 2^31 - 1 draws are required")
-    return need
+    return _obs_workspace_bytes("arp_predictive_workspace_bytes", N, R, "predictive_check", "2^31 - 1")
 
 
 def predictive_check(trace, table, n0=0, n1=None, seed=0, draw_offset=0, want_y_rep=False):
@@ -684,25 +712,18 @@ def predictive_check(trace, table, n0=0, n1=None, seed=0, draw_offset=0, want_y_
     draw r) is a function of (seed, n, draw_offset + r) alone: `draw_offset` is the global number of this trace's first
     draw when the draws of a job are spread over calls or ranks.  A block of chains of a wider trace is read in place;
     the workspace is owned here."""
-    x, S, Cn, D, row_stride = _lib.trace_view(trace, "predictive_check")
-    n1 = table.N if n1 is None else int(n1)
-    n0 = int(n0)
-    if not 0 <= n0 < n1 <= table.N:
-        raise ValueError("predictive_check: 0 <= n0 < n1 <= %d observations is required" % table.N)
-    R = S * Cn
-    if R == 0 or D == 0:
-        raise ValueError("predictive_check: an empty trace")
+    view, n0, n1, R = _table_call(trace, table, n0, n1, "predictive_check")
+    dev = view[0].device
     if int(draw_offset) < 0:
         raise ValueError("predictive_check: draw_offset >= 0 is required")
-    draw_stats = torch.empty(R, len(PPC_DRAW_COLUMNS), dtype=torch.float64, device=x.device)
-    obs_sums = torch.empty(n1 - n0, len(PPC_OBS_COLUMNS), dtype=torch.float64, device=x.device)
-    y_rep = torch.empty(n1 - n0, R, dtype=torch.float32, device=x.device) if want_y_rep else None
-    mask = torch.empty(R, dtype=torch.uint8, device=x.device)
-    n_masked = torch.zeros((), dtype=torch.int64, device=x.device)
-    _lib.call(x.device, _lib.lib().arp_predictive_check, _lib.ptr(x), S, Cn, D, row_stride, table.kind, _lib.ptr(table.idx),
-              _lib.ptr(table.w), table.T, _lib.ptr(table.y), _lib.ptr(table.scale_idx), _lib.ptr(table.log_scale), n0, n1,
-              int(seed) & 0xFFFFFFFFFFFFFFFF, int(draw_offset), _lib.ptr(draw_stats), _lib.ptr(obs_sums), _lib.ptr(y_rep), R,
-              _lib.ptr(mask), _lib.ptr(n_masked), workspace=predictive_workspace_bytes(n1 - n0, R))
+    draw_stats = torch.empty(R, len(PPC_DRAW_COLUMNS), dtype=torch.float64, device=dev)
+    obs_sums = torch.empty(n1 - n0, len(PPC_OBS_COLUMNS), dtype=torch.float64, device=dev)
+    y_rep = torch.empty(n1 - n0, R, dtype=torch.float32, device=dev) if want_y_rep else None
+    mask = torch.empty(R, dtype=torch.uint8, device=dev)
+    n_masked = torch.zeros((), dtype=torch.int64, device=dev)
+    _lib.call(dev, _lib.lib().arp_predictive_check, *_table_args(view, table, n0, n1), int(seed) & 0xFFFFFFFFFFFFFFFF,
+              int(draw_offset), _lib.ptr(draw_stats), _lib.ptr(obs_sums), _lib.ptr(y_rep), R, _lib.ptr(mask), _lib.ptr(n_masked),
+              workspace=predictive_workspace_bytes(n1 - n0, R))
     return draw_stats, obs_sums, y_rep, mask, n_masked
 
 
@@ -823,10 +844,7 @@ LooPredSummary = collections.namedtuple("LooPredSummary", ["observations", "left
 
 def loo_predictive_workspace_bytes(N, R):
     """Bytes of device workspace `loo_predictive` takes for N observations of R draws; raises on a shape that is refused."""
-    need = int(_lib.lib().arp_loo_predictive_workspace_bytes(int(N), int(R)))
-    if need <= 0:
-        raise ValueError("loo_predictive: 1 <= N < 2^31 observations of 1 ... 2^31 - 1 draws are required")
-    return need
+    return _obs_workspace_bytes("arp_loo_predictive_workspace_bytes", N, R, "loo_predictive", "2^31 - 1")
 
 
 def loo_predictive(trace, table, lw, n0=0, n1=None):
@@ -837,22 +855,12 @@ def loo_predictive(trace, table, lw, n0=0, n1=None):
     with lw != -inf and W = exp(lw): sum W, sum W^2, sum W mu, sum W (mu^2 + var), sum W pit and the draws counted, mu, var
     and pit as predictive_check defines them.  A block of chains of a wider trace is read in place; the workspace is
     owned here."""
-    x, S, Cn, D, row_stride = _lib.trace_view(trace, "loo_predictive")
-    n1 = table.N if n1 is None else int(n1)
-    n0 = int(n0)
-    if not 0 <= n0 < n1 <= table.N:
-        raise ValueError("loo_predictive: 0 <= n0 < n1 <= %d observations is required" % table.N)
-    R = S * Cn
-    if R == 0 or D == 0:
-        raise ValueError("loo_predictive: an empty trace")
-    if not (torch.is_tensor(lw) and lw.is_cuda and lw.dtype == torch.float64 and lw.dim() == 2 and lw.shape[0] >= n1 - n0
-            and lw.shape[1] >= R and lw.stride(1) == 1 and (lw.stride(0) >= R or lw.shape[0] == 1)):
-        raise ValueError("loo_predictive: lw must be a float64 [>= n1 - n0, >= S C] matrix on the GPU with unit column stride")
-    lw_stride = int(lw.stride(0)) if lw.shape[0] > 1 else max(R, int(lw.shape[1]))
-    obs_sums = torch.empty(n1 - n0, len(LOO_PRED_COLUMNS), dtype=torch.float64, device=x.device)
-    _lib.call(x.device, _lib.lib().arp_loo_predictive, _lib.ptr(x), S, Cn, D, row_stride, table.kind, _lib.ptr(table.idx),
-              _lib.ptr(table.w), table.T, _lib.ptr(table.y), _lib.ptr(table.scale_idx), _lib.ptr(table.log_scale), n0, n1,
-              _lib.ptr(lw), lw_stride, _lib.ptr(obs_sums), workspace=loo_predictive_workspace_bytes(n1 - n0, R))
+    view, n0, n1, R = _table_call(trace, table, n0, n1, "loo_predictive")
+    dev = view[0].device
+    lw, lw_stride = _draw_matrix(lw, torch.float64, n1 - n0, R, "loo_predictive", "lw")
+    obs_sums = torch.empty(n1 - n0, len(LOO_PRED_COLUMNS), dtype=torch.float64, device=dev)
+    _lib.call(dev, _lib.lib().arp_loo_predictive, *_table_args(view, table, n0, n1), _lib.ptr(lw), lw_stride,
+              _lib.ptr(obs_sums), workspace=loo_predictive_workspace_bytes(n1 - n0, R))
     return obs_sums
 
 
@@ -967,18 +975,8 @@ def psis_weights(ll, mask=None):
     """(out, lw) of `arp_psis_weights` for ll [N, R] float32 on the GPU: out [N, 8] float64 is psis_loo's bit for bit, lw
     [N, R] float64 the max-shifted, Pareto-smoothed log weight of every draw (raw where the row was not fitted, -inf for a
     masked draw, NaN throughout the kept draws of a row with a non-finite kept ll).  The workspace is owned here."""
-    if not (torch.is_tensor(ll) and ll.is_cuda and ll.dtype == torch.float32 and ll.dim() == 2):
-        raise ValueError("psis_weights: a float32 [N, R] matrix on the GPU is required (there is no CPU fallback)")
-    N, R = (int(v) for v in ll.shape)
-    if N == 0 or R == 0:
-        raise ValueError("psis_weights: an empty matrix")
-    if not (ll.stride(1) == 1 and (N == 1 or ll.stride(0) >= R)):
-        ll = ll.contiguous()
-    stride = int(ll.stride(0)) if N > 1 else R
-    _lib.device_operand(mask, torch.uint8, (R,), "psis_weights", "mask", "R")
-    need = int(_lib.lib().arp_psis_weights_workspace_bytes(N, R))
-    if need <= 0:
-        raise ValueError("psis_weights: 1 <= N < 2^31 observations of 1 ... 2^24 draws are required")
+    ll, N, R, stride = _ll_matrix(ll, mask, "psis_weights")
+    need = _obs_workspace_bytes("arp_psis_weights_workspace_bytes", N, R, "psis_weights", "2^24")
     out = torch.empty(N, 8, dtype=torch.float64, device=ll.device)
     lw = torch.empty(N, R, dtype=torch.float64, device=ll.device)
     _lib.call(ll.device, _lib.lib().arp_psis_weights, _lib.ptr(ll), N, R, stride, _lib.ptr(mask), _lib.ptr(out), _lib.ptr(lw), R,

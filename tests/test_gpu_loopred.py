@@ -8,8 +8,8 @@ the project's standing allowance for second-order terms, the second part the flo
 and sum W^2 carry the second part only; the count is exact.  Nothing is fitted to the device's output.
 
 The real pipeline once (pointwise_loglik -> psis_weights -> loo_predictive) against the reference on the device's own lw,
-and that lw against the reference's draw-order weights within the tolerance of tests/test_gpu_vicheck.py; the structural
-properties; a statistical tie with a closed form; the refusals.
+and that lw against the reference's draw-order weights within the tolerance of tests/test_gpu_vicheck.py; unit weights
+against predictive_check's own sums, to float64 association; the structural properties; a statistical tie with a closed form; the refusals.
 
 The tie (test_closed_form_of_a_normal_mean): N = 20, R = 8 192, RandomState(1).  Checked on the CPU from the reference
 alone when the test was written: the worst of the 60 ratios lies 0.99 se from the closed form (bound here: 4 se; a change
@@ -175,6 +175,33 @@ def test_block_of_chains_read_in_place_is_bitwise_its_copy(gpu, kind):
     a = run(gpu, block, table, lw)
     assert np.array_equal(bits(a), bits(run(gpu, block.contiguous(), table, lw)))
     check(gpu, table, block.contiguous().cpu().numpy(), lw, what="block", got=a)
+
+
+@pytest.mark.parametrize("kind", (pp.NORMAL, pp.BERNOULLI))
+@pytest.mark.parametrize("shape, D", (((3, 3, 1, 63), 9), ((25, 5, 1, 65), 9), ((5, 5, 2, 32), 255)))
+def test_unit_weights_reproduce_the_predictive_check_sums(gpu, shape, D, kind):
+    """The two kernels share their predictive terms (csrc/obs_table.h), seen from outside: with lw = 0 throughout and no
+    masked draw, sum W mu, sum W (mu^2 + var) and sum W pit are sums of the very float32 values predictive_check adds into
+    obs_sums[:, 0:3]; only the float64 association differs (the two butterflies, the chain over tiles).  Either side is
+    within (R - 1) 2^-53 sum_r |h_r| of the exact sum of the same terms, so |a - b| <= R 2^-52 sum_r |h_r|, sum |h| from the
+    float64 reference; sum W and the count are R exactly.  Terms computed by other operations would leave a gap of order
+    2^-24 sum |h|.  One ragged tile, two tiles with a one-lane tail, a full tile at the widest state."""
+    from autoreparam_amd import diagnostics
+    table, x3, seed = make_case(kind, D, shape)
+    _, N, S, Cn = shape
+    R = S * Cn
+    xd = torch.as_tensor(x3, device=gpu)
+    dt = diagnostics.upload_table(table, D, gpu)
+    _, obs, _, _, count = diagnostics.predictive_check(xd, dt, seed=seed)
+    loo = diagnostics.loo_predictive(xd, dt, torch.zeros(N, R, dtype=torch.float64, device=gpu)).cpu().numpy()
+    obs = obs.cpu().numpy()
+    assert int(count.item()) == 0
+    assert np.all(loo[:, 0] == R) and np.all(loo[:, 5] == R)
+    r = pp.reference(table, x3.reshape(R, D))
+    for j, h in enumerate((r.mu, r.m2, r.pit)):
+        gap, allow = np.abs(loo[:, 2 + j] - obs[:, j]), R * F64 * np.abs(h).sum(1)
+        print("%s: largest gap %.3g of %.3g allowed" % (lr.COLUMNS[2 + j], gap.max(), allow[gap.argmax()]))
+        assert np.all(gap <= allow), (lr.COLUMNS[2 + j], float(np.max(gap / allow)))
 
 
 def tie_case():
