@@ -301,6 +301,31 @@ def report_ppc(results):
     return lines
 
 
+def report_psens(results):
+    """Build-specific: the power-scaling sensitivity report of every sampling run that recorded one
+    (--sensitivity_diagnostics; the last run of each file): the largest prior and likelihood sensitivity with their
+    elements, and the flagged elements -- prior-data conflicts, and elements with a weak likelihood or a strong prior
+    (sensitivity above 0.05; Kallioinen et al. 2023).  The prior is the joint density of all latent sites."""
+    lines = []
+    for m, r in results.items():
+        if "psens_draws" not in r:
+            continue
+        last = _last(r, "psens_")
+        if last["psens_draws"] is None:
+            lines.append("{}: power-scaling sensitivity not computed".format(m))
+            continue
+        conflict, weak = last["psens_conflict_elements"] or [], last["psens_weak_likelihood_elements"] or []
+        lines.append("{}: power-scaling sensitivity: prior max {} ({}), likelihood max {} ({}); prior-data conflict: {}; weak "
+                     "likelihood / strong prior: {}; worst Pareto k-hat {} (threshold {}); {} draws of {} chains, {} left "
+                     "out, {} constant element(s); {}".format(
+                         m, _fmt(last["psens_prior_max"]), last["psens_prior_max_element"], _fmt(last["psens_likelihood_max"]),
+                         last["psens_likelihood_max_element"], ", ".join(conflict) or "none", ", ".join(weak) or "none",
+                         _fmt(last["psens_pareto_k_max"]), _fmt(last["psens_pareto_k_threshold"]), last["psens_draws"],
+                         last["psens_chains"], last["psens_draws_left_out"], last["psens_elements_left_out"],
+                         _secs(last.get("psens_time_sec"))))
+    return lines
+
+
 def report_vi(results):
     """Build-specific: the fit check of every VI result file that holds one (--vi_diagnostics): the Pareto k-hat of the
     importance ratios p / q against its threshold, the ELBO of the final parameters next to the optimiser's own figure, the
@@ -341,7 +366,7 @@ def report_loo_compare(path_a, path_b):
 
 def main(argv=None):
     ap = argparse.ArgumentParser()
-    for f in ("elbos", "ess", "reparams", "normalize_times", "rhat", "energy", "trajectory", "geometry", "loo", "ppc", "vi"):
+    for f in ("elbos", "ess", "reparams", "normalize_times", "rhat", "energy", "trajectory", "geometry", "loo", "ppc", "vi", "psens"):
         ap.add_argument("--" + f, action="store_true")
     ap.add_argument("--loo_compare", default="", help="A_loo.npz,B_loo.npz: the paired elpd_loo difference of two models")
     ap.add_argument("--model", default="all")
@@ -367,7 +392,8 @@ def main(argv=None):
                             ("energy", lambda: report_energy(results, root, name)),
                             ("trajectory", lambda: report_trajectory(results, root, name)),
                             ("geometry", lambda: report_geometry(results, root, name)), ("loo", lambda: report_loo(results)),
-                            ("ppc", lambda: report_ppc(results)), ("vi", lambda: report_vi(results))):
+                            ("ppc", lambda: report_ppc(results)), ("vi", lambda: report_vi(results)),
+                            ("psens", lambda: report_psens(results))):
             if getattr(args, flag):
                 print("\n".join(lines()) + "\n")
 

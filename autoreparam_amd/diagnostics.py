@@ -20,7 +20,10 @@ its leave-one-out counterpart (`loo_predictive` on `arp_loo_predictive`: the sam
 smoothed weights of `psis_weights`; `loo_predictive_summary`: the LOO predictive mean and sd, the LOO-PIT); and
 the one report that judges the variational fit the sampler inherits its steps and its start from (`vi_check` on
 `arp_vi_draws`, `arp_psis_weights` and `arp_vi_fold`; `vi_check_summary`: the Pareto k-hat of the importance ratios p / q,
-the ELBO and its gradient at the final parameters, the importance-corrected loc and scale; Yao et al. 2018).
+the ELBO and its gradient at the final parameters, the importance-corrected loc and scale; Yao et al. 2018); and
+power-scaling sensitivity (`powerscale_lw`, `element_order` on `arp_element_order`, `cjs_sums` on `arp_cjs_sums`,
+`loglik_total`; `psens_summary`: how far every marginal moves when the prior or the likelihood is raised to a power
+slightly off 1, as a cumulative Jensen-Shannon distance; Kallioinen et al. 2023).
 
 Build-specific (the reference runs 100 chains and reports the within-chain ESS only).  The per-chain moments come from
 one pass over a trace that is already on the device (`arp_split_moments`) or from the in-kernel statistics of a
@@ -1087,3 +1090,135 @@ def vi_check_summary(elem, tot, out8, loc, scale, e0, logp_const):
                           num(ess), num(evidence), num(evidence_se), num(evidence - elbo),
                           num(np.sqrt(evidence_se * evidence_se + elbo_se * elbo_se)), g_loc, g_loc_se, g_scale, g_scale_se,
                           gap, shift, ratio, e0 + cm, is_sd)
+
+
+# ---- power-scaling sensitivity: how much of a marginal is the prior's, how much the data's (csrc/psens.hip) ----
+PSENS_DELTA = 0.01                # alpha = 1 + delta and 1 / (1 + delta) (Kallioinen et al. 2023; priorsense, ArviZ psens)
+PSENS_THRESHOLD = 0.05            # a sensitivity above it is reported (the same sources)
+CJS_COLUMNS = ("kept", "sum_w", "sum_wu", "sum_wu_sq", "a_pq", "a_qp", "i_p", "i_q")
+CJS_MAX_ROWS = 8                  # the most weight rows arp_cjs_sums takes
+# the weight rows of the report, in the order powerscale_lw writes and psens_summary reads them: the last is the
+# unweighted one (lw = 0), which gives the pooled mean and sd the shifts are measured in
+PSENS_ROWS = ("prior_lower", "prior_upper", "likelihood_lower", "likelihood_upper", "unweighted")
+# The report (psens_summary), [D] float64, NaN for a constant element: prior, likelihood: the sensitivities;
+# mean_shift_*: (weighted mean - pooled mean) / pooled sd of the upper row; sd_ratio_*: weighted sd / pooled sd of the
+# upper row.  constant: the number of constant elements; conflict, weak_likelihood: the indices of the diagnosed elements.
+PsensSummary = collections.namedtuple("PsensSummary", ["prior", "likelihood", "mean_shift_prior", "mean_shift_likelihood",
+                                                       "sd_ratio_prior", "sd_ratio_likelihood", "constant", "conflict",
+                                                       "weak_likelihood"])
+
+
+def loglik_total(ll, total):
+    """`arp_loglik_total`: adds every draw's column of ll [n, R] float32 on the GPU (rows may be further apart than R) to
+    total [R] float64, in place, observations ascending -- tiles walked in ascending order compose bit for bit.  Returns
+    total."""
+    ll, n, R, stride = _ll_matrix(ll, None, "loglik_total")
+    _lib.device_operand(total, torch.float64, (R,), "loglik_total", "total", "R")
+    if total is None:
+        raise ValueError("loglik_total: total is required")
+    _lib.call(ll.device, _lib.lib().arp_loglik_total, _lib.ptr(ll), n, R, stride, _lib.ptr(total))
+    return total
+
+
+def element_order(trace, want_sorted=True):
+    """(order, sorted) of `arp_element_order` for a recorded [S, C, D] float32 trace on the GPU: order [D, S C] int32 (the
+    words are unsigned), order[d, i] the draw index r = s C + c of the i-th smallest value of element d, ties in
+    ascending r; sorted [D, S C] float32, those values (None without want_sorted).  A leading or inner block of chains of
+    a wider trace is taken in place, as rank_normalize takes it; the workspace is owned here."""
+    x, S, Cn, D, row_stride = _lib.trace_view(trace, "element_order")
+    if S == 0 or Cn == 0 or D == 0:
+        raise ValueError("element_order: an empty trace")
+    L = _lib.lib()
+    need = int(L.arp_element_order_workspace_bytes(S, Cn, D))
+    if need <= 0:
+        _lib.check(1)
+    order = torch.empty(D, S * Cn, dtype=torch.int32, device=x.device)
+    values = torch.empty(D, S * Cn, dtype=torch.float32, device=x.device) if want_sorted else None
+    _lib.call(x.device, L.arp_element_order, _lib.ptr(x), S, Cn, D, row_stride, _lib.ptr(order), _lib.ptr(values),
+              workspace=need)
+    return order, values
+
+
+def cjs_sums(values, order, lw, shift=None):
+    """out [K, D, 8] float64 device tensor of `arp_cjs_sums` (CJS_COLUMNS): values, order [D, N] as element_order returns
+    them, lw [K, >= N] float64 on the GPU with unit column stride (1 <= K <= 8 rows of log weights, psis_weights'; -inf
+    leaves a draw out of its row), shift: an optional [D] float32 device tensor the weighted moments are taken about."""
+    if not (torch.is_tensor(values) and values.is_cuda and values.dtype == torch.float32 and values.dim() == 2
+            and values.is_contiguous()):
+        raise ValueError("cjs_sums: sorted values must be a contiguous float32 [D, N] matrix on the GPU (there is no CPU fallback)")
+    D, N = (int(v) for v in values.shape)
+    if D == 0 or N == 0:
+        raise ValueError("cjs_sums: an empty matrix")
+    _lib.device_operand(order, torch.int32, (D, N), "cjs_sums", "order", "D, N")
+    _lib.device_operand(shift, torch.float32, (D,), "cjs_sums", "shift", "D")
+    if order is None or not (torch.is_tensor(lw) and lw.dim() == 2 and 1 <= int(lw.shape[0]) <= CJS_MAX_ROWS):
+        raise ValueError("cjs_sums: order and 1 ... 8 rows of lw are required")
+    K = int(lw.shape[0])
+    lw, lw_stride = _draw_matrix(lw, torch.float64, K, N, "cjs_sums", "lw")
+    out = torch.empty(K, D, len(CJS_COLUMNS), dtype=torch.float64, device=values.device)
+    _lib.call(values.device, _lib.lib().arp_cjs_sums, _lib.ptr(values), _lib.ptr(order), N, D, _lib.ptr(lw), lw_stride, K,
+              _lib.ptr(shift), _lib.ptr(out))
+    return out
+
+
+def powerscale_lw(log_prior, log_likelihood, left_out=None):
+    """(out, lw) for the power-scaled prior and likelihood of R draws: log_prior, log_likelihood [R] float64 device tensors
+    (additive constants cancel), left_out an optional [R] bool or uint8 device tensor.  The four rows PSENS_ROWS[:4] are
+    the log ratios (alpha - 1) * component at alpha = 1 / (1 + PSENS_DELTA) and 1 + PSENS_DELTA; psis_weights takes the
+    NEGATED log ratio as float32 (about its mean over the draws kept, which cancels too, so that float32 resolves the
+    ratios and not the component's size).  out [4, 8] float64: PSIS_COLUMNS per row, out[:, 1] the k-hat; lw [5, R] float64:
+    the smoothed log weights of the four rows and PSENS_ROWS[4], 0 for a draw kept; -inf throughout for a draw left out."""
+    if not (torch.is_tensor(log_prior) and log_prior.is_cuda and log_prior.dim() == 1 and log_prior.numel() > 0
+            and torch.is_tensor(log_likelihood) and log_likelihood.shape == log_prior.shape):
+        raise ValueError("powerscale_lw: log_prior and log_likelihood of one shape [R] on the GPU are required")
+    R = int(log_prior.numel())
+    dev = log_prior.device
+    mask = torch.zeros(R, dtype=torch.uint8, device=dev) if left_out is None else left_out.to(torch.uint8).contiguous()
+    kept = mask == 0
+    rows = []
+    for component in (log_prior, log_likelihood):
+        c = component.to(torch.float64)
+        centre = torch.where(kept, c, torch.zeros_like(c)).sum() / kept.sum().clamp(min=1)
+        c = torch.where(kept, c - centre, torch.zeros_like(c))
+        for alpha in (1.0 / (1.0 + PSENS_DELTA), 1.0 + PSENS_DELTA):
+            rows.append((-(alpha - 1.0) * c).to(torch.float32))
+    out, lw4 = psis_weights(torch.stack(rows).contiguous(), mask)
+    base = torch.where(kept, torch.zeros(R, dtype=torch.float64, device=dev),
+                       torch.full((R,), float("-inf"), dtype=torch.float64, device=dev))
+    return out, torch.cat([lw4, base[None]], dim=0).contiguous()
+
+
+def _cjs_distance(s):
+    """The cumulative Jensen-Shannon distance of one weight row from its [D, 8] sums; NaN for a constant element."""
+    a_pq, a_qp, i_p, i_q = s[:, 4], s[:, 5], s[:, 6], s[:, 7]
+    ln4 = 2.0 * np.log(2.0)
+    cjs_pq = np.maximum(0.0, a_pq + (i_q - i_p) / ln4)
+    cjs_qp = np.maximum(0.0, a_qp + (i_p - i_q) / ln4)
+    return np.sqrt((cjs_pq + cjs_qp) / (i_p + i_q))
+
+
+def psens_summary(sums):
+    """Power-scaling sensitivity, the single place where its statistics are defined -> PsensSummary; pure numpy float64.
+    sums [5, D, 8]: cjs_sums of the rows PSENS_ROWS.  Per row
+      cjs_pq = max(0, A_pq + (I_q - I_p) / (2 ln 2)),  cjs_qp = max(0, A_qp + (I_p - I_q) / (2 ln 2)),
+      dist = sqrt((cjs_pq + cjs_qp) / (I_p + I_q))                  (NaN for a constant element: 0 / 0)
+    and sensitivity = (dist_lower + dist_upper) / (2 log2(1 + PSENS_DELTA)), for the prior and for the likelihood.  With
+    the pooled mean and sd from the unweighted row, mean = sum W u / sum W, sd = sqrt(sum W u^2 / sum W - mean^2):
+    mean_shift = (mean_upper - mean_pooled) / sd_pooled, sd_ratio = sd_upper / sd_pooled.  Diagnosis against
+    PSENS_THRESHOLD: prior above and likelihood above -- prior-data conflict; prior above only -- weak likelihood (or a
+    strong prior); a NaN is above nothing."""
+    s = np.asarray(_lib.host64(sums), np.float64)
+    if s.ndim != 3 or s.shape[0] != len(PSENS_ROWS) or s.shape[2] != len(CJS_COLUMNS):
+        raise ValueError("psens_summary: sums must be [5, D, 8] (PSENS_ROWS, CJS_COLUMNS)")
+    with np.errstate(divide="ignore", invalid="ignore"):
+        dist = [_cjs_distance(s[k]) for k in range(4)]
+        scale = 2.0 * np.log2(1.0 + PSENS_DELTA)
+        prior, likelihood = (dist[0] + dist[1]) / scale, (dist[2] + dist[3]) / scale
+        mean = s[:, :, 2] / s[:, :, 1]
+        sd = np.sqrt(np.maximum(s[:, :, 3] / s[:, :, 1] - mean * mean, 0.0))
+        shift = [np.where(sd[4] > 0, (mean[k] - mean[4]) / sd[4], np.nan) for k in (1, 3)]
+        ratio = [np.where(sd[4] > 0, sd[k] / sd[4], np.nan) for k in (1, 3)]
+        above_p, above_l = prior > PSENS_THRESHOLD, likelihood > PSENS_THRESHOLD
+    return PsensSummary(prior, likelihood, shift[0], shift[1], ratio[0], ratio[1],
+                        int(np.sum(np.isnan(prior) | np.isnan(likelihood))),
+                        np.flatnonzero(above_p & above_l), np.flatnonzero(above_p & ~above_l))

@@ -122,6 +122,21 @@ _DEFS = [
                                     "matching; an observation with a high Pareto k-hat is as unreliable here as its "
                                     "elpd_loo.  Every other output of --predictive_diagnostics is bit for bit unchanged.  "
                                     "One process only: a sharded job writes null."),
+    ("sensitivity_diagnostics", bool, False, "Sampling runs, with --convergence_diagnostics: how much of each posterior "
+                                             "marginal comes from the prior, how much from the data?  Power-scaling "
+                                             "sensitivity (Kallioinen, Paananen, Buerkner, Vehtari 2023; priorsense, ArviZ "
+                                             "psens) on the draws --predictive_diagnostics takes (--loo_draws of the chains "
+                                             "split R-hat covers, centred): the prior -- the joint density of all latent "
+                                             "sites, the hierarchical layers included -- and the likelihood are raised to "
+                                             "1 / 1.01 and 1.01, the draws importance-weighted by the Pareto-smoothed ratios "
+                                             "(arp_psis_weights), every element's pooled draws ordered (arp_element_order) and "
+                                             "the cumulative Jensen-Shannon distance between the unweighted and the weighted "
+                                             "ECDF folded on the device (arp_cjs_sums).  Sensitivities above 0.05 are "
+                                             "diagnosed: prior and likelihood -- prior-data conflict; prior alone -- weak "
+                                             "likelihood or strong prior (psens_* JSON keys, <base>_psens.npz; analyze "
+                                             "--psens).  delta is fixed, no power-scaling sequence, no choice of prior sites.  "
+                                             "One process only: a sharded job writes null.  Refused for neals_funnel, which "
+                                             "has no observations."),
     ("vi_diagnostics", bool, False, "--inference=VI: judge the mean-field FIT the sampler takes its step sizes, its initial "
                                     "population and (cVIP, dVIP) its parameterisation from.  After the fit's clock has "
                                     "stopped, --vi_check_draws draws from the fitted q in the coordinates of the "

@@ -368,14 +368,17 @@ def _convergence_report(kernel_results, model_config, flags, dev):
     (A collective when ws > 1: every rank calls it.)"""
     trace = getattr(kernel_results, "trace", None)
     if not getattr(flags, "convergence_diagnostics", True) or trace is None:
+        keys = {}
         if getattr(flags, "convergence_diagnostics", True) and getattr(flags, "predictive_checks", False):
             keys = _loo_null("no chain has its trace on the device", flags) if getattr(flags, "predictive_diagnostics", False) \
                 else OrderedDict()
             keys.update(_ppc_null("no chain has its trace on the device"))
-            return keys, None
-        if getattr(flags, "convergence_diagnostics", True) and getattr(flags, "predictive_diagnostics", False):
-            return _loo_null("no chain has its trace on the device", flags), None
-        return {}, None
+        elif getattr(flags, "convergence_diagnostics", True) and getattr(flags, "predictive_diagnostics", False):
+            keys = _loo_null("no chain has its trace on the device", flags)
+        if getattr(flags, "convergence_diagnostics", True) and getattr(flags, "sensitivity_diagnostics", False):
+            keys = OrderedDict(keys)
+            keys.update(_psens_null("no chain has its trace on the device"))
+        return keys, None
     clock = time.time()
     spec = model_config.model
     S, C_local, D = (int(v) for v in trace.shape)
@@ -434,7 +437,9 @@ def _convergence_report(kernel_results, model_config, flags, dev):
             (getattr(flags, "predictive_diagnostics", False), LOO_ARRAYS,
              lambda: _loo_report(kernel_results, trace, k, spec, flags, arrays)),     # (--loo_predictive: a second tag)
             (getattr(flags, "predictive_checks", False), PPC_ARRAYS,               # (n_split: already all-reduced)
-             lambda: _ppc_report(kernel_results, trace, k, n_split, spec, flags, dev))):
+             lambda: _ppc_report(kernel_results, trace, k, n_split, spec, flags, dev)),
+            (getattr(flags, "sensitivity_diagnostics", False), PSENS_ARRAYS,
+             lambda: _psens_report(trace, k, spec, flags, split.mean))):
         if asked:
             side_keys, side_arrays = report()
             keys.update(side_keys)
@@ -1072,6 +1077,147 @@ def save_ppc(file_path_base, arrays):
     np.savez(file_path_base + "_ppc.npz", **arrays)
 
 
+PSENS_ARRAYS = "psens/"              # where _convergence_report leaves the arrays of <base>_psens.npz
+PSENS_SHOWN = 8                      # conflict elements the warning names
+PSENS_KEYS = ("psens_draws", "psens_draws_left_out", "psens_chains", "psens_steps", "psens_elements_left_out",
+              "psens_prior_max", "psens_prior_max_element", "psens_likelihood_max", "psens_likelihood_max_element",
+              "psens_conflict_elements", "psens_weak_likelihood_elements", "psens_pareto_k_max", "psens_pareto_k_threshold",
+              "psens_time_sec")
+
+
+def check_sensitivity(flags):
+    """--sensitivity_diagnostics against the job, before anything runs: check_predictive_checks' rule -- raises ValueError
+    for a model without observations (neals_funnel), which has no likelihood to tell from its prior."""
+    if getattr(flags, "sensitivity_diagnostics", False) and flags.model == "neals_funnel":
+        raise ValueError("--sensitivity_diagnostics: neals_funnel has no observations, so there is no likelihood to "
+                         "power-scale against the prior")
+
+
+def _psens_null(why):
+    """Every key of the sensitivity report as null, with the one message that says why."""
+    util.print_("    power-scaling sensitivity: not computed, {}".format(why))
+    return OrderedDict((key, None) for key in PSENS_KEYS)
+
+
+def psens_keys(summary, names, pareto_k, R, left_out, n_chains, n_steps):
+    """The JSON keys of the sensitivity report (all but psens_time_sec) from a diagnostics.PsensSummary, the elements'
+    names, the four k-hat of the power-scaled ratios, the draws taken `R` and how many of them were left out; pure numpy."""
+    used = int(R) - int(left_out)
+    p_max, p_at = _nan_max(summary.prior)
+    l_max, l_at = _nan_max(summary.likelihood)
+    k_max, _ = _nan_max(pareto_k)
+    return OrderedDict([
+        ("psens_draws", used), ("psens_draws_left_out", int(left_out)), ("psens_chains", int(n_chains)),
+        ("psens_steps", int(n_steps)), ("psens_elements_left_out", int(summary.constant)),
+        ("psens_prior_max", _finite_or_none(p_max)), ("psens_prior_max_element", names[p_at] if p_at >= 0 else None),
+        ("psens_likelihood_max", _finite_or_none(l_max)), ("psens_likelihood_max_element", names[l_at] if l_at >= 0 else None),
+        ("psens_conflict_elements", [names[i] for i in summary.conflict]),
+        ("psens_weak_likelihood_elements", [names[i] for i in summary.weak_likelihood]),
+        ("psens_pareto_k_max", _finite_or_none(k_max)),
+        ("psens_pareto_k_threshold", _finite_or_none(diagnostics.pareto_k_threshold(used)))])
+
+
+def _psens_report(trace, k, spec, flags, pooled_mean=None):
+    """--sensitivity_diagnostics: how much of each posterior marginal comes from the prior, how much from the data?
+    Power-scaling sensitivity (Kallioinen, Paananen, Buerkner, Vehtari 2023; priorsense, ArviZ psens) over the draws the
+    predictive report takes -- the leading `k` chains of the device trace, the chains split R-hat covers, at
+    clamp(--loo_draws // k, 1, S) evenly spaced recorded steps (loo_steps), centred.  The likelihood of a draw is its
+    pointwise log-likelihoods (diagnostics.pointwise_loglik, in the observation tiles of the predictive report) folded by
+    diagnostics.loglik_total; the prior is the centred log joint at the same draws minus that -- the joint density of ALL
+    latent sites, the hierarchical layers included -- from an engine of the report's own set to CP, so that nothing of the
+    run's state is touched.  A draw the log-likelihood masks or whose log joint is not finite is left out and counted.  The
+    prior and the likelihood are raised to 1 / (1 + delta) and 1 + delta (diagnostics.powerscale_lw: Pareto-smoothed
+    weights), every element's pooled draws are ordered (diagnostics.element_order) and the weighted ECDFs folded
+    (diagnostics.cjs_sums, about `pooled_mean`); the statistics are diagnostics.psens_summary's.  The order of an element's
+    draws needs them on one device: a sharded job (world size > 1) writes null, says so once, and enters no collective --
+    the rule of the rank reports.  delta is fixed; no power-scaling sequence; no choice of prior sites.
+    Returns (JSON keys, arrays of <base>_psens.npz or None)."""
+    import torch
+    from . import engine as engine_lib
+    if parallel.world()[1] > 1:
+        return _psens_null("the chains of a sharded job are on several devices (the order of an element's pooled draws "
+                           "needs them on one)"), None
+    clock = time.time()
+    S, _, D = (int(v) for v in trace.shape)
+    k = int(k) if S > 0 else 0
+    if k <= 0:
+        return _psens_null("no chain has its trace on the device"), None
+    if D > diagnostics.LOGLIK_MAX_D:
+        return _psens_null("the model has more than {} elements".format(diagnostics.LOGLIK_MAX_D)), None
+    steps = loo_steps(S, k, getattr(flags, "loo_draws", 65536))
+    if not steps:
+        return _psens_null("more than {} chains".format(diagnostics.PSIS_MAX_DRAWS)), None
+    dev = trace.device
+    table = diagnostics.upload_table(spec.observation_table(), D, dev)
+    draws = trace[torch.as_tensor(steps, device=dev), :k].contiguous()               # [len(steps), k, D]: a copy, D floats a draw
+    R, N = len(steps) * k, table.N
+    rows = loo_tile_rows(N, R)
+    ll_buffer = torch.empty(rows, R, dtype=torch.float32, device=dev)
+    log_lik = torch.zeros(R, dtype=torch.float64, device=dev)
+    mask = None
+    for n0 in range(0, N, rows):
+        ll, mask, _ = diagnostics.pointwise_loglik(draws, table, n0, min(N, n0 + rows), out=ll_buffer)
+        diagnostics.loglik_total(ll, log_lik)                                        # (ascending tiles: bitwise one call)
+    del ll_buffer
+    eng = engine_lib.Engine(spec, dev)                                               # the report's own handle: the run's stay as they are
+    eng.set_param(0, "CP")
+    log_joint = eng.logp_grad(draws.reshape(R, D), which=0)[0].to(torch.float64)
+    del eng
+    log_prior = log_joint - log_lik
+    left = (mask != 0) | ~torch.isfinite(log_prior)
+    left_out = int(left.sum().item())
+    out8, lw = diagnostics.powerscale_lw(log_prior, log_lik, left)
+    order, values = diagnostics.element_order(draws)
+    centre = np.zeros(D) if pooled_mean is None else np.asarray(pooled_mean, np.float64).reshape(D)
+    centre = np.nan_to_num(centre, nan=0.0, posinf=0.0, neginf=0.0).astype(np.float32)
+    sums = diagnostics.cjs_sums(values, order, lw, torch.as_tensor(centre, device=dev)).cpu().numpy()
+    del order, values, lw
+    summary = diagnostics.psens_summary(sums)
+    names = element_names(spec)
+    pareto_k = out8.cpu().numpy()[:, 1]
+    keys = psens_keys(summary, names, pareto_k, R, left_out, k, len(steps))
+    util.print_("    power-scaling sensitivity over {} draws ({} step(s) of {} chains, {} left out), {} elements ({} constant): "
+                "prior max {} ({}), likelihood max {} ({}); {} prior-data conflict(s), {} element(s) with a weak likelihood "
+                "or a strong prior".format(
+                    keys["psens_draws"], len(steps), k, left_out, D, keys["psens_elements_left_out"],
+                    _fmt(keys["psens_prior_max"]), keys["psens_prior_max_element"], _fmt(keys["psens_likelihood_max"]),
+                    keys["psens_likelihood_max_element"], len(keys["psens_conflict_elements"]),
+                    len(keys["psens_weak_likelihood_elements"])))
+    if keys["psens_conflict_elements"]:
+        shown = keys["psens_conflict_elements"][:PSENS_SHOWN]
+        util.print_("    WARNING: prior-data conflict (prior and likelihood sensitivity above {}) for: {}{} -- prior and data "
+                    "pull these marginals apart; no reparameterisation repairs that (all of them: <base>_psens.npz)".format(
+                        diagnostics.PSENS_THRESHOLD, ", ".join(shown),
+                        " and {} more".format(len(keys["psens_conflict_elements"]) - len(shown))
+                        if len(keys["psens_conflict_elements"]) > len(shown) else ""))
+    threshold = keys["psens_pareto_k_threshold"]
+    with np.errstate(invalid="ignore"):
+        high = int(np.sum(~(pareto_k <= threshold))) if threshold is not None else int(np.sum(~np.isfinite(pareto_k)))
+    if high:
+        util.print_("    WARNING: Pareto k-hat above {} for {} of the 4 power-scaled weight rows (not fitted ones included): "
+                    "their sensitivities are unreliable".format(_fmt(threshold), high))
+    arrays = OrderedDict([("elements", np.asarray(names)), ("y", np.asarray(table.y_host, np.float32)),
+                          ("model", np.asarray(spec.name)), ("pareto_k", pareto_k),
+                          ("log_prior", log_prior.cpu().numpy()), ("log_likelihood", log_lik.cpu().numpy()),
+                          ("left_out", left.cpu().numpy())])
+    _by_part(spec, arrays, (("prior", summary.prior), ("likelihood", summary.likelihood),
+                            ("mean_shift_prior", summary.mean_shift_prior),
+                            ("mean_shift_likelihood", summary.mean_shift_likelihood),
+                            ("sd_ratio_prior", summary.sd_ratio_prior), ("sd_ratio_likelihood", summary.sd_ratio_likelihood)))
+    keys["psens_time_sec"] = time.time() - clock
+    return keys, arrays
+
+
+def save_psens(file_path_base, arrays):
+    """`<base>_psens.npz` (build-specific, --sensitivity_diagnostics): `elements`, the elements' names in trace order; `y`,
+    the observations; `model`; `pareto_k` [4], the k-hat of the power-scaled ratios (prior lower, prior upper, likelihood
+    lower, likelihood upper); `log_prior`, `log_likelihood` [R] float64 of the draws taken (without the constants the
+    density omits) and `left_out` [R]; per latent part `prior/<part>`, `likelihood/<part>` (the sensitivities, NaN for a
+    constant element), `mean_shift_prior/<part>`, `mean_shift_likelihood/<part>`, `sd_ratio_prior/<part>` and
+    `sd_ratio_likelihood/<part>` (the upper row's weighted mean shift in pooled sd and its sd ratio)."""
+    np.savez(file_path_base + "_psens.npz", **arrays)
+
+
 def _fit_chains(trace, k, workspace_bytes):
     """The largest of k, k/2, k/4, ... leading chains whose z-score trace and the `workspace_bytes(S, k, D)` next to it
     fit the free device memory."""
@@ -1259,13 +1405,13 @@ def save_geometry(file_path_base, arrays):
 
 def _save_diagnostics(file_path_base, arrays):
     """The side files of the convergence report: <base>_rhat.npz and, where the probes ran, <base>_energy.npz,
-    <base>_trajectory.npz, <base>_geometry.npz, <base>_loo.npz, <base>_loopred.npz and <base>_ppc.npz."""
+    <base>_trajectory.npz, <base>_geometry.npz, <base>_loo.npz, <base>_loopred.npz, <base>_ppc.npz and <base>_psens.npz."""
     if arrays is None:
         return
     # (tag _convergence_report left a side file's arrays under, its saver), in the order the files are written after _rhat.npz
     side = [(arrays.pop(tag, None), save) for tag, save in (
         (GEOMETRY_ARRAYS, save_geometry), (ENERGY_ARRAYS, save_energy), (TRAJECTORY_ARRAYS, save_trajectory),
-        (LOO_ARRAYS, save_loo), (LOO_PRED_ARRAYS, save_loo_pred), (PPC_ARRAYS, save_ppc))]
+        (LOO_ARRAYS, save_loo), (LOO_PRED_ARRAYS, save_loo_pred), (PPC_ARRAYS, save_ppc), (PSENS_ARRAYS, save_psens))]
     save_rhat(file_path_base, arrays)
     for side_arrays, save in side:
         if side_arrays is not None:
@@ -1556,6 +1702,7 @@ def main(argv=None, flags=FLAGS, out=None):
         raise NotImplementedError("--reparameterise_variational is not supported by this build (SURVEY.md section 2)")
     check_predictive(flags)
     check_predictive_checks(flags)
+    check_sensitivity(flags)
     check_vi_diagnostics(flags)
     ws = int(os.environ.get("WORLD_SIZE", "1"))
     if ws > 1:

@@ -585,6 +585,53 @@ int arp_loo_predictive(const float* x, int64_t n_samples, int64_t n_chains, int3
                        const float* log_scale, int64_t n0, int64_t n1, const double* lw, int64_t lw_stride,
                        double* obs_sums, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* Power-scaling sensitivity (csrc/psens.hip; Kallioinen, Paananen, Buerkner, Vehtari 2023; priorsense, ArviZ psens): the
+ * three device pieces below the smoothed weights of arp_psis_weights.  Device pointers; asynchronous; everything is
+ * refused before any launch with 1 (arp_last_error).
+ *
+ * arp_loglik_total: the log-likelihood of every draw from a tile of pointwise values.  For every draw r:
+ *   acc = total[r];  for n = 0 ... n_obs - 1: acc += (double)ll[n * ll_stride + r];  total[r] = acc
+ * strictly sequential in n, so walking the observations in several tiles (ascending, into the same total) gives bitwise
+ * the result of one call; exact against float64 sequential addition.  A masked draw is the caller's business
+ * (arp_pointwise_loglik writes 0 there).  Refused: a NULL pointer, n_obs < 1, n_draws < 1 or >= 2^31,
+ * ll_stride < n_draws. */
+int arp_loglik_total(const float* ll, int64_t n_obs, int64_t n_draws, int64_t ll_stride, double* total, void* stream);
+
+/* arp_element_order: the order of every element's pooled draws with the draw index carried along.  Trace addressing and
+ * shape refusals are arp_rank_normalize's: element d of draw s of chain c is x[s * row_stride + c * D + d], read in place,
+ * row_stride >= n_chains * D, N = n_samples * n_chains < 2^31.
+ *   order[d * N + i]   the draw index r = s * n_chains + c of the i-th smallest value of element d      uint32 [D][N]
+ *   sorted[d * N + i]  that value (from its key: -0 reads +0)                                   float [D][N], may be NULL
+ * The order is that of arp_rank_normalize's keys (sign-flipped bits, -0 as +0, subnormals distinct, +-inf as numbers);
+ * ties go in ascending r (a stable sort: the LSD radix sort of csrc/segment_sort.h, which arp_rank_normalize runs without
+ * the payload).  A NaN lands at the end its sign bit sends it to and neither faults nor hangs.  Integers only: exact, and
+ * no output depends on the grid or on the order atomics resolve in.  The workspace (arp_element_order_workspace_bytes: two
+ * key buffers and one index buffer of the trace's size and the sort's counts; 0 for a shape that is refused) is the
+ * caller's, 256-byte aligned.  Refused: what arp_rank_normalize refuses of the trace, a NULL x or order, a workspace that is
+ * missing, too small or misaligned. */
+int64_t arp_element_order_workspace_bytes(int64_t n_samples, int64_t n_chains, int32_t D);
+int arp_element_order(const float* x, int64_t n_samples, int64_t n_chains, int32_t D, int64_t row_stride, uint32_t* order,
+                      float* sorted, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* arp_cjs_sums: what the cumulative Jensen-Shannon distance between the unweighted and the weighted ECDF of every element
+ * is made of, for K weight rows at once.  sorted and order [D][N] are arp_element_order's; lw[k * lw_stride + r] (double)
+ * is the log weight of draw r in row k, as arp_psis_weights writes it, 1 <= K <= 8; shift [D] float, may be NULL (0).  A
+ * draw with lw = -inf is left out of row k altogether, by select (it counts in neither ECDF); a NaN lw enters and carries
+ * through.  Everything is float64 after the loads.  Per (k, d), with the kept draws in sorted order i = 1 ... n',
+ * W_i = exp(lw), P_i = i / n', Q_i = (sum_{j <= i} W_j) / sum W, M_i = (P_i + Q_i) / 2, b_i = x_(i+1) - x_(i) (of the kept
+ * draws), log2 of 0 taken as 0, u = x - shift[d]:
+ *   out[k][d][8] = { n', sum W, sum W u, sum W u^2,
+ *                    A_pq = sum_{i < n'} b_i P_i (log2 P_i - log2 M_i),  A_qp = sum_{i < n'} b_i Q_i (log2 Q_i - log2 M_i),
+ *                    I_p = sum_{i < n'} b_i P_i,  I_q = sum_{i < n'} b_i Q_i }
+ * n' < 2 gives zeros in the last four.  n' is exact.  Scan and reduction orders depend on N alone and there are no float
+ * atomics: two calls give bitwise equal output.  First-order bounds, c = ceil(N / 256) (derivation: csrc/psens.hip):
+ *   sum W, sum W u, sum W u^2, I_p:  (c + 64) 2^-52 times the sum of the absolute terms;  I_q: twice that;
+ *   A_pq, A_qp:  (c + 64) 2^-52 (sum b (|P log2 P| + |Q log2 Q| + (P + Q) |log2 M|) + 2 (I_p + I_q) / ln 2).
+ * Refused: a NULL sorted, order, lw or out, N < 1 or >= 2^31, D < 1, more than 2^35 values, K outside 1 ... 8,
+ * lw_stride < N. */
+int arp_cjs_sums(const float* sorted, const uint32_t* order, int64_t N, int32_t D, const double* lw, int64_t lw_stride,
+                 int32_t K, const float* shift, double* out, void* stream);
+
 /* Check of a mean-field normal fit (csrc/vicheck.hip; Yao, Vehtari, Simpson, Gelman 2018, "Yes, but did it work?"): draws
  * from q = N(loc, diag(scale^2)) in the coordinates the fit was made in.  For draw r, g = draw_offset + r, and element
  * d = 4 e + i: ONE call philox4x32_10(counter = (e, lo32(g), hi32(g), 0), key = (lo32(seed), hi32(seed))) per (r, e); words
