@@ -305,7 +305,8 @@ def report_psens(results):
     """Build-specific: the power-scaling sensitivity report of every sampling run that recorded one
     (--sensitivity_diagnostics; the last run of each file): the largest prior and likelihood sensitivity with their
     elements, and the flagged elements -- prior-data conflicts, and elements with a weak likelihood or a strong prior
-    (sensitivity above 0.05; Kallioinen et al. 2023).  The prior is the joint density of all latent sites."""
+    (sensitivity above 0.05; Kallioinen et al. 2023).  The prior is the joint density of all latent sites; a run with
+    --sensitivity_prior_parts gets a second line, for the priors of the named parts alone."""
     lines = []
     for m, r in results.items():
         if "psens_draws" not in r:
@@ -323,6 +324,16 @@ def report_psens(results):
                          _fmt(last["psens_pareto_k_max"]), _fmt(last["psens_pareto_k_threshold"]), last["psens_draws"],
                          last["psens_chains"], last["psens_draws_left_out"], last["psens_elements_left_out"],
                          _secs(last.get("psens_time_sec"))))
+        if last.get("psens_sites"):
+            # --sensitivity_prior_parts: the same draws with the priors of the named parts power-scaled alone
+            conflict = last["psens_sites_conflict_elements"] or []
+            weak = last["psens_sites_weak_likelihood_elements"] or []
+            lines.append("{}: power-scaling sensitivity to the priors of {} alone: prior max {} ({}); prior-data conflict: {}; "
+                         "weak likelihood / strong prior: {}; worst Pareto k-hat {}; {} left out; joint gap {}; {}".format(
+                             m, ", ".join(last["psens_sites"]), _fmt(last["psens_sites_prior_max"]),
+                             last["psens_sites_prior_max_element"], ", ".join(conflict) or "none", ", ".join(weak) or "none",
+                             _fmt(last["psens_sites_pareto_k_max"]), last["psens_sites_draws_left_out"],
+                             _fmt(last["psens_sites_joint_gap_max"]), _secs(last.get("psens_sites_time_sec"))))
     return lines
 
 

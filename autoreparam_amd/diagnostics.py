@@ -23,7 +23,9 @@ the one report that judges the variational fit the sampler inherits its steps an
 the ELBO and its gradient at the final parameters, the importance-corrected loc and scale; Yao et al. 2018); and
 power-scaling sensitivity (`powerscale_lw`, `element_order` on `arp_element_order`, `cjs_sums` on `arp_cjs_sums`,
 `loglik_total`; `psens_summary`: how far every marginal moves when the prior or the likelihood is raised to a power
-slightly off 1, as a cumulative Jensen-Shannon distance; Kallioinen et al. 2023).
+slightly off 1, as a cumulative Jensen-Shannon distance; Kallioinen et al. 2023), with the log prior density of every
+latent site, summed over chosen groups of elements, for power-scaling chosen priors alone (`upload_site_table`,
+`site_logprior` on `arp_site_logprior`).
 
 Build-specific (the reference runs 100 chains and reports the within-chain ESS only).  The per-chain moments come from
 one pass over a trace that is already on the device (`arp_split_moments`) or from the in-kernel statistics of a
@@ -1159,6 +1161,77 @@ def cjs_sums(values, order, lw, shift=None):
     _lib.call(values.device, _lib.lib().arp_cjs_sums, _lib.ptr(values), _lib.ptr(order), N, D, _lib.ptr(lw), lw_stride, K,
               _lib.ptr(shift), _lib.ptr(out))
     return out
+
+
+# A latent site table (models.SiteTable) in device memory: D and P (the number of parts) as ints; the columns as contiguous
+# device tensors (form, part [D] int32; loc_idx, scale_idx [D, 2] int32; loc_w, scale_w [D, 2] and loc0, log_scale0, norm [D]
+# float32); host: a models.SiteTable of the same columns as numpy arrays, the float ones ROUNDED to float32 -- what the
+# kernel reads, for a float64 evaluation of the very same table.
+DeviceSiteTable = collections.namedtuple("DeviceSiteTable", ["D", "P", "form", "loc_idx", "loc_w", "loc0", "scale_idx", "scale_w",
+                                                             "log_scale0", "norm", "part", "host"])
+SITE_TERMS = 2                    # terms of a site's loc and of its log-scale (include/autoreparam.h: ARP_SITE_TERMS)
+
+
+def upload_site_table(table, D, device):
+    """models.SiteTable -> DeviceSiteTable on `device`, checked against a state of D elements as upload_table checks an
+    observation table: one row per element, every index in [0, D), every form in {0, 1, 2}, part >= 0 -- and the ancestral
+    order: a term of non-zero weight points at an element before its own.  The float columns are rounded to float32."""
+    D = int(D)
+    form, part = (np.ascontiguousarray(v, np.int32).reshape(-1) for v in (table.form, table.part))
+    loc_idx, scale_idx = (np.ascontiguousarray(v, np.int32) for v in (table.loc_idx, table.scale_idx))
+    loc_w, scale_w = (np.ascontiguousarray(v, np.float32) for v in (table.loc_w, table.scale_w))
+    loc0, log_scale0, norm = (np.ascontiguousarray(v, np.float32).reshape(-1) for v in (table.loc0, table.log_scale0, table.norm))
+    if D < 1 or not all(v.size == D for v in (form, part, loc0, log_scale0, norm)):
+        raise ValueError("site table: form, loc0, log_scale0, norm and part must have one entry per element (%d)" % D)
+    if not all(v.shape == (D, SITE_TERMS) for v in (loc_idx, loc_w, scale_idx, scale_w)):
+        raise ValueError("site table: loc_idx, loc_w, scale_idx and scale_w of shape [%d, %d] are required" % (D, SITE_TERMS))
+    if min(loc_idx.min(), scale_idx.min()) < 0 or max(loc_idx.max(), scale_idx.max()) >= D:
+        raise ValueError("site table: an index lies outside the state's %d elements" % D)
+    if not np.isin(form, (0, 1, 2)).all():
+        raise ValueError("site table: form must be 0 (Normal), 1 (Normal, softplus scale) or 2 (log-Gamma)")
+    if part.min() < 0:
+        raise ValueError("site table: part must not be negative")
+    d = np.arange(D)[:, None]
+    if not all(np.all((w == 0) | (i < d)) for i, w in ((loc_idx, loc_w), (scale_idx, scale_w))):
+        raise ValueError("site table: a term of non-zero weight must point at an earlier element (the ancestral order)")
+    dev = lambda a: torch.as_tensor(a, device=device)
+    host = type(table)(form, loc_idx, loc_w, loc0, scale_idx, scale_w, log_scale0, norm, part)
+    return DeviceSiteTable(D, int(part.max()) + 1, dev(form), dev(loc_idx), dev(loc_w), dev(loc0), dev(scale_idx), dev(scale_w),
+                           dev(log_scale0), dev(norm), dev(part), host)
+
+
+def site_logprior(trace, table, group_of=None, want_elements=False):
+    """(group_lp, elem_lp, mask, n_masked) of `arp_site_logprior` for a recorded CENTRED [S, C, D] float32 trace on the GPU
+    and a DeviceSiteTable: group_lp [S C, G] float64, the log prior density of every group of elements at draw s C + c
+    (the float32 element values added in float64, in a fixed order); elem_lp [S C, D] float32, the elements' own values
+    (None without want_elements); mask [S C] uint8 and n_masked as pointwise_loglik's -- a masked draw's rows are 0.
+    group_of: the group of every element, anything numpy reads as [D] integers (validated into [0, G), G = its largest
+    entry + 1 <= D; need not be contiguous; a group without elements is 0); None: the table's parts.  A leading or inner
+    block of chains of a wider trace is read in place, as pointwise_loglik reads it."""
+    who = "site_logprior"
+    x, S, Cn, D, row_stride = _lib.trace_view(trace, who)
+    R = S * Cn
+    if R == 0 or D == 0:
+        raise ValueError("%s: an empty trace" % who)
+    if D != table.D:
+        raise ValueError("%s: the trace has %d elements, the table %d" % (who, D, table.D))
+    dev = x.device
+    if group_of is None:
+        groups, G = table.part, table.P
+    else:
+        g = np.asarray(group_of)
+        if g.shape != (D,) or g.dtype.kind not in "iu" or g.min() < 0 or g.max() >= D:
+            raise ValueError("%s: group_of must be [%d] integers in [0, G), G <= D" % (who, D))
+        groups, G = torch.as_tensor(np.ascontiguousarray(g, np.int32), device=dev), int(g.max()) + 1
+    group_lp = torch.empty(R, G, dtype=torch.float64, device=dev)
+    elem_lp = torch.empty(R, D, dtype=torch.float32, device=dev) if want_elements else None
+    mask = torch.empty(R, dtype=torch.uint8, device=dev)
+    n_masked = torch.zeros((), dtype=torch.int64, device=dev)
+    _lib.call(dev, _lib.lib().arp_site_logprior, _lib.ptr(x), S, Cn, D, row_stride, _lib.ptr(table.form), _lib.ptr(table.loc_idx),
+              _lib.ptr(table.loc_w), _lib.ptr(table.loc0), _lib.ptr(table.scale_idx), _lib.ptr(table.scale_w),
+              _lib.ptr(table.log_scale0), _lib.ptr(table.norm), _lib.ptr(groups), G, _lib.ptr(group_lp), _lib.ptr(elem_lp),
+              _lib.ptr(mask), _lib.ptr(n_masked))
+    return group_lp, elem_lp, mask, n_masked
 
 
 def powerscale_lw(log_prior, log_likelihood, left_out=None):

@@ -134,9 +134,21 @@ _DEFS = [
                                              "ECDF folded on the device (arp_cjs_sums).  Sensitivities above 0.05 are "
                                              "diagnosed: prior and likelihood -- prior-data conflict; prior alone -- weak "
                                              "likelihood or strong prior (psens_* JSON keys, <base>_psens.npz; analyze "
-                                             "--psens).  delta is fixed, no power-scaling sequence, no choice of prior sites.  "
+                                             "--psens).  delta is fixed, no power-scaling sequence; a choice of prior sites: "
+                                             "--sensitivity_prior_parts.  "
                                              "One process only: a sharded job writes null.  Refused for neals_funnel, which "
                                              "has no observations."),
+    ("sensitivity_prior_parts", str, "", "With --sensitivity_diagnostics only: NAME[,NAME...], latent parts of the model (a "
+                                         "part is one of the model's random variables, e.g. b1,log_sigma_a for election).  A "
+                                         "second report on the same draws power-scales the priors of the named parts ALONE "
+                                         "-- the sum of their sites' log densities (arp_site_logprior over "
+                                         "ModelSpec.site_table) -- instead of the joint prior, which in a hierarchical model "
+                                         "also scales the group level: is the posterior sensitive to the priors I chose?  "
+                                         "(psens_sites_* JSON keys, <base>_psens_sites.npz; analyze --psens prints a second "
+                                         "line).  Every output of --sensitivity_diagnostics is bit for bit unchanged.  The "
+                                         "selection is by part, not by element; delta is fixed and there is no power-scaling "
+                                         "sequence here either.  Refused: a name that is no part of the model, a duplicate, "
+                                         "an empty name, the flag without --sensitivity_diagnostics."),
     ("vi_diagnostics", bool, False, "--inference=VI: judge the mean-field FIT the sampler takes its step sizes, its initial "
                                     "population and (cVIP, dVIP) its parameterisation from.  After the fit's clock has "
                                     "stopped, --vi_check_draws draws from the fitted q in the coordinates of the "

@@ -377,7 +377,7 @@ def _convergence_report(kernel_results, model_config, flags, dev):
             keys = _loo_null("no chain has its trace on the device", flags)
         if getattr(flags, "convergence_diagnostics", True) and getattr(flags, "sensitivity_diagnostics", False):
             keys = OrderedDict(keys)
-            keys.update(_psens_null("no chain has its trace on the device"))
+            keys.update(_psens_null("no chain has its trace on the device", flags))
         return keys, None
     clock = time.time()
     spec = model_config.model
@@ -439,7 +439,7 @@ def _convergence_report(kernel_results, model_config, flags, dev):
             (getattr(flags, "predictive_checks", False), PPC_ARRAYS,               # (n_split: already all-reduced)
              lambda: _ppc_report(kernel_results, trace, k, n_split, spec, flags, dev)),
             (getattr(flags, "sensitivity_diagnostics", False), PSENS_ARRAYS,
-             lambda: _psens_report(trace, k, spec, flags, split.mean))):
+             lambda: _psens_report(trace, k, spec, flags, split.mean, arrays))):
         if asked:
             side_keys, side_arrays = report()
             keys.update(side_keys)
@@ -1093,10 +1093,43 @@ def check_sensitivity(flags):
                          "power-scale against the prior")
 
 
-def _psens_null(why):
-    """Every key of the sensitivity report as null, with the one message that says why."""
+PSENS_SITES_ARRAYS = "psens_sites/"  # where _psens_report leaves the arrays of <base>_psens_sites.npz (--sensitivity_prior_parts)
+PSENS_SITE_KEYS = ("psens_sites", "psens_sites_draws_left_out", "psens_sites_prior_max", "psens_sites_prior_max_element",
+                   "psens_sites_conflict_elements", "psens_sites_weak_likelihood_elements", "psens_sites_pareto_k_max",
+                   "psens_sites_joint_gap_max", "psens_sites_time_sec")
+
+
+def prior_parts(flags):
+    """The names --sensitivity_prior_parts gives, in the order given; [] without the flag."""
+    text = getattr(flags, "sensitivity_prior_parts", "") or ""
+    return text.split(",") if text else []
+
+
+def check_sensitivity_sites(flags):
+    """--sensitivity_prior_parts against the job, before anything runs -- raises ValueError for the flag without
+    --sensitivity_diagnostics, an empty name, a duplicate and a name that is not a latent part of the model."""
+    names = prior_parts(flags)
+    if not names:
+        return
+    if not getattr(flags, "sensitivity_diagnostics", False):
+        raise ValueError("--sensitivity_prior_parts is read with --sensitivity_diagnostics only")
+    if "" in names:
+        raise ValueError("--sensitivity_prior_parts: an empty name in {!r}".format(flags.sensitivity_prior_parts))
+    if len(set(names)) != len(names):
+        raise ValueError("--sensitivity_prior_parts: {} is named twice".format(
+            ", ".join(sorted({n for n in names if names.count(n) > 1}))))
+    parts = models.spec_by_name(flags.model, dataset=getattr(flags, "dataset", None)).part_names
+    unknown = [n for n in names if n not in parts]
+    if unknown:
+        raise ValueError("--sensitivity_prior_parts: {} is no latent part of {}; its parts: {}".format(
+            ", ".join(unknown), flags.model, ", ".join(parts)))
+
+
+def _psens_null(why, flags=None):
+    """Every key of the sensitivity report as null, with the one message that says why; those of --sensitivity_prior_parts
+    with them where it is set."""
     util.print_("    power-scaling sensitivity: not computed, {}".format(why))
-    return OrderedDict((key, None) for key in PSENS_KEYS)
+    return OrderedDict((key, None) for key in PSENS_KEYS + (PSENS_SITE_KEYS if prior_parts(flags) else ()))
 
 
 def psens_keys(summary, names, pareto_k, R, left_out, n_chains, n_steps):
@@ -1117,7 +1150,79 @@ def psens_keys(summary, names, pareto_k, R, left_out, n_chains, n_steps):
         ("psens_pareto_k_threshold", _finite_or_none(diagnostics.pareto_k_threshold(used)))])
 
 
-def _psens_report(trace, k, spec, flags, pooled_mean=None):
+def site_prior_split(draws, site_table, selected):
+    """(log_prior_selected, log_prior_rest) [R] float64 device tensors for centred draws [steps, chains, D] on the GPU, a
+    diagnostics.DeviceSiteTable and `selected` [P] bool: diagnostics.site_logprior with groups = parts, the steps walked
+    in blocks whose [rows, P] float64 output stays within LOO_CHUNK_BYTES, and the chosen parts' columns added in
+    ascending part order (the others' likewise): sequential float64 additions on the device, row by row -- the blocks
+    compose bit for bit."""
+    import torch
+    n_steps, k, _ = (int(v) for v in draws.shape)
+    P = site_table.P
+    per_block = max(1, LOO_CHUNK_BYTES // (8 * P * k))
+    sel, rest = (torch.zeros(n_steps * k, dtype=torch.float64, device=draws.device) for _ in range(2))
+    for s0 in range(0, n_steps, per_block):
+        s1 = min(n_steps, s0 + per_block)
+        by_part = diagnostics.site_logprior(draws[s0:s1], site_table)[0]
+        for p in range(P):
+            (sel if selected[p] else rest)[s0 * k:s1 * k] += by_part[:, p]
+    return sel, rest
+
+
+def _psens_sites_report(names, draws, spec, log_prior, logp_const, log_lik, left, order, values, centre):
+    """--sensitivity_prior_parts: the second report of _psens_report, on its draws, its left-out mask, its log-likelihood
+    and its element order -- the prior that is power-scaled is the sum of the named parts' site densities
+    (site_prior_split) instead of the joint one.  A draw whose selected prior is not finite joins the left-out draws of
+    this report only.  diagnostics.powerscale_lw, cjs_sums and psens_summary as there: no second definition.
+    psens_sites_joint_gap_max: the largest |sum of ALL parts - (log_prior + logp_const)| over the draws kept -- how far the
+    two routes to the prior are apart (the float32 rounding of the engine's log joint); written, never warned about.
+    Returns (JSON keys, arrays of <base>_psens_sites.npz)."""
+    import torch
+    clock = time.time()
+    dev = draws.device
+    selected = np.asarray([name in names for name in spec.part_names])
+    site_table = diagnostics.upload_site_table(spec.site_table(), spec.D, dev)
+    sel, rest = site_prior_split(draws, site_table, selected)
+    left = left | ~torch.isfinite(sel)
+    kept = ~left
+    gap = torch.where(kept, ((sel + rest) - (log_prior + logp_const)).abs(), torch.zeros_like(sel))
+    gap = float(gap.max().item()) if bool(kept.any().item()) else float("nan")
+    out8, lw = diagnostics.powerscale_lw(sel, log_lik, left)
+    summary = diagnostics.psens_summary(diagnostics.cjs_sums(values, order, lw, centre).cpu().numpy())
+    del lw
+    elements = element_names(spec)
+    pareto_k = out8.cpu().numpy()[:2, 1]                       # (the prior rows: the likelihood's are the first report's)
+    p_max, p_at = _nan_max(summary.prior)
+    chosen = [name for name in spec.part_names if name in names]
+    keys = OrderedDict([
+        ("psens_sites", chosen), ("psens_sites_draws_left_out", int(left.sum().item())),
+        ("psens_sites_prior_max", _finite_or_none(p_max)), ("psens_sites_prior_max_element", elements[p_at] if p_at >= 0 else None),
+        ("psens_sites_conflict_elements", [elements[i] for i in summary.conflict]),
+        ("psens_sites_weak_likelihood_elements", [elements[i] for i in summary.weak_likelihood]),
+        ("psens_sites_pareto_k_max", _finite_or_none(_nan_max(pareto_k)[0])),
+        ("psens_sites_joint_gap_max", _finite_or_none(gap))])
+    util.print_("    power-scaling sensitivity to the priors of {} alone: prior max {} ({}); {} prior-data conflict(s), {} "
+                "element(s) with a weak likelihood or a strong prior".format(
+                    ", ".join(chosen), _fmt(keys["psens_sites_prior_max"]), keys["psens_sites_prior_max_element"],
+                    len(keys["psens_sites_conflict_elements"]), len(keys["psens_sites_weak_likelihood_elements"])))
+    if keys["psens_sites_conflict_elements"]:
+        shown = keys["psens_sites_conflict_elements"][:PSENS_SHOWN]
+        util.print_("    WARNING: prior-data conflict (prior and likelihood sensitivity above {}) with the priors of {} for: {}{} "
+                    "-- these priors and the data pull these marginals apart; no reparameterisation repairs that (all of "
+                    "them: <base>_psens_sites.npz)".format(
+                        diagnostics.PSENS_THRESHOLD, ", ".join(chosen), ", ".join(shown),
+                        " and {} more".format(len(keys["psens_sites_conflict_elements"]) - len(shown))
+                        if len(keys["psens_sites_conflict_elements"]) > len(shown) else ""))
+    arrays = OrderedDict([("parts", np.asarray(spec.part_names)), ("selected", selected),
+                          ("log_prior_selected", sel.cpu().numpy()), ("log_prior_rest", rest.cpu().numpy()),
+                          ("left_out", left.cpu().numpy()), ("pareto_k", pareto_k)])
+    _by_part(spec, arrays, (("prior", summary.prior), ("mean_shift_prior", summary.mean_shift_prior),
+                            ("sd_ratio_prior", summary.sd_ratio_prior)))
+    keys["psens_sites_time_sec"] = time.time() - clock
+    return keys, arrays
+
+
+def _psens_report(trace, k, spec, flags, pooled_mean=None, side=None):
     """--sensitivity_diagnostics: how much of each posterior marginal comes from the prior, how much from the data?
     Power-scaling sensitivity (Kallioinen, Paananen, Buerkner, Vehtari 2023; priorsense, ArviZ psens) over the draws the
     predictive report takes -- the leading `k` chains of the device trace, the chains split R-hat covers, at
@@ -1130,23 +1235,26 @@ def _psens_report(trace, k, spec, flags, pooled_mean=None):
     weights), every element's pooled draws are ordered (diagnostics.element_order) and the weighted ECDFs folded
     (diagnostics.cjs_sums, about `pooled_mean`); the statistics are diagnostics.psens_summary's.  The order of an element's
     draws needs them on one device: a sharded job (world size > 1) writes null, says so once, and enters no collective --
-    the rule of the rank reports.  delta is fixed; no power-scaling sequence; no choice of prior sites.
+    the rule of the rank reports.  delta is fixed; no power-scaling sequence.  The choice of prior sites is
+    --sensitivity_prior_parts: a second report on the same draws, mask, likelihood and order whose prior is the named
+    parts' own (_psens_sites_report); its keys join these, its arrays are left in `side` under PSENS_SITES_ARRAYS, and it
+    changes nothing of the first report.  Its keys are null whenever these are.
     Returns (JSON keys, arrays of <base>_psens.npz or None)."""
     import torch
     from . import engine as engine_lib
     if parallel.world()[1] > 1:
         return _psens_null("the chains of a sharded job are on several devices (the order of an element's pooled draws "
-                           "needs them on one)"), None
+                           "needs them on one)", flags), None
     clock = time.time()
     S, _, D = (int(v) for v in trace.shape)
     k = int(k) if S > 0 else 0
     if k <= 0:
-        return _psens_null("no chain has its trace on the device"), None
+        return _psens_null("no chain has its trace on the device", flags), None
     if D > diagnostics.LOGLIK_MAX_D:
-        return _psens_null("the model has more than {} elements".format(diagnostics.LOGLIK_MAX_D)), None
+        return _psens_null("the model has more than {} elements".format(diagnostics.LOGLIK_MAX_D), flags), None
     steps = loo_steps(S, k, getattr(flags, "loo_draws", 65536))
     if not steps:
-        return _psens_null("more than {} chains".format(diagnostics.PSIS_MAX_DRAWS)), None
+        return _psens_null("more than {} chains".format(diagnostics.PSIS_MAX_DRAWS), flags), None
     dev = trace.device
     table = diagnostics.upload_table(spec.observation_table(), D, dev)
     draws = trace[torch.as_tensor(steps, device=dev), :k].contiguous()               # [len(steps), k, D]: a copy, D floats a draw
@@ -1162,6 +1270,7 @@ def _psens_report(trace, k, spec, flags, pooled_mean=None):
     eng = engine_lib.Engine(spec, dev)                                               # the report's own handle: the run's stay as they are
     eng.set_param(0, "CP")
     log_joint = eng.logp_grad(draws.reshape(R, D), which=0)[0].to(torch.float64)
+    logp_const = float(eng.logp_const(0))
     del eng
     log_prior = log_joint - log_lik
     left = (mask != 0) | ~torch.isfinite(log_prior)
@@ -1170,8 +1279,9 @@ def _psens_report(trace, k, spec, flags, pooled_mean=None):
     order, values = diagnostics.element_order(draws)
     centre = np.zeros(D) if pooled_mean is None else np.asarray(pooled_mean, np.float64).reshape(D)
     centre = np.nan_to_num(centre, nan=0.0, posinf=0.0, neginf=0.0).astype(np.float32)
-    sums = diagnostics.cjs_sums(values, order, lw, torch.as_tensor(centre, device=dev)).cpu().numpy()
-    del order, values, lw
+    centre = torch.as_tensor(centre, device=dev)
+    sums = diagnostics.cjs_sums(values, order, lw, centre).cpu().numpy()
+    del lw
     summary = diagnostics.psens_summary(sums)
     names = element_names(spec)
     pareto_k = out8.cpu().numpy()[:, 1]
@@ -1204,6 +1314,14 @@ def _psens_report(trace, k, spec, flags, pooled_mean=None):
                             ("mean_shift_prior", summary.mean_shift_prior),
                             ("mean_shift_likelihood", summary.mean_shift_likelihood),
                             ("sd_ratio_prior", summary.sd_ratio_prior), ("sd_ratio_likelihood", summary.sd_ratio_likelihood)))
+    names_chosen = prior_parts(flags)
+    if names_chosen:
+        site_keys, site_arrays = _psens_sites_report(names_chosen, draws, spec, log_prior, logp_const, log_lik, left, order,
+                                                     values, centre)
+        keys.update(site_keys)
+        if side is not None:
+            side[PSENS_SITES_ARRAYS] = site_arrays
+    del order, values
     keys["psens_time_sec"] = time.time() - clock
     return keys, arrays
 
@@ -1216,6 +1334,16 @@ def save_psens(file_path_base, arrays):
     constant element), `mean_shift_prior/<part>`, `mean_shift_likelihood/<part>`, `sd_ratio_prior/<part>` and
     `sd_ratio_likelihood/<part>` (the upper row's weighted mean shift in pooled sd and its sd ratio)."""
     np.savez(file_path_base + "_psens.npz", **arrays)
+
+
+def save_psens_sites(file_path_base, arrays):
+    """`<base>_psens_sites.npz` (build-specific, --sensitivity_prior_parts): `parts`, the model's latent parts in trace order,
+    and `selected` [P] bool, the ones whose priors were power-scaled; `log_prior_selected`, `log_prior_rest` [R] float64 of
+    the draws _psens.npz holds: the sums of the chosen parts' site log densities and of the others' (normalisers included);
+    `left_out` [R] (the first report's and the draws whose selected prior is not finite); `pareto_k` [2], the k-hat of the
+    prior's power-scaled ratios (lower, upper); per latent part `prior/<part>`, `mean_shift_prior/<part>` and
+    `sd_ratio_prior/<part>` as in _psens.npz, for the chosen priors."""
+    np.savez(file_path_base + "_psens_sites.npz", **arrays)
 
 
 def _fit_chains(trace, k, workspace_bytes):
@@ -1405,13 +1533,15 @@ def save_geometry(file_path_base, arrays):
 
 def _save_diagnostics(file_path_base, arrays):
     """The side files of the convergence report: <base>_rhat.npz and, where the probes ran, <base>_energy.npz,
-    <base>_trajectory.npz, <base>_geometry.npz, <base>_loo.npz, <base>_loopred.npz, <base>_ppc.npz and <base>_psens.npz."""
+    <base>_trajectory.npz, <base>_geometry.npz, <base>_loo.npz, <base>_loopred.npz, <base>_ppc.npz, <base>_psens.npz and
+    <base>_psens_sites.npz."""
     if arrays is None:
         return
     # (tag _convergence_report left a side file's arrays under, its saver), in the order the files are written after _rhat.npz
     side = [(arrays.pop(tag, None), save) for tag, save in (
         (GEOMETRY_ARRAYS, save_geometry), (ENERGY_ARRAYS, save_energy), (TRAJECTORY_ARRAYS, save_trajectory),
-        (LOO_ARRAYS, save_loo), (LOO_PRED_ARRAYS, save_loo_pred), (PPC_ARRAYS, save_ppc), (PSENS_ARRAYS, save_psens))]
+        (LOO_ARRAYS, save_loo), (LOO_PRED_ARRAYS, save_loo_pred), (PPC_ARRAYS, save_ppc), (PSENS_ARRAYS, save_psens),
+        (PSENS_SITES_ARRAYS, save_psens_sites))]
     save_rhat(file_path_base, arrays)
     for side_arrays, save in side:
         if side_arrays is not None:
@@ -1703,6 +1833,7 @@ def main(argv=None, flags=FLAGS, out=None):
     check_predictive(flags)
     check_predictive_checks(flags)
     check_sensitivity(flags)
+    check_sensitivity_sites(flags)
     check_vi_diagnostics(flags)
     ws = int(os.environ.get("WORLD_SIZE", "1"))
     if ws > 1:

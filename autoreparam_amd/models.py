@@ -8,6 +8,7 @@ Edward2 program; here it is a :class:`ModelSpec` (same role: it defines the join
 density, evaluated natively by the engine instead of by TensorFlow).
 """
 import collections
+import math
 import os
 
 import numpy as np
@@ -25,6 +26,11 @@ ModelConfig = collections.namedtuple(
 # ModelSpec.observation_table: the likelihood of every observation as arp_pointwise_loglik reads it
 ObservationTable = collections.namedtuple("ObservationTable", ("kind", "idx", "w", "y", "scale_idx", "log_scale"))
 OBS_NORMAL, OBS_BERNOULLI = 0, 1     # include/autoreparam.h: ARP_OBS_NORMAL, ARP_OBS_BERNOULLI
+# ModelSpec.site_table: the prior of every latent element as arp_site_logprior reads it
+SiteTable = collections.namedtuple("SiteTable", ("form", "loc_idx", "loc_w", "loc0", "scale_idx", "scale_w", "log_scale0",
+                                                 "norm", "part"))
+SITE_NORMAL, SITE_NORMAL_SOFTPLUS, SITE_LOG_GAMMA = 0, 1, 2     # include/autoreparam.h: ARP_SITE_*
+SITE_TERMS = 2                                                  # ARP_SITE_TERMS
 
 
 class ModelSpec(object):
@@ -177,6 +183,90 @@ class ModelSpec(object):
         return ObservationTable(kind, idx, w, y, np.ascontiguousarray(scale_idx, dtype=np.int32),
                                 np.ascontiguousarray(log_scale, dtype=np.float32))
 
+    def site_table(self):
+        """One row per latent element d, in trace order, for `arp_site_logprior` -> SiteTable: the prior-side twin of
+        observation_table.  Every latent site here is a Normal whose loc and log-scale are affine in at most SITE_TERMS
+        EARLIER elements of the centred state, or the log of a Gamma variable:
+          loc_d = loc0[d] + sum_t loc_w[d][t] x[loc_idx[d][t]],  s_d = log_scale0[d] + sum_t scale_w[d][t] x[scale_idx[d][t]]
+          form SITE_NORMAL:           x_d ~ Normal(loc_d, exp(s_d))
+          form SITE_NORMAL_SOFTPLUS:  x_d ~ Normal(loc_d, softplus(s_d))
+          form SITE_LOG_GAMMA:        x_d = log g, g ~ Gamma(shape loc0[d], rate exp(s_d)): lp = loc0 x - exp(s + x) + norm
+        form, part [D] int32; loc_idx, scale_idx [D, 2] int32; loc_w, scale_w [D, 2], loc0, log_scale0, norm [D] float64
+        (the uploader rounds them to float32); padding terms have w = 0, idx = 0.  norm is the additive normaliser:
+        -0.5 log(2 pi) for a Normal, shape log(rate) - lgamma(shape) for the log-Gamma form.  part[d] indexes part_names.
+        The rows restate the reference's model programs (the lines: oracle/ed2_ref.py's header and
+        _spec_german_gammascale's docstring); electric's one-hot quirk is restated as observation_table restates it -- a
+        grade_pair outside [0, depth) is a term of weight 0.  Every term of non-zero weight points at an element before
+        d (the ancestral order: the table can be walked front to back to draw from the prior); asserted here.  A function
+        of the data alone, as observation_table is."""
+        r, off = self.raw, dict(zip(self.part_names, (int(o) for o in self.offsets[:-1])))
+        mid, D = self.model_id, self.D
+        form = np.full(D, SITE_NORMAL, np.int32)
+        loc_idx, scale_idx = np.zeros((D, SITE_TERMS), np.int32), np.zeros((D, SITE_TERMS), np.int32)
+        loc_w, scale_w = np.zeros((D, SITE_TERMS)), np.zeros((D, SITE_TERMS))
+        loc0, log_scale0, norm = np.zeros(D), np.zeros(D), np.full(D, -0.5 * np.log(2.0 * np.pi))
+
+        def rows(name):
+            k = self.part_names.index(name)
+            return np.arange(self.offsets[k], self.offsets[k + 1])
+
+        def term(idx_col, w_col, name, t, index, weight):
+            """term t of the part's rows: weight * x[index] (arrays over the part's elements, or scalars)"""
+            d = rows(name)
+            index, weight = np.broadcast_to(np.asarray(index), d.shape), np.broadcast_to(np.asarray(weight, np.float64), d.shape)
+            idx_col[d, t] = np.where(weight != 0, index, 0)
+            w_col[d, t] = weight
+
+        if mid == _lib.MODEL_EIGHT_SCHOOLS:
+            log_scale0[rows("mu")] = log_scale0[rows("log_tau")] = np.log(5.0)
+            term(loc_idx, loc_w, "theta", 0, off["mu"], 1.0)
+            term(scale_idx, scale_w, "theta", 0, off["log_tau"], 1.0)
+        elif mid in (_lib.MODEL_RADON, _lib.MODEL_RADON_STDDVS):
+            term(loc_idx, loc_w, "m", 0, off["mua"], 1.0)
+            term(loc_idx, loc_w, "m", 1, off["b1"], np.asarray(r["u"], np.float64).reshape(-1))
+        elif mid == _lib.MODEL_NEALS_FUNNEL:
+            log_scale0[rows("x1")] = np.log(3.0)
+            term(scale_idx, scale_w, "x2", 0, off["x1"], 0.5)
+        elif mid == _lib.MODEL_GERMAN_CREDIT:
+            log_scale0[rows("overall_log_scale")] = np.log(10.0)
+            bls = rows("beta_log_scales")
+            if dict(self.options).get("german_prior") == "gamma":
+                shape, rate = 0.5, 0.5
+                form[bls] = SITE_LOG_GAMMA
+                loc0[bls], log_scale0[bls] = shape, np.log(rate)
+                norm[bls] = shape * np.log(rate) - math.lgamma(shape)
+                term(scale_idx, scale_w, "beta", 0, off["overall_log_scale"], 1.0)
+                term(scale_idx, scale_w, "beta", 1, bls, 1.0)
+            else:
+                term(loc_idx, loc_w, "beta_log_scales", 0, off["overall_log_scale"], 1.0)
+                term(scale_idx, scale_w, "beta", 0, bls, 1.0)
+        elif mid == _lib.MODEL_ELECTION:
+            for name in ("mua", "b1", "b2"):
+                log_scale0[rows(name)] = np.log(100.0)
+            log_scale0[rows("log_sigma_a")] = np.log(10.0)
+            term(loc_idx, loc_w, "a", 0, off["mua"], 1.0)
+            term(scale_idx, scale_w, "a", 0, off["log_sigma_a"], 1.0)
+        elif mid == _lib.MODEL_ELECTRIC:
+            log_scale0[rows("b")] = np.log(100.0)
+            gp = np.asarray(r["grade_pair"]).astype(np.int64).reshape(-1)
+            ok = (gp >= 0) & (gp < int(r["n_grade_pair"]))
+            term(loc_idx, loc_w, "a", 0, off["mua"] + np.where(ok, gp, 0), np.where(ok, 100.0, 0.0))
+        elif mid == _lib.MODEL_TIME_SERIES:
+            for t in range(len(r["y"])):
+                for name, sigma in (("alpha%d" % t, "sigma_alpha"), ("mu%d" % t, "sigma_mu")):
+                    form[rows(name)] = SITE_NORMAL_SOFTPLUS
+                    term(scale_idx, scale_w, name, 0, off[sigma], 1.0)
+                if t > 0:
+                    term(loc_idx, loc_w, "alpha%d" % t, 0, off["alpha%d" % (t - 1)], 1.0)
+                    term(loc_idx, loc_w, "alpha%d" % t, 1, off["mu%d" % (t - 1)], 1.0)
+                    term(loc_idx, loc_w, "mu%d" % t, 0, off["mu%d" % (t - 1)], 1.0)
+        else:
+            raise ValueError("unknown model id")
+        part = np.repeat(np.arange(len(self.part_names)), self.part_sizes).astype(np.int32)
+        d = np.arange(D)[:, None]
+        assert all(np.all((w == 0) | (i < d)) for i, w in ((loc_idx, loc_w), (scale_idx, scale_w))), "site table: not ancestral"
+        return SiteTable(form, loc_idx, loc_w, loc0, scale_idx, scale_w, log_scale0, norm, part)
+
     def dataset(self):
         """(ctypes Dataset, keep-alive list) for arp_model_create."""
         keep = []
@@ -301,9 +391,9 @@ def _spec_election():
                      [(), (), (S,), (), ()], r, {"y": r["y"].reshape(-1, 1)}, scalar_loc=("a",))
 
 
-def get_model_by_name(model_name, dataset=None):
-    """Reference: models.py:1144-1175 (the four BASELINE models and the scalar-Normal hierarchical models of
-    SURVEY 8f-3; the GP / MVN / Wishart models are out of scope, DESIGN.md section 8)."""
+def spec_by_name(model_name, dataset=None):
+    """The ModelSpec get_model_by_name builds its ModelConfig around: the frozen data and the latent parts, nothing on the
+    device."""
     if model_name == "8schools":
         spec = _spec_eight_schools()
     elif model_name == "radon":
@@ -326,6 +416,13 @@ def get_model_by_name(model_name, dataset=None):
         raise Exception("unknown model {} (this build covers 8schools, radon, radon_stddvs, "
                         "neals_funnel, electric, time_series, german_credit_lognormalcentered, "
                         "german_credit_gammascale, election)".format(model_name))
+    return spec
+
+
+def get_model_by_name(model_name, dataset=None):
+    """Reference: models.py:1144-1175 (the four BASELINE models and the scalar-Normal hierarchical models of
+    SURVEY 8f-3; the GP / MVN / Wishart models are out of scope, DESIGN.md section 8)."""
+    spec = spec_by_name(model_name, dataset)
     from . import engine  # deferred: converters run on the device
 
     varnames = spec.part_names

@@ -632,6 +632,42 @@ int arp_element_order(const float* x, int64_t n_samples, int64_t n_chains, int32
 int arp_cjs_sums(const float* sorted, const uint32_t* order, int64_t N, int32_t D, const double* lw, int64_t lw_stride,
                  int32_t K, const float* shift, double* out, void* stream);
 
+/* Per-site log prior of recorded draws (csrc/prior.hip; needs no model handle): the prior-side twin of
+ * arp_pointwise_loglik.  For a block of recorded steps of the CENTRED trace x (arp_pointwise_loglik's addressing and
+ * row_stride rule) and a latent site table in device memory -- one row per element d, ARP_SITE_TERMS terms each,
+ *   loc_d = loc0[d] + sum_t loc_w[d * 2 + t] * x[loc_idx[d * 2 + t]]
+ *   s_d   = log_scale0[d] + sum_t scale_w[d * 2 + t] * x[scale_idx[d * 2 + t]]
+ *   form ARP_SITE_NORMAL:           z = (x_d - loc_d) * exp(-s_d);  lp = -0.5 * z^2 - s_d + norm[d]
+ *   form ARP_SITE_NORMAL_SOFTPLUS:  sigma = max(s_d, 0) + log1p(exp(-|s_d|));  z = (x_d - loc_d) / sigma;
+ *                                   lp = -0.5 * z^2 - log(sigma) + norm[d]
+ *   form ARP_SITE_LOG_GAMMA:        lp = loc0[d] * x_d - exp(s_d + x_d) + norm[d]
+ *                                   (x = log g, g ~ Gamma(shape loc0, rate exp(log_scale0)), Jacobian included; the loc
+ *                                   terms are not read)
+ * -- it writes, for draw r = step * n_chains + chain,
+ *   elem_lp[r * D + d]   float, the density of element d; elem_lp may be NULL, which leaves every other output bitwise as it is
+ *   group_lp[r * G + g]  double, the sum of the float32 values of the elements with group_of[d] == g, added in float64 in
+ *                        an order that is a function of (D, group_of) alone (no float atomics: two calls give bitwise equal
+ *                        output); group_of need not be contiguous; a group without elements is 0
+ *   mask, *n_masked      as arp_pointwise_loglik's; the elem_lp and group_lp entries of a masked draw are written as 0 by select.
+ * NaN and +-inf of a finite draw are results; nothing is clamped but the indices (into [0, D); group_of into [0, G)); a form
+ * other than 1 or 2 is read as 0.  float32, contraction off, the loc and s chains in term order from loc0 / log_scale0,
+ * rounded once per operation: with u = 2^-24, A_loc = |loc0| + sum_t |w_t x_t|, A_s = |log_scale0| + sum_t |w_t x_t|, to
+ * first order against the exact value of the same float32 inputs (derivation: csrc/prior.hip)
+ *   |loc_dev - loc| <= 3 u A_loc,   |s_dev - s| <= 3 u A_s
+ *   form 0:  |lp_dev - lp| <= u (3 A_loc exp(-s) |z| + z^2 (5 + 3 A_s) + 4 A_s + |lp|)
+ *   form 1:  |lp_dev - lp| <= u (3 A_loc |z| / sigma + z^2 (4 + B) + B + 3 |log sigma| + |lp|),  B = (3 A_s + 3) / sigma + 1
+ *   form 2:  |lp_dev - lp| <= u (2 |loc0 x| + E (3 + 3 A_s + |s + x|) + |lp|),  E = exp(s + x)
+ *   |group_lp - sum| <= the sum of its elements' bounds + (n_g + 4) 2^-53 sum |elem_lp|     (n_g elements in the group)
+ * Nothing is read past the last element of the trace block.  Asynchronous.  Refused before any launch: a NULL pointer
+ * other than elem_lp, D < 1 or D > 255, a trace shape the other diagnostics refuse, row_stride < n_chains * D, G < 1 or
+ * G > D. */
+enum { ARP_SITE_NORMAL = 0, ARP_SITE_NORMAL_SOFTPLUS = 1, ARP_SITE_LOG_GAMMA = 2, ARP_SITE_TERMS = 2 };
+int arp_site_logprior(const float* x, int64_t n_samples, int64_t n_chains, int32_t D, int64_t row_stride,
+                      const int32_t* form, const int32_t* loc_idx, const float* loc_w, const float* loc0,
+                      const int32_t* scale_idx, const float* scale_w, const float* log_scale0, const float* norm,
+                      const int32_t* group_of, int32_t G, double* group_lp, float* elem_lp /* may be NULL */,
+                      uint8_t* mask, int64_t* n_masked, void* stream);
+
 /* Check of a mean-field normal fit (csrc/vicheck.hip; Yao, Vehtari, Simpson, Gelman 2018, "Yes, but did it work?"): draws
  * from q = N(loc, diag(scale^2)) in the coordinates the fit was made in.  For draw r, g = draw_offset + r, and element
  * d = 4 e + i: ONE call philox4x32_10(counter = (e, lo32(g), hi32(g), 0), key = (lo32(seed), hi32(seed))) per (r, e); words
