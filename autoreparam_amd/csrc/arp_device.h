@@ -25,9 +25,36 @@ ARP_DEV void store_f4(float4* dst, const float4& v) {
   else *dst = v;
 }
 
-template <bool STREAM>
+// How a global store leaves the CU.  kStoreThrough = agent-scope write-through (`sc1`): the bytes go to memory and the line
+// is dropped from the XCD's L2, so a workgroup on another XCD can read them once the storing wave's `s_waitcnt vmcnt(0)` has
+// passed -- no L2 write-back (kernels.h: relay_end).  Only bytes handed from workgroup to workgroup inside a launch take it.
+// (an int, not an enum: `true` still names a trace row's policy)
+constexpr int kStorePlain = 0, kStoreStream = 1, kStoreThrough = 2;
+
+// 16 bytes write-through.  The compiler has no 16-byte atomic store, so the instruction is written out; `s_nop 1` keeps the
+// next instruction off the data registers until the store has read them.  It is not counted in the compiler's vmcnt
+// bookkeeping: the counter can only stand higher than the compiler believes, so its own waits wait longer, never shorter,
+// and the publishing wave's wait is the explicit one in relay_end.
+ARP_DEV void store_v4_through(void* dst, v4f_nt v) {
+  asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" : : "v"(dst), "v"(v) : "memory");
+}
+// 4 bytes write-through: a relaxed agent-scope atomic store is `global_store_dword ... sc1`
+ARP_DEV void store_u32_through(uint32_t* dst, uint32_t v) {
+  __hip_atomic_store(dst, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+ARP_DEV void store_f32_through(float* dst, float v) {
+  store_u32_through(reinterpret_cast<uint32_t*>(dst), __float_as_uint(v));
+}
+
+template <int POLICY>
 ARP_DEV void store_v4(v4f_nt* dst, v4f_nt v) {
-  if constexpr (STREAM) __builtin_nontemporal_store(v, dst);
+  if constexpr (POLICY == kStoreStream) __builtin_nontemporal_store(v, dst);
+  else if constexpr (POLICY == kStoreThrough) store_v4_through(dst, v);
+  else *dst = v;
+}
+template <int POLICY>
+ARP_DEV void store_f1(float* dst, float v) {
+  if constexpr (POLICY == kStoreThrough) store_f32_through(dst, v);
   else *dst = v;
 }
 

@@ -50,6 +50,7 @@ struct HmcParams {
   unsigned long long seg_timeout;   // ticks of the 100 MHz clock a segment waits for the one before it
   int seg_fault;                    // test hook (ARP_DEBUG=1 ARP_RELAY_FAULT=1): segments never raise their flag
   int seg_start[kSegTable + 1];     // first step of every segment, then n_steps (segs <= kSegTable)
+  int seg_mode;                     // hand-over form: kRelayThrough | kRelayGroup (relay_end, relay_begin); lives in SGPRs
 #ifdef ARP_EXP_RELAY_STAMPS         // timing experiment only (tools/relay_stamps.py): kStamps words per ticket
   unsigned long long* seg_stamps;
 #endif
@@ -89,7 +90,24 @@ __host__ __device__ __forceinline__ void rec_schedule(HmcParams& P) {
 // on expiry the launch is marked failed -- device word for the other waiters, pinned host word for arp_model_check -- and
 // every workgroup still waiting returns at once (seg < 0).  Segments that ran before have stored their steps, so such a launch
 // leaves its chains partly advanced -- discard them.
+//
+// The hand-over itself has two forms on either side, chosen per launch in HmcParams::seg_mode (relay_host.h: kRelayMode;
+// ARP_RELAY_PUBLISH / ARP_RELAY_ACQUIRE under ARP_DEBUG=1; profiles/r08_relay_handover.txt has the measurements):
+//   publish, fence form: plain stores, then in every storing wave an agent release (`buffer_wbl2 sc1`: the XCD's L2 written
+//     back) and an explicit `s_waitcnt vmcnt(0)`, the barrier, thread 0's flag.
+//   publish, write-through form (kRelayThrough): EVERY handed-over byte leaves through an `sc1` store (kStoreThrough), every
+//     storing wave waits `s_waitcnt vmcnt(0)`, the barrier, thread 0's flag -- no L2 write-back.  Valid only where the
+//     epilogue's bytes are all that travel: the statistics planes and rec_accept are read-modify-written with plain stores
+//     inside the step loop, so such launches take the fence form whatever was asked (relay_through).
+//   acquire, wave form: after the barrier behind the poll every wave invalidates (`buffer_inv sc1`) and waits for it.
+//   acquire, group form (kRelayGroup): thread 0's wave polls, invalidates this CU's L1 once and waits for the invalidate to
+//     complete BEFORE the barrier it releases the other waves through; they then load with plain loads.  L1 is per CU.
+// The waits are written as inline asm on purpose.  The compiler removes the `s_waitcnt vmcnt(0)` it emits behind
+// `buffer_wbl2` (or `buffer_inv`) as soon as it can prove the wave's memory counter empty in front of the fence -- a waited
+// load, an `s_waitcnt` builtin -- and the flag store (or the barrier) then overtakes the write-back (the invalidate).  Inline
+// asm is invisible to that pass.
 // ---------------------------------------------------------------------------
+constexpr int kRelayThrough = 1, kRelayGroup = 2;     // HmcParams::seg_mode
 struct RelayId { unsigned bid; int seg; };
 // Timing experiment only (-DARP_EXP_RELAY_STAMPS; tools/relay_stamps.py, profiles/r07_relay_schedule.txt): thread 0 of every
 // workgroup of a relay launch writes the 100 MHz clock at kernel entry (0), after the ticket wait (1), at the first step (2),
@@ -150,10 +168,22 @@ ARP_DEV RelayId relay_begin(HmcParams& P, const int* seg_start) {
           if (failed) { s_relay[1] = 1u; break; }
         }
       }
-      __syncthreads();
-      // EVERY wave takes the acquire itself, in front of its own loads (this CU's L1, stale L2 lines of other XCDs' data): the
-      // memory model orders a wave's loads behind ITS OWN invalidate, not behind another wave's through a barrier
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+      if (P.seg_mode & kRelayGroup) {
+        // ONE acquire per workgroup: the polling wave invalidates (this CU's L1, stale L2 lines of other XCDs' data) and
+        // waits for the invalidate to complete, then joins the barrier -- which therefore opens only behind it, and the
+        // other waves' plain loads find the lines gone.  Without the wait the barrier could open under a pending invalidate.
+        if (__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) == 0) {
+          __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        }
+        __syncthreads();
+      } else {
+        __syncthreads();
+        // every wave takes the acquire itself, in front of its own loads, and waits for it: the wait is pinned (asm), the
+        // compiler's own falls away when it can prove the wave's counter empty in front of the fence (see above)
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      }
       if (__builtin_amdgcn_readfirstlane((int)s_relay[1])) r.seg = -1;
     }
 #ifdef ARP_EXP_RELAY_STAMPS
@@ -169,14 +199,43 @@ ARP_DEV RelayId relay_begin(HmcParams& P, const int* seg_start) {
   }
   return r;
 }
-ARP_DEV void relay_end(const HmcParams& P, RelayId r) {
+// Whether this launch's epilogues publish write-through (wave-uniform, asked once per epilogue): the form was asked for, and
+// the epilogue's bytes are all that travel between segments -- no statistics planes, no rec_accept counters (both are
+// read-modify-written with plain stores inside the step loop) -- and the per-chain quadruples can be stored 16 bytes at a time.
+// STATS: the instantiation that folds statistics from LDS; it has planes by construction.
+template <bool STATS = false>
+ARP_DEV bool relay_through(const HmcParams& P) {
+  if constexpr (STATS) return false;
+  return P.segs > 1 && (P.seg_mode & kRelayThrough) != 0 && !P.stats && !P.rec_accept && !P.rec_accept1 &&
+         ((reinterpret_cast<uintptr_t>(P.adapt) | reinterpret_cast<uintptr_t>(P.adapt1) | reinterpret_cast<uintptr_t>(P.rng)) & 15) == 0;
+}
+// The per-chain words of a write-through epilogue.  A chain's adaptation quadruple goes as ONE 16-byte store: its fourth
+// word, which no kernel uses, is rewritten with the value it is loaded with here (the load is issued before any store
+// of the epilogue, and the compiler waits for it where the store takes it).
+ARP_DEV float adapt_spare(const float* adapt, size_t c) { return adapt[c * 4 + 3]; }
+ARP_DEV void store_adapt_through(float* adapt, size_t c, float kappa, float esum, float logavg, float spare) {
+  store_v4_through(adapt + c * 4, v4f_nt{kappa, esum, logavg, spare});
+}
+ARP_DEV void store_rng_through(uint32_t* rs, const Rng& rng) {
+  store_v4_through(rs, v4f_nt{__uint_as_float(rng.x), __uint_as_float(rng.c), 0.0f, 0.0f});
+}
+// `through`: what relay_through said when the epilogue chose its stores
+ARP_DEV void relay_end(const HmcParams& P, RelayId r, bool through) {
   if (P.segs > 1) {
-    // EVERY storing wave releases its own stores (write-back of the XCD's L2 behind them, then vmcnt(0)) before the barrier.
-    // Round 5 / early round 6 let the waves only drain (`s_waitcnt vmcnt(0)`) and thread 0 alone write L2 back after the
-    // barrier: with the ticket order (consecutive segments of a block on arbitrary XCDs) one run in ten then handed a stale
-    // cache line or two to the next segment (tests/diagnostics/relay_race_probe.py: 14 of 120 repetitions at 8 192 chains;
-    // 0 of 120 with this form) -- a write-back issued by ANOTHER wave does not order behind this wave's stores.
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+    if (through) {
+      // every handed-over byte left through an sc1 store: each storing wave waits for its own, nothing is written back
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    } else {
+      // EVERY storing wave releases its own stores (write-back of the XCD's L2 behind them) and WAITS for the write-back
+      // before the barrier the flag store sits behind.  The wait is the hazard: `buffer_wbl2` completes asynchronously,
+      // and the `s_waitcnt vmcnt(0)` the compiler puts behind it is dropped when the wave's counter is provably empty in
+      // front of the fence.  Round 5 / early round 6 let the waves only drain and thread 0 alone fence after the barrier --
+      // thread 0's wave had just waited, its fence lost its wait, and the flag overtook the write-back: one run in ten then
+      // handed a stale cache line or two to the next segment (tests/diagnostics/relay_race_probe.py: 14 of 120
+      // repetitions at 8 192 chains; 0 of 120 with this form).  Hence the wait in asm, which no pass removes.
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
     __syncthreads();
     if (threadIdx.x == 0 && !P.seg_fault) {
       __hip_atomic_store(P.seg_flags + r.bid, P.seg_epoch + (unsigned)r.seg + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -254,7 +313,7 @@ ARP_DEV float* lane_stage(float* own) {
   __shared__ __attribute__((aligned(16))) float s_stage_own[lane_stage_alias<Lane>::value ? 4 : (kBlock / 64) * stage_floats<Lane>()]; \
   float* const s_stage = lane_stage<Lane>(s_stage_own)
 
-template <bool STREAM = false, class Lane>
+template <int POLICY = kStorePlain, class Lane>       // arp_device.h: kStorePlain, kStoreStream (`true`), kStoreThrough
 ARP_DEV void store_row_wave(const Lane& M, float* stage, float* gdst, int cl, int D, int nvalid,
                             const float (&v)[Lane::ND]) {
   float* row = stage + cl * D;
@@ -282,16 +341,16 @@ ARP_DEV void store_row_wave(const Lane& M, float* stage, float* gdst, int cl, in
       for (int u = 0; u < 4; ++u) {
         const int k = k0 + 256 * u;
         if (k + 3 < nvalid) {
-          store_v4<STREAM>(reinterpret_cast<v4f_nt*>(gdst + k), t[u]);
+          store_v4<POLICY>(reinterpret_cast<v4f_nt*>(gdst + k), t[u]);
         } else if (k < nvalid) {
-          gdst[k] = t[u][0];
-          if (k + 1 < nvalid) gdst[k + 1] = t[u][1];
-          if (k + 2 < nvalid) gdst[k + 2] = t[u][2];
+          store_f1<POLICY>(gdst + k, t[u][0]);
+          if (k + 1 < nvalid) store_f1<POLICY>(gdst + k + 1, t[u][1]);
+          if (k + 2 < nvalid) store_f1<POLICY>(gdst + k + 2, t[u][2]);
         }
       }
     }
   } else {
-    for (int k = lane; k < nvalid; k += 64) gdst[k] = stage[k];
+    for (int k = lane; k < nvalid; k += 64) store_f1<POLICY>(gdst + k, stage[k]);
   }
   __builtin_amdgcn_wave_barrier();
 }
@@ -823,19 +882,34 @@ __global__ __launch_bounds__(kBlock, Lane::MINW) void hmc_kernel(
   asm volatile("" : "+v"(c2));
   long long cw2 = cw0;
   asm volatile("" : "+v"(cw2));
-  store_row_wave(M, stage, P.q + cw2 * D, cl, D, nvalid, q);
-  store_row_wave(M, stage, P.grad + cw2 * D, cl, D, nvalid, g);
   uint32_t* rs2 = P.rng + ((size_t)c2 * kRngSlots + slot) * 4;
-  if (live) {
-    rs = rs2;
-    rs[0] = rng.x; rs[1] = rng.c; rs[2] = 0u; rs[3] = 0u;
-    if (slot == 0) {
-      P.logp[c2] = lp;
-      P.adapt[c2 * 4 + 0] = kappa; P.adapt[c2 * 4 + 1] = esum; P.adapt[c2 * 4 + 2] = logavg;
-      P.accept_count[c2] = nacc;
+  const bool through = relay_through(P);      // a relay segment that hands its state on write-through (relay_end)
+  if (through) {
+    const float spare = adapt_spare(P.adapt, (size_t)c2);
+    store_row_wave<kStoreThrough>(M, stage, P.q + cw2 * D, cl, D, nvalid, q);
+    store_row_wave<kStoreThrough>(M, stage, P.grad + cw2 * D, cl, D, nvalid, g);
+    if (live) {
+      store_rng_through(rs2, rng);
+      if (slot == 0) {
+        store_f32_through(P.logp + c2, lp);
+        store_adapt_through(P.adapt, (size_t)c2, kappa, esum, logavg, spare);
+        store_u32_through(P.accept_count + c2, nacc);
+      }
+    }
+  } else {
+    store_row_wave(M, stage, P.q + cw2 * D, cl, D, nvalid, q);
+    store_row_wave(M, stage, P.grad + cw2 * D, cl, D, nvalid, g);
+    if (live) {
+      rs = rs2;
+      rs[0] = rng.x; rs[1] = rng.c; rs[2] = 0u; rs[3] = 0u;
+      if (slot == 0) {
+        P.logp[c2] = lp;
+        P.adapt[c2 * 4 + 0] = kappa; P.adapt[c2 * 4 + 1] = esum; P.adapt[c2 * 4 + 2] = logavg;
+        P.accept_count[c2] = nacc;
+      }
     }
   }
-  relay_end(P, rid);
+  relay_end(P, rid, through);
 }
 
 // ---------------------------------------------------------------------------
@@ -960,18 +1034,32 @@ __global__ __launch_bounds__(kBlock, Lane::MINW) void interleaved_kernel(
   asm volatile("" : "+v"(c2));
   long long cw2 = cw0;
   asm volatile("" : "+v"(cw2));
-  store_row_wave(M, stage, P.q + cw2 * D, cl, D, nvalid, q);
   uint32_t* rs2 = P.rng + ((size_t)c2 * kRngSlots + slot) * 4;
-  if (live) {
-    rs = rs2;
-    rs[0] = rng.x; rs[1] = rng.c; rs[2] = 0u; rs[3] = 0u;
-    if (slot == 0) {
-      P.adapt[c2 * 4 + 0] = kap[0]; P.adapt[c2 * 4 + 1] = es[0]; P.adapt[c2 * 4 + 2] = la_[0];
-      P.adapt1[c2 * 4 + 0] = kap[1]; P.adapt1[c2 * 4 + 1] = es[1]; P.adapt1[c2 * 4 + 2] = la_[1];
-      P.accept_count[c2] = nacc0; P.accept_count1[c2] = nacc1;
+  const bool through = relay_through(P);      // a relay segment that hands its state on write-through (relay_end)
+  if (through) {
+    const float spare0 = adapt_spare(P.adapt, (size_t)c2), spare1 = adapt_spare(P.adapt1, (size_t)c2);
+    store_row_wave<kStoreThrough>(M, stage, P.q + cw2 * D, cl, D, nvalid, q);
+    if (live) {
+      store_rng_through(rs2, rng);
+      if (slot == 0) {
+        store_adapt_through(P.adapt, (size_t)c2, kap[0], es[0], la_[0], spare0);
+        store_adapt_through(P.adapt1, (size_t)c2, kap[1], es[1], la_[1], spare1);
+        store_u32_through(P.accept_count + c2, nacc0); store_u32_through(P.accept_count1 + c2, nacc1);
+      }
+    }
+  } else {
+    store_row_wave(M, stage, P.q + cw2 * D, cl, D, nvalid, q);
+    if (live) {
+      rs = rs2;
+      rs[0] = rng.x; rs[1] = rng.c; rs[2] = 0u; rs[3] = 0u;
+      if (slot == 0) {
+        P.adapt[c2 * 4 + 0] = kap[0]; P.adapt[c2 * 4 + 1] = es[0]; P.adapt[c2 * 4 + 2] = la_[0];
+        P.adapt1[c2 * 4 + 0] = kap[1]; P.adapt1[c2 * 4 + 1] = es[1]; P.adapt1[c2 * 4 + 2] = la_[1];
+        P.accept_count[c2] = nacc0; P.accept_count1[c2] = nacc1;
+      }
     }
   }
-  relay_end(P, rid);
+  relay_end(P, rid, through);
 }
 
 // ---------------------------------------------------------------------------

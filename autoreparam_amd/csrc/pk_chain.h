@@ -231,29 +231,38 @@ ARP_DEV float pk_transition(const T& M, Rng& rng, int L, float kappa, const floa
 }
 
 // the copy half of kernels.h: store_row_wave as a real call (cold path; keeps its address arithmetic out of the callers)
-__device__ __noinline__ void copy_stage_rows(const float* stage, float* gdst, int nvalid) {
+template <int POLICY>
+ARP_DEV void copy_stage_rows_as(const float* stage, float* gdst, int nvalid) {
   const int lane = threadIdx.x & 63;
   if ((reinterpret_cast<uintptr_t>(gdst) & 15) == 0) {
     for (int k = lane * 4; k < nvalid; k += 256) {
       const float4 t = *reinterpret_cast<const float4*>(stage + k);
       if (k + 3 < nvalid) {
-        *reinterpret_cast<float4*>(gdst + k) = t;
+        if constexpr (POLICY == kStoreThrough) store_v4_through(gdst + k, v4f_nt{t.x, t.y, t.z, t.w});
+        else *reinterpret_cast<float4*>(gdst + k) = t;
       } else {
-        gdst[k] = t.x;
-        if (k + 1 < nvalid) gdst[k + 1] = t.y;
-        if (k + 2 < nvalid) gdst[k + 2] = t.z;
+        store_f1<POLICY>(gdst + k, t.x);
+        if (k + 1 < nvalid) store_f1<POLICY>(gdst + k + 1, t.y);
+        if (k + 2 < nvalid) store_f1<POLICY>(gdst + k + 2, t.z);
       }
     }
   } else {
-    for (int k = lane; k < nvalid; k += 64) gdst[k] = stage[k];
+    for (int k = lane; k < nvalid; k += 64) store_f1<POLICY>(gdst + k, stage[k]);
   }
+}
+__device__ __noinline__ void copy_stage_rows(const float* stage, float* gdst, int nvalid) {
+  copy_stage_rows_as<kStorePlain>(stage, gdst, nvalid);
+}
+// the same with every byte written through (a relay segment's ragged last wave: kernels.h, relay_end)
+__device__ __noinline__ void copy_stage_rows_through(const float* stage, float* gdst, int nvalid) {
+  copy_stage_rows_as<kStoreThrough>(stage, gdst, nvalid);
 }
 
 // A wave's rows (its 64/K consecutive chains) to a [C][D] array: store_row_wave of kernels.h with the state in pairs and,
 // when the wave is full and D is the instantiation's own dimension (the reference's PA: 68 = 4 x 17 counties), every
 // offset a compile-time constant -- the staging writes are ds_write2_b32 off one base, the copy is an unrolled run of
 // ds_read_b128 / global_store_dwordx4 off a wave-uniform base: no address arithmetic on the vector pipe.
-template <bool STREAM = false, class T>
+template <int POLICY = kStorePlain, class T>       // arp_device.h: kStorePlain, kStoreStream (`true`), kStoreThrough
 ARP_DEV void pk_store_rows(const T& M, float* stage, float* gdst, int cl, int D, int nvalid,
                               const float (&xg)[T::NG], const v2f (&xc)[T::NP]) {
   constexpr int K = T::K, NL = T::NL, DC = T::DCAP, NV = (64 / K) * DC;
@@ -287,7 +296,7 @@ ARP_DEV void pk_store_rows(const T& M, float* stage, float* gdst, int cl, int D,
     for (int it = 0; it < NIT; ++it) t[it] = reinterpret_cast<const v4f_nt*>(s4)[word(it)];
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-    for (int it = 0; it < NIT; ++it) store_v4<STREAM>(reinterpret_cast<v4f_nt*>(g4) + word(it), t[it]);
+    for (int it = 0; it < NIT; ++it) store_v4<POLICY>(reinterpret_cast<v4f_nt*>(g4) + word(it), t[it]);
     __builtin_amdgcn_wave_barrier();
   } else if (nvalid == (64 / K) * D && (nvalid & 3) == 0 && (reinterpret_cast<uintptr_t>(gdst) & 15) == 0) {
     // a full wave of a county count that leaves padding slices (D < DCAP: PA at 8 lanes per chain, the strong-scaling
@@ -317,7 +326,7 @@ ARP_DEV void pk_store_rows(const T& M, float* stage, float* gdst, int cl, int D,
     for (int it = 0; it < NIT; ++it) t[it] = reinterpret_cast<const v4f_nt*>(s4)[word(it)];
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-    for (int it = 0; it < NIT; ++it) store_v4<STREAM>(reinterpret_cast<v4f_nt*>(g4) + word(it), t[it]);
+    for (int it = 0; it < NIT; ++it) store_v4<POLICY>(reinterpret_cast<v4f_nt*>(g4) + word(it), t[it]);
     __builtin_amdgcn_wave_barrier();
   } else {   // ragged tail of the launch, or an unaligned destination: general offsets, out-of-line copy
     float* row = stage + cl * D;
@@ -330,7 +339,8 @@ ARP_DEV void pk_store_rows(const T& M, float* stage, float* gdst, int cl, int D,
     for (int i = 0; i < NL; ++i)
       if (M.lvalid(i)) e[K * i] = xc[i >> 1][i & 1];
     __builtin_amdgcn_wave_barrier();
-    copy_stage_rows(stage, gdst, nvalid);
+    if constexpr (POLICY == kStoreThrough) copy_stage_rows_through(stage, gdst, nvalid);
+    else copy_stage_rows(stage, gdst, nvalid);
     __builtin_amdgcn_wave_barrier();
   }
 }
@@ -561,18 +571,33 @@ __global__ __launch_bounds__(kBlock, (STATS || MODE == ARP_PK_VIP_MINW2) && T::M
   size_t c2 = (size_t)c;
   asm volatile("" : "+v"(c2));
   const long long cw2 = cw0;
-  pk_store_rows(M, stage, P.q + cw2 * D, cl, D, nvalid, qg, qc);
-  pk_store_rows(M, stage, P.grad + cw2 * D, cl, D, nvalid, gg_, gc);
-  if (live) {
-    uint32_t* rs2 = P.rng + ((size_t)c2 * kRngSlots + slot) * 4;
-    rs2[0] = rng.x; rs2[1] = rng.c; rs2[2] = 0u; rs2[3] = 0u;
-    if (slot == 0) {
-      P.logp[c2] = lp;
-      P.adapt[c2 * 4 + 0] = kappa; P.adapt[c2 * 4 + 1] = esum; P.adapt[c2 * 4 + 2] = logavg;
-      P.accept_count[c2] = nacc;
+  const bool through = relay_through<STATS>(P);      // a relay segment that hands its state on write-through (kernels.h: relay_end)
+  if (through) {
+    const float spare = adapt_spare(P.adapt, c2);
+    pk_store_rows<kStoreThrough>(M, stage, P.q + cw2 * D, cl, D, nvalid, qg, qc);
+    pk_store_rows<kStoreThrough>(M, stage, P.grad + cw2 * D, cl, D, nvalid, gg_, gc);
+    if (live) {
+      store_rng_through(P.rng + ((size_t)c2 * kRngSlots + slot) * 4, rng);
+      if (slot == 0) {
+        store_f32_through(P.logp + c2, lp);
+        store_adapt_through(P.adapt, c2, kappa, esum, logavg, spare);
+        store_u32_through(P.accept_count + c2, nacc);
+      }
+    }
+  } else {
+    pk_store_rows(M, stage, P.q + cw2 * D, cl, D, nvalid, qg, qc);
+    pk_store_rows(M, stage, P.grad + cw2 * D, cl, D, nvalid, gg_, gc);
+    if (live) {
+      uint32_t* rs2 = P.rng + ((size_t)c2 * kRngSlots + slot) * 4;
+      rs2[0] = rng.x; rs2[1] = rng.c; rs2[2] = 0u; rs2[3] = 0u;
+      if (slot == 0) {
+        P.logp[c2] = lp;
+        P.adapt[c2 * 4 + 0] = kappa; P.adapt[c2 * 4 + 1] = esum; P.adapt[c2 * 4 + 2] = logavg;
+        P.accept_count[c2] = nacc;
+      }
     }
   }
-  relay_end(P, rid);
+  relay_end(P, rid, through);
 }
 
 // Interleaved sampling on the packed chain layer for lane models whose change of coordinates is NOT a unit-Jacobian
@@ -704,17 +729,31 @@ __global__ __launch_bounds__(kBlock, STATS && T::MINW > 2 ? 2 : T::MINW) void pk
   size_t c2 = (size_t)c;
   asm volatile("" : "+v"(c2));
   const long long cw2 = cw0;
-  pk_store_rows(M, stage, P.q + cw2 * D, cl, D, nvalid, qg, qc);
-  if (live) {
-    uint32_t* rs2 = P.rng + ((size_t)c2 * kRngSlots + slot) * 4;
-    rs2[0] = rng.x; rs2[1] = rng.c; rs2[2] = 0u; rs2[3] = 0u;
-    if (slot == 0) {
-      P.adapt[c2 * 4 + 0] = kap[0]; P.adapt[c2 * 4 + 1] = es[0]; P.adapt[c2 * 4 + 2] = la_[0];
-      P.adapt1[c2 * 4 + 0] = kap[1]; P.adapt1[c2 * 4 + 1] = es[1]; P.adapt1[c2 * 4 + 2] = la_[1];
-      P.accept_count[c2] = nacc0; P.accept_count1[c2] = nacc1;
+  const bool through = relay_through<STATS>(P);      // a relay segment that hands its state on write-through (kernels.h: relay_end)
+  if (through) {
+    const float spare0 = adapt_spare(P.adapt, c2), spare1 = adapt_spare(P.adapt1, c2);
+    pk_store_rows<kStoreThrough>(M, stage, P.q + cw2 * D, cl, D, nvalid, qg, qc);
+    if (live) {
+      store_rng_through(P.rng + ((size_t)c2 * kRngSlots + slot) * 4, rng);
+      if (slot == 0) {
+        store_adapt_through(P.adapt, c2, kap[0], es[0], la_[0], spare0);
+        store_adapt_through(P.adapt1, c2, kap[1], es[1], la_[1], spare1);
+        store_u32_through(P.accept_count + c2, nacc0); store_u32_through(P.accept_count1 + c2, nacc1);
+      }
+    }
+  } else {
+    pk_store_rows(M, stage, P.q + cw2 * D, cl, D, nvalid, qg, qc);
+    if (live) {
+      uint32_t* rs2 = P.rng + ((size_t)c2 * kRngSlots + slot) * 4;
+      rs2[0] = rng.x; rs2[1] = rng.c; rs2[2] = 0u; rs2[3] = 0u;
+      if (slot == 0) {
+        P.adapt[c2 * 4 + 0] = kap[0]; P.adapt[c2 * 4 + 1] = es[0]; P.adapt[c2 * 4 + 2] = la_[0];
+        P.adapt1[c2 * 4 + 0] = kap[1]; P.adapt1[c2 * 4 + 1] = es[1]; P.adapt1[c2 * 4 + 2] = la_[1];
+        P.accept_count[c2] = nacc0; P.accept_count1[c2] = nacc1;
+      }
     }
   }
-  relay_end(P, rid);
+  relay_end(P, rid, through);
 }
 
 }  // namespace arp

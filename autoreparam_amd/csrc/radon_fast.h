@@ -356,19 +356,35 @@ __global__ __launch_bounds__(kBlock, T::MINW) void radon_interleaved_kernel(Rado
   size_t c2 = (size_t)c;
   asm volatile("" : "+v"(c2));
   const long long cw2 = cw0;
-  pk_store_rows(M, stage, P.q + cw2 * D, cl, D, nvalid, qg, qc);
-  if (P.grad) pk_store_rows(M, stage, P.grad + cw2 * D, cl, D, nvalid, gg_, gc);
-  if (live) {
-    uint32_t* rs2 = P.rng + ((size_t)c2 * kRngSlots + slot) * 4;
-    rs2[0] = rng.x; rs2[1] = rng.c; rs2[2] = 0u; rs2[3] = 0u;
-    if (slot == 0) {
-      if (P.grad) P.logp[c2] = lp;
-      P.adapt[c2 * 4 + 0] = kap[0]; P.adapt[c2 * 4 + 1] = es[0]; P.adapt[c2 * 4 + 2] = la_[0];
-      P.adapt1[c2 * 4 + 0] = kap[1]; P.adapt1[c2 * 4 + 1] = es[1]; P.adapt1[c2 * 4 + 2] = la_[1];
-      P.accept_count[c2] = nacc0; P.accept_count1[c2] = nacc1;
+  const bool through = relay_through<STATS>(P);      // a relay segment that hands its state on write-through (kernels.h: relay_end)
+  if (through) {
+    const float spare0 = adapt_spare(P.adapt, c2), spare1 = adapt_spare(P.adapt1, c2);
+    pk_store_rows<kStoreThrough>(M, stage, P.q + cw2 * D, cl, D, nvalid, qg, qc);
+    if (P.grad) pk_store_rows<kStoreThrough>(M, stage, P.grad + cw2 * D, cl, D, nvalid, gg_, gc);
+    if (live) {
+      store_rng_through(P.rng + ((size_t)c2 * kRngSlots + slot) * 4, rng);
+      if (slot == 0) {
+        if (P.grad) store_f32_through(P.logp + c2, lp);
+        store_adapt_through(P.adapt, c2, kap[0], es[0], la_[0], spare0);
+        store_adapt_through(P.adapt1, c2, kap[1], es[1], la_[1], spare1);
+        store_u32_through(P.accept_count + c2, nacc0); store_u32_through(P.accept_count1 + c2, nacc1);
+      }
+    }
+  } else {
+    pk_store_rows(M, stage, P.q + cw2 * D, cl, D, nvalid, qg, qc);
+    if (P.grad) pk_store_rows(M, stage, P.grad + cw2 * D, cl, D, nvalid, gg_, gc);
+    if (live) {
+      uint32_t* rs2 = P.rng + ((size_t)c2 * kRngSlots + slot) * 4;
+      rs2[0] = rng.x; rs2[1] = rng.c; rs2[2] = 0u; rs2[3] = 0u;
+      if (slot == 0) {
+        if (P.grad) P.logp[c2] = lp;
+        P.adapt[c2 * 4 + 0] = kap[0]; P.adapt[c2 * 4 + 1] = es[0]; P.adapt[c2 * 4 + 2] = la_[0];
+        P.adapt1[c2 * 4 + 0] = kap[1]; P.adapt1[c2 * 4 + 1] = es[1]; P.adapt1[c2 * 4 + 2] = la_[1];
+        P.accept_count[c2] = nacc0; P.accept_count1[c2] = nacc1;
+      }
     }
   }
-  relay_end(P, rid);
+  relay_end(P, rid, through);
 }
 
 }  // namespace arp

@@ -7,7 +7,9 @@
 // writes the seg_* fields of the parameters a kernel gets, and returns what it decided as a RelayGeometry; relay_release
 // gives the allocation back behind the launch.  No HIP kernel and nothing of the model handle in here.
 // Experiments (ARP_DEBUG=1 only): ARP_SEGMENTS=n forces the count, ARP_SEGMENT_RATIO=percent the taper, ARP_SEGMENT_LENS=
-// n0,n1,... both, as explicit lengths; ARP_RELAY_TIMEOUT_MS and ARP_RELAY_FAULT=1 bring the failure path on demand.
+// n0,n1,... both, as explicit lengths (of a launch of any length; the others cut launches from 256 steps on); ARP_RELAY_PUBLISH=
+// fence|through and ARP_RELAY_ACQUIRE=wave|group choose the hand-over's form; ARP_RELAY_TIMEOUT_MS and ARP_RELAY_FAULT=1 bring
+// the failure path on demand.
 #pragma once
 #include <map>
 #include <mutex>
@@ -53,6 +55,10 @@ constexpr int kSegRatioPct = 70;
 struct RelayCut { int ratio_pct = kSegRatioPct; int n_lens = 0; int lens[kSegTable] = {}; };
 constexpr int kSegsDecide = 0;                                // RelayAsk::segs: the launcher decides with its kernel's occupancy
 constexpr unsigned long long kSegTimeout = 6000000000ull;     // a minute of the 100 MHz clock
+// The hand-over's form where nothing else is asked (kernels.h: relay_begin / relay_end have the forms): chosen by measurement,
+// a form is taken only where every run with it was shorter than every run without (profiles/r08_relay_handover.txt).  The
+// write-through publish is (headline launch - 1.1 %); one acquire per workgroup did not separate and stays behind its switch.
+constexpr int kRelayMode = kRelayThrough;
 // What an entry point hands a chain launcher beside the kernel's parameters.  As constructed it asks for no relay.
 struct RelayAsk {
   int cus = 0;                    // CUs of the handle's device (relay decisions are made for it, not for the current one)
@@ -62,6 +68,7 @@ struct RelayAsk {
   unsigned* flags = nullptr; int blocks = 0;
   unsigned* err_host = nullptr;   // the handle's pinned word a timed-out hand-over is reported through (relay_failed)
   unsigned long long timeout = kSegTimeout; int fault = 0;     // (test hook: segments never raise their flag)
+  int mode = kRelayMode;          // the hand-over's form (kernels.h: kRelayThrough | kRelayGroup)
 #ifdef ARP_EXP_RELAY_STAMPS
   unsigned long long* stamps = nullptr;
 #endif
@@ -69,7 +76,7 @@ struct RelayAsk {
 // no relay: the launch's steps in one segment (P.n_steps is set)
 inline void relay_off(HmcParams& P) {
   P.segs = 1; P.seg_len = P.n_steps; P.seg_blocks = 0; P.seg_epoch = 0; P.seg_flags = nullptr;
-  P.seg_ctrl = nullptr; P.seg_err_host = nullptr; P.seg_timeout = kSegTimeout; P.seg_fault = 0;
+  P.seg_ctrl = nullptr; P.seg_err_host = nullptr; P.seg_timeout = kSegTimeout; P.seg_fault = 0; P.seg_mode = 0;
   for (int& v : P.seg_start) v = 0;
 #ifdef ARP_EXP_RELAY_STAMPS
   P.seg_stamps = nullptr;
@@ -104,6 +111,7 @@ inline RelayGeometry relay_plan(HmcParams& P, const RelayAsk& ask, int blocks, F
   if (segs > 1) {
     P.segs = segs; P.seg_len = (P.n_steps + segs - 1) / segs; P.seg_blocks = blocks; P.seg_epoch = 0u; P.seg_flags = ask.flags;
     P.seg_ctrl = ask.flags + ask.blocks; P.seg_err_host = ask.err_host; P.seg_timeout = ask.timeout; P.seg_fault = ask.fault;
+    P.seg_mode = ask.mode;
 #ifdef ARP_EXP_RELAY_STAMPS
     P.seg_stamps = ask.stamps;
 #endif
@@ -145,17 +153,34 @@ inline int relay_explicit_cut(const char* list, int n_steps, RelayCut* cut) {
   cut->n_lens = n;
   return 0;
 }
+// ARP_RELAY_PUBLISH=fence|through, ARP_RELAY_ACQUIRE=wave|group: `name` set to `off` clears `bit` of *mode, to `on` sets it;
+// anything else is refused, never replaced
+inline int relay_mode_switch(const char* name, const char* off, const char* on, int bit, int* mode) {
+  const char* e = debug_switch(name);
+  if (!e) return 0;
+  if (std::string(e) == on) { *mode |= bit; return 0; }
+  if (std::string(e) == off) { *mode &= ~bit; return 0; }
+  set_error(std::string(name) + ": want '" + off + "' or '" + on + "', got '" + e + "'");
+  return 1;
+}
 // The ask of one launch of cfg's chains at K lanes per chain on a handle's device (`cus`, `err_host`: arp_model).  Where the
 // launch cannot be cut -- `allowed` false, a short launch, few blocks -- *ask stays what RelayAsk() is and nothing is allocated.
 inline int relay_prepare(int cus, unsigned* err_host, const arp_hmc_config* cfg, int K, bool allowed, hipStream_t stream,
                          RelayAsk* ask) {
   *ask = RelayAsk(); ask->cus = cus;
-  if (!allowed || cfg->n_steps < 256) return 0;
+  // the hand-over's form (A/B and tests): a value that is none is refused on every chain launch, cut or not
+  int mode = kRelayMode;
+  if (relay_mode_switch("ARP_RELAY_PUBLISH", "fence", "through", kRelayThrough, &mode) ||
+      relay_mode_switch("ARP_RELAY_ACQUIRE", "wave", "group", kRelayGroup, &mode)) return 1;
+  if (!allowed) return 0;
   int segs = kSegsDecide, dbg = 0;
-  if (debug_int("ARP_SEGMENTS", &dbg) && dbg >= 1 && dbg <= 64) segs = dbg;
   RelayCut cut;
+  // explicit lengths cut a launch of any length (the hand-over tests' short launches); everything else starts at 256 steps
+  const char* lens = debug_switch("ARP_SEGMENT_LENS");
+  if (!lens && cfg->n_steps < 256) return 0;
+  if (debug_int("ARP_SEGMENTS", &dbg) && dbg >= 1 && dbg <= 64) segs = dbg;
   if (debug_int("ARP_SEGMENT_RATIO", &dbg) && dbg >= 1 && dbg <= 100) cut.ratio_pct = dbg;
-  if (const char* lens = debug_switch("ARP_SEGMENT_LENS")) {
+  if (lens) {
     if (relay_explicit_cut(lens, cfg->n_steps, &cut)) return 1;
     segs = cut.n_lens;
   }
@@ -177,6 +202,7 @@ inline int relay_prepare(int cus, unsigned* err_host, const arp_hmc_config* cfg,
     (void)hipFreeAsync(flags, stream);
     ARP_HIP_OK(zeroed);
   }
+  ask->mode = mode;
   ask->segs = segs; ask->cut = cut; ask->flags = (unsigned*)flags; ask->blocks = (int)blocks; ask->err_host = err_host;
 #ifdef ARP_EXP_RELAY_STAMPS
   ask->stamps = (unsigned long long*)((char*)flags + stamps_at);
