@@ -12,7 +12,9 @@ import numpy as np
 import pytest
 import torch
 
+import psis_checks as pc
 import psis_ref as pr
+from psis_checks import device
 
 pytestmark = pytest.mark.gpu
 
@@ -21,7 +23,7 @@ RS = (1, 4, 5, 24, 25, 26, 224, 225, 226, 255, 256, 257, 1024, 4097, 70001)
 # |elpd_loo - ref| (all three at N = 257, R = 300; at R = 70 001, M = 794: 4.7e-15, 6.1e-15, 6.2e-15 -- float64
 # throughout, four orders of magnitude below what a float32 step would leave); the tests allow 16 x these
 K_MEASURED, SIGMA_MEASURED, ELPD_MEASURED = 7.55e-15, 8.6e-15, 1.78e-14
-FACTOR = 16.0
+FACTOR = pc.FACTOR             # 16
 
 
 def rows_for(R, seed):
@@ -42,47 +44,9 @@ def rows_for(R, seed):
     return [n for n, _ in rows], np.stack([v for _, v in rows]).astype(np.float32)
 
 
-def device(gpu, ll, mask=None, pad=0):
-    from autoreparam_amd import diagnostics
-    N, R = ll.shape
-    buf = torch.full((N, R + pad), float("nan"), dtype=torch.float32, device=gpu)      # (the padding is never read)
-    buf[:, :R] = torch.as_tensor(ll, device=gpu)
-    md = None if mask is None else torch.as_tensor(np.ascontiguousarray(mask, np.uint8), device=gpu)
-    view = buf[:, :R] if pad else buf
-    assert pad == 0 or (view.stride(0) == R + pad and not view.is_contiguous()) or N == 1
-    return diagnostics.psis_loo(view, md).cpu().numpy()
-
-
 def compare(got, ref, ll, mask, what):
-    """The columns against the definition; returns the largest deviations (k, sigma relative, elpd) for the record."""
-    keep = np.ones(ll.shape[1], bool) if mask is None else np.asarray(mask) == 0
-    worst = np.zeros(3)
-    for n in range(ll.shape[0]):
-        g, r, row = got[n], ref[n], ll[n][keep].astype(np.float64)
-        tag = (what, n)
-        assert g[4] == r[4] and g[7] == r[7], (tag, g, r)                              # tail_len, draws_used
-        assert g[5] == r[5] or (np.isnan(g[5]) and np.isnan(r[5])), (tag, g[5], r[5])   # cutoff
-        for c in (0, 1, 2, 3, 6):                                                      # the same kind of non-finite value
-            assert np.isfinite(g[c]) == np.isfinite(r[c]), (tag, c, g, r)
-            if not np.isfinite(r[c]):
-                assert (np.isnan(g[c]) and np.isnan(r[c])) or g[c] == r[c], (tag, c, g[c], r[c])
-        Rk = row.size
-        if np.isfinite(r[2]):
-            big = np.abs(row).max()
-            assert abs(g[2] - r[2]) <= (Rk + 32) * 2.0 ** -53 + 4 * 2.0 ** -53 * big, (tag, "lppd", g[2], r[2])
-        if np.isfinite(r[3]):
-            big = np.abs(row).max()
-            assert abs(g[3] - r[3]) <= (Rk + 8) * 2.0 ** -52 * r[3] + Rk * (2.0 ** -52 * big) ** 2, (tag, "p_waic", g[3], r[3])
-        if np.isfinite(r[1]):
-            dk, ds = abs(g[1] - r[1]), abs(g[6] - r[6]) / abs(r[6])
-            worst[0], worst[1] = max(worst[0], dk), max(worst[1], ds)
-            assert dk <= FACTOR * K_MEASURED, (tag, "pareto_k", g[1], r[1], dk)
-            assert ds <= FACTOR * SIGMA_MEASURED, (tag, "gpd_sigma", g[6], r[6], ds)
-        if np.isfinite(r[0]):
-            de = abs(g[0] - r[0])
-            worst[2] = max(worst[2], de)
-            assert de <= FACTOR * ELPD_MEASURED, (tag, "elpd_loo", g[0], r[0], de)
-    return worst
+    """psis_checks.compare at this file's measured constants; the largest deviations (k, sigma relative, elpd)."""
+    return pc.compare(got, ref, ll, mask, what, (K_MEASURED, SIGMA_MEASURED, ELPD_MEASURED))[:3]
 
 
 @pytest.mark.parametrize("R", RS)

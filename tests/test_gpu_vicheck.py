@@ -14,7 +14,9 @@ import numpy as np
 import pytest
 import torch
 
+import psis_checks as pc
 import vicheck_ref as vr
+from psis_checks import device_weights
 from vicheck_ref import Case, check_known_answer, R as R_KNOWN, SEED as SEED_KNOWN
 
 pytestmark = pytest.mark.gpu
@@ -24,7 +26,7 @@ U = 2.0 ** -24
 # MI355X (at R = 70 001, M = 794; 4.4e-15 at R = 4 097, below 1e-15 up to R = 257); the tests allow 16 x this, and the
 # figure itself must stay below 1e-10
 LW_MEASURED = 1.62e-14
-FACTOR = 16.0
+FACTOR = pc.FACTOR             # 16
 
 
 # ---- arp_vi_draws ----
@@ -90,48 +92,9 @@ def rows_for(R, seed):
     return [n for n, _ in rows], np.stack([v for _, v in rows]).astype(np.float32)
 
 
-def device_weights(gpu, ll, mask=None, pad=0):
-    from autoreparam_amd import diagnostics
-    N, R = ll.shape
-    buf = torch.full((N, R + pad), float("nan"), dtype=torch.float32, device=gpu)
-    buf[:, :R] = torch.as_tensor(ll, device=gpu)
-    md = None if mask is None else torch.as_tensor(np.ascontiguousarray(mask, np.uint8), device=gpu)
-    view = buf[:, :R] if pad else buf
-    out, lw = diagnostics.psis_weights(view, md)
-    loo = diagnostics.psis_loo(view, md)
-    assert np.array_equal(out.cpu().numpy().view(np.uint64), loo.cpu().numpy().view(np.uint64))       # bit for bit
-    return out.cpu().numpy(), lw.cpu().numpy()
-
-
 def compare_weights(lw, ll, mask, names, what):
-    """Every row against the definition; returns the largest deviation at a smoothed position."""
-    worst = 0.0
-    for n in range(ll.shape[0]):
-        tag = (what, names[n])
-        _, ref, tail = vr.weights_row(ll[n], mask)
-        keep = np.ones(ll.shape[1], bool) if mask is None else np.asarray(mask) == 0
-        got = lw[n]
-        assert np.all(np.isneginf(got[~keep])), tag
-        if np.isnan(ref[keep]).any():
-            assert np.isnan(got[keep]).all(), tag
-            continue
-        kept = ll[n][keep].astype(np.float64)
-        raw = np.full(ll.shape[1], -np.inf)
-        raw[keep] = kept.min() - kept
-        differs = np.flatnonzero(keep & (got != raw))
-        ref_differs = np.flatnonzero(keep & (ref != raw))
-        assert set(differs) <= set(tail) and set(ref_differs) <= set(tail), (tag, differs.size, ref_differs.size, tail.size)
-        # (a smoothed weight may coincide with the raw one -- the truncation at 0 of the largest -- on either side: such
-        # a position is held to the tolerance below like every other member of the tail)
-        clear = ref_differs[np.abs(ref[ref_differs] - raw[ref_differs]) > 1e-9]
-        assert set(clear) <= set(differs), tag
-        rest = np.setdiff1d(np.flatnonzero(keep), tail)
-        assert np.array_equal(got[rest], ref[rest]), tag                                  # raw positions: exact
-        if tail.size:
-            dev = np.abs(got[tail] - ref[tail]) / np.maximum(np.abs(ref[tail]), 1.0)
-            worst = max(worst, float(dev.max()))
-            assert dev.max() <= FACTOR * LW_MEASURED, (tag, dev.max())
-    return worst
+    """psis_checks.compare_weights at this file's measured constant; the largest deviation at a smoothed position."""
+    return pc.compare_weights(lw, ll, mask, names, what, LW_MEASURED)
 
 
 @pytest.mark.parametrize("R", (4, 25, 26, 257, 4097, 70001))
