@@ -337,6 +337,38 @@ def report_psens(results):
     return lines
 
 
+def report_prior(results):
+    """Build-specific: the prior predictive checks of every sampling run that recorded them (--prior_predictive_checks; the
+    last run of each file), two lines each: where the observed mean and sd sit among the prior-predicted ones with the
+    prior 90 % band of the replicated mean and sd next to the observed values; and the least contracted element with the
+    largest |z-score|.  Nothing is marked: no threshold can be derived for a prior predictive p-value -- a weak prior is
+    meant to be wider than the data."""
+    lines = []
+    for m, r in results.items():
+        if "prior_draws" not in r:
+            continue
+        last = _last(r, "prior_")
+        if last["prior_draws"] is None:
+            lines.append("{}: prior predictive checks not computed".format(m))
+            continue
+        stats = ("mean", "sd", "min", "max", "deviance")
+        lines.append("{}: prior predictive p-values {}; prior 90 % band of the replicated mean {} ... {} (median {}, observed "
+                     "{}), of the replicated sd {} ... {} (median {}, observed {}); replicated min above {}, max below {} in "
+                     "95 % of the draws; {} observations, {} prior draws, {} left out; {}".format(
+                         m, ", ".join("{} {}".format(s, _fmt(last["prior_p_" + s])) for s in stats),
+                         _fmt(last["prior_rep_mean_q05"]), _fmt(last["prior_rep_mean_q95"]), _fmt(last["prior_rep_mean_q50"]),
+                         _fmt(last["prior_obs_mean"]), _fmt(last["prior_rep_sd_q05"]), _fmt(last["prior_rep_sd_q95"]),
+                         _fmt(last["prior_rep_sd_q50"]), _fmt(last["prior_obs_sd"]), _fmt(last["prior_rep_min_q05"]),
+                         _fmt(last["prior_rep_max_q95"]), last["prior_observations"], last["prior_draws"],
+                         last["prior_draws_left_out"], _secs(last.get("prior_time_sec"))))
+        lines.append("{}: prior to posterior: least contraction {} ({}), largest |z-score| {} ({}); {} element(s) left out "
+                     "(quantile scale of the prior, moment scale of the posterior)".format(
+                         m, _fmt(last["prior_contraction_min"]), last["prior_contraction_min_element"],
+                         _fmt(last["prior_z_score_max_abs"]), last["prior_z_score_max_element"],
+                         last["prior_elements_left_out"]))
+    return lines
+
+
 def report_vi(results):
     """Build-specific: the fit check of every VI result file that holds one (--vi_diagnostics): the Pareto k-hat of the
     importance ratios p / q against its threshold, the ELBO of the final parameters next to the optimiser's own figure, the
@@ -377,7 +409,7 @@ def report_loo_compare(path_a, path_b):
 
 def main(argv=None):
     ap = argparse.ArgumentParser()
-    for f in ("elbos", "ess", "reparams", "normalize_times", "rhat", "energy", "trajectory", "geometry", "loo", "ppc", "vi", "psens"):
+    for f in ("elbos", "ess", "reparams", "normalize_times", "rhat", "energy", "trajectory", "geometry", "loo", "ppc", "vi", "psens", "prior"):
         ap.add_argument("--" + f, action="store_true")
     ap.add_argument("--loo_compare", default="", help="A_loo.npz,B_loo.npz: the paired elpd_loo difference of two models")
     ap.add_argument("--model", default="all")
@@ -404,7 +436,7 @@ def main(argv=None):
                             ("trajectory", lambda: report_trajectory(results, root, name)),
                             ("geometry", lambda: report_geometry(results, root, name)), ("loo", lambda: report_loo(results)),
                             ("ppc", lambda: report_ppc(results)), ("vi", lambda: report_vi(results)),
-                            ("psens", lambda: report_psens(results))):
+                            ("psens", lambda: report_psens(results)), ("prior", lambda: report_prior(results))):
             if getattr(args, flag):
                 print("\n".join(lines()) + "\n")
 

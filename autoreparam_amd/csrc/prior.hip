@@ -56,26 +56,14 @@
 // table's indices: obs_table.h; group_of is clamped into [0, G) as the indices are into [0, D), and a form other than 1
 // or 2 is read as 0.
 #include "obs_table.h"
+#include "site_table.h"
 
 #pragma clang fp contract(off)
 
 namespace arp {
 namespace {
 
-constexpr int kSiteTerms = 2;                    // ARP_SITE_TERMS
 constexpr int kSiteSlots = 2 * kObsWaves;        // the first and the last run of every wave's quarter
-
-// c + sum_t w[d][t] row[idx[d][t]], in term order
-__device__ __forceinline__ float site_chain(const float* row, const int* idx, const float* w, float c, int d, int D) {
-  const int* ip = idx + d * kSiteTerms;
-  const float* wp = w + d * kSiteTerms;
-#pragma unroll
-  for (int k = 0; k < kSiteTerms; ++k) {
-    const int i = min(max(ip[k], 0), D - 1);
-    c = c + wp[k] * row[i];
-  }
-  return c;
-}
 
 __global__ __launch_bounds__(kObsThreads) void site_kernel(const float* __restrict__ x, long long R, unsigned n_chains, int D,
                                                            long long stride, const int* __restrict__ form,

@@ -25,7 +25,9 @@ power-scaling sensitivity (`powerscale_lw`, `element_order` on `arp_element_orde
 `loglik_total`; `psens_summary`: how far every marginal moves when the prior or the likelihood is raised to a power
 slightly off 1, as a cumulative Jensen-Shannon distance; Kallioinen et al. 2023), with the log prior density of every
 latent site, summed over chosen groups of elements, for power-scaling chosen priors alone (`upload_site_table`,
-`site_logprior` on `arp_site_logprior`).
+`site_logprior` on `arp_site_logprior`); and the prior itself (`site_prior_draws` on `arp_site_prior_draws`: ancestral draws
+from the site table; `prior_predictive_summary`, `prior_contraction_summary`: what data the prior generates, and how far
+the data moved every marginal away from it).
 
 Build-specific (the reference runs 100 chains and reports the within-chain ESS only).  The per-chain moments come from
 one pass over a trace that is already on the device (`arp_split_moments`) or from the in-kernel statistics of a
@@ -37,6 +39,7 @@ means:  rhat = sqrt(((n-1)/n W + B/n) / W),  pooled sd = sqrt((n-1)/n W + B/n), 
 """
 import collections
 import ctypes as C
+import math
 
 import numpy as np
 import torch
@@ -752,6 +755,15 @@ def _ppc_observed(y):
     return float(y.mean()), sd, float(y.min()), float(y.max())
 
 
+def _ppc_replicated(c, N):
+    """(mean, sd, min, max) of the replicated data set of every row of c, the [R', 8] draw statistics over all N
+    observations: mean = c0 / N, sd^2 = (c1 - c0^2 / N) / (N - 1) (NaN for N < 2), min = c2, max = c3.  One definition for
+    the p-values (ppc_counts) and the prior predictive quantiles (prior_predictive_summary)."""
+    with np.errstate(divide="ignore", invalid="ignore"):
+        rep_sd = np.sqrt(np.maximum(c[:, 1] - c[:, 0] * c[:, 0] / N, 0.0) / (N - 1)) if N > 1 else np.full(c.shape[0], np.nan)
+        return c[:, 0] / N, rep_sd, c[:, 2], c[:, 3]
+
+
 def ppc_counts(draw_stats, y, mask=None):
     """The [PPC_COUNTS] float64 vector behind the p-values, from the [R, 8] draw statistics of ALL N observations and the
     observed y [N]: additive over draws, so a job whose draws are spread over ranks adds its ranks' vectors.  mask: [R],
@@ -774,8 +786,8 @@ def ppc_counts(draw_stats, y, mask=None):
     out[0], out[1] = c.shape[0], used.size - c.shape[0]
     obs_mean, obs_sd, obs_min, obs_max = _ppc_observed(y)
     with np.errstate(divide="ignore", invalid="ignore"):
-        rep_sd = np.sqrt(np.maximum(c[:, 1] - c[:, 0] * c[:, 0] / N, 0.0) / (N - 1)) if N > 1 else np.full(c.shape[0], np.nan)
-        pairs = ((c[:, 0] / N, obs_mean), (rep_sd, obs_sd), (c[:, 2], obs_min), (c[:, 3], obs_max), (c[:, 4], c[:, 5]))
+        rep_mean, rep_sd, rep_min, rep_max = _ppc_replicated(c, N)
+        pairs = ((rep_mean, obs_mean), (rep_sd, obs_sd), (rep_min, obs_min), (rep_max, obs_max), (c[:, 4], c[:, 5]))
         for j, (rep, obs) in enumerate(pairs):
             out[2 + j] = np.sum(rep >= obs)
             out[2 + len(pairs) + j] = np.sum(rep)
@@ -1232,6 +1244,117 @@ def site_logprior(trace, table, group_of=None, want_elements=False):
               _lib.ptr(table.log_scale0), _lib.ptr(table.norm), _lib.ptr(groups), G, _lib.ptr(group_lp), _lib.ptr(elem_lp),
               _lib.ptr(mask), _lib.ptr(n_masked))
     return group_lp, elem_lp, mask, n_masked
+
+
+SITE_MAX_DRAWS = 1 << 24          # the most draws arp_site_prior_draws takes
+
+
+def site_prior_draws(table, draws, seed=0, draw_offset=0, device=None, out=None):
+    """(x, undrawn) of `arp_site_prior_draws`: `draws` ancestral draws from the prior a DeviceSiteTable describes, x
+    [draws, D] float32 -- as x[None] a centred trace of one step and `draws` chains, which predictive_check, site_logprior
+    and element_order take in place -- and undrawn [draws] uint8, non-zero for a draw one of whose log-Gamma elements ran
+    out of attempts (its element is NaN; 32 rejections in a row: not expected to be seen).  Draw r is a function of (seed,
+    draw_offset + r) alone.  device: the table's when None; a table on another device is refused.  out: an optional
+    float32 [draws, >= D] device matrix with unit column stride, written in place in its first D columns (the others are
+    not touched).  Refused here, before any call: what the kernel refuses."""
+    who = "site_prior_draws"
+    if not isinstance(table, DeviceSiteTable):
+        raise ValueError("%s: a DeviceSiteTable is required (upload_site_table)" % who)
+    D, R = int(table.D), int(draws)
+    if not 1 <= D <= LOGLIK_MAX_D:
+        raise ValueError("%s: 1 <= D <= %d elements are required" % (who, LOGLIK_MAX_D))
+    if not 1 <= R <= SITE_MAX_DRAWS:
+        raise ValueError("%s: 1 <= draws <= 2^24 is required" % who)
+    if int(draw_offset) < 0:
+        raise ValueError("%s: draw_offset >= 0 is required" % who)
+    dev = table.form.device
+    if dev.type != "cuda":
+        raise ValueError("%s: the table must be on the GPU (there is no CPU fallback)" % who)
+    if device is not None and torch.device(device) != dev and torch.device(device) != torch.device(dev.type):
+        raise ValueError("%s: the table is on %s, not on %s" % (who, dev, device))
+    if out is None:
+        x, stride = torch.empty(R, D, dtype=torch.float32, device=dev), D
+    else:
+        x, stride = _rows_out(out, R, D, who, "out")
+        if x.device != dev:
+            raise ValueError("%s: out must be on the table's device" % who)
+    undrawn = torch.empty(R, dtype=torch.uint8, device=dev)
+    _lib.call(dev, _lib.lib().arp_site_prior_draws, D, _lib.ptr(table.form), _lib.ptr(table.loc_idx), _lib.ptr(table.loc_w),
+              _lib.ptr(table.loc0), _lib.ptr(table.scale_idx), _lib.ptr(table.scale_w), _lib.ptr(table.log_scale0), R,
+              int(seed) & 0xFFFFFFFFFFFFFFFF, int(draw_offset), _lib.ptr(x), stride, _lib.ptr(undrawn))
+    return x, undrawn
+
+
+# ---- prior predictive checks: what the prior says before it has seen data, and how far the data moved it ----
+PRIOR_QUANTILES = (0.05, 0.5, 0.95)
+PRIOR_Z90 = 1.6448536269514722    # the standard normal's 95 % point: (q95 - q05) / (2 z) is the sd of a normal
+# prior_predictive_summary.  draws_used, draws_left_out: ints.  quantiles: a dict over PPC_STATISTICS[:4] of the (5 %, 50 %,
+# 95 %) order statistics of the replicated statistic over the draws used, or None where it is not defined (no draw used; sd,
+# min and max of Bernoulli data).
+PriorPredictiveSummary = collections.namedtuple("PriorPredictiveSummary", ["draws_used", "draws_left_out", "quantiles"])
+# prior_contraction_summary.  prior_sd_robust, contraction, z_score: [D] float64, NaN for an element left out;
+# left_out: how many there are.
+PriorContractionSummary = collections.namedtuple("PriorContractionSummary", ["prior_sd_robust", "contraction", "z_score",
+                                                                           "left_out"])
+
+
+def order_statistic_index(p, n):
+    """The 0-based index of the order statistic x_(ceil(p n)) among n sorted values (the inverse of the empirical
+    distribution function), clamped into [0, n)."""
+    return int(min(max(math.ceil(float(p) * int(n)) - 1, 0), int(n) - 1))
+
+
+def prior_predictive_summary(draw_stats, y, kind, mask=None):
+    """What data the prior alone generates, on the scale of y -> PriorPredictiveSummary; pure numpy float64.  draw_stats
+    [R, 8] over ALL N observations (PPC_DRAW_COLUMNS) of replicated data sets drawn at PRIOR draws, y [N], kind 0 (Normal)
+    or 1 (Bernoulli-logit), mask [R] (non-zero: the draw is left out).  Per statistic of mean, sd, min, max of a replicated
+    data set (ppc_counts' definitions, one helper) the order statistics x_(ceil(p R')) at p = 5 %, 50 %, 95 % over the R'
+    draws used; a NaN (a replicated data set with an infinite value has no sd) sorts last, as +inf would.  sd, min and max
+    are None for Bernoulli data and sd for a single observation, as in ppc_from_counts.  The p-values next to these are
+    ppc_summary's, on the same draw_stats: nothing is defined twice."""
+    c = _lib.host64(draw_stats).reshape(-1, len(PPC_DRAW_COLUMNS))
+    y = np.asarray(_lib.host64(y), np.float64).reshape(-1)
+    N = y.size
+    if N < 1:
+        raise ValueError("prior_predictive_summary: at least one observation is required")
+    used = np.ones(c.shape[0], bool) if mask is None else (_lib.host64(mask).reshape(-1) == 0)
+    if used.size != c.shape[0]:
+        raise ValueError("prior_predictive_summary: mask must have one entry per draw")
+    c = c[used]
+    n = int(c.shape[0])
+    normal = int(kind) == 0
+    defined = {"mean": True, "sd": normal and N > 1, "min": normal, "max": normal}
+    at = [order_statistic_index(p, n) for p in PRIOR_QUANTILES] if n else []
+    quantiles = {}
+    for name, rep in zip(PPC_STATISTICS[:4], _ppc_replicated(c, N)):
+        s = np.sort(rep)
+        quantiles[name] = tuple(float(s[i]) for i in at) if defined[name] and n else None
+    return PriorPredictiveSummary(n, int(used.size) - n, quantiles)
+
+
+def prior_contraction_summary(q05, q50, q95, post_mean, post_sd):
+    """How far every marginal has contracted from prior to posterior (Betancourt's posterior contraction and z-score;
+    Schad, Betancourt, Vasishth 2021) -> PriorContractionSummary; pure numpy float64, [D] each: the prior's 5 %, 50 % and
+    95 % points and the posterior's mean and sd.
+      prior_sd_robust = (q95 - q05) / (2 * 1.6448536269514722),  the sd of the normal with that 90 % interval
+      contraction     = 1 - (post_sd / prior_sd_robust)^2        near 1: the data decided; near 0: the prior did; below 0:
+                                                                 the posterior is WIDER than the prior's central part
+      z_score         = (post_mean - q50) / prior_sd_robust      where the posterior sits in the prior, in prior sds
+    The prior's scale is quantile-based ON PURPOSE: under log_sigma ~ N(0, 10) the marginal prior variance of a group effect
+    is of the order e^200 and its sample variance means nothing, while the central 90 % interval is well defined and
+    well estimated.  The posterior's scale is a moment (the sd split R-hat already pooled): the two are the same thing for a
+    normal marginal only, so a heavy-tailed prior marginal reads as more contracted than a moment scale would say.  An
+    element whose prior interval is empty (a constant element) or not finite is NaN in all three and counted."""
+    q05, q50, q95, m, sd = (np.asarray(_lib.host64(v), np.float64).reshape(-1) for v in (q05, q50, q95, post_mean, post_sd))
+    if not all(v.size == q05.size for v in (q50, q95, m, sd)):
+        raise ValueError("prior_contraction_summary: five vectors of one length are required")
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        scale = (q95 - q05) / (2.0 * PRIOR_Z90)
+        ok = np.isfinite(scale) & (scale > 0) & np.isfinite(q50)
+        scale = np.where(ok, scale, np.nan)
+        contraction = 1.0 - (sd / scale) ** 2
+        z = (m - q50) / scale
+    return PriorContractionSummary(scale, contraction, z, int(np.sum(~ok)))
 
 
 def powerscale_lw(log_prior, log_likelihood, left_out=None):

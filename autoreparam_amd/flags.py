@@ -149,6 +149,23 @@ _DEFS = [
                                          "selection is by part, not by element; delta is fixed and there is no power-scaling "
                                          "sequence here either.  Refused: a name that is no part of the model, a duplicate, "
                                          "an empty name, the flag without --sensitivity_diagnostics."),
+    ("prior_predictive_checks", bool, False, "Sampling runs, with --convergence_diagnostics: prior predictive checks, the "
+                                             "first step of the Bayesian workflow (Gabry et al. 2019) -- what data does the "
+                                             "model generate before it has seen any, and how far did the data move every "
+                                             "marginal?  --loo_draws ancestral draws from the latent site table "
+                                             "(arp_site_prior_draws over ModelSpec.site_table; no device trace is needed), one "
+                                             "replicated data set each (arp_predictive_check): where the observed mean, sd, "
+                                             "min, max and deviance sit among the prior-predicted ones and the prior 90 % band "
+                                             "of the replicated mean and sd; and per element the posterior contraction "
+                                             "1 - (posterior sd / prior sd)^2 and the z-score (posterior mean - prior median) "
+                                             "/ prior sd, the prior's sd taken from its 5 % and 95 % points (a log-scale prior "
+                                             "N(0, 10) has no usable sample variance), the posterior's the pooled moment "
+                                             "(prior_* JSON keys, <base>_prior.npz; analyze --prior).  No warning: no "
+                                             "threshold can be derived for a prior predictive p-value, a weak prior is meant "
+                                             "to be wider than the data.  No prior draws at new covariates, no "
+                                             "simulation-based calibration, no user-defined statistic.  Rank 0 of a sharded "
+                                             "job runs it alone.  Every other output is bit for bit unchanged.  Refused for "
+                                             "neals_funnel, which has no observations."),
     ("vi_diagnostics", bool, False, "--inference=VI: judge the mean-field FIT the sampler takes its step sizes, its initial "
                                     "population and (cVIP, dVIP) its parameterisation from.  After the fit's clock has "
                                     "stopped, --vi_check_draws draws from the fitted q in the coordinates of the "

@@ -378,6 +378,10 @@ def _convergence_report(kernel_results, model_config, flags, dev):
         if getattr(flags, "convergence_diagnostics", True) and getattr(flags, "sensitivity_diagnostics", False):
             keys = OrderedDict(keys)
             keys.update(_psens_null("no chain has its trace on the device", flags))
+        if getattr(flags, "convergence_diagnostics", True) and getattr(flags, "prior_predictive_checks", False):
+            keys = OrderedDict(keys)
+            keys.update(_prior_null("no chain has its trace on the device, so there is no pooled posterior to set the "
+                                    "prior against"))
         return keys, None
     clock = time.time()
     spec = model_config.model
@@ -439,7 +443,10 @@ def _convergence_report(kernel_results, model_config, flags, dev):
             (getattr(flags, "predictive_checks", False), PPC_ARRAYS,               # (n_split: already all-reduced)
              lambda: _ppc_report(kernel_results, trace, k, n_split, spec, flags, dev)),
             (getattr(flags, "sensitivity_diagnostics", False), PSENS_ARRAYS,
-             lambda: _psens_report(trace, k, spec, flags, split.mean, arrays))):
+             lambda: _psens_report(trace, k, spec, flags, split.mean, arrays)),
+            (getattr(flags, "prior_predictive_checks", False), PRIOR_ARRAYS,         # (mean and sd: already all-reduced)
+             lambda: _prior_report(spec, flags, trace.device, *((whole.mean, whole.sd) if streaming else
+                                                                 (split.mean, split.sd))))):
         if asked:
             side_keys, side_arrays = report()
             keys.update(side_keys)
@@ -1346,6 +1353,142 @@ def save_psens_sites(file_path_base, arrays):
     np.savez(file_path_base + "_psens_sites.npz", **arrays)
 
 
+PRIOR_ARRAYS = "prior/"              # where _convergence_report leaves the arrays of <base>_prior.npz
+PRIOR_SEED = 0x5052494F              # the report's own seed constant, as PPC_SEED is the posterior checks'
+PRIOR_KEYS = ("prior_draws", "prior_draws_left_out", "prior_observations", "prior_p_mean", "prior_p_sd", "prior_p_min",
+              "prior_p_max", "prior_p_deviance", "prior_rep_mean_q05", "prior_rep_mean_q50", "prior_rep_mean_q95",
+              "prior_rep_sd_q05", "prior_rep_sd_q50", "prior_rep_sd_q95", "prior_rep_min_q05", "prior_rep_max_q95",
+              "prior_obs_mean", "prior_obs_sd", "prior_contraction_min", "prior_contraction_min_element",
+              "prior_z_score_max_abs", "prior_z_score_max_element", "prior_elements_left_out", "prior_time_sec")
+
+
+def check_prior_predictive(flags):
+    """--prior_predictive_checks against the job, before anything runs: check_predictive_checks' rule -- raises ValueError
+    for a model without observations (neals_funnel), whose prior predicts no data."""
+    if getattr(flags, "prior_predictive_checks", False) and flags.model == "neals_funnel":
+        raise ValueError("--prior_predictive_checks: neals_funnel has no observations, so there is no data for its prior to "
+                         "predict")
+
+
+def _prior_null(why):
+    """Every key of the prior predictive checks as null, with the one message that says why."""
+    util.print_("    prior predictive checks: not computed, {}".format(why))
+    return OrderedDict((key, None) for key in PRIOR_KEYS)
+
+
+def prior_keys(summary, predictive, contraction, names):
+    """The JSON keys of the prior predictive checks (all but prior_time_sec) from a diagnostics.PpcSummary of replicated
+    data at PRIOR draws, the PriorPredictiveSummary of the same draw statistics and a PriorContractionSummary; `names`:
+    element_names.  Pure Python."""
+    num = lambda v: None if v is None else _finite_or_none(v)
+    keys = OrderedDict([("prior_draws", int(summary.draws_used)), ("prior_draws_left_out", int(summary.draws_left_out)),
+                        ("prior_observations", int(summary.observations))])
+    for name in diagnostics.PPC_STATISTICS:
+        keys["prior_p_" + name] = num(summary.p[name])
+    q = {name: v if v is not None else (None, None, None) for name, v in predictive.quantiles.items()}
+    keys.update([("prior_rep_mean_q05", num(q["mean"][0])), ("prior_rep_mean_q50", num(q["mean"][1])),
+                 ("prior_rep_mean_q95", num(q["mean"][2])), ("prior_rep_sd_q05", num(q["sd"][0])),
+                 ("prior_rep_sd_q50", num(q["sd"][1])), ("prior_rep_sd_q95", num(q["sd"][2])),
+                 ("prior_rep_min_q05", num(q["min"][0])), ("prior_rep_max_q95", num(q["max"][2])),
+                 ("prior_obs_mean", num(summary.obs["mean"])), ("prior_obs_sd", num(summary.obs["sd"]))])
+    least, at = _nan_max(-np.asarray(contraction.contraction, np.float64))
+    far, at_z = _nan_max(np.abs(np.asarray(contraction.z_score, np.float64)))
+    keys.update([("prior_contraction_min", _finite_or_none(-least)), ("prior_contraction_min_element", names[at] if at >= 0 else None),
+                 ("prior_z_score_max_abs", _finite_or_none(far)), ("prior_z_score_max_element", names[at_z] if at_z >= 0 else None),
+                 ("prior_elements_left_out", int(contraction.left_out))])
+    return keys
+
+
+def _prior_report(spec, flags, dev, post_mean, post_sd):
+    """--prior_predictive_checks: what does the model say BEFORE it has seen data, and how far did the data move it?  The
+    first step of the Bayesian workflow (Gabry, Simpson, Vehtari, Betancourt, Gelman 2019; Gelman et al. 2020).
+    R = --loo_draws ancestral draws from the model's latent site table (diagnostics.site_prior_draws), keyed by a seed
+    derived from --seed and PRIOR_SEED; they need no device trace.  A draw one of whose elements is not finite (which
+    predictive_check masks) or could not be drawn is left out and counted.
+      * The predictive side: one replicated data set per draw at the observed covariates (diagnostics.predictive_check on
+        the draws as a [1, R, D] trace, under the next seed -- the draws' own would hand element d and observation d the
+        same Philox words), in _ppc_report's tiles of observations; diagnostics.ppc_summary says where the observed mean,
+        sd, min, max and deviance sit among the prior-predicted ones, diagnostics.prior_predictive_summary gives the 5 %,
+        50 % and 95 % points of the replicated statistics.
+      * The contraction side: every element's kept draws are ordered (diagnostics.element_order), its 5 %, 50 % and 95 %
+        points gathered on the device and set against `post_mean` and `post_sd`, the pooled posterior moments split R-hat
+        has already all-reduced (diagnostics.prior_contraction_summary: contraction and z-score on a QUANTILE scale of the
+        prior against a MOMENT scale of the posterior).
+    No warning and no threshold: none can be derived for a prior predictive p-value -- a weakly informative prior is MEANT
+    to be wider than the data, so p-values near 0 or 1 for min and max are the expected reading, not a finding.  No prior
+    draws at new covariates, no simulation-based calibration, no user-defined statistic.  Rank 0 of a sharded job runs it
+    alone and enters no collective (the other ranks return nothing).  Returns (JSON keys, arrays of <base>_prior.npz or None)."""
+    import torch
+    if parallel.world()[0] != 0:
+        return {}, None
+    clock = time.time()
+    D = int(spec.D)
+    if D > diagnostics.LOGLIK_MAX_D:
+        return _prior_null("the model has more than {} elements".format(diagnostics.LOGLIK_MAX_D)), None
+    R = int(min(max(int(getattr(flags, "loo_draws", 65536)), 1), diagnostics.SITE_MAX_DRAWS))
+    seed = (int(flags.seed) * 0x9E3779B97F4A7C15 + PRIOR_SEED) & 0xFFFFFFFFFFFFFFFF
+    site = diagnostics.upload_site_table(spec.site_table(), D, dev)
+    x, undrawn = diagnostics.site_prior_draws(site, R, seed=seed)
+    host_table = spec.observation_table()
+    N, kind = int(np.asarray(host_table.y).size), int(host_table.kind)
+    y = np.asarray(host_table.y, np.float32).reshape(-1)
+    table = diagnostics.upload_table(host_table, D, dev)
+    draws = x[None]                                                                      # [1, R, D]: one step, R chains
+    rows = ppc_tile_rows(N, R, diagnostics.predictive_workspace_bytes)
+    stats, sums, mask = None, [], None
+    for n0 in range(0, N, rows):
+        part, obs, _, mask, _ = diagnostics.predictive_check(draws, table, n0, min(N, n0 + rows),
+                                                             seed=(seed + 1) & 0xFFFFFFFFFFFFFFFF)
+        stats = part if stats is None else diagnostics.combine_draw_stats(stats, part)
+        sums.append(obs)
+    left = (mask != 0) | (undrawn != 0)                                                  # (an undrawn element is NaN: masked too)
+    stats_host, obs_sums, left_host = _lib.host64(stats), _lib.host64(torch.cat(sums, dim=0)), left.cpu().numpy()
+    summary = diagnostics.ppc_summary(stats_host, obs_sums, y, kind, left_host)
+    predictive = diagnostics.prior_predictive_summary(stats_host, y, kind, left_host)
+    kept = int(summary.draws_used)
+    quantiles = np.full((D, len(diagnostics.PRIOR_QUANTILES)), np.nan)
+    if kept > 0:
+        _, values = diagnostics.element_order(x[~left][None].contiguous(), want_sorted=True)
+        at = [diagnostics.order_statistic_index(p, kept) for p in diagnostics.PRIOR_QUANTILES]
+        quantiles = _lib.host64(values[:, at])
+        del values
+    nan = np.full(D, np.nan)
+    contraction = diagnostics.prior_contraction_summary(
+        quantiles[:, 0], quantiles[:, 1], quantiles[:, 2], nan if post_mean is None else np.asarray(post_mean, np.float64).reshape(D),
+        nan if post_sd is None else np.asarray(post_sd, np.float64).reshape(D))
+    names = element_names(spec)
+    keys = prior_keys(summary, predictive, contraction, names)
+    util.print_("    prior predictive checks over {} observations, {} prior draws ({} left out): the observed mean sits at "
+                "p = {} and the observed sd at p = {} among the prior-predicted ones (min {}, max {}, deviance {}); prior "
+                "90 % band of the replicated mean {} ... {} against {} observed, of the replicated sd {} ... {} against {} "
+                "observed (no threshold: a weak prior is meant to be wider than the data)".format(
+                    N, keys["prior_draws"], keys["prior_draws_left_out"], _fmt(keys["prior_p_mean"]), _fmt(keys["prior_p_sd"]),
+                    _fmt(keys["prior_p_min"]), _fmt(keys["prior_p_max"]), _fmt(keys["prior_p_deviance"]),
+                    _fmt(keys["prior_rep_mean_q05"]), _fmt(keys["prior_rep_mean_q95"]), _fmt(keys["prior_obs_mean"]),
+                    _fmt(keys["prior_rep_sd_q05"]), _fmt(keys["prior_rep_sd_q95"]), _fmt(keys["prior_obs_sd"])))
+    util.print_("    prior to posterior over {} elements ({} left out): least contraction {} ({}), largest |z-score| {} ({}) "
+                "-- quantile scale of the prior, moment scale of the posterior".format(
+                    D, keys["prior_elements_left_out"], _fmt(keys["prior_contraction_min"]), keys["prior_contraction_min_element"],
+                    _fmt(keys["prior_z_score_max_abs"]), keys["prior_z_score_max_element"]))
+    arrays = OrderedDict([("elements", np.asarray(names)), ("y", y), ("model", np.asarray(spec.name)),
+                          ("draw_stats", stats_host), ("left_out", left_host),
+                          ("predictive_mean", summary.predictive_mean), ("predictive_sd", summary.predictive_sd)])
+    _by_part(spec, arrays, (("prior_q05", quantiles[:, 0]), ("prior_median", quantiles[:, 1]), ("prior_q95", quantiles[:, 2]),
+                            ("contraction", contraction.contraction), ("z_score", contraction.z_score)))
+    keys["prior_time_sec"] = time.time() - clock
+    return keys, arrays
+
+
+def save_prior(file_path_base, arrays):
+    """`<base>_prior.npz` (build-specific, --prior_predictive_checks): `elements`, the elements' names in trace order; `y`
+    [N], the observations; `model`; `draw_stats` [R, 8] float64, the per-draw sums of diagnostics.PPC_DRAW_COLUMNS of the data
+    sets replicated at the PRIOR draws (zeros for a draw left out) and `left_out` [R]; `predictive_mean`, `predictive_sd`
+    [N], the prior predictive mean and sd of every observation; per latent part `prior_q05/<part>`, `prior_median/<part>`,
+    `prior_q95/<part>` (order statistics of the kept draws), `contraction/<part>` and `z_score/<part>` (NaN for an element
+    left out)."""
+    np.savez(file_path_base + "_prior.npz", **arrays)
+
+
 def _fit_chains(trace, k, workspace_bytes):
     """The largest of k, k/2, k/4, ... leading chains whose z-score trace and the `workspace_bytes(S, k, D)` next to it
     fit the free device memory."""
@@ -1533,15 +1676,15 @@ def save_geometry(file_path_base, arrays):
 
 def _save_diagnostics(file_path_base, arrays):
     """The side files of the convergence report: <base>_rhat.npz and, where the probes ran, <base>_energy.npz,
-    <base>_trajectory.npz, <base>_geometry.npz, <base>_loo.npz, <base>_loopred.npz, <base>_ppc.npz, <base>_psens.npz and
-    <base>_psens_sites.npz."""
+    <base>_trajectory.npz, <base>_geometry.npz, <base>_loo.npz, <base>_loopred.npz, <base>_ppc.npz, <base>_psens.npz,
+    <base>_psens_sites.npz and <base>_prior.npz."""
     if arrays is None:
         return
     # (tag _convergence_report left a side file's arrays under, its saver), in the order the files are written after _rhat.npz
     side = [(arrays.pop(tag, None), save) for tag, save in (
         (GEOMETRY_ARRAYS, save_geometry), (ENERGY_ARRAYS, save_energy), (TRAJECTORY_ARRAYS, save_trajectory),
         (LOO_ARRAYS, save_loo), (LOO_PRED_ARRAYS, save_loo_pred), (PPC_ARRAYS, save_ppc), (PSENS_ARRAYS, save_psens),
-        (PSENS_SITES_ARRAYS, save_psens_sites))]
+        (PSENS_SITES_ARRAYS, save_psens_sites), (PRIOR_ARRAYS, save_prior))]
     save_rhat(file_path_base, arrays)
     for side_arrays, save in side:
         if side_arrays is not None:
@@ -1834,6 +1977,7 @@ def main(argv=None, flags=FLAGS, out=None):
     check_predictive_checks(flags)
     check_sensitivity(flags)
     check_sensitivity_sites(flags)
+    check_prior_predictive(flags)
     check_vi_diagnostics(flags)
     ws = int(os.environ.get("WORLD_SIZE", "1"))
     if ws > 1:

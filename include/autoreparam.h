@@ -668,6 +668,48 @@ int arp_site_logprior(const float* x, int64_t n_samples, int64_t n_chains, int32
                       const int32_t* group_of, int32_t G, double* group_lp, float* elem_lp /* may be NULL */,
                       uint8_t* mask, int64_t* n_masked, void* stream);
 
+/* Ancestral draws from the prior (csrc/prior_draw.hip; needs no model handle): arp_site_logprior's table columns walked
+ * front to back, n_draws times -- what a prior predictive check (Gabry et al. 2019) starts from.  x is [n_draws][row_stride]
+ * float, columns d >= D are not touched; a contiguous result reads as a centred trace of one step and n_draws chains, so
+ * arp_predictive_check, arp_site_logprior and arp_element_order take it in place.  Elements are drawn in ascending d;
+ * loc_d and s_d are arp_site_logprior's float32 chains (term order, contraction off, indices clamped into [0, D)) over the
+ * elements of the same draw drawn before d -- an element not drawn yet reads as 0, and the table is in ancestral order
+ * (ModelSpec.site_table), so a term of non-zero weight never points at one.  g = draw_offset + r is the global draw number.
+ *   forms ARP_SITE_NORMAL, ARP_SITE_NORMAL_SOFTPLUS:  ONE call philox4x32_10(counter = (d, lo32(g), hi32(g), 0), key =
+ *     (lo32(seed), hi32(seed)));  z = sqrt(-2 log(u')) * cospi(2 a) from words 0 and 1, u' and a formed exactly as
+ *     arp_predictive_check forms them, through logf, sqrtf, cospif;  x_d = loc_d + sigma_d * z, rounded twice, sigma_d =
+ *     expf(s_d), or max(s_d, 0) + log1p(exp(-|s_d|)) for the softplus form
+ *   form ARP_SITE_LOG_GAMMA:  x_d = log g, g ~ Gamma(shape k = loc0[d], rate exp(s_d)); the loc terms are not read.
+ *     Marsaglia and Tsang (2000) in log space:  boost = k < 1;  a = boost ? k + 1 : k;  dd = a - 1/3;  c = 1 / sqrt(9 dd);
+ *     attempt j = 0 ... 31 uses philox4x32_10(counter = (d, lo32(g), hi32(g), 1 + j), same key):  z from words (0, 1) as
+ *     above;  t = 1 + c z, rejected if t <= 0;  U = fma((float)w2, 2^-32, 2^-33);  accepted iff
+ *       log U < ((0.5 z^2 + dd) - dd ((t t) t)) + (3 dd) log t
+ *     and then  x_d = ((log dd + 3 log t) + (boost ? log(U_b) / k : 0)) - s_d,  U_b formed as U from w3 of that attempt.
+ *     After 32 rejections (every attempt accepts with probability above 0.95) x_d = NaN and undrawn[r] = 1.  k <= 0 or a
+ *     non-finite k gives NaN without an attempt.
+ *   undrawn: NULL, or [n_draws] bytes, written 0 or 1 for every draw; NULL leaves x bitwise as it is.
+ * The value of (d, g) is a function of (seed, d, g) and the draw's earlier elements alone: rows [0, n) at draw_offset k
+ * equal rows [k, k + n) at offset 0, bit for bit; two calls give bitwise equal output; no result depends on the launch
+ * shape; no atomics.  A form other than 1 or 2 is read as 0.  float32, contraction off; with u = 2^-24, A_loc and A_s as
+ * arp_site_logprior's, |z_dev - z| <= 18 u |z|, to first order against the exact value of the same float32 parents, the
+ * same table and the same Philox words (derivation: csrc/prior_draw.hip; library functions at the OpenCL full-profile
+ * limits):
+ *   form 0:  |x_dev - x| <= u (3 A_loc + exp(s) |z| (25 + 3 A_s) + |x|)
+ *   form 1:  |x_dev - x| <= u (3 A_loc + |z| (3 A_s + 6 + 20 sigma) + |x|)
+ *   form 2:  |x_dev - x| <= u (5 + 6 |log dd| + 3 T + 21 |log t| + |L| + [boost: (1 + 7 |log U_b|) / k] + |L + B| + 3 A_s + |x|),
+ *            T = 29 |t - 1| / t + 1,  L = log dd + 3 log t,  B = boost ? log(U_b) / k : 0
+ *   the accept margin m = ((0.5 z^2 + dd) - dd t^3 + 3 dd log t) - log U is within
+ *            E_m = u (19 z^2 + 6 dd + 8 dd t^3 + 39 dd |log t| + |0.5 z^2 + dd - dd t^3| + |m + log U| + 1 + 6 |log U|
+ *                     + 3 dd |1 - t^3| T)
+ *   of its exact value; an attempt with |m| <= E_m is undecided -- float32 and float64 may disagree about accepting it, and
+ *   the form-2 bound holds for an element none of whose attempts up to the accepting one is undecided.
+ * Asynchronous.  Refused before any launch: a NULL pointer other than undrawn, D < 1 or D > 255, n_draws < 1 or above 2^24,
+ * row_stride < D, draw_offset < 0. */
+int arp_site_prior_draws(int32_t D, const int32_t* form, const int32_t* loc_idx, const float* loc_w, const float* loc0,
+                         const int32_t* scale_idx, const float* scale_w, const float* log_scale0, int64_t n_draws,
+                         uint64_t seed, int64_t draw_offset, float* x, int64_t row_stride, uint8_t* undrawn /* may be NULL */,
+                         void* stream);
+
 /* Check of a mean-field normal fit (csrc/vicheck.hip; Yao, Vehtari, Simpson, Gelman 2018, "Yes, but did it work?"): draws
  * from q = N(loc, diag(scale^2)) in the coordinates the fit was made in.  For draw r, g = draw_offset + r, and element
  * d = 4 e + i: ONE call philox4x32_10(counter = (e, lo32(g), hi32(g), 0), key = (lo32(seed), hi32(seed))) per (r, e); words
