@@ -1,6 +1,6 @@
 """Pretty-printer for the result files main.py writes (reference analyze.py:30-185):
 
-    python -m autoreparam_amd.analyze --results_dir=. --model=radon_MN --elbos --ess --rhat --energy --trajectory --geometry --loo --ppc --vi --reparams
+    python -m autoreparam_amd.analyze --results_dir=. --model=radon_MN --elbos --ess --rhat --energy --trajectory --geometry --loo --ppc --vi --sbc --reparams
     python -m autoreparam_amd.analyze --loo_compare=radon_MN/CP_tied_loo.npz,radon_stddvs_MN/CP_tied_loo.npz
 
 The reference's method list is stale (`cVIP_exp_tied`, analyze.py:19-26) and it expects a
@@ -407,9 +407,36 @@ def report_loo_compare(path_a, path_b):
             str(a["model"]), str(b["model"]), diff, se, int(np.asarray(a["y"]).size))]
 
 
+def report_sbc(results):
+    """Build-specific: simulation-based calibration of every method that recorded it (--inference=SBC writes
+    <method>_sbc.json next to the method's own file): the worst quantity with its p-value and the two shape figures, then
+    the quantities whose ranks are not uniform (p below 1 % over the quantities, Bonferroni: a convention)."""
+    lines = []
+    for m, r in results.items():
+        if "sbc_replications" not in r:
+            continue
+        name = m[:-len("_sbc")] if m.endswith("_sbc") else m
+        lines.append("{}: simulation-based calibration: worst {} with p = {} (Kolmogorov distance {} of {}; threshold {}); "
+                     "largest |rank mean z| {} ({}); rank variance ratio {} ({}) ... {} ({}); posterior z-score mean within "
+                     "{}, sd {} ... {}; {} replicates, {} left out, {} chains x {} step(s) = {} draws, {} leapfrog steps; "
+                     "acceptance {}, median smallest ESS {}; fit {}, mcmc {}, fold {}, all {}".format(
+                         name, r["sbc_p_min_element"], _fmt(r["sbc_p_min"]), _fmt(r["sbc_ks_max"]), r["sbc_ks_max_element"],
+                         _fmt(r["sbc_p_threshold"]), _fmt(r["sbc_rank_mean_z_max_abs"]), r["sbc_rank_mean_z_max_abs_element"],
+                         _fmt(r["sbc_rank_var_ratio_min"]), r["sbc_rank_var_ratio_min_element"],
+                         _fmt(r["sbc_rank_var_ratio_max"]), r["sbc_rank_var_ratio_max_element"],
+                         _fmt(r["sbc_post_z_mean_max_abs"]), _fmt(r["sbc_post_z_sd_min"]), _fmt(r["sbc_post_z_sd_max"]),
+                         r["sbc_replications"], r["sbc_replications_left_out"], r["sbc_chains"], r["sbc_steps"], r["sbc_draws"],
+                         r["sbc_leapfrog_steps"], _fmt(r["sbc_accept_rate_mean"]), _fmt(r["sbc_ess_min_median"]),
+                         _secs(r["sbc_fit_time_sec"]), _secs(r["sbc_mcmc_time_sec"]), _secs(r["sbc_fold_time_sec"]),
+                         _secs(r["sbc_time_sec"])))
+        lines.append("{}: ranks not uniform: {}".format(name, ", ".join(r["sbc_miscalibrated_elements"]) or "none"))
+    return lines
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
-    for f in ("elbos", "ess", "reparams", "normalize_times", "rhat", "energy", "trajectory", "geometry", "loo", "ppc", "vi", "psens", "prior"):
+    for f in ("elbos", "ess", "reparams", "normalize_times", "rhat", "energy", "trajectory", "geometry", "loo", "ppc", "vi", "psens", "prior",
+              "sbc"):
         ap.add_argument("--" + f, action="store_true")
     ap.add_argument("--loo_compare", default="", help="A_loo.npz,B_loo.npz: the paired elpd_loo difference of two models")
     ap.add_argument("--model", default="all")
@@ -428,6 +455,9 @@ def main(argv=None):
         results = load(root, name)
         if not results:
             continue
+        # <method>_sbc.json is a report of its own, not a method's result file: only --sbc reads it
+        calibration = {m: r for m, r in results.items() if m.endswith("_sbc") and "sbc_replications" in r}
+        results = {m: r for m, r in results.items() if m not in calibration}
         print(" ******  {}  ****** ".format(name))
         for flag, lines in (("elbos", lambda: report_elbos(results)), ("reparams", lambda: report_reparams(results)),
                             ("ess", lambda: report_ess(results, args.normalize_times)),
@@ -436,7 +466,8 @@ def main(argv=None):
                             ("trajectory", lambda: report_trajectory(results, root, name)),
                             ("geometry", lambda: report_geometry(results, root, name)), ("loo", lambda: report_loo(results)),
                             ("ppc", lambda: report_ppc(results)), ("vi", lambda: report_vi(results)),
-                            ("psens", lambda: report_psens(results)), ("prior", lambda: report_prior(results))):
+                            ("psens", lambda: report_psens(results)), ("prior", lambda: report_prior(results)),
+                            ("sbc", lambda: report_sbc(calibration))):
             if getattr(args, flag):
                 print("\n".join(lines()) + "\n")
 

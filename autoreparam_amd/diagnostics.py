@@ -799,10 +799,15 @@ def _pit_calibration(pit):
     """(pit_ks, coverage_90) of a non-empty vector of PIT values: the Kolmogorov distance of their empirical distribution
     from the uniform, and the share of them in [0.05, 0.95].  One definition for the posterior PIT (ppc_from_counts) and
     the leave-one-out PIT (loo_predictive_summary)."""
-    s = np.sort(pit)
+    return kolmogorov_distance(pit), float(np.mean((pit >= 0.05) & (pit <= 0.95)))
+
+
+def kolmogorov_distance(u):
+    """The Kolmogorov distance sup |F_n - F| of the empirical distribution of a non-empty vector of values in [0, 1]
+    from the uniform one.  The one definition behind ppc_pit_ks, loo_pit_ks and sbc_summary's ks."""
+    s = np.sort(u)
     i = np.arange(1, s.size + 1, dtype=np.float64)
-    ks = float(max(np.max(i / s.size - s), np.max(s - (i - 1.0) / s.size)))
-    return ks, float(np.mean((pit >= 0.05) & (pit <= 0.95)))
+    return float(max(np.max(i / s.size - s), np.max(s - (i - 1.0) / s.size)))
 
 
 def ppc_from_counts(counts, obs_sums, y, kind):
@@ -1418,3 +1423,129 @@ def psens_summary(sums):
     return PsensSummary(prior, likelihood, shift[0], shift[1], ratio[0], ratio[1],
                         int(np.sum(np.isnan(prior) | np.isnan(likelihood))),
                         np.flatnonzero(above_p & above_l), np.flatnonzero(above_p & ~above_l))
+
+
+# ---- simulation-based calibration: where the truths sit among the refits' draws (csrc/sbc.hip) ----
+SBC_MAX_Q = 256                   # the most quantities arp_sbc_fold takes (csrc/sbc.hip: kSbcMaxQ)
+SBC_MAX_DRAWS = 1 << 24           # the most draws per replicate
+SBC_MAX_REPLICATES = 1 << 20      # the most replicates
+# sbc_summary.  replications: N', the replicates not left out; left_out: how many were; draws: L; names: the quantities.
+# Per replicate and quantity, [N, Q] float64 with NaN rows for a replicate left out: u (the rank value), post_bias
+# (posterior mean - truth), post_sd, post_z.  Per quantity, [Q] float64 (NaN where N' is too small): ks, ks_p, rank_mean_z,
+# rank_var_ratio, rank_var_z, post_z_mean, post_z_sd; constant [Q] bool: every draw of every kept replicate equals its truth.
+SbcSummary = collections.namedtuple("SbcSummary", ["replications", "left_out", "draws", "names", "u", "post_bias", "post_sd",
+                                                   "post_z", "ks", "ks_p", "rank_mean_z", "rank_var_ratio", "rank_var_z",
+                                                   "post_z_mean", "post_z_sd", "constant"])
+
+
+def sbc_fold(draws, truth):
+    """(counts, sums, left_out, n_left_out) of `arp_sbc_fold` for draws [N, L, Q] and truth [N, Q], float32 device
+    tensors: counts [N, Q, 2] int32 = (#{x < t}, #{x == t}) and sums [N, Q, 2] float64 = (sum (x - t), sum (x - t)^2) over
+    the L draws x of replicate r's quantity q against its truth t; left_out [N] uint8, 1 for a replicate whose truth or
+    any of whose draws is not finite (its counts and sums are 0); n_left_out: their count, an int64 device scalar.  An
+    inner block of a wider buffer -- draws[:, :l, :q] of [N, L', Q'], truth[:, :q] -- is read in place, through its
+    strides; any other layout is copied.  Refused here, before any call: what the kernel refuses."""
+    who = "sbc_fold"
+    if not (torch.is_tensor(draws) and torch.is_tensor(truth) and draws.is_cuda and truth.is_cuda
+            and draws.dtype == torch.float32 and truth.dtype == torch.float32 and draws.dim() == 3 and truth.dim() == 2):
+        raise ValueError("%s: float32 draws [N, L, Q] and truth [N, Q] on the GPU are required (there is no CPU fallback)" % who)
+    N, L, Q = (int(v) for v in draws.shape)
+    if tuple(truth.shape) != (N, Q) or truth.device != draws.device:
+        raise ValueError("%s: truth must be [%d, %d] on the draws' device" % (who, N, Q))
+    if not 1 <= Q <= SBC_MAX_Q:
+        raise ValueError("%s: 1 <= Q <= %d quantities are required" % (who, SBC_MAX_Q))
+    if not 1 <= L <= SBC_MAX_DRAWS:
+        raise ValueError("%s: 1 <= L <= 2^24 draws per replicate are required" % who)
+    if not 1 <= N <= SBC_MAX_REPLICATES:
+        raise ValueError("%s: 1 <= N <= 2^20 replicates are required" % who)
+    # (the stride of an axis of length 1 means nothing)
+    row = int(draws.stride(1)) if L > 1 else Q
+    rep = int(draws.stride(0)) if N > 1 else L * row
+    if not ((draws.stride(2) == 1 or Q == 1) and row >= Q and rep >= L * row):
+        draws = draws.contiguous()
+        row, rep = Q, L * Q
+    t_stride = int(truth.stride(0)) if N > 1 else Q
+    if not ((truth.stride(1) == 1 or Q == 1) and t_stride >= Q):
+        truth, t_stride = truth.contiguous(), Q
+    dev = draws.device
+    counts = torch.empty(N, Q, 2, dtype=torch.int32, device=dev)
+    sums = torch.empty(N, Q, 2, dtype=torch.float64, device=dev)
+    left_out = torch.empty(N, dtype=torch.uint8, device=dev)
+    n_left_out = torch.zeros((), dtype=torch.int64, device=dev)
+    _lib.call(dev, _lib.lib().arp_sbc_fold, _lib.ptr(draws), N, L, Q, rep, row, _lib.ptr(truth), t_stride, _lib.ptr(counts),
+              _lib.ptr(sums), _lib.ptr(left_out), _lib.ptr(n_left_out))
+    return counts, sums, left_out, n_left_out
+
+
+def kolmogorov_p_value(ks, n):
+    """The asymptotic p-value of a Kolmogorov distance `ks` of n values, in Stephens' (1970) form:
+    lambda = (sqrt n + 0.12 + 0.11 / sqrt n) ks,  p = 2 sum_{j >= 1} (-1)^(j - 1) exp(-2 j^2 lambda^2), clipped to [0, 1];
+    1 for lambda < 0.3 (the alternating series has not settled there, and the value is 1 to nine digits); NaN for n < 1."""
+    if n < 1 or not np.isfinite(ks):
+        return float("nan")
+    root = math.sqrt(n)
+    lam = (root + 0.12 + 0.11 / root) * float(ks)
+    if lam < 0.3:
+        return 1.0
+    j = np.arange(1, 101, dtype=np.float64)
+    p = 2.0 * float(np.sum((-1.0) ** (j - 1.0) * np.exp(-2.0 * j * j * lam * lam)))
+    return min(max(p, 0.0), 1.0)
+
+
+def sbc_summary(counts, sums, n_draws, left_out=None, names=None):
+    """Simulation-based calibration, the single place where its statistics are defined -> SbcSummary; pure numpy
+    float64.  counts, sums [N, Q, 2] as sbc_fold returns them, n_draws = L, left_out [N] (non-zero: the replicate enters
+    nothing), names [Q].  Over the N' replicates kept, per quantity:
+      u = (less + equal / 2 + 1 / 2) / (L + 1)          the mid-rank on (0, 1): deterministic, ties split evenly
+      ks, ks_p                                          kolmogorov_distance of the u from uniform, kolmogorov_p_value
+      rank_mean_z = (mean u - 1/2) sqrt(12 N')          its sign: on which side of the truth the posterior sits
+      rank_var_ratio = 12 s^2,  rank_var_z = (s^2 - 1/12) sqrt(180 N')     s^2 the sample variance of u; Var(s^2) is about
+                                                        (mu_4 - sigma^4) / N' = (1/80 - 1/144) / N' = 1 / (180 N').  A ratio
+                                                        above 1 is a U-shaped histogram, a posterior too narrow; below 1
+                                                        one too wide
+      post_bias = s1 / L,  post_sd = sqrt((s2 - s1^2 / L) / (L - 1)) (NaN for L = 1),  post_z = post_bias / post_sd;
+      post_z_mean, post_z_sd: mean and sd of the finite post_z over the replicates -- near 0 and 1
+    A constant column (every draw equal to its truth) has u = 1/2 everywhere and is flagged in `constant`."""
+    c = np.asarray(counts.cpu() if torch.is_tensor(counts) else counts).astype(np.float64)
+    s = _lib.host64(sums)
+    if c.ndim != 3 or c.shape[2] != 2 or s.shape != c.shape:
+        raise ValueError("sbc_summary: counts and sums of one [N, Q, 2] shape are required")
+    N, Q = c.shape[:2]
+    L = int(n_draws)
+    if L < 1:
+        raise ValueError("sbc_summary: n_draws >= 1 is required")
+    kept = np.ones(N, bool) if left_out is None else (_lib.host64(left_out).reshape(-1) == 0)
+    if kept.size != N:
+        raise ValueError("sbc_summary: left_out must have one entry per replicate")
+    names = list(names) if names is not None else ["q%d" % q for q in range(Q)]
+    if len(names) != Q:
+        raise ValueError("sbc_summary: names must have one entry per quantity")
+    n = int(kept.sum())
+    nan_q = np.full(Q, np.nan)
+    u = np.full((N, Q), np.nan)
+    u[kept] = (c[kept, :, 0] + 0.5 * c[kept, :, 1] + 0.5) / (L + 1.0)
+    bias, sd, z = np.full((N, Q), np.nan), np.full((N, Q), np.nan), np.full((N, Q), np.nan)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        bias[kept] = s[kept, :, 0] / L
+        if L > 1:
+            sd[kept] = np.sqrt(np.maximum(s[kept, :, 1] - s[kept, :, 0] ** 2 / L, 0.0) / (L - 1.0))
+        z[kept] = bias[kept] / sd[kept]
+    ks, ks_p, mean_z, var_ratio, var_z, z_mean, z_sd = (nan_q.copy() for _ in range(7))
+    uk = u[kept]
+    for q in range(Q):
+        if n >= 1:
+            ks[q] = kolmogorov_distance(uk[:, q])
+            ks_p[q] = kolmogorov_p_value(ks[q], n)
+            mean_z[q] = (uk[:, q].mean() - 0.5) * math.sqrt(12.0 * n)
+        if n >= 2:
+            s2 = float(np.var(uk[:, q], ddof=1))
+            var_ratio[q] = 12.0 * s2
+            var_z[q] = (s2 - 1.0 / 12.0) * math.sqrt(180.0 * n)
+        zq = z[kept, q]
+        zq = zq[np.isfinite(zq)]
+        if zq.size >= 1:
+            z_mean[q] = zq.mean()
+        if zq.size >= 2:
+            z_sd[q] = zq.std(ddof=1)
+    constant = np.all(c[kept, :, 1] == L, axis=0) if n else np.zeros(Q, bool)
+    return SbcSummary(n, N - n, L, names, u, bias, sd, z, ks, ks_p, mean_z, var_ratio, var_z, z_mean, z_sd, constant)

@@ -378,6 +378,14 @@ def engine_for(spec, device=None):
     return _engines[key]
 
 
+def release(spec):
+    """Forget the cached Engines of `spec` (every device): their model handles are destroyed once nothing else holds them.
+    For a caller that makes many specs in one process (sbc.run_sbc: one per replicate); _engines is keyed by id(spec) and
+    would otherwise keep every handle alive."""
+    for key in [key for key in _engines if key[0] == id(spec)]:
+        del _engines[key]
+
+
 def _convert(spec, reparam, to_centered):
     def fn(state_parts):
         eng = engine_for(spec)

@@ -10,7 +10,8 @@ _DEFS = [
     # name, type, default, help
     ("model", str, "8schools", "Model to be used."),
     ("dataset", str, "", "Dataset to be used."),
-    ("inference", str, "VI", "Inference method to be used: VI, HMCtuning, or HMC."),
+    ("inference", str, "VI", "Inference method to be used: VI, HMCtuning, HMC, or SBC (simulation-based calibration of the "
+                             "whole VI + HMC flow on data simulated from the prior: --sbc_replications)."),
     ("method", str, "CP", "Method to be used: CP, NCP, i (only if inference = HMC), cVIP, dVIP."),
     ("learnable_parameterisation_type", str, "eig", "Type of learnable parameterisation (scalar models ignore it)."),
     ("reparameterise_variational", bool, False, "Not supported by this build (off in the reference too)."),
@@ -178,6 +179,19 @@ _DEFS = [
                                     "changes no step size and no initial state.  A result file written without the flag "
                                     "is checked from its stored fit, without refitting."),
     ("vi_check_draws", int, 65536, "With --vi_diagnostics: the draws from q, 1024 ... 2^20."),
+    ("sbc_replications", int, 256, "--inference=SBC: N in 8 ... 16384, the replicates of simulation-based calibration (Talts "
+                                   "et al. 2018).  Each is one ancestral draw from the prior (arp_site_prior_draws), one data "
+                                   "set simulated from it at the observed covariates (arp_predictive_check) and one refit of "
+                                   "the whole flow on that data -- the VI fit, then --num_chains chains of HMC with "
+                                   "--num_leapfrog_steps, seeded by --seed + 1 + r -- whose draws at --sbc_steps recorded steps "
+                                   "are ranked against the truth, per element and for the joint log-likelihood "
+                                   "(arp_sbc_fold).  Uniform ranks are what a sampler of the model's posterior returns "
+                                   "(sbc_* keys in <method>_sbc.json, <method>_sbc.npz; analyze --sbc).  --method=CP or NCP, "
+                                   "one process, a model with observations."),
+    ("sbc_steps", int, 1, "--inference=SBC: how many evenly spaced recorded steps of every replicate's trace are ranked (the "
+                          "last among them), 1 ... the recorded steps of the run; L = sbc_steps * num_chains draws per "
+                          "replicate.  Draws of consecutive steps are dependent: above 1 the rank histogram gains a U-shape "
+                          "of its own."),
     ("lanes_per_chain", int, 0, "Lanes of a wave64 a chain is spread over (0 = automatic)."),
 ]
 

@@ -21,6 +21,7 @@ import numpy as np
 
 from . import _lib, diagnostics, graphs, inference, models, parallel, util
 from . import engine as _engine
+from . import sbc as _sbc
 from .flags import FLAGS, check_vi_check_draws
 
 
@@ -1979,6 +1980,7 @@ def main(argv=None, flags=FLAGS, out=None):
     check_sensitivity_sites(flags)
     check_prior_predictive(flags)
     check_vi_diagnostics(flags)
+    _sbc.check_sbc(flags)
     ws = int(os.environ.get("WORLD_SIZE", "1"))
     if ws > 1:
         # launched by torch.distributed.run: one rank per GPU, RCCL for the statistics exchange
@@ -2020,6 +2022,8 @@ def main(argv=None, flags=FLAGS, out=None):
     file_path = os.path.join(results_dir, filename)
     if flags.inference == "VI":
         return run_vi(model_config, results_dir, file_path, flags)
+    if flags.inference == "SBC":
+        return _sbc.run_sbc(model_config, results_dir, file_path, flags, out=out)
     if flags.inference not in ("HMC", "HMCtuning"):
         raise Exception("unknown inference {}".format(flags.inference))
     try:

@@ -8,6 +8,7 @@ Edward2 program; here it is a :class:`ModelSpec` (same role: it defines the join
 density, evaluated natively by the engine instead of by TensorFlow).
 """
 import collections
+import copy
 import math
 import os
 
@@ -118,6 +119,23 @@ class ModelSpec(object):
         k = self.part_names.index(name)
         shared = name in (self.scalar_loc if which == "a" else self.scalar_scale)
         return () if shared else self.part_shapes[k]
+
+    def with_observations(self, y):
+        """A spec of the same model on other observations: `raw["y"]` and every entry of `observed` hold `y` (anything numpy
+        reads, one value per observation, in observation_table's order) in the original's dtypes and shapes; everything
+        else -- covariates, parts, options -- is shared with this spec, which is not touched.  What a refit on replicated
+        data runs on (sbc.run_sbc).  A model without observations (neals_funnel) is refused."""
+        if "y" not in self.raw:
+            raise ValueError("%s has no observations to replace" % self.name)
+        old = np.asarray(self.raw["y"])
+        y = np.asarray(y)
+        if y.size != old.size:
+            raise ValueError("%s: %d observations are required, not %d" % (self.name, old.size, y.size))
+        new = copy.copy(self)
+        new.raw = dict(self.raw)
+        new.raw["y"] = np.ascontiguousarray(y.reshape(old.shape).astype(old.dtype))
+        new.observed = {name: new.raw["y"].reshape(np.shape(v)).astype(np.asarray(v).dtype) for name, v in self.observed.items()}
+        return new
 
     def observation_table(self):
         """One row per observation for `arp_pointwise_loglik` -> ObservationTable, or None for a model without data
@@ -422,7 +440,12 @@ def spec_by_name(model_name, dataset=None):
 def get_model_by_name(model_name, dataset=None):
     """Reference: models.py:1144-1175 (the four BASELINE models and the scalar-Normal hierarchical models of
     SURVEY 8f-3; the GP / MVN / Wishart models are out of scope)."""
-    spec = spec_by_name(model_name, dataset)
+    return model_config_for(spec_by_name(model_name, dataset))
+
+
+def model_config_for(spec):
+    """The ModelConfig around a ModelSpec: what get_model_by_name returns for the frozen data, and what a refit on
+    replicated data (ModelSpec.with_observations; sbc.run_sbc) is handed."""
     from . import engine  # deferred: converters run on the device
 
     varnames = spec.part_names

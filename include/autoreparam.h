@@ -710,6 +710,27 @@ int arp_site_prior_draws(int32_t D, const int32_t* form, const int32_t* loc_idx,
                          uint64_t seed, int64_t draw_offset, float* x, int64_t row_stride, uint8_t* undrawn /* may be NULL */,
                          void* stream);
 
+/* The fold of simulation-based calibration (csrc/sbc.hip; needs no model handle; Talts, Betancourt, Simpson, Vehtari,
+ * Gelman 2018): where the truth of every replicate sits among the posterior draws a refit on its simulated data returned.
+ * draws is [n_rep][n_draws][Q] float in device memory, element (r, i, q) at draws[r * rep_stride + i * row_stride + q]
+ * (rep_stride >= n_draws * row_stride, row_stride >= Q: an inner block of a wider buffer is read in place); truth is
+ * [n_rep][Q] float, element (r, q) at truth[r * truth_stride + q] (truth_stride >= Q).  Outputs (device memory, contiguous),
+ * per replicate r and quantity q over the replicate's n_draws rows, x = draws (r, i, q), t = truth (r, q):
+ *   counts [n_rep][Q][2] int32:  #{x < t}, #{x == t}   (-0.0 == 0.0 counts as equal; denormals compare as themselves)
+ *   sums   [n_rep][Q][2] double: sum (x - t), sum (x - t)^2 -- the subtraction in float64, rounded once, the square
+ *     rounded once (contraction off), each sum the chain over rows i = 0 ... n_draws - 1 in that order: the order of
+ *     addition does not depend on the launch shape or on the strides, and each sum is within (n_draws - 1) 2^-53 sum |term|
+ *     of the exact sum of the same float64 terms, to first order
+ *   left_out [n_rep] uint8: 1 for a replicate whose truth or any of whose draws has a non-finite element; its counts and
+ *     sums are written as 0 (by select, not by a product); 0 otherwise
+ *   n_left_out: int64 scalar, the number of such replicates (an integer count)
+ * No float atomics; two calls give bitwise equal outputs; nothing is read past the last addressed element, and the
+ * padding the strides leave is never read.  Asynchronous.  Refused before any launch: a NULL pointer, Q < 1 or Q > 256,
+ * n_draws < 1 or above 2^24, n_rep < 1 or above 2^20, row_stride < Q, rep_stride < n_draws * row_stride, truth_stride < Q. */
+int arp_sbc_fold(const float* draws, int64_t n_rep, int64_t n_draws, int32_t Q, int64_t rep_stride, int64_t row_stride,
+                 const float* truth, int64_t truth_stride, int32_t* counts, double* sums, uint8_t* left_out,
+                 int64_t* n_left_out, void* stream);
+
 /* Check of a mean-field normal fit (csrc/vicheck.hip; Yao, Vehtari, Simpson, Gelman 2018, "Yes, but did it work?"): draws
  * from q = N(loc, diag(scale^2)) in the coordinates the fit was made in.  For draw r, g = draw_offset + r, and element
  * d = 4 e + i: ONE call philox4x32_10(counter = (e, lo32(g), hi32(g), 0), key = (lo32(seed), hi32(seed))) per (r, e); words
