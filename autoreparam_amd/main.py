@@ -19,10 +19,13 @@ from collections import OrderedDict
 
 import numpy as np
 
-from . import _lib, diagnostics, graphs, inference, models, parallel, util
+from . import _lib, diagnostics, graphs, inference, models, parallel, report_common, util
 from . import engine as _engine
 from . import sbc as _sbc
 from .flags import FLAGS, check_vi_check_draws
+from .report_common import (LOO_CHUNK_BYTES, _finite_or_none, _fmt, _nan_max, _null_keys, _write_json_atomic, derived_seed,
+                            element_names, joint_loglik, loo_steps, next_seed, ppc_tile_rows, probe_steps, replicate_tiles,
+                            select_draws)
 
 
 def _vip_suffix(flags):
@@ -188,7 +191,7 @@ def _vi_check_report(model_config, fit, actual_reparam, file_path, flags):
     eng = _engine.engine_for(spec, torch.device(flags.device))
     eng.set_param(0, (a, b))
     draws = check_vi_check_draws(flags.vi_check_draws)
-    seed = (int(flags.seed) * 0x9E3779B97F4A7C15 + VI_CHECK_SEED) & 0xFFFFFFFFFFFFFFFF
+    seed = derived_seed(flags.seed, VI_CHECK_SEED)
     chk = diagnostics.vi_check(eng, loc, scale, which=0, draws=draws, seed=seed)
     summary = diagnostics.vi_check_summary(chk.elem, chk.tot, chk.out8, loc, scale, chk.e0, chk.logp_const)
     keys = vi_check_keys(summary, draws, chk.left_out, element_names(spec))
@@ -324,22 +327,6 @@ def _ess_report(info, model_config, flags, dev, ess_parts=None):
 RHAT_WARN = 1.01          # the customary threshold above which chains are said not to have mixed
 
 
-def _finite_or_none(x):
-    """A JSON number, or None (written as null) for NaN / inf: `nan` is not JSON and never equals itself."""
-    x = float(x)
-    return x if np.isfinite(x) else None
-
-
-def _nan_max(x):
-    """(largest finite entry, its index), or (nan, -1) when there is none."""
-    x = np.asarray(x, np.float64)
-    ok = np.flatnonzero(np.isfinite(x))
-    if not ok.size:
-        return float("nan"), -1
-    at = int(ok[x[ok].argmax()])
-    return float(x[at]), at
-
-
 def _reduced(blocks, dev):
     """The `blocks` (arrays, tensors or scalars), summed over the ranks of the job in ONE all-reduce of their ravelled
     concatenation, as float64 numpy arrays of their own shapes."""
@@ -355,10 +342,6 @@ def _by_part(spec, arrays, rows):
             arrays["%s/%s" % (key, name)] = part
 
 
-def _fmt(v):
-    return "n/a" if v is None else "{:.4g}".format(v)
-
-
 def _convergence_report(kernel_results, model_config, flags, dev):
     """Build-specific (--convergence_diagnostics): do the chains of this run agree with each other?  Split R-hat of every
     element over the chains whose trace is on the device (all of them in a whole-trace run; the --ess_chains subset of a
@@ -369,20 +352,10 @@ def _convergence_report(kernel_results, model_config, flags, dev):
     (A collective when ws > 1: every rank calls it.)"""
     trace = getattr(kernel_results, "trace", None)
     if not getattr(flags, "convergence_diagnostics", True) or trace is None:
-        keys = {}
-        if getattr(flags, "convergence_diagnostics", True) and getattr(flags, "predictive_checks", False):
-            keys = _loo_null("no chain has its trace on the device", flags) if getattr(flags, "predictive_diagnostics", False) \
-                else OrderedDict()
-            keys.update(_ppc_null("no chain has its trace on the device"))
-        elif getattr(flags, "convergence_diagnostics", True) and getattr(flags, "predictive_diagnostics", False):
-            keys = _loo_null("no chain has its trace on the device", flags)
-        if getattr(flags, "convergence_diagnostics", True) and getattr(flags, "sensitivity_diagnostics", False):
-            keys = OrderedDict(keys)
-            keys.update(_psens_null("no chain has its trace on the device", flags))
-        if getattr(flags, "convergence_diagnostics", True) and getattr(flags, "prior_predictive_checks", False):
-            keys = OrderedDict(keys)
-            keys.update(_prior_null("no chain has its trace on the device, so there is no pooled posterior to set the "
-                                    "prior against"))
+        keys = OrderedDict()
+        for row in SIDE_REPORTS if getattr(flags, "convergence_diagnostics", True) else ():
+            if row.null is not None and getattr(flags, row.flag, False):      # asked for, and says that it cannot run
+                keys.update(row.null(flags))
         return keys, None
     clock = time.time()
     spec = model_config.model
@@ -432,41 +405,20 @@ def _convergence_report(kernel_results, model_config, flags, dev):
     if int(getattr(flags, "superchain_size", 0) or 0) >= 2:
         keys.update(_nested_report(trace, moments, int(flags.superchain_size), dev, arrays, by_part))
     # the reports with a side file of their own: the file's arrays wait under a tag (_save_diagnostics takes them out again)
-    for asked, tag, report in (
-            (getattr(flags, "energy_diagnostics", False), ENERGY_ARRAYS,
-             lambda: _energy_report(kernel_results, trace, spec, flags, dev)),
-            (int(getattr(flags, "trajectory_profile", 0) or 0) != 0, TRAJECTORY_ARRAYS,      # (the sd: already all-reduced)
-             lambda: _trajectory_report(kernel_results, trace, spec, flags, dev, whole.sd if streaming else split.sd)),
-            (getattr(flags, "geometry_diagnostics", False), GEOMETRY_ARRAYS,
-             lambda: _geometry_report(kernel_results, trace, k, spec, flags, dev, split.mean)),
-            (getattr(flags, "predictive_diagnostics", False), LOO_ARRAYS,
-             lambda: _loo_report(kernel_results, trace, k, spec, flags, arrays)),     # (--loo_predictive: a second tag)
-            (getattr(flags, "predictive_checks", False), PPC_ARRAYS,               # (n_split: already all-reduced)
-             lambda: _ppc_report(kernel_results, trace, k, n_split, spec, flags, dev)),
-            (getattr(flags, "sensitivity_diagnostics", False), PSENS_ARRAYS,
-             lambda: _psens_report(trace, k, spec, flags, split.mean, arrays)),
-            (getattr(flags, "prior_predictive_checks", False), PRIOR_ARRAYS,         # (mean and sd: already all-reduced)
-             lambda: _prior_report(spec, flags, trace.device, *((whole.mean, whole.sd) if streaming else
-                                                                 (split.mean, split.sd))))):
-        if asked:
-            side_keys, side_arrays = report()
+    pooled = whole if streaming else split                        # (n_split, the means and the sds: already all-reduced)
+    run = _Run(kernel_results, trace, k, n_split, spec, flags, dev, arrays, split.mean, pooled.mean, pooled.sd)
+    for row in SIDE_REPORTS:
+        if row.report is not None and getattr(flags, row.flag, False):
+            side_keys, side_arrays = row.report(run)
             keys.update(side_keys)
             if side_arrays is not None:
-                arrays[tag] = side_arrays
+                arrays[row.tag] = side_arrays
     keys["diagnostics_time_sec"] = time.time() - clock
     return keys, arrays
 
 
 ENERGY_ARRAYS = "energy/"            # where _convergence_report leaves the arrays of <base>_energy.npz among those of _rhat.npz
 ENERGY_WHERE_MAX = 1024              # divergent rows whose states <base>_energy.npz keeps
-
-
-def probe_steps(S, R):
-    """The recorded steps an energy probe visits: R evenly spaced of S, the first and the last among them; all S if S < R."""
-    S, R = int(S), int(R)
-    if S <= 0 or R <= 0:
-        return []
-    return sorted({int(round(v)) for v in np.linspace(0, S - 1, min(S, R))})
 
 
 def _probe_walk(ctx, trace, flags, seed_constant):
@@ -479,7 +431,7 @@ def _probe_walk(ctx, trace, flags, seed_constant):
     step S)."""
     eng, S = ctx.engine, int(trace.shape[0])
     steps = [-1] + probe_steps(S, int(getattr(flags, "energy_probe_steps", 8)))
-    seed = (int(flags.seed) * 0x9E3779B97F4A7C15 + seed_constant) & 0xFFFFFFFFFFFFFFFF
+    seed = derived_seed(flags.seed, seed_constant)
     centred_final = eng.transform(ctx.q, which=0, to_centered=True) if int(ctx.q.shape[0]) > 0 else ctx.q
 
     def visits():
@@ -645,17 +597,6 @@ GEOMETRY_KERNEL_KEYS = tuple(key for key in GEOMETRY_KEYS if key not in (
     "geometry_rows", "geometry_rows_left_out", "geometry_chains", "geometry_condition_number_centred"))
 
 
-def element_names(spec):
-    """One name per element of the flat state, in trace order: `tau` for a scalar part, `m[17]`, `z[2,3]` otherwise."""
-    names = []
-    for name, shape in zip(spec.part_names, spec.part_shapes):
-        if not len(shape):
-            names.append(name)
-        else:
-            names.extend("%s[%s]" % (name, ",".join(str(int(i)) for i in idx)) for idx in np.ndindex(*shape))
-    return names
-
-
 def geometry_chunk_steps(S, k, D, budget=GEOMETRY_CHUNK_BYTES):
     """Whole recorded steps per chunk of the geometry report: k chains of D floats each, three times over (the
     transformed rows and their [n, 2 D] companion), within `budget` bytes; at least one."""
@@ -785,7 +726,6 @@ def _geometry_report(kernel_results, trace, k, spec, flags, dev, pooled_mean):
 
 
 LOO_ARRAYS = "loo/"                  # where _convergence_report leaves the arrays of <base>_loo.npz
-LOO_CHUNK_BYTES = 256 << 20          # a tile's [observations, draws] float32 log-likelihoods stay below this
 LOO_KEYS = ("loo_draws", "loo_draws_left_out", "loo_chains", "loo_steps", "loo_observations", "elpd_loo", "elpd_loo_se",
             "p_loo", "elpd_waic", "elpd_waic_se", "p_waic", "pareto_k_max", "pareto_k_max_observation",
             "pareto_k_threshold", "pareto_k_above_threshold", "loo_nonfinite_observations", "loo_time_sec")
@@ -807,27 +747,14 @@ def check_predictive(flags):
                          "log-likelihood to cross-validate")
 
 
-def loo_steps(S, k, draws):
-    """The recorded steps the predictive report takes its draws from: clamp(draws // k, 1, S) evenly spaced of S, the last
-    one among them (probe_steps, the rule of --energy_probe_steps, counted from the end: a single step is the last), and
-    no more than arp_psis_loo takes draws of."""
-    k, S = max(int(k), 1), int(S)
-    want = max(1, min(S, int(draws) // k))
-    return sorted(S - 1 - s for s in probe_steps(S, min(want, diagnostics.PSIS_MAX_DRAWS // k)))
-
-
 def loo_tile_rows(N, R, budget=None):
-    """Observations per tile of the predictive report: rows of R float32 within `budget` bytes (LOO_CHUNK_BYTES); at
-    least one."""
-    budget = LOO_CHUNK_BYTES if budget is None else int(budget)
-    return int(max(1, min(max(int(N), 1), budget // max(1, 4 * int(R)))))
+    """report_common.loo_tile_rows within THIS module's LOO_CHUNK_BYTES, the budget of every tile the reports here size."""
+    return report_common.loo_tile_rows(N, R, LOO_CHUNK_BYTES if budget is None else budget)
 
 
 def _loo_null(why, flags=None):
-    """Every key of the predictive report as null, with the one message that says why; with --loo_predictive those of the
-    leave-one-out predictive report too (no message of their own)."""
-    util.print_("    PSIS-LOO / WAIC: not computed, {}".format(why))
-    return OrderedDict((key, None) for key in LOO_KEYS + (LOO_PRED_KEYS if getattr(flags, "loo_predictive", False) else ()))
+    """Every key of the predictive report, and with --loo_predictive of that report too, as null; one message says why."""
+    return _null_keys("PSIS-LOO / WAIC", why, LOO_KEYS + (LOO_PRED_KEYS if getattr(flags, "loo_predictive", False) else ()))
 
 
 def loo_pred_keys(summary):
@@ -887,17 +814,10 @@ def _loo_report(kernel_results, trace, k, spec, flags, side=None):
         return _loo_null("the chains of a sharded job are on several devices (a tail fit needs all draws of an "
                          "observation on one)", flags), None
     clock = time.time()
-    S, _, D = (int(v) for v in trace.shape)
-    k = int(k) if S > 0 else 0
-    if k <= 0:
-        return _loo_null("no chain has its trace on the device", flags), None
-    if D > diagnostics.LOGLIK_MAX_D:
-        return _loo_null("the model has more than {} elements".format(diagnostics.LOGLIK_MAX_D), flags), None
-    steps = loo_steps(S, k, getattr(flags, "loo_draws", 65536))
-    if not steps:
-        return _loo_null("more than {} chains".format(diagnostics.PSIS_MAX_DRAWS), flags), None
-    table = diagnostics.upload_table(spec.observation_table(), D, trace.device)
-    draws = trace[torch.as_tensor(steps, device=trace.device), :k].contiguous()      # [len(steps), k, D]: a copy, D floats a draw
+    why, steps, draws = select_draws(trace, k, k, flags)
+    if why:
+        return _loo_null(why, flags), None
+    table = diagnostics.upload_table(spec.observation_table(), int(trace.shape[2]), trace.device)
     R, N = len(steps) * k, table.N
     rows = loo_tile_rows(N, R, LOO_CHUNK_BYTES // 3) if pred else loo_tile_rows(N, R)
     ll_buffer = torch.empty(rows, R, dtype=torch.float32, device=trace.device)
@@ -981,21 +901,9 @@ def check_predictive_checks(flags):
         raise ValueError("--predictive_checks: neals_funnel has no observations, so there is no data to replicate")
 
 
-def ppc_tile_rows(N, R, workspace_bytes, budget=None):
-    """Observations per tile of the predictive checks: loo_tile_rows, halved until `workspace_bytes(rows, R)` -- the
-    kernel's partial sums, the only [observations, draws]-sized memory this report takes -- is within the budget too; at
-    least one."""
-    budget = LOO_CHUNK_BYTES if budget is None else int(budget)
-    rows = loo_tile_rows(N, R, budget)
-    while rows > 1 and workspace_bytes(rows, R) > budget:
-        rows = (rows + 1) // 2
-    return rows
-
-
 def _ppc_null(why):
     """Every key of the predictive checks as null, with the one message that says why."""
-    util.print_("    posterior predictive checks: not computed, {}".format(why))
-    return OrderedDict((key, None) for key in PPC_KEYS)
+    return _null_keys("posterior predictive checks", why, PPC_KEYS)
 
 
 def ppc_keys(summary, n_chains, n_steps):
@@ -1014,47 +922,29 @@ def ppc_keys(summary, n_chains, n_steps):
 
 def _ppc_report(kernel_results, trace, k, k_total, spec, flags, dev):
     """--predictive_checks: does data simulated from the fitted MODEL look like the data?  Over the draws the predictive
-    report takes -- the leading `k` chains of this rank's device trace, the chains split R-hat covers (`k_total` of them in
-    the whole job, already all-reduced), at clamp(--loo_draws // k_total, 1, S) evenly spaced recorded steps (loo_steps) --
-    one replicated data set per draw at the observed covariates (diagnostics.predictive_check, from the model's
-    observation table), folded on the device into per-draw test statistics and per-observation predictive sums, in tiles
-    of observations (ppc_tile_rows) combined on the device.  The random numbers are keyed by (seed, observation, global
-    draw number), the seed derived from --seed and PPC_SEED; a rank's first global draw number is its chain offset times
-    the number of steps.  Every quantity is a sum over draws: the counts behind the p-values and the per-observation sums go
-    through ONE all-reduce, and a sharded job reports real numbers (rank 0 writes them; <base>_ppc.npz then holds the
-    draw statistics of rank 0's draws).  The posterior PIT (the LOO-PIT: --loo_predictive); no group-level statistics; no user-defined
-    statistic.  Returns (JSON keys, arrays of <base>_ppc.npz or None).  (A collective when ws > 1: every rank calls it.)"""
-    import torch
+    report takes (select_draws: the leading `k` chains of this rank's device trace, the chains split R-hat covers, at the
+    steps that `k_total`, their number in the whole job, already all-reduced, gives) one replicated data set per draw at the
+    observed covariates, folded on the device into per-draw test statistics and per-observation predictive sums
+    (replicate_tiles).  The random numbers are keyed by (seed, observation, global draw number), the seed derived from
+    --seed and PPC_SEED; a rank's first global draw number is its chain offset times the number of steps.  Every quantity
+    is a sum over draws: the counts behind the p-values and the per-observation sums go through ONE all-reduce, and a
+    sharded job reports real numbers (rank 0 writes them; <base>_ppc.npz then holds the draw statistics of rank 0's draws).
+    The posterior PIT (the LOO-PIT: --loo_predictive); no group-level statistics; no user-defined statistic.
+    Returns (JSON keys, arrays of <base>_ppc.npz or None).  (A collective when ws > 1: every rank calls it.)"""
     clock = time.time()
-    S, _, D = (int(v) for v in trace.shape)
-    k = int(k) if S > 0 else 0
-    if int(k_total) <= 0 or S <= 0:
-        return _ppc_null("no chain has its trace on the device"), None
-    if D > diagnostics.LOGLIK_MAX_D:
-        return _ppc_null("the model has more than {} elements".format(diagnostics.LOGLIK_MAX_D)), None
-    steps = loo_steps(S, k_total, getattr(flags, "loo_draws", 65536))
-    if not steps:
-        return _ppc_null("more than {} chains".format(diagnostics.PSIS_MAX_DRAWS)), None
+    why, steps, draws = select_draws(trace, k, k_total, flags)
+    if why:
+        return _ppc_null(why), None
     host_table = spec.observation_table()
     N, kind = int(np.asarray(host_table.y).size), int(host_table.kind)
     y = np.asarray(host_table.y, np.float32).reshape(-1)
-    seed = (int(flags.seed) * 0x9E3779B97F4A7C15 + PPC_SEED) & 0xFFFFFFFFFFFFFFFF
-    ctx = getattr(kernel_results, "probe", None)
-    draw_offset = (int(ctx.chain_offset) if ctx is not None else 0) * len(steps)
+    draw_offset = int(getattr(getattr(kernel_results, "probe", None), "chain_offset", 0)) * len(steps)
     counts, obs_sums, stats_host = np.zeros(diagnostics.PPC_COUNTS), np.zeros((N, len(diagnostics.PPC_OBS_COLUMNS))), None
-    if k > 0:
-        table = diagnostics.upload_table(host_table, D, trace.device)
-        draws = trace[torch.as_tensor(steps, device=trace.device), :k].contiguous()      # [len(steps), k, D]: a copy, D floats a draw
-        R = len(steps) * k
-        rows = ppc_tile_rows(N, R, diagnostics.predictive_workspace_bytes)
-        stats, sums, mask = None, [], None
-        for n0 in range(0, N, rows):
-            part, obs, _, mask, _ = diagnostics.predictive_check(draws, table, n0, min(N, n0 + rows), seed=seed,
-                                                                 draw_offset=draw_offset)
-            stats = part if stats is None else diagnostics.combine_draw_stats(stats, part)
-            sums.append(obs)
-        stats_host, obs_sums = _lib.host64(stats), _lib.host64(torch.cat(sums, dim=0))
-        counts = diagnostics.ppc_counts(stats_host, y, mask)                             # (the same draws for every tile)
+    if draws is not None:                                                    # (None: an idle rank, zeros into the all-reduce)
+        table = diagnostics.upload_table(host_table, int(trace.shape[2]), trace.device)
+        stats, sums, mask = replicate_tiles(draws, table, derived_seed(flags.seed, PPC_SEED), draw_offset, budget=LOO_CHUNK_BYTES)
+        stats_host, obs_sums = _lib.host64(stats), _lib.host64(sums)
+        counts = diagnostics.ppc_counts(stats_host, y, mask)
     counts, obs_sums = _reduced([counts, obs_sums], dev)
     summary = diagnostics.ppc_from_counts(counts, obs_sums, y, kind)
     keys = ppc_keys(summary, k_total, len(steps))
@@ -1134,10 +1024,8 @@ def check_sensitivity_sites(flags):
 
 
 def _psens_null(why, flags=None):
-    """Every key of the sensitivity report as null, with the one message that says why; those of --sensitivity_prior_parts
-    with them where it is set."""
-    util.print_("    power-scaling sensitivity: not computed, {}".format(why))
-    return OrderedDict((key, None) for key in PSENS_KEYS + (PSENS_SITE_KEYS if prior_parts(flags) else ()))
+    """Every key of the sensitivity report, and of --sensitivity_prior_parts where set, as null; one message says why."""
+    return _null_keys("power-scaling sensitivity", why, PSENS_KEYS + (PSENS_SITE_KEYS if prior_parts(flags) else ()))
 
 
 def psens_keys(summary, names, pareto_k, R, left_out, n_chains, n_steps):
@@ -1233,49 +1121,34 @@ def _psens_sites_report(names, draws, spec, log_prior, logp_const, log_lik, left
 def _psens_report(trace, k, spec, flags, pooled_mean=None, side=None):
     """--sensitivity_diagnostics: how much of each posterior marginal comes from the prior, how much from the data?
     Power-scaling sensitivity (Kallioinen, Paananen, Buerkner, Vehtari 2023; priorsense, ArviZ psens) over the draws the
-    predictive report takes -- the leading `k` chains of the device trace, the chains split R-hat covers, at
-    clamp(--loo_draws // k, 1, S) evenly spaced recorded steps (loo_steps), centred.  The likelihood of a draw is its
-    pointwise log-likelihoods (diagnostics.pointwise_loglik, in the observation tiles of the predictive report) folded by
-    diagnostics.loglik_total; the prior is the centred log joint at the same draws minus that -- the joint density of ALL
-    latent sites, the hierarchical layers included -- from an engine of the report's own set to CP, so that nothing of the
-    run's state is touched.  A draw the log-likelihood masks or whose log joint is not finite is left out and counted.  The
-    prior and the likelihood are raised to 1 / (1 + delta) and 1 + delta (diagnostics.powerscale_lw: Pareto-smoothed
-    weights), every element's pooled draws are ordered (diagnostics.element_order) and the weighted ECDFs folded
-    (diagnostics.cjs_sums, about `pooled_mean`); the statistics are diagnostics.psens_summary's.  The order of an element's
-    draws needs them on one device: a sharded job (world size > 1) writes null, says so once, and enters no collective --
-    the rule of the rank reports.  delta is fixed; no power-scaling sequence.  The choice of prior sites is
-    --sensitivity_prior_parts: a second report on the same draws, mask, likelihood and order whose prior is the named
-    parts' own (_psens_sites_report); its keys join these, its arrays are left in `side` under PSENS_SITES_ARRAYS, and it
-    changes nothing of the first report.  Its keys are null whenever these are.
-    Returns (JSON keys, arrays of <base>_psens.npz or None)."""
+    predictive report takes (select_draws: the leading `k` chains of the device trace, the chains split R-hat covers),
+    centred.  The likelihood of a draw is joint_loglik's, in the observation tiles of the predictive report; the prior is
+    the centred log joint at the same draws minus that -- the joint density of ALL latent sites, the hierarchical layers
+    included -- from an engine of the report's own set to CP, so that nothing of the run's state is touched.  A draw the
+    log-likelihood masks or whose log joint is not finite is left out and counted.  The prior and the likelihood are raised
+    to 1 / (1 + delta) and 1 + delta (diagnostics.powerscale_lw: Pareto-smoothed weights), every element's pooled draws are
+    ordered (diagnostics.element_order) and the weighted ECDFs folded (diagnostics.cjs_sums, about `pooled_mean`); the
+    statistics are diagnostics.psens_summary's.  The order of an element's draws needs them on one device: a sharded job
+    (world size > 1) writes null, says so once, and enters no collective -- the rule of the rank reports.  delta is fixed;
+    no power-scaling sequence.  The choice of prior sites is --sensitivity_prior_parts: a second report on the same draws,
+    mask, likelihood and order whose prior is the named parts' own (_psens_sites_report); its keys join these, its arrays
+    are left in `side` under PSENS_SITES_ARRAYS, and it changes nothing of the first report.  Its keys are null whenever
+    these are.  Returns (JSON keys, arrays of <base>_psens.npz or None)."""
     import torch
-    from . import engine as engine_lib
     if parallel.world()[1] > 1:
         return _psens_null("the chains of a sharded job are on several devices (the order of an element's pooled draws "
                            "needs them on one)", flags), None
     clock = time.time()
-    S, _, D = (int(v) for v in trace.shape)
-    k = int(k) if S > 0 else 0
-    if k <= 0:
-        return _psens_null("no chain has its trace on the device", flags), None
-    if D > diagnostics.LOGLIK_MAX_D:
-        return _psens_null("the model has more than {} elements".format(diagnostics.LOGLIK_MAX_D), flags), None
-    steps = loo_steps(S, k, getattr(flags, "loo_draws", 65536))
-    if not steps:
-        return _psens_null("more than {} chains".format(diagnostics.PSIS_MAX_DRAWS), flags), None
-    dev = trace.device
+    why, steps, draws = select_draws(trace, k, k, flags)
+    if why:
+        return _psens_null(why, flags), None
+    k, D, dev, R = int(k), int(trace.shape[2]), trace.device, len(steps) * int(k)
     table = diagnostics.upload_table(spec.observation_table(), D, dev)
-    draws = trace[torch.as_tensor(steps, device=dev), :k].contiguous()               # [len(steps), k, D]: a copy, D floats a draw
-    R, N = len(steps) * k, table.N
-    rows = loo_tile_rows(N, R)
+    rows = loo_tile_rows(table.N, R)
     ll_buffer = torch.empty(rows, R, dtype=torch.float32, device=dev)
-    log_lik = torch.zeros(R, dtype=torch.float64, device=dev)
-    mask = None
-    for n0 in range(0, N, rows):
-        ll, mask, _ = diagnostics.pointwise_loglik(draws, table, n0, min(N, n0 + rows), out=ll_buffer)
-        diagnostics.loglik_total(ll, log_lik)                                        # (ascending tiles: bitwise one call)
+    log_lik, mask = joint_loglik(draws, table, ll_buffer, rows)
     del ll_buffer
-    eng = engine_lib.Engine(spec, dev)                                               # the report's own handle: the run's stay as they are
+    eng = _engine.Engine(spec, dev)                                                  # the report's own handle: the run's stay as they are
     eng.set_param(0, "CP")
     log_joint = eng.logp_grad(draws.reshape(R, D), which=0)[0].to(torch.float64)
     logp_const = float(eng.logp_const(0))
@@ -1373,8 +1246,7 @@ def check_prior_predictive(flags):
 
 def _prior_null(why):
     """Every key of the prior predictive checks as null, with the one message that says why."""
-    util.print_("    prior predictive checks: not computed, {}".format(why))
-    return OrderedDict((key, None) for key in PRIOR_KEYS)
+    return _null_keys("prior predictive checks", why, PRIOR_KEYS)
 
 
 def prior_keys(summary, predictive, contraction, names):
@@ -1419,7 +1291,6 @@ def _prior_report(spec, flags, dev, post_mean, post_sd):
     to be wider than the data, so p-values near 0 or 1 for min and max are the expected reading, not a finding.  No prior
     draws at new covariates, no simulation-based calibration, no user-defined statistic.  Rank 0 of a sharded job runs it
     alone and enters no collective (the other ranks return nothing).  Returns (JSON keys, arrays of <base>_prior.npz or None)."""
-    import torch
     if parallel.world()[0] != 0:
         return {}, None
     clock = time.time()
@@ -1427,23 +1298,14 @@ def _prior_report(spec, flags, dev, post_mean, post_sd):
     if D > diagnostics.LOGLIK_MAX_D:
         return _prior_null("the model has more than {} elements".format(diagnostics.LOGLIK_MAX_D)), None
     R = int(min(max(int(getattr(flags, "loo_draws", 65536)), 1), diagnostics.SITE_MAX_DRAWS))
-    seed = (int(flags.seed) * 0x9E3779B97F4A7C15 + PRIOR_SEED) & 0xFFFFFFFFFFFFFFFF
+    seed = derived_seed(flags.seed, PRIOR_SEED)
     site = diagnostics.upload_site_table(spec.site_table(), D, dev)
     x, undrawn = diagnostics.site_prior_draws(site, R, seed=seed)
-    host_table = spec.observation_table()
-    N, kind = int(np.asarray(host_table.y).size), int(host_table.kind)
-    y = np.asarray(host_table.y, np.float32).reshape(-1)
-    table = diagnostics.upload_table(host_table, D, dev)
-    draws = x[None]                                                                      # [1, R, D]: one step, R chains
-    rows = ppc_tile_rows(N, R, diagnostics.predictive_workspace_bytes)
-    stats, sums, mask = None, [], None
-    for n0 in range(0, N, rows):
-        part, obs, _, mask, _ = diagnostics.predictive_check(draws, table, n0, min(N, n0 + rows),
-                                                             seed=(seed + 1) & 0xFFFFFFFFFFFFFFFF)
-        stats = part if stats is None else diagnostics.combine_draw_stats(stats, part)
-        sums.append(obs)
+    table = diagnostics.upload_table(spec.observation_table(), D, dev)
+    N, kind, y = table.N, table.kind, table.y_host
+    stats, sums, mask = replicate_tiles(x[None], table, next_seed(seed), budget=LOO_CHUNK_BYTES)      # [1, R, D]: one step, R chains
     left = (mask != 0) | (undrawn != 0)                                                  # (an undrawn element is NaN: masked too)
-    stats_host, obs_sums, left_host = _lib.host64(stats), _lib.host64(torch.cat(sums, dim=0)), left.cpu().numpy()
+    stats_host, obs_sums, left_host = _lib.host64(stats), _lib.host64(sums), left.cpu().numpy()
     summary = diagnostics.ppc_summary(stats_host, obs_sums, y, kind, left_host)
     predictive = diagnostics.prior_predictive_summary(stats_host, y, kind, left_host)
     kept = int(summary.draws_used)
@@ -1675,21 +1537,40 @@ def save_geometry(file_path_base, arrays):
     np.savez(file_path_base + "_geometry.npz", **arrays)
 
 
+# what _convergence_report hands a side report (k: the leading chains split R-hat covers; the moments: already all-reduced)
+_Run = collections.namedtuple("_Run", "kernel_results trace k n_split spec flags dev arrays split_mean pooled_mean pooled_sd")
+# A report with a side file, in run order: its flag; the tag its arrays wait under among those of _rhat.npz; null(flags) -> its
+# keys as null without a device trace; its writer; report(run) -> (JSON keys, arrays or None), or None: the row above leaves them.
+SideReport = collections.namedtuple("SideReport", "flag tag null save report")
+_NO_TRACE = "no chain has its trace on the device"
+SIDE_REPORTS = (
+    SideReport("energy_diagnostics", ENERGY_ARRAYS, None, save_energy,
+               lambda r: _energy_report(r.kernel_results, r.trace, r.spec, r.flags, r.dev)),
+    SideReport("trajectory_profile", TRAJECTORY_ARRAYS, None, save_trajectory,             # (LMAX: 0 is off)
+               lambda r: _trajectory_report(r.kernel_results, r.trace, r.spec, r.flags, r.dev, r.pooled_sd)),
+    SideReport("geometry_diagnostics", GEOMETRY_ARRAYS, None, save_geometry,
+               lambda r: _geometry_report(r.kernel_results, r.trace, r.k, r.spec, r.flags, r.dev, r.split_mean)),
+    SideReport("predictive_diagnostics", LOO_ARRAYS, lambda flags: _loo_null(_NO_TRACE, flags), save_loo,
+               lambda r: _loo_report(r.kernel_results, r.trace, r.k, r.spec, r.flags, r.arrays)),
+    SideReport(None, LOO_PRED_ARRAYS, None, save_loo_pred, None),
+    SideReport("predictive_checks", PPC_ARRAYS, lambda flags: _ppc_null(_NO_TRACE), save_ppc,
+               lambda r: _ppc_report(r.kernel_results, r.trace, r.k, r.n_split, r.spec, r.flags, r.dev)),
+    SideReport("sensitivity_diagnostics", PSENS_ARRAYS, lambda flags: _psens_null(_NO_TRACE, flags), save_psens,
+               lambda r: _psens_report(r.trace, r.k, r.spec, r.flags, r.split_mean, r.arrays)),
+    SideReport(None, PSENS_SITES_ARRAYS, None, save_psens_sites, None),
+    SideReport("prior_predictive_checks", PRIOR_ARRAYS,
+               lambda flags: _prior_null(_NO_TRACE + ", so there is no pooled posterior to set the prior against"), save_prior,
+               lambda r: _prior_report(r.spec, r.flags, r.trace.device, r.pooled_mean, r.pooled_sd)))
+
+
 def _save_diagnostics(file_path_base, arrays):
-    """The side files of the convergence report: <base>_rhat.npz and, where the probes ran, <base>_energy.npz,
-    <base>_trajectory.npz, <base>_geometry.npz, <base>_loo.npz, <base>_loopred.npz, <base>_ppc.npz, <base>_psens.npz,
-    <base>_psens_sites.npz and <base>_prior.npz."""
+    """<base>_rhat.npz, then the side file of every row of SIDE_REPORTS whose arrays _convergence_report left under its tag."""
     if arrays is None:
         return
-    # (tag _convergence_report left a side file's arrays under, its saver), in the order the files are written after _rhat.npz
-    side = [(arrays.pop(tag, None), save) for tag, save in (
-        (GEOMETRY_ARRAYS, save_geometry), (ENERGY_ARRAYS, save_energy), (TRAJECTORY_ARRAYS, save_trajectory),
-        (LOO_ARRAYS, save_loo), (LOO_PRED_ARRAYS, save_loo_pred), (PPC_ARRAYS, save_ppc), (PSENS_ARRAYS, save_psens),
-        (PSENS_SITES_ARRAYS, save_psens_sites), (PRIOR_ARRAYS, save_prior))]
+    side = [(row.save, arrays.pop(row.tag)) for row in SIDE_REPORTS if row.tag in arrays]
     save_rhat(file_path_base, arrays)
-    for side_arrays, save in side:
-        if side_arrays is not None:
-            save(file_path_base, side_arrays)
+    for save, side_arrays in side:
+        save(file_path_base, side_arrays)
 
 
 def save_rhat(file_path_base, arrays):
@@ -1935,17 +1816,6 @@ def save_hmc_results(file_path, **record):
     for key, value in record.items():
         history.setdefault(key, []).append(value)
     _write_json_atomic(file_path, history)
-
-
-def _write_json_atomic(file_path, obj):
-    """A reader (another rank at the top of its next phase, a later run) sees the old file or the new one, never a
-    half-written one: write next to it, then rename over it."""
-    tmp = "%s.tmp.%d" % (file_path, os.getpid())
-    with open(tmp, "w") as f:
-        json.dump(obj, f)
-        f.flush()
-        os.fsync(f.fileno())
-    os.replace(tmp, file_path)
 
 
 def save_ess(file_path_base, samples, normalized_ess_final, param_names, num_chains_to_save=0):

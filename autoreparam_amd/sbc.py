@@ -17,6 +17,8 @@ import numpy as np
 
 from . import diagnostics, inference, models, util
 from . import engine as _engine
+from .report_common import (_finite_or_none, _fmt, _nan_max, _write_json_atomic, derived_seed, element_names, joint_loglik,
+                            loo_tile_rows, next_seed, probe_steps, replicate_tiles)
 
 SBC_SEED = 0x53424331                # the report's own seed constant, as PRIOR_SEED is the prior predictive checks'
 SBC_REPLICATIONS_MIN, SBC_REPLICATIONS_MAX = 8, 16384
@@ -70,10 +72,9 @@ def check_sbc(flags):
 
 
 def sbc_steps_of(S, k):
-    """The recorded steps whose draws are ranked: k evenly spaced of S, the last among them (main.loo_steps' rule: counted
-    from the end, a single step is the last)."""
-    from . import main as _main
-    return sorted(int(S) - 1 - s for s in _main.probe_steps(int(S), int(k)))
+    """The recorded steps whose draws are ranked: k evenly spaced of S, the last among them (report_common.loo_steps' rule:
+    counted from the end, a single step is the last)."""
+    return sorted(int(S) - 1 - s for s in probe_steps(int(S), int(k)))
 
 
 def _direction(mean_z, var_z, var_ratio):
@@ -88,7 +89,6 @@ def sbc_keys(summary):
     per-replicate figures and the clocks -- are run_sbc's); pure Python.  Of every per-quantity family the entry that
     stands out, with the quantity's name.  sbc_p_threshold = SBC_P_LEVEL / Q, Bonferroni at the customary 1 %: a
     convention.  sbc_miscalibrated_elements: the quantities with ks_p below it, smallest p first."""
-    from .main import _finite_or_none, _nan_max
     s = summary
     Q = len(s.names)
     keys = OrderedDict([("sbc_replications", int(s.replications + s.left_out)), ("sbc_replications_left_out", int(s.left_out)),
@@ -116,7 +116,6 @@ def sbc_keys(summary):
 
 def sbc_line(keys, summary):
     """The one printed line: the worst quantity, its p and its two shape figures."""
-    from .main import _fmt
     name = keys["sbc_p_min_element"]
     at = summary.names.index(name) if name is not None else -1
     fig = lambda v: _fmt(float(v[at]) if at >= 0 and np.isfinite(v[at]) else None)
@@ -131,7 +130,6 @@ def sbc_line(keys, summary):
 
 def sbc_warning(keys, summary):
     """The one warning, or None: up to SBC_SHOWN quantities with p below the threshold, and which way each is off."""
-    from .main import _fmt
     names = keys["sbc_miscalibrated_elements"]
     if not names:
         return None
@@ -170,24 +168,14 @@ def _replicate_flags(flags, r, chains):
 
 
 def _joint_loglik(rows, table, y, ll_buffer, tile_rows):
-    """The joint log-likelihood of the data `y` ([n] float32 on the device) at every row of `rows` [R, D]: the uploaded
-    observation table with only its y column replaced, pointwise in tiles of observations (diagnostics.pointwise_loglik),
-    observations ascending (diagnostics.loglik_total).  Returns (total [R] float64, mask [R])."""
-    import torch
-    table = table._replace(y=y, y_host=None)
-    R = int(rows.shape[0])
-    total = torch.zeros(R, dtype=torch.float64, device=rows.device)
-    mask = None
-    for n0 in range(0, table.N, tile_rows):
-        ll, mask, _ = diagnostics.pointwise_loglik(rows[None], table, n0, min(table.N, n0 + tile_rows), out=ll_buffer)
-        diagnostics.loglik_total(ll, total)
-    return total, mask
+    """joint_loglik of the data `y` [n] at the rows [R, D]: the uploaded table with only y replaced, one reused `ll_buffer`."""
+    return joint_loglik(rows[None], table._replace(y=y, y_host=None), ll_buffer, tile_rows)
 
 
 def run_sbc(model_config, results_dir, file_path, flags, out=None):
     """--inference=SBC.  N = --sbc_replications truths are drawn from the uploaded site table under a seed derived from
     --seed and SBC_SEED, one replicated data set each under the next seed (main._prior_report says why not the same), in
-    main.ppc_tile_rows tiles of observations.  A replicate whose draw is undrawn or masked or whose data hold a non-finite
+    replicate_tiles' tiles of observations.  A replicate whose draw is undrawn or masked or whose data hold a non-finite
     value is left out before any refit, and counted.  Every other replicate r is refitted the way run_vi and run_hmc fit:
     ModelSpec.with_observations -> models.model_config_for -> main.create_target_graph -> inference.find_best_learning_rate
     -> util.variational_inits_from_params -> inference.hmc with seed --seed + 1 + r and chain_offset r M, so that no two
@@ -200,7 +188,7 @@ def run_sbc(model_config, results_dir, file_path, flags, out=None):
     method's files; the fit file of the real data is neither read nor written.  With `out`, out["sbc"] holds the device
     buffer ("draws"), the truth tensor ("truth"), the replicated data [observations, N] ("data") and the summary."""
     import torch
-    from . import main as _main
+    from .main import create_target_graph        # the refit is what the command line builds (main imports this module)
     base = file_path[:-5] + SBC_SUFFIX
     if os.path.exists(base + ".json"):
         util.print_("Already ran experiment {}-{} on model {} with dataset {}. Skipping".format(
@@ -228,18 +216,12 @@ def run_sbc(model_config, results_dir, file_path, flags, out=None):
                 "steps, {} recorded step(s) ranked".format(flags.inference, flags.method, flags.model, flags.dataset, N, M,
                                                            flags.num_leapfrog_steps, len(steps)))
     # ---- 1. truths and data ----
-    seed = (int(flags.seed) * 0x9E3779B97F4A7C15 + SBC_SEED) & 0xFFFFFFFFFFFFFFFF
+    seed = derived_seed(flags.seed, SBC_SEED)
     site = diagnostics.upload_site_table(spec.site_table(), D, dev)
     x, undrawn = diagnostics.site_prior_draws(site, N, seed=seed)
     table = diagnostics.upload_table(host_table, D, dev)
     y_all = torch.empty(n_obs, N, dtype=torch.float32, device=dev)
-    rows = _main.ppc_tile_rows(n_obs, N, diagnostics.predictive_workspace_bytes)
-    mask = None
-    for n0 in range(0, n_obs, rows):
-        n1 = min(n_obs, n0 + rows)
-        _, _, y_rep, mask, _ = diagnostics.predictive_check(x[None], table, n0, n1, seed=(seed + 1) & 0xFFFFFFFFFFFFFFFF,
-                                                            want_y_rep=True)
-        y_all[n0:n1] = y_rep
+    _, _, mask = replicate_tiles(x[None], table, next_seed(seed), y_rep_out=y_all)   # (the statistics: not wanted here)
     skipped = ((mask != 0) | (undrawn != 0) | ~torch.isfinite(y_all).all(dim=0)).cpu().numpy()
     y_host = y_all.t().contiguous().cpu().numpy()                                   # [N, n_obs]
     buffer = torch.zeros(N, L, Q, dtype=torch.float32, device=dev)
@@ -249,9 +231,8 @@ def run_sbc(model_config, results_dir, file_path, flags, out=None):
     accept_rate, ess_min, elbo = nan.copy(), nan.copy(), nan.copy()
     fit_time = mcmc_time = 0.0
     step_index = torch.as_tensor(steps, device=dev)
-    ll_rows = _main.loo_tile_rows(n_obs, L + 1)
+    ll_rows = loo_tile_rows(n_obs, L + 1)
     ll_buffer = torch.empty(ll_rows, L + 1, dtype=torch.float32, device=dev)
-    names = _main.element_names(spec)
     for r in range(N):
         if skipped[r]:
             continue
@@ -259,7 +240,7 @@ def run_sbc(model_config, results_dir, file_path, flags, out=None):
         config_r = models.model_config_for(spec_r)
         flags_r = _replicate_flags(flags, r, M)
         try:
-            target, _, elbo_graph, vp, lp, reparam = _main.create_target_graph(config_r, results_dir, flags_r)
+            target, _, elbo_graph, vp, lp, reparam = create_target_graph(config_r, results_dir, flags_r)
             tick = time.time()
             try:
                 fit = inference.find_best_learning_rate(elbo_graph, vp, learnable_parameters_prior=None, learnable_parameters=lp,
@@ -305,15 +286,14 @@ def run_sbc(model_config, results_dir, file_path, flags, out=None):
     tick = time.time()
     counts, sums, left_out, _ = diagnostics.sbc_fold(buffer, truth)
     left_host = left_out.cpu().numpy()
-    summary = diagnostics.sbc_summary(counts, sums, L, left_host, names + [LOG_LIKELIHOOD])
+    summary = diagnostics.sbc_summary(counts, sums, L, left_host, element_names(spec) + [LOG_LIKELIHOOD])
     fold_time = time.time() - tick
     # ---- 5. outputs ----
     keys = sbc_keys(summary)
     kept = left_host == 0
-    median = lambda v: _main._finite_or_none(np.median(v[kept & np.isfinite(v)])) if np.any(kept & np.isfinite(v)) else None
-    mean = lambda v: _main._finite_or_none(np.mean(v[kept & np.isfinite(v)])) if np.any(kept & np.isfinite(v)) else None
+    kept_only = lambda fold, v: _finite_or_none(fold(v[kept & np.isfinite(v)])) if np.any(kept & np.isfinite(v)) else None
     keys.update([("sbc_chains", M), ("sbc_steps", len(steps)), ("sbc_leapfrog_steps", int(flags.num_leapfrog_steps)),
-                 ("sbc_accept_rate_mean", mean(accept_rate)), ("sbc_ess_min_median", median(ess_min)),
+                 ("sbc_accept_rate_mean", kept_only(np.mean, accept_rate)), ("sbc_ess_min_median", kept_only(np.median, ess_min)),
                  ("sbc_fit_time_sec", fit_time), ("sbc_mcmc_time_sec", mcmc_time), ("sbc_fold_time_sec", fold_time)])
     util.print_(sbc_line(keys, summary))
     warning = sbc_warning(keys, summary)
@@ -330,7 +310,7 @@ def run_sbc(model_config, results_dir, file_path, flags, out=None):
     save_sbc(base, arrays)
     keys["sbc_time_sec"] = time.time() - clock
     record = OrderedDict((key, keys[key]) for key in SBC_KEYS)
-    _main._write_json_atomic(base + ".json", record)
+    _write_json_atomic(base + ".json", record)
     if out is not None:
         out["sbc"] = {"draws": buffer, "truth": truth, "data": y_all, "summary": summary}
     return record
