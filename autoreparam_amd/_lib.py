@@ -86,7 +86,7 @@ SYMBOLS = ["arp_version", "arp_last_error", "arp_model_create", "arp_model_destr
            "arp_predictive_workspace_bytes", "arp_predictive_check",
            "arp_loo_predictive_workspace_bytes", "arp_loo_predictive",
            "arp_loglik_total", "arp_element_order_workspace_bytes", "arp_element_order", "arp_cjs_sums",
-           "arp_site_logprior", "arp_site_prior_draws", "arp_sbc_fold",
+           "arp_site_logprior", "arp_site_prior_draws", "arp_site_redraw", "arp_sbc_fold",
            "arp_adapt_probe", "arp_clock_probe", "arp_energy_probe",
            "arp_trajectory_probe", "arp_jump_workspace_bytes", "arp_jump_sums"]
 
@@ -209,6 +209,9 @@ def lib():
     L.arp_site_prior_draws.argtypes = [C.c_int32] + [C.c_void_p] * 7 + [C.c_int64, C.c_uint64, C.c_int64, C.c_void_p, C.c_int64,
                                                                        C.c_void_p, C.c_void_p]
     L.arp_site_prior_draws.restype = C.c_int
+    L.arp_site_redraw.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int64] + [C.c_void_p] * 8 + [
+        C.c_uint64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+    L.arp_site_redraw.restype = C.c_int
     L.arp_sbc_fold.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_int64,
                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.arp_sbc_fold.restype = C.c_int

@@ -280,7 +280,8 @@ def report_ppc(results):
     """Build-specific: the posterior predictive checks of every sampling run that recorded them (--predictive_checks; the
     last run of each file): the predictive p-values of mean, sd, min, max and deviance, the replicated against the
     observed mean and sd, and the calibration of the PIT values.  The posterior PIT, not LOO-PIT; an extreme p-value is
-    marked by the customary reading (outside [0.01, 0.99]), not by a derived threshold."""
+    marked by the customary reading (outside [0.01, 0.99]), not by a derived threshold.  A run with
+    --predictive_checks_redraw gets a second line: the mixed predictive check's figures, each with the posterior one."""
     lines = []
     for m, r in results.items():
         if "ppc_observations" not in r:
@@ -298,6 +299,21 @@ def report_ppc(results):
                          _fmt(last["ppc_coverage_90"]), last["ppc_observations"], last["ppc_draws"], last["ppc_chains"],
                          last["ppc_draws_left_out"], _secs(last.get("ppc_time_sec")),
                          "   <-- EXTREME: " + ", ".join(extreme) if extreme else ""))
+        if last.get("ppc_mixed_draws") is not None:
+            # the mixed predictive check (--predictive_checks_redraw), with the posterior figure next to each of its own: a
+            # mixed p-value or PIT distance that is extreme where the posterior one is not is a misfit of the redrawn layer,
+            # which a check at group effects fitted to the data cannot see
+            pair = lambda key: "{} (posterior {})".format(_fmt(last.get("ppc_mixed_" + key)), _fmt(last.get("ppc_" + key)))
+            mixed_extreme = [s for s in stats if last.get("ppc_mixed_p_" + s) is not None
+                             and not 0.01 <= last["ppc_mixed_p_" + s] <= 0.99]
+            outliers = last.get("ppc_mixed_pit_extreme_observations")
+            lines.append("      mixed predictive, {} redrawn ({} elements): p-values {}; replicated sd {}; PIT Kolmogorov distance "
+                         "{}, 90 % coverage {}; {} observation(s) with an extreme mixed PIT; {} draws, {} left out; {}{}".format(
+                             ",".join(last.get("ppc_mixed_parts") or []), last.get("ppc_mixed_elements"),
+                             ", ".join("{} {}".format(s, pair("p_" + s)) for s in stats), pair("rep_sd"), pair("pit_ks"),
+                             pair("coverage_90"), "n/a" if outliers is None else len(outliers), last["ppc_mixed_draws"],
+                             last.get("ppc_mixed_draws_left_out"), _secs(last.get("ppc_mixed_time_sec")),
+                             "   <-- EXTREME: " + ", ".join(mixed_extreme) if mixed_extreme else ""))
     return lines
 
 

@@ -1,7 +1,8 @@
 // Ancestral draws from the prior (include/autoreparam.h: arp_site_prior_draws): the model's latent site table
 // (autoreparam_amd/models.py: ModelSpec.site_table) walked front to back, n_draws times -- the generating twin of
 // arp_site_logprior (prior.hip), what a prior predictive check and the prior-to-posterior contraction are computed from.
-// Model-independent; needs no model handle.  Build-specific: the reference never draws from a prior.
+// Model-independent; needs no model handle.  Build-specific: the reference never draws from a prior.  The draw of one
+// element, as specified below, is site_draw.h's site_draw_element, which site_redraw.hip walks the same table with.
 //
 //   loc_d = loc0[d] + sum_t loc_w[d][t] x[loc_idx[d][t]],   s_d = log_scale0[d] + sum_t scale_w[d][t] x[scale_idx[d][t]]
 //   form 0 (Normal, scale exp(s)):       x_d = loc_d + exp(s_d) z
@@ -74,22 +75,12 @@
 //  * A term of weight 0 multiplies what it points at: 0 times an infinite parent is NaN, as in arp_site_logprior.
 #include "arp_device.h"
 #include "obs_table.h"
-#include "site_table.h"
+#include "site_draw.h"
 
 #pragma clang fp contract(off)
 
 namespace arp {
 namespace {
-
-constexpr int kPdAttempts = 32;
-constexpr long long kPdMaxR = 1ll << 24;
-constexpr float kTwoPowM32 = 2.3283064365386963e-10f, kTwoPowM33 = 1.1641532182693481e-10f;
-
-// ppc.hip's z from words 0 and 1
-__device__ __forceinline__ float draw_z(uint32_t w0, uint32_t w1) {
-  const float up = fmaf((float)w0, kTwoPowM32, kTwoPowM33);
-  return sqrtf(-2.0f * logf(up)) * cospif(2.0f * angle_rev(w1));
-}
 
 __global__ __launch_bounds__(kObsDraws) void prior_draw_kernel(int D, const int* __restrict__ form, const int* __restrict__ loc_idx,
                                                                const float* __restrict__ loc_w, const float* __restrict__ loc0,
@@ -110,44 +101,7 @@ __global__ __launch_bounds__(kObsDraws) void prior_draw_kernel(int D, const int*
   for (int d = 0; d < D; ++d) row[d] = 0.0f;     // an element that is not drawn yet reads as 0
   bool failed = false;
   for (int d = 0; d < D; ++d) {
-    const int f = form[d];
-    const float s = site_chain(row, scale_idx, scale_w, log_scale0[d], d, D);
-    float v;
-    uint32_t rnd[4];
-    if (f == 2) {
-      const float k = loc0[d];
-      v = __builtin_nanf("");
-      if (k > 0.0f && k < __builtin_inff()) {    // (wave-uniform)
-        const bool boost = k < 1.0f;
-        const float a = boost ? k + 1.0f : k;
-        const float dd = a - (1.0f / 3.0f);
-        const float c = 1.0f / sqrtf(9.0f * dd);
-        const float dd3 = 3.0f * dd;
-        bool done = false;
-        for (int j = 0; j < kPdAttempts && !__all(done); ++j) {
-          philox4x32_10((uint32_t)d, g_lo, g_hi, 1u + (uint32_t)j, key0, key1, rnd);
-          const float z = draw_z(rnd[0], rnd[1]);
-          const float t = 1.0f + c * z;
-          const float U = fmaf((float)rnd[2], kTwoPowM32, kTwoPowM33);
-          const float lt = logf(t);              // NaN for t < 0: the comparison below is then false as well
-          const float rhs = ((0.5f * (z * z) + dd) - dd * ((t * t) * t)) + dd3 * lt;
-          if (!done && t > 0.0f && logf(U) < rhs) {
-            const float Ub = fmaf((float)rnd[3], kTwoPowM32, kTwoPowM33);
-            const float b = boost ? logf(Ub) / k : 0.0f;
-            v = ((logf(dd) + 3.0f * lt) + b) - s;
-            done = true;
-          }
-        }
-        failed = failed || !done;
-      }
-    } else {
-      philox4x32_10((uint32_t)d, g_lo, g_hi, 0u, key0, key1, rnd);
-      const float z = draw_z(rnd[0], rnd[1]);
-      const float loc = site_chain(row, loc_idx, loc_w, loc0[d], d, D);
-      const float sigma = f == 1 ? fmaxf(s, 0.0f) + log1pf(expf(-fabsf(s))) : expf(s);
-      v = loc + sigma * z;
-    }
-    row[d] = v;
+    row[d] = site_draw_element(row, d, D, form, loc_idx, loc_w, loc0, scale_idx, scale_w, log_scale0, g_lo, g_hi, key0, key1, failed);
   }
   if (undrawn && lane < nrows) undrawn[r0 + lane] = failed ? 1 : 0;
   __syncthreads();

@@ -27,7 +27,9 @@ slightly off 1, as a cumulative Jensen-Shannon distance; Kallioinen et al. 2023)
 latent site, summed over chosen groups of elements, for power-scaling chosen priors alone (`upload_site_table`,
 `site_logprior` on `arp_site_logprior`); and the prior itself (`site_prior_draws` on `arp_site_prior_draws`: ancestral draws
 from the site table; `prior_predictive_summary`, `prior_contraction_summary`: what data the prior generates, and how far
-the data moved every marginal away from it).
+the data moved every marginal away from it), and the same walk over recorded draws (`site_redraw` on `arp_site_redraw`: the
+parts `redraw_selection` flags drawn anew from their conditional prior, the rest kept -- the rows a mixed predictive check
+replicates its data from).
 
 Build-specific (the reference runs 100 chains and reports the within-chain ESS only).  The per-chain moments come from
 one pass over a trace that is already on the device (`arp_split_moments`) or from the in-kernel statistics of a
@@ -1288,6 +1290,108 @@ def site_prior_draws(table, draws, seed=0, draw_offset=0, device=None, out=None)
               _lib.ptr(table.loc0), _lib.ptr(table.scale_idx), _lib.ptr(table.scale_w), _lib.ptr(table.log_scale0), R,
               int(seed) & 0xFFFFFFFFFFFFFFFF, int(draw_offset), _lib.ptr(x), stride, _lib.ptr(undrawn))
     return x, undrawn
+
+
+def site_redraw(trace, table, redraw, seed=0, draw_offset=0, out=None):
+    """(x, undrawn) of `arp_site_redraw` for a recorded CENTRED [S, C, D] float32 trace on the GPU, a DeviceSiteTable and
+    `redraw`, [D] flags (anything numpy reads, or a uint8 device tensor): x [S C, D] float32, row s C + c the recorded draw
+    (s, c) with every flagged element drawn anew from its conditional prior given the rest of the row -- exactly as
+    site_prior_draws draws it, its parents read from the row being built -- and every other element as recorded, bit for
+    bit; as x[None] a centred trace of one step and S C chains, which predictive_check takes in place.  undrawn [S C] uint8
+    as site_prior_draws'.  Row r is a function of (seed, draw_offset + r), the flags and its own recorded row alone:
+    `draw_offset` is the global number of this trace's first draw.  A block of chains of a wider trace is read in place,
+    as pointwise_loglik reads it.  out: as site_prior_draws'.  WHICH elements may be flagged is `redraw_selection`'s rule,
+    not checked here.  Refused here, before any call: what the kernel refuses."""
+    who = "site_redraw"
+    if not isinstance(table, DeviceSiteTable):
+        raise ValueError("%s: a DeviceSiteTable is required (upload_site_table)" % who)
+    D = int(table.D)
+    if not 1 <= D <= LOGLIK_MAX_D:
+        raise ValueError("%s: 1 <= D <= %d elements are required" % (who, LOGLIK_MAX_D))
+    if int(draw_offset) < 0:
+        raise ValueError("%s: draw_offset >= 0 is required" % who)
+    flags = redraw if torch.is_tensor(redraw) else np.asarray(redraw)
+    if tuple(flags.shape) != (D,) or (torch.is_tensor(flags) and flags.dtype != torch.uint8) or \
+            (not torch.is_tensor(flags) and flags.dtype.kind not in "biu"):
+        raise ValueError("%s: redraw must be [%d] flags (bool or integers; a tensor: uint8)" % (who, D))
+    x, S, Cn, Dx, row_stride = _lib.trace_view(trace, who)
+    R = S * Cn
+    if R == 0 or Dx == 0:
+        raise ValueError("%s: an empty trace" % who)
+    if Dx != D:
+        raise ValueError("%s: the trace has %d elements, the table %d" % (who, Dx, D))
+    if R > SITE_MAX_DRAWS:
+        raise ValueError("%s: at most 2^24 draws (S C) are taken" % who)
+    dev = x.device
+    if table.form.device != dev:
+        raise ValueError("%s: the table must be on the trace's device" % who)
+    if torch.is_tensor(flags):
+        flags = flags.to(dev).contiguous()
+    else:
+        flags = torch.as_tensor(np.ascontiguousarray(flags != 0, np.uint8), device=dev)
+    if out is None:
+        rows, stride = torch.empty(R, D, dtype=torch.float32, device=dev), D
+    else:
+        rows, stride = _rows_out(out, R, D, who, "out")
+        if rows.device != dev:
+            raise ValueError("%s: out must be on the trace's device" % who)
+        if rows.data_ptr() == x.data_ptr():
+            raise ValueError("%s: out must not be the trace (the rows are rebuilt from the recorded ones)" % who)
+    undrawn = torch.empty(R, dtype=torch.uint8, device=dev)
+    _lib.call(dev, _lib.lib().arp_site_redraw, _lib.ptr(x), S, Cn, D, row_stride, _lib.ptr(table.form), _lib.ptr(table.loc_idx),
+              _lib.ptr(table.loc_w), _lib.ptr(table.loc0), _lib.ptr(table.scale_idx), _lib.ptr(table.scale_w),
+              _lib.ptr(table.log_scale0), _lib.ptr(flags), int(seed) & 0xFFFFFFFFFFFFFFFF, int(draw_offset), _lib.ptr(rows), stride,
+              _lib.ptr(undrawn))
+    return rows, undrawn
+
+
+REDRAW_FLAG = "--predictive_checks_redraw"
+
+
+def redraw_selection(site_table, part_names, names):
+    """The [D] uint8 flags site_redraw takes for the latent parts `names` of a model: 1 for every element of a named part.
+    The ONE place where the rule of a mixed predictive check's selection is defined; pure numpy.  site_table: a
+    models.SiteTable (or the host copy of an uploaded one); part_names: the model's, which site_table.part indexes.
+    Raises ValueError, naming the flag and the model's parts, for an empty name, a duplicate, a name that is no part --
+    and for a selection that is not closed under descent: if an element that stays as recorded has a term of non-zero
+    weight (in its loc or its log-scale; the log-Gamma form does not read its loc terms) at a flagged element, it was drawn
+    GIVEN the recorded value of what is now redrawn, and the row is a draw from no distribution the model defines
+    (mua redrawn, the m drawn from it kept).  The message names the parts that would have to be added (the closure)."""
+    parts = [str(p) for p in part_names]
+    names = [str(n) for n in names]
+    tail = "; the model's parts: %s" % ", ".join(parts)
+    if not names or "" in names:
+        raise ValueError("%s: an empty name in %r%s" % (REDRAW_FLAG, ",".join(names), tail))
+    if len(set(names)) != len(names):
+        raise ValueError("%s: %s is named twice%s" % (REDRAW_FLAG, ", ".join(sorted({n for n in names if names.count(n) > 1})), tail))
+    unknown = [n for n in names if n not in parts]
+    if unknown:
+        raise ValueError("%s: %s is no latent part of the model%s" % (REDRAW_FLAG, ", ".join(unknown), tail))
+    part = np.asarray(site_table.part, np.int64).reshape(-1)
+    form = np.asarray(site_table.form, np.int64).reshape(-1)
+    D = part.size
+    chosen = np.zeros(len(parts), bool)
+    chosen[[parts.index(n) for n in names]] = True
+    closed = chosen.copy()
+    columns = ((np.asarray(site_table.loc_idx), np.asarray(site_table.loc_w), form != 2),
+               (np.asarray(site_table.scale_idx), np.asarray(site_table.scale_w), np.ones(D, bool)))
+    while True:                                  # the parts of every element that descends from a flagged one
+        flagged = closed[part]
+        hangs = np.zeros(D, bool)
+        for idx, w, read in columns:
+            at = np.clip(np.asarray(idx, np.int64), 0, D - 1)
+            hangs |= read & np.any((np.asarray(w) != 0) & flagged[at], axis=1)
+        more = np.zeros(len(parts), bool)
+        more[part[hangs & ~flagged]] = True
+        if not more.any():
+            break
+        closed |= more
+    missing = [p for k, p in enumerate(parts) if closed[k] and not chosen[k]]
+    if missing:
+        raise ValueError("%s: %s would stay as recorded although drawn from what is redrawn (%s) -- such a row is a draw from "
+                         "no distribution the model defines; add %s%s" % (
+                             REDRAW_FLAG, ", ".join(missing), ", ".join(n for n in parts if n in names), ",".join(missing), tail))
+    return chosen[part].astype(np.uint8)
 
 
 # ---- prior predictive checks: what the prior says before it has seen data, and how far the data moved it ----

@@ -112,6 +112,24 @@ _DEFS = [
                                        "no user-defined statistic.  "
                                        "Every quantity is a sum over draws: sharded jobs included.  Refused for "
                                        "neals_funnel, which has no observations."),
+    ("predictive_checks_redraw", str, "", "With --predictive_checks only: PART[,PART...], latent parts of the model (e.g. m for "
+                                          "radon, theta for 8schools, beta_log_scales,beta for "
+                                          "german_credit_gammascale).  The MIXED predictive check (Gelman, Meng, Stern 1996; "
+                                          "Marshall, Spiegelhalter 2007) next to the posterior one, on the same draws: every "
+                                          "draw keeps its hyperparameters, the named parts are drawn anew from their "
+                                          "conditional prior given them (arp_site_redraw over ModelSpec.site_table) and the "
+                                          "data are replicated from the redrawn rows (arp_predictive_check).  The posterior "
+                                          "check replicates at group effects fitted to the very data they are checked "
+                                          "against; the mixed one asks whether a NEW group under these hyperparameters would "
+                                          "have produced an observation -- leave-group-out cross-validation without a refit "
+                                          "(ppc_mixed_* JSON keys, <base>_ppc_mixed.npz; analyze --ppc prints a second line).  "
+                                          "Every output of --predictive_checks is bit for bit unchanged.  The selection is by "
+                                          "part, not by element or group; the data are replicated at the observed "
+                                          "covariates; no per-group test statistics.  Refused: the flag without "
+                                          "--predictive_checks, neals_funnel, a name that is no part of the model, a "
+                                          "duplicate, an empty name, and a selection that is not closed under descent -- a "
+                                          "part that stays as recorded although it was drawn from a redrawn one (mua without "
+                                          "m); the message names the parts to add."),
     ("loo_predictive", bool, False, "With --predictive_diagnostics only: the leave-one-out predictive report.  The predictive "
                                     "mean, variance and PIT value of every observation at every draw, folded with the "
                                     "Pareto-smoothed weights of its own leave-one-out posterior (arp_psis_weights, "

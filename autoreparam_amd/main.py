@@ -901,9 +901,61 @@ def check_predictive_checks(flags):
         raise ValueError("--predictive_checks: neals_funnel has no observations, so there is no data to replicate")
 
 
-def _ppc_null(why):
-    """Every key of the predictive checks as null, with the one message that says why."""
-    return _null_keys("posterior predictive checks", why, PPC_KEYS)
+PPC_MIXED_ARRAYS = "ppc_mixed/"      # where _ppc_report leaves the arrays of <base>_ppc_mixed.npz among those of _ppc.npz
+PPC_MIXED_SEED = 0x50504D58          # the mixed check's own seed constant: its redraws, and (the next seed) its replicates
+PPC_MIXED_SHOWN = 8                  # observations with an extreme mixed PIT the printed line names
+PPC_MIXED_KEYS = ("ppc_mixed_parts", "ppc_mixed_elements", "ppc_mixed_draws", "ppc_mixed_draws_left_out", "ppc_mixed_p_mean",
+                  "ppc_mixed_p_sd", "ppc_mixed_p_min", "ppc_mixed_p_max", "ppc_mixed_p_deviance", "ppc_mixed_rep_mean",
+                  "ppc_mixed_rep_sd", "ppc_mixed_pit_ks", "ppc_mixed_coverage_90", "ppc_mixed_pit_extreme_observations",
+                  "ppc_mixed_pit_min_observation", "ppc_mixed_time_sec")
+
+
+def redraw_parts(flags):
+    """The names --predictive_checks_redraw gives, in the order given; [] without the flag."""
+    text = getattr(flags, "predictive_checks_redraw", "") or ""
+    return text.split(",") if text else []
+
+
+def check_predictive_redraw(flags):
+    """--predictive_checks_redraw against the job, before anything runs -- raises ValueError for the flag without
+    --predictive_checks, for neals_funnel (no observations) and for whatever diagnostics.redraw_selection refuses: an empty
+    name, a duplicate, a name that is no latent part, a selection that is not closed under descent."""
+    names = redraw_parts(flags)
+    if not names:
+        return
+    if not getattr(flags, "predictive_checks", False):
+        raise ValueError("--predictive_checks_redraw is read with --predictive_checks only")
+    if flags.model == "neals_funnel":
+        raise ValueError("--predictive_checks_redraw: neals_funnel has no observations, so there is no data to replicate")
+    spec = models.spec_by_name(flags.model, dataset=getattr(flags, "dataset", None))
+    diagnostics.redraw_selection(spec.site_table(), spec.part_names, names)
+
+
+def _ppc_null(why, flags=None):
+    """Every key of the predictive checks, and of --predictive_checks_redraw where set, as null; one message says why."""
+    return _null_keys("posterior predictive checks", why, PPC_KEYS + (PPC_MIXED_KEYS if redraw_parts(flags) else ()))
+
+
+def ppc_mixed_keys(summary, chosen, n_elements, kind):
+    """The JSON keys of the mixed predictive check (all but ppc_mixed_time_sec) from the diagnostics.PpcSummary of the data
+    replicated at the REDRAWN rows, the parts redrawn (in part order) and how many elements they hold; pure Python.  The
+    nulls of Bernoulli data are those of ppc_keys; the two PIT keys are per observation and Normal data's alone, as
+    ppc_pit_ks is."""
+    num = lambda v: None if v is None else _finite_or_none(v)
+    keys = OrderedDict([("ppc_mixed_parts", list(chosen)), ("ppc_mixed_elements", int(n_elements)),
+                        ("ppc_mixed_draws", int(summary.draws_used)), ("ppc_mixed_draws_left_out", int(summary.draws_left_out))])
+    for name in diagnostics.PPC_STATISTICS:
+        keys["ppc_mixed_p_" + name] = num(summary.p[name])
+    keys.update([("ppc_mixed_rep_mean", num(summary.rep["mean"])), ("ppc_mixed_rep_sd", num(summary.rep["sd"])),
+                 ("ppc_mixed_pit_ks", num(summary.pit_ks)), ("ppc_mixed_coverage_90", num(summary.coverage_90))])
+    pit = np.asarray(summary.pit, np.float64)
+    defined = int(kind) == 0 and summary.draws_used > 0 and pit.size > 0
+    with np.errstate(invalid="ignore"):
+        extreme = np.flatnonzero((pit < PPC_EXTREME[0]) | (pit > PPC_EXTREME[1])) if defined else []
+    at = _nan_max(-pit)[1] if defined else -1                              # (the smallest finite PIT)
+    keys["ppc_mixed_pit_extreme_observations"] = [int(n) for n in extreme] if defined else None
+    keys["ppc_mixed_pit_min_observation"] = at if at >= 0 else None
+    return keys
 
 
 def ppc_keys(summary, n_chains, n_steps):
@@ -930,11 +982,26 @@ def _ppc_report(kernel_results, trace, k, k_total, spec, flags, dev):
     is a sum over draws: the counts behind the p-values and the per-observation sums go through ONE all-reduce, and a
     sharded job reports real numbers (rank 0 writes them; <base>_ppc.npz then holds the draw statistics of rank 0's draws).
     The posterior PIT (the LOO-PIT: --loo_predictive); no group-level statistics; no user-defined statistic.
+    --predictive_checks_redraw=PART[,PART...]: the MIXED predictive check (Gelman, Meng, Stern 1996; Marshall,
+    Spiegelhalter 2007) on the same draws, the same tiles and the same global draw numbers.  The posterior check replicates
+    y at group effects that were fitted to that very y, so it cannot say whether the effects look like draws from their own
+    prior layer; here every draw keeps its hyperparameters, the named parts are drawn anew from their conditional prior
+    given them (diagnostics.site_redraw over ModelSpec.site_table, the selection diagnostics.redraw_selection's, seeded by
+    --seed and PPC_MIXED_SEED) and the data are replicated from the redrawn rows as a one-step trace [1, R, D]
+    (replicate_tiles under the next seed -- the redraws' own would hand element d and observation d the same Philox
+    words).  ppc_counts and ppc_from_counts as above, the counts and sums in the SAME all-reduce: no new statistic, no
+    second definition, and real numbers from a sharded job.  The mixed PIT of an observation asks whether a NEW group under
+    these hyperparameters would have produced it -- leave-group-out cross-validation without a refit.  Every PPC_KEYS value
+    and every array of <base>_ppc.npz is the unflagged run's; the keys are null whenever the posterior check's are; the
+    arrays of <base>_ppc_mixed.npz wait among the returned ones under PPC_MIXED_ARRAYS, where save_ppc finds them.
+    Selection by part, not by element or group; the data are still replicated at the observed covariates; no per-group
+    statistics.
     Returns (JSON keys, arrays of <base>_ppc.npz or None).  (A collective when ws > 1: every rank calls it.)"""
     clock = time.time()
     why, steps, draws = select_draws(trace, k, k_total, flags)
     if why:
-        return _ppc_null(why), None
+        return _ppc_null(why, flags), None
+    names = redraw_parts(flags)
     host_table = spec.observation_table()
     N, kind = int(np.asarray(host_table.y).size), int(host_table.kind)
     y = np.asarray(host_table.y, np.float32).reshape(-1)
@@ -945,7 +1012,25 @@ def _ppc_report(kernel_results, trace, k, k_total, spec, flags, dev):
         stats, sums, mask = replicate_tiles(draws, table, derived_seed(flags.seed, PPC_SEED), draw_offset, budget=LOO_CHUNK_BYTES)
         stats_host, obs_sums = _lib.host64(stats), _lib.host64(sums)
         counts = diagnostics.ppc_counts(stats_host, y, mask)
-    counts, obs_sums = _reduced([counts, obs_sums], dev)
+    mixed, mixed_time = None, 0.0
+    if names:
+        mixed_clock = time.time()
+        redrawn = diagnostics.redraw_selection(spec.site_table(), spec.part_names, names)
+        mixed_counts, mixed_sums, mixed_stats = np.zeros_like(counts), np.zeros_like(obs_sums), None
+        if draws is not None:
+            seed = derived_seed(flags.seed, PPC_MIXED_SEED)
+            site = diagnostics.upload_site_table(spec.site_table(), int(trace.shape[2]), trace.device)
+            rows, undrawn = diagnostics.site_redraw(draws, site, redrawn, seed=seed, draw_offset=draw_offset)
+            stats, sums, mask = replicate_tiles(rows[None], table, next_seed(seed), draw_offset, budget=LOO_CHUNK_BYTES)
+            left = (mask != 0) | (undrawn != 0)                              # (an undrawn element is NaN: masked too)
+            mixed_stats, mixed_sums = _lib.host64(stats), _lib.host64(sums)
+            mixed_counts = diagnostics.ppc_counts(mixed_stats, y, left)
+            del rows
+        mixed_time = time.time() - mixed_clock
+        counts, obs_sums, mixed_counts, mixed_sums = _reduced([counts, obs_sums, mixed_counts, mixed_sums], dev)
+        mixed = (redrawn, mixed_counts, mixed_sums, mixed_stats)
+    else:
+        counts, obs_sums = _reduced([counts, obs_sums], dev)
     summary = diagnostics.ppc_from_counts(counts, obs_sums, y, kind)
     keys = ppc_keys(summary, k_total, len(steps))
     p = OrderedDict((name, keys["ppc_p_" + name]) for name in diagnostics.PPC_STATISTICS)
@@ -964,15 +1049,74 @@ def _ppc_report(kernel_results, trace, k, k_total, spec, flags, dev):
                           ("pit", summary.pit), ("y", y),
                           ("draw_stats", stats_host if stats_host is not None else np.zeros((0, len(diagnostics.PPC_DRAW_COLUMNS)))),
                           ("model", np.asarray(spec.name))])
+    more = OrderedDict()
+    if mixed is not None:
+        mixed_clock = time.time()
+        more, mixed_arrays = _ppc_mixed_report(mixed, names, keys, spec, y, kind)
+        arrays[PPC_MIXED_ARRAYS] = mixed_arrays                               # (save_ppc takes them out again: a file of their own)
+        more["ppc_mixed_time_sec"] = mixed_time + (time.time() - mixed_clock)
     keys["ppc_time_sec"] = time.time() - clock
+    keys.update(more)                                                        # (PPC_KEYS in their order, then PPC_MIXED_KEYS)
     return keys, arrays
+
+
+def _ppc_mixed_report(mixed, names, posterior_keys, spec, y, kind):
+    """The second half of --predictive_checks_redraw (_ppc_report): from the all-reduced counts and sums of the data
+    replicated at the redrawn rows to the keys, the printed comparison and the arrays of <base>_ppc_mixed.npz.
+    mixed: (redrawn [D] uint8, counts, obs_sums, this rank's draw statistics or None); posterior_keys: the posterior
+    check's keys, which the line sets the mixed figures next to -- that comparison is the report."""
+    redrawn, counts, obs_sums, stats_host = mixed
+    summary = diagnostics.ppc_from_counts(counts, obs_sums, y, kind)
+    chosen = [name for name in spec.part_names if name in names]
+    keys = ppc_mixed_keys(summary, chosen, int(np.sum(redrawn != 0)), kind)
+    pair = lambda key: "{} ({})".format(_fmt(keys["ppc_mixed_" + key]), _fmt(posterior_keys["ppc_" + key]))
+    util.print_("    mixed predictive checks, {} redrawn from the conditional prior ({} elements), {} draws ({} left out) -- "
+                "mixed (posterior): p-values mean {}, sd {}, min {}, max {}, deviance {}; replicated sd {}; PIT Kolmogorov "
+                "distance {}, 90 % coverage {}".format(
+                    ", ".join(chosen), keys["ppc_mixed_elements"], keys["ppc_mixed_draws"], keys["ppc_mixed_draws_left_out"],
+                    pair("p_mean"), pair("p_sd"), pair("p_min"), pair("p_max"), pair("p_deviance"), pair("rep_sd"),
+                    pair("pit_ks"), pair("coverage_90")))
+    extreme = [name for name in diagnostics.PPC_STATISTICS if keys["ppc_mixed_p_" + name] is not None
+               and not PPC_EXTREME[0] <= keys["ppc_mixed_p_" + name] <= PPC_EXTREME[1]]
+    if extreme:
+        util.print_("    WARNING: mixed predictive p-value outside [{}, {}] for: {} -- data sets replicated from NEW draws of {} "
+                    "under the fitted hyperparameters (almost) never or (almost) always exceed the observed statistic; "
+                    "customarily read as a misfit of that layer of the model, which the posterior check, at effects fitted "
+                    "to the data, cannot see (a convention, not a derived threshold)".format(
+                        PPC_EXTREME[0], PPC_EXTREME[1], ", ".join(extreme), ", ".join(chosen)))
+    out = keys["ppc_mixed_pit_extreme_observations"]
+    if out:
+        util.print_("    {} of {} observations have a mixed PIT outside [{}, {}] -- outliers against a new draw of {}: {}{} "
+                    "(the PIT values: <base>_ppc_mixed.npz)".format(
+                        len(out), int(y.size), PPC_EXTREME[0], PPC_EXTREME[1], ", ".join(chosen),
+                        ", ".join(str(n) for n in out[:PPC_MIXED_SHOWN]), ", ..." if len(out) > PPC_MIXED_SHOWN else ""))
+    arrays = OrderedDict([("parts", np.asarray(chosen)), ("redrawn", np.asarray(redrawn, np.uint8)),
+                          ("predictive_mean", summary.predictive_mean), ("predictive_sd", summary.predictive_sd),
+                          ("pit", summary.pit), ("y", y),
+                          ("draw_stats", stats_host if stats_host is not None else np.zeros((0, len(diagnostics.PPC_DRAW_COLUMNS)))),
+                          ("model", np.asarray(spec.name))])
+    return keys, arrays
+
+
+def save_ppc_mixed(file_path_base, arrays):
+    """`<base>_ppc_mixed.npz` (build-specific, --predictive_checks_redraw): `parts`, the parts redrawn, in part order, and
+    `redrawn` [D] uint8, their elements; per observation `predictive_mean`, `predictive_sd` and `pit` [N] float64 of the
+    MIXED predictive distribution and `y` [N]; `draw_stats` [R, 8] float64 as in <base>_ppc.npz, of the data sets replicated
+    at the redrawn rows (zeros for a draw left out); `model`."""
+    np.savez(file_path_base + "_ppc_mixed.npz", **arrays)
 
 
 def save_ppc(file_path_base, arrays):
     """`<base>_ppc.npz` (build-specific, --predictive_checks): per observation `predictive_mean`, `predictive_sd` and `pit`
     [N] float64 and `y` [N], the observations themselves; `draw_stats` [R, 8] float64, the per-draw sums of
-    diagnostics.PPC_DRAW_COLUMNS (zeros for a draw left out); `model`, the model's name."""
+    diagnostics.PPC_DRAW_COLUMNS (zeros for a draw left out); `model`, the model's name.  With --predictive_checks_redraw
+    the mixed check's arrays wait under PPC_MIXED_ARRAYS and go to a file of their own (save_ppc_mixed): <base>_ppc.npz
+    holds what it holds without the flag."""
+    arrays = OrderedDict(arrays)
+    mixed = arrays.pop(PPC_MIXED_ARRAYS, None)
     np.savez(file_path_base + "_ppc.npz", **arrays)
+    if mixed is not None:
+        save_ppc_mixed(file_path_base, mixed)
 
 
 PSENS_ARRAYS = "psens/"              # where _convergence_report leaves the arrays of <base>_psens.npz
@@ -1553,7 +1697,7 @@ SIDE_REPORTS = (
     SideReport("predictive_diagnostics", LOO_ARRAYS, lambda flags: _loo_null(_NO_TRACE, flags), save_loo,
                lambda r: _loo_report(r.kernel_results, r.trace, r.k, r.spec, r.flags, r.arrays)),
     SideReport(None, LOO_PRED_ARRAYS, None, save_loo_pred, None),
-    SideReport("predictive_checks", PPC_ARRAYS, lambda flags: _ppc_null(_NO_TRACE), save_ppc,
+    SideReport("predictive_checks", PPC_ARRAYS, lambda flags: _ppc_null(_NO_TRACE, flags), save_ppc,
                lambda r: _ppc_report(r.kernel_results, r.trace, r.k, r.n_split, r.spec, r.flags, r.dev)),
     SideReport("sensitivity_diagnostics", PSENS_ARRAYS, lambda flags: _psens_null(_NO_TRACE, flags), save_psens,
                lambda r: _psens_report(r.trace, r.k, r.spec, r.flags, r.split_mean, r.arrays)),
@@ -1846,6 +1990,7 @@ def main(argv=None, flags=FLAGS, out=None):
         raise NotImplementedError("--reparameterise_variational is not supported by this build (SURVEY.md section 2)")
     check_predictive(flags)
     check_predictive_checks(flags)
+    check_predictive_redraw(flags)
     check_sensitivity(flags)
     check_sensitivity_sites(flags)
     check_prior_predictive(flags)

@@ -710,6 +710,42 @@ int arp_site_prior_draws(int32_t D, const int32_t* form, const int32_t* loc_idx,
                          uint64_t seed, int64_t draw_offset, float* x, int64_t row_stride, uint8_t* undrawn /* may be NULL */,
                          void* stream);
 
+/* Conditional redraw of recorded draws (csrc/site_redraw.hip; needs no model handle): what a mixed predictive check
+ * (Gelman, Meng, Stern 1996; Marshall, Spiegelhalter 2007) replicates its data from -- the hyperparameters of every
+ * posterior draw kept, the group-level elements drawn anew from their conditional prior given them.  x is a block of
+ * recorded steps of the CENTRED trace [n_samples][n_chains][D], read in place with arp_pointwise_loglik's addressing and
+ * row_stride rule; the table columns are arp_site_prior_draws'; redraw is [D] bytes in device memory.  out is
+ * [R][out_stride] float, R = n_samples * n_chains, row r = step * n_chains + chain; columns d >= D are not touched.  For
+ * draw r, g = draw_offset + r its global number, the table is walked front to back:
+ *   redraw[d] == 0:  out[r][d] = x[r][d], bit for bit (NaN and +-inf included)
+ *   redraw[d] != 0:  out[r][d] is drawn exactly as arp_site_prior_draws draws element d of draw g: the same three forms, the
+ *     same float32 operation order with contraction off, the same philox4x32_10 counter (d, lo32(g), hi32(g), j) and key
+ *     (lo32(seed), hi32(seed)), the same 32 attempts of the log-Gamma form and the same undrawn rule (one copy of the code:
+ *     csrc/site_draw.h).  Its parents are read from the row being built: the redrawn value where the parent is flagged, the
+ *     recorded one where it is not.
+ * The row starts as the recorded value in every unflagged column and 0 in every flagged one: a flagged element reads as 0
+ * until it is redrawn, as "not drawn yet" does in arp_site_prior_draws, and the flagged columns of x never enter a result
+ * (they are not read).  With every element flagged, out is arp_site_prior_draws' x at the same seed and draw_offset, bit
+ * for bit; with none, it is x.
+ *   undrawn: NULL, or [R] bytes, written 0 or 1 for every draw (1: a flagged log-Gamma element ran out of attempts and is
+ *     NaN); NULL leaves out bitwise as it is.
+ * The value of (d, g) is a function of (seed, d, g), the flags and the draw's own row alone: a block of steps [s0, s1) at
+ * draw_offset s0 * n_chains equals those rows of the whole, bit for bit; two calls give bitwise equal output; no result
+ * depends on the launch shape or on other draws; no atomics.  The error bounds of a redrawn element are
+ * arp_site_prior_draws' above, as they stand, against the exact value of the same float32 parents, the same table and the
+ * same Philox words, and so is the rule for an undecided attempt.
+ * WHICH elements are flagged is not policed here: a selection that is not closed under descent (an unflagged element with
+ * a term of non-zero weight at a flagged one) is walked like any other and gives rows that are draws from no distribution
+ * the model defines.  That rule is the host's: diagnostics.redraw_selection.
+ * Nothing is read past the last element of the trace block, and no padding is read or written.  Asynchronous.  Refused
+ * before any launch: a NULL pointer other than undrawn, D < 1 or D > 255, a trace shape or row_stride that
+ * arp_pointwise_loglik refuses, more than 2^24 draws, out_stride < D, draw_offset < 0, out == x. */
+int arp_site_redraw(const float* x, int64_t n_samples, int64_t n_chains, int32_t D, int64_t row_stride,
+                    const int32_t* form, const int32_t* loc_idx, const float* loc_w, const float* loc0,
+                    const int32_t* scale_idx, const float* scale_w, const float* log_scale0,
+                    const uint8_t* redraw /* [D], device */, uint64_t seed, int64_t draw_offset, float* out, int64_t out_stride,
+                    uint8_t* undrawn /* may be NULL */, void* stream);
+
 /* The fold of simulation-based calibration (csrc/sbc.hip; needs no model handle; Talts, Betancourt, Simpson, Vehtari,
  * Gelman 2018): where the truth of every replicate sits among the posterior draws a refit on its simulated data returned.
  * draws is [n_rep][n_draws][Q] float in device memory, element (r, i, q) at draws[r * rep_stride + i * row_stride + q]
