@@ -314,6 +314,20 @@ def report_ppc(results):
                              pair("coverage_90"), "n/a" if outliers is None else len(outliers), last["ppc_mixed_draws"],
                              last.get("ppc_mixed_draws_left_out"), _secs(last.get("ppc_mixed_time_sec")),
                              "   <-- EXTREME: " + ", ".join(mixed_extreme) if mixed_extreme else ""))
+        if last.get("ppc_group_draws") is not None:
+            # the grouped check (--predictive_checks_groups): the ends of the groups' p-values of the mean, and the groups
+            # beyond the Bonferroni threshold; the mixed figures next to them where the run has both flags
+            ends = lambda pre: "{} ({}) ... {} ({})".format(_fmt(last.get(pre + "p_mean_min")), last.get(pre + "p_mean_min_group"),
+                                                            _fmt(last.get(pre + "p_mean_max")), last.get(pre + "p_mean_max_group"))
+            flagged = lambda pre: "n/a" if last.get(pre + "extreme_groups") is None else (", ".join(last[pre + "extreme_groups"]) or "none")
+            mixed = last.get("ppc_group_mixed_draws") is not None
+            lines.append("      grouped predictive by {}: {} groups ({} empty, {} observations in none); p-value of the group mean, "
+                         "smallest ... largest {}{}; beyond the threshold {}: {}{}; {} draws; {}".format(
+                             last.get("ppc_group_part"), last.get("ppc_groups"), last.get("ppc_groups_empty"),
+                             last.get("ppc_group_observations_left_out"), ends("ppc_group_"),
+                             ", mixed " + ends("ppc_group_mixed_") if mixed else "", _fmt(last.get("ppc_group_p_threshold")),
+                             flagged("ppc_group_"), ", mixed " + flagged("ppc_group_mixed_") if mixed else "",
+                             last["ppc_group_draws"], _secs(last.get("ppc_group_time_sec"))))
     return lines
 
 

@@ -2,7 +2,9 @@
 // observation n at draw r of a centred trace, drawn from the model's observation table (autoreparam_amd/models.py:
 // ModelSpec.observation_table) and folded on the spot into per-draw test statistics and per-observation predictive
 // moments -- does data simulated from the fitted model look like the data?  Model-independent; the table, the tile of
-// draws, eta_n and s_n, and the predictive terms mu, var, z_obs, e, p and pit of the two kinds of data: obs_table.h.
+// draws, eta_n and s_n, and the predictive terms mu, var, z_obs, e, p and pit of the two kinds of data: obs_table.h.  The
+// per-(n, r) body -- the Philox call, y_rep, the two deviances -- is ppc_terms.h's, which ppc_group.hip (the same replicated
+// values folded by group) calls too: the random numbers, the arithmetic and the bounds below hold for both.
 //
 //   Normal:     y_rep = eta + exp(s) z;  dev(v) = ((v - eta) exp(-s))^2 + 2 s + log 2 pi
 //   Bernoulli:  y_rep = (u < p);  dev(v) = -2 (v eta - (max(eta, 0) + log1p(e)))
@@ -67,15 +69,14 @@
 //    select; they store nothing.
 #include "arp_device.h"
 #include "obs_table.h"
+#include "ppc_terms.h"
 
 #pragma clang fp contract(off)
 
 namespace arp {
 namespace {
 
-constexpr int kPcCols = 8;                       // columns of draw_stats
 constexpr int kPcObsCols = 4;                    // columns of obs_sums
-constexpr float kLog2PiF = 1.8378770664093453f;
 
 __device__ __forceinline__ double wave_sum(double v) {
 #pragma unroll
@@ -110,33 +111,10 @@ __global__ __launch_bounds__(kObsThreads) void ppc_kernel(
   double a_y = 0.0, a_yy = 0.0, a_dr = 0.0, a_do = 0.0, a_mu = 0.0, a_n = 0.0;
   float a_min = __builtin_inff(), a_max = -__builtin_inff();
   for (long long n = nb + wave; n < ne; n += kObsWaves) {
-    const float eta = obs_eta(row, idx, w, n, T, D);
+    const PpcTerms pc = ppc_terms(row, kind, T, D, idx, w, y, scale_idx, log_scale, n, g_lo, g_hi, key0, key1);
     const float yn = y[n];
-    uint32_t rnd[4];
-    philox4x32_10((uint32_t)n, g_lo, g_hi, 0u, key0, key1, rnd);
-    float yr, dev_r, dev_o;
-    PredTerms pt;
-    if (kind == 0) {
-      const float s = obs_log_scale(row, scale_idx, log_scale, n, D);
-      const float es = expf(s), ems = expf(-s);
-      const float up = fmaf((float)rnd[0], 2.3283064365386963e-10f, 1.1641532182693481e-10f);
-      const float z = sqrtf(-2.0f * logf(up)) * cospif(2.0f * angle_rev(rnd[1]));
-      yr = eta + es * z;
-      pt = normal_terms(eta, yn, es, ems);
-      const float zo = pt.aux, zr = (yr - eta) * ems;
-      const float two_s = 2.0f * s;
-      dev_r = (zr * zr + two_s) + kLog2PiF;
-      dev_o = (zo * zo + two_s) + kLog2PiF;
-    } else {
-      pt = bernoulli_terms(eta, yn);
-      const float e = pt.aux, p = pt.mu;
-      const float u01 = (float)(rnd[0] >> 8) * 5.9604644775390625e-08f;
-      yr = u01 < p ? 1.0f : 0.0f;
-      const float sp = fmaxf(eta, 0.0f) + log1pf(e);
-      dev_r = -2.0f * (yr * eta - sp);
-      dev_o = -2.0f * (yn * eta - sp);
-    }
-    const float mu = pt.mu, m2 = pt.m2, pit = pt.pit;
+    const float yr = pc.yr, dev_r = pc.dev_r, dev_o = pc.dev_o;
+    const float mu = pc.pt.mu, m2 = pc.pt.m2, pit = pc.pt.pit;
     // along the observations (this lane's draw)
     a_y += (double)yr;
     a_yy += (double)yr * (double)yr;

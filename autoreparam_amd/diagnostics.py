@@ -29,7 +29,9 @@ latent site, summed over chosen groups of elements, for power-scaling chosen pri
 from the site table; `prior_predictive_summary`, `prior_contraction_summary`: what data the prior generates, and how far
 the data moved every marginal away from it), and the same walk over recorded draws (`site_redraw` on `arp_site_redraw`: the
 parts `redraw_selection` flags drawn anew from their conditional prior, the rest kept -- the rows a mixed predictive check
-replicates its data from).
+replicates its data from); and the predictive check per group of observations (`group_selection`: the groups a latent part
+forms; `group_predictive_check` on `arp_group_predictive_check`: the same replicated data folded per group and draw;
+`ppc_group_counts`, `ppc_group_summary`: `ppc_counts` and `ppc_from_counts` applied group by group).
 
 Build-specific (the reference runs 100 chains and reports the within-chain ESS only).  The per-chain moments come from
 one pass over a trace that is already on the device (`arp_split_moments`) or from the in-kernel statistics of a
@@ -853,6 +855,151 @@ def ppc_summary(draw_stats, obs_sums, y, kind, mask=None):
     counterpart #{y_rep <= y} / R_used.  Calibration, Normal data only: pit_ks and coverage_90.  = ppc_from_counts of
     ppc_counts: a job whose draws are spread over ranks adds the counts and obs_sums of its ranks first."""
     return ppc_from_counts(ppc_counts(draw_stats, y, mask), obs_sums, y, kind)
+
+
+# ---- grouped predictive check: the same replicated data folded per group of observations (csrc/ppc_group.hip) ----
+GROUPS_FLAG = "--predictive_checks_groups"
+# order [n_grouped] and group_start [G + 1] int32 on the device (include/autoreparam.h: arp_group_predictive_check);
+# sizes [G]: the groups' sizes, host int64
+DeviceGroups = collections.namedtuple("DeviceGroups", ["G", "n_obs", "n_grouped", "order", "group_start", "sizes"])
+# Per group ([G] float64 arrays in dicts over PPC_STATISTICS, NaN where ppc_from_counts says None): p, rep, obs as
+# PpcSummary's, each over the observations of one group; draws_used, draws_left_out: ints, of the whole job; sizes [G] int64
+PpcGroupSummary = collections.namedtuple("PpcGroupSummary", ["draws_used", "draws_left_out", "sizes", "p", "rep", "obs"])
+
+
+def group_selection(table, spec, part):
+    """(group_of [N] int32, names) -- THE grouping rule of the grouped predictive check (--predictive_checks_groups=PART):
+    the groups are the elements of the latent part `part` of `spec` (anything with part_names, part_shapes and offsets),
+    group_of[n] is the element of it that the linear predictor of observation n of `table` (ModelSpec.observation_table)
+    reads with a non-zero weight, -1 when it reads none (such an observation is in no group); names: one per element, as
+    the geometry report names them (`m[17]`).  An element nobody reads is an empty group.  Pure numpy.  Refused, by a
+    ValueError that names the flag: a name that is no part; a part of one element (that is the whole-data check); a part
+    no observation reads; a part of which some observation reads more than one element (beta of German credit: a
+    regression coefficient groups nothing)."""
+    from .report_common import element_names
+    names = list(spec.part_names)
+    if part not in names:
+        raise ValueError("%s: %s is no latent part of %s; its parts: %s" % (GROUPS_FLAG, part, spec.name, ", ".join(names)))
+    k = names.index(part)
+    lo, hi = int(spec.offsets[k]), int(spec.offsets[k + 1])
+    if hi - lo < 2:
+        raise ValueError("%s: %s has one element, so its one group is all the data: that is --predictive_checks itself"
+                         % (GROUPS_FLAG, part))
+    idx, w = np.asarray(table.idx, np.int64), np.asarray(table.w)
+    reads = (w != 0) & (idx >= lo) & (idx < hi)
+    if not reads.any():
+        raise ValueError("%s: no observation's linear predictor reads %s" % (GROUPS_FLAG, part))
+    first = np.where(reads, idx - lo, hi - lo).min(axis=1)
+    last = np.where(reads, idx - lo, -1).max(axis=1)
+    several = np.flatnonzero(reads.any(axis=1) & (first != last))
+    if several.size:
+        raise ValueError("%s: %d observation(s) read more than one element of %s (the first: observation %d), so its elements "
+                         "do not group the data" % (GROUPS_FLAG, several.size, part, int(several[0])))
+    return last.astype(np.int32), element_names(spec)[lo:hi]
+
+
+def group_order(group_of, n_groups):
+    """(order [n_grouped], group_start [n_groups + 1]) int32 of group_of [N] (entries in [-1, n_groups)): the grouped
+    observations sorted by group, ascending observation index within a group, and where every group's stretch begins."""
+    group_of = np.asarray(group_of, np.int64).reshape(-1)
+    G = int(n_groups)
+    if G < 1 or (group_of.size and (group_of.min() < -1 or group_of.max() >= G)):
+        raise ValueError("group_order: group_of entries in [-1, %d) and at least one group are required" % G)
+    grouped = np.flatnonzero(group_of >= 0)
+    order = grouped[np.argsort(group_of[grouped], kind="stable")]
+    start = np.concatenate([[0], np.cumsum(np.bincount(group_of[grouped], minlength=G))])
+    return order.astype(np.int32), start.astype(np.int32)
+
+
+def upload_groups(order, group_start, n_obs, device):
+    """order and group_start (group_order's) -> DeviceGroups on `device`, checked against a table of n_obs observations
+    first, as upload_table checks idx: every order entry in [0, n_obs), group_start ascending from 0 to len(order) -- the
+    kernel addresses the table and `order` with them."""
+    order = np.ascontiguousarray(order, np.int32).reshape(-1)
+    start = np.ascontiguousarray(group_start, np.int32).reshape(-1)
+    n_obs = int(n_obs)
+    if start.size < 2:
+        raise ValueError("observation groups: at least one group is required (group_start has n_groups + 1 entries)")
+    if order.size and (order.min() < 0 or order.max() >= n_obs):
+        raise ValueError("observation groups: an order entry lies outside the table's %d observations" % n_obs)
+    if start[0] != 0 or start[-1] != order.size or np.any(np.diff(start.astype(np.int64)) < 0):
+        raise ValueError("observation groups: group_start must ascend from 0 to the %d grouped observations" % order.size)
+    dev = lambda a: torch.as_tensor(a, device=device)
+    # (an empty order still needs an address: one unread entry)
+    return DeviceGroups(int(start.size - 1), n_obs, int(order.size), dev(order if order.size else np.zeros(1, np.int32)),
+                        dev(start), np.diff(start.astype(np.int64)))
+
+
+def group_predictive_check(trace, table, groups, g0=0, g1=None, seed=0, draw_offset=0):
+    """(group_stats, mask, n_masked) of `arp_group_predictive_check` for a recorded CENTRED [S, C, D] float32 trace on the
+    GPU, a DeviceTable (whole) and the groups [g0, g1) of a DeviceGroups over it, all device tensors: group_stats
+    [g1 - g0, S C, 8] float64, PPC_DRAW_COLUMNS over the observations of one group (an empty group: 0, 0, +inf, -inf, 0,
+    0, 0, 0; a draw left out: a zero row); mask, n_masked as predictive_check's.  The replicated value of (observation n,
+    draw r) is predictive_check's under the same seed and draw_offset, bit for bit, and a group's row depends neither on
+    [g0, g1) nor on how the draws are spread over calls.  A block of chains of a wider trace is read in place."""
+    who = "group_predictive_check"
+    view, _, _, R = _table_call(trace, table, 0, None, who)
+    dev = view[0].device
+    g1 = groups.G if g1 is None else int(g1)
+    g0 = int(g0)
+    if groups.n_obs != table.N:
+        raise ValueError("%s: the groups were uploaded for a table of %d observations, not %d" % (who, groups.n_obs, table.N))
+    if not 0 <= g0 < g1 <= groups.G:
+        raise ValueError("%s: 0 <= g0 < g1 <= %d groups is required" % (who, groups.G))
+    if int(draw_offset) < 0:
+        raise ValueError("%s: draw_offset >= 0 is required" % who)
+    stats = torch.empty(g1 - g0, R, len(PPC_DRAW_COLUMNS), dtype=torch.float64, device=dev)
+    mask = torch.empty(R, dtype=torch.uint8, device=dev)
+    n_masked = torch.zeros((), dtype=torch.int64, device=dev)
+    _lib.call(dev, _lib.lib().arp_group_predictive_check, *_table_args(view, table, 0, table.N)[:-2], table.N,
+              _lib.ptr(groups.order), groups.n_grouped, _lib.ptr(groups.group_start), groups.G, g0, g1,
+              int(seed) & 0xFFFFFFFFFFFFFFFF, int(draw_offset), _lib.ptr(stats), _lib.ptr(mask), _lib.ptr(n_masked))
+    return stats, mask, n_masked
+
+
+def ppc_group_counts(group_stats, y, group_of, mask=None, g0=0):
+    """[G', PPC_COUNTS] float64: row i is ppc_counts(group_stats[i], y[group_of == g0 + i], mask) -- the one definition of
+    the statistics (_ppc_replicated, _ppc_observed), applied to the observations of one group -- for the [G', R, 8]
+    statistics of the groups g0 ... g0 + G' - 1 (group_predictive_check).  An empty group yields a zero row; a group of one
+    has no sd (NaN compares false: its count is 0, and ppc_from_counts leaves it out).  Additive over draws, as
+    ppc_counts is."""
+    c = _lib.host64(group_stats)
+    if c.ndim != 3 or c.shape[2] != len(PPC_DRAW_COLUMNS):
+        raise ValueError("ppc_group_counts: [G, R, 8] group statistics are required")
+    y = np.asarray(_lib.host64(y), np.float64).reshape(-1)
+    group_of = np.asarray(group_of).reshape(-1)
+    if group_of.size != y.size:
+        raise ValueError("ppc_group_counts: group_of must have one entry per observation")
+    mask = None if mask is None else _lib.host64(mask)                         # (one copy from the device, not one per group)
+    out = np.zeros((c.shape[0], PPC_COUNTS))
+    for i in range(c.shape[0]):
+        members = y[group_of == int(g0) + i]
+        if members.size:
+            out[i] = ppc_counts(c[i], members, mask)
+    return out
+
+
+def ppc_group_summary(counts, y, group_of, kind):
+    """The per-group report from the (all-reduced) [G, PPC_COUNTS] counts of `ppc_group_counts` -> PpcGroupSummary: every
+    group's p, rep and obs are ppc_from_counts' of its own counts and observations (its rules: no sd for a group of one
+    or for Bernoulli data, nothing without a draw), NaN where that says None -- so an empty group is NaN throughout."""
+    counts = np.asarray(counts, np.float64).reshape(-1, PPC_COUNTS)
+    y = np.asarray(_lib.host64(y), np.float64).reshape(-1)
+    group_of = np.asarray(group_of).reshape(-1)
+    G = counts.shape[0]
+    p, rep, obs = ({name: np.full(G, np.nan) for name in PPC_STATISTICS} for _ in range(3))
+    sizes = np.bincount(group_of[group_of >= 0], minlength=G).astype(np.int64)
+    for g in range(G):
+        members = y[group_of == g]
+        s = ppc_from_counts(counts[g], np.zeros((members.size, len(PPC_OBS_COLUMNS))), members, kind)
+        for name in PPC_STATISTICS:
+            for to, frm in ((p, s.p), (rep, s.rep), (obs, s.obs)):
+                if frm[name] is not None:
+                    to[name][g] = frm[name]
+    filled = np.flatnonzero(sizes > 0)
+    used = int(round(counts[filled[0], 0])) if filled.size else 0
+    left = int(round(counts[filled[0], 1])) if filled.size else 0
+    return PpcGroupSummary(used, left, sizes, p, rep, obs)
 
 
 # ---- leave-one-out predictive report: the predictive quantities folded with the PSIS weights (csrc/loopred.hip) ----

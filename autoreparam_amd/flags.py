@@ -108,8 +108,8 @@ _DEFS = [
                                        "Gelman, Meng, Stern 1996), folded on the device: posterior predictive p-values of "
                                        "the mean, sd, min, max and deviance, the predictive mean and sd of every observation "
                                        "and its PIT value with their calibration (ppc_* JSON keys, <base>_ppc.npz).  The "
-                                       "posterior PIT (the leave-one-out PIT: --loo_predictive); no group-level statistics, "
-                                       "no user-defined statistic.  "
+                                       "posterior PIT (the leave-one-out PIT: --loo_predictive); group-level statistics: "
+                                       "--predictive_checks_groups; no user-defined statistic.  "
                                        "Every quantity is a sum over draws: sharded jobs included.  Refused for "
                                        "neals_funnel, which has no observations."),
     ("predictive_checks_redraw", str, "", "With --predictive_checks only: PART[,PART...], latent parts of the model (e.g. m for "
@@ -125,11 +125,30 @@ _DEFS = [
                                           "(ppc_mixed_* JSON keys, <base>_ppc_mixed.npz; analyze --ppc prints a second line).  "
                                           "Every output of --predictive_checks is bit for bit unchanged.  The selection is by "
                                           "part, not by element or group; the data are replicated at the observed "
-                                          "covariates; no per-group test statistics.  Refused: the flag without "
+                                          "covariates; per-group test statistics: --predictive_checks_groups.  Refused: the flag without "
                                           "--predictive_checks, neals_funnel, a name that is no part of the model, a "
                                           "duplicate, an empty name, and a selection that is not closed under descent -- a "
                                           "part that stays as recorded although it was drawn from a redrawn one (mua without "
                                           "m); the message names the parts to add."),
+    ("predictive_checks_groups", str, "", "With --predictive_checks only: PART, one latent part of the model whose elements "
+                                          "group the observations (m for radon: the counties; a for election: the states; a "
+                                          "or b for electric; theta for 8schools).  The predictive check per GROUP: the same "
+                                          "replicated data, bit for bit, folded per group and draw (arp_group_predictive_check) "
+                                          "into the posterior predictive p-values of every group's mean, sd, min, max and "
+                                          "deviance -- a whole-data mean over 919 observations hides a county of six that the "
+                                          "model cannot produce (ppc_group_* JSON keys, <base>_ppc_groups.npz; analyze --ppc "
+                                          "prints a line).  With --predictive_checks_redraw the same per group at the redrawn "
+                                          "group effects (ppc_group_mixed_*; Marshall, Spiegelhalter 2007): which group is "
+                                          "not a draw from its prior layer.  A group is the set of observations whose linear "
+                                          "predictor reads one element of the part; an observation that reads none is in no "
+                                          "group, an element nobody reads is an empty group; both are counted in the keys.  "
+                                          "Groups are flagged at 0.005 / (non-empty groups), Bonferroni at the customary 1 %, "
+                                          "when the draws resolve that.  Every other output is bit for bit unchanged.  One "
+                                          "part per run; no groups by covariate; no user-defined statistic; the posterior "
+                                          "p-values are conservative, the group effect having been fitted to the group.  "
+                                          "Refused: the flag without --predictive_checks, neals_funnel, a name that is no "
+                                          "part, a part of one element (the whole-data check), a part no observation reads, "
+                                          "a part of which an observation reads several elements (beta of German credit)."),
     ("loo_predictive", bool, False, "With --predictive_diagnostics only: the leave-one-out predictive report.  The predictive "
                                     "mean, variance and PIT value of every observation at every draw, folded with the "
                                     "Pareto-smoothed weights of its own leave-one-out posterior (arp_psis_weights, "

@@ -24,8 +24,8 @@ from . import engine as _engine
 from . import sbc as _sbc
 from .flags import FLAGS, check_vi_check_draws
 from .report_common import (LOO_CHUNK_BYTES, _finite_or_none, _fmt, _nan_max, _null_keys, _write_json_atomic, derived_seed,
-                            element_names, joint_loglik, loo_steps, next_seed, ppc_tile_rows, probe_steps, replicate_tiles,
-                            select_draws)
+                            element_names, joint_loglik, loo_steps, next_seed, ppc_tile_rows, probe_steps, replicate_groups,
+                            replicate_tiles, select_draws)
 
 
 def _vip_suffix(flags):
@@ -931,9 +931,121 @@ def check_predictive_redraw(flags):
     diagnostics.redraw_selection(spec.site_table(), spec.part_names, names)
 
 
+PPC_GROUP_ARRAYS = "ppc_groups/"     # where _ppc_report leaves the arrays of <base>_ppc_groups.npz among those of _ppc.npz
+PPC_GROUP_SHOWN = 8                  # extreme groups the warning names
+PPC_GROUP_LEVEL = 0.005              # 1 % two-sided, shared among the non-empty groups (Bonferroni): a convention
+PPC_GROUP_STATISTICS = ("mean", "sd", "deviance")     # the statistics whose smallest and largest group p-value are keys
+_PPC_GROUP_SUFFIXES = (("part", "groups", "groups_empty", "observations_left_out", "draws")
+                       + tuple("p_%s_%s%s" % (name, end, tail) for name in PPC_GROUP_STATISTICS for end in ("min", "max")
+                               for tail in ("", "_group")) + ("p_threshold", "extreme_groups", "time_sec"))
+# (ppc_groups and ppc_groups_empty: the two counts read better without the second "group")
+PPC_GROUP_KEYS = tuple(("ppc_" if suffix.startswith("groups") else "ppc_group_") + suffix for suffix in _PPC_GROUP_SUFFIXES)
+PPC_GROUP_MIXED_KEYS = tuple("ppc_group_mixed_" + suffix for suffix in _PPC_GROUP_SUFFIXES)
+
+
+def groups_part(flags):
+    """The part --predictive_checks_groups names; "" without the flag."""
+    return getattr(flags, "predictive_checks_groups", "") or ""
+
+
+def check_predictive_groups(flags):
+    """--predictive_checks_groups against the job, before anything runs -- raises ValueError for the flag without
+    --predictive_checks, for neals_funnel (no observations) and for whatever diagnostics.group_selection refuses: a name
+    that is no part, a part of one element, a part no observation reads, a part whose elements do not group the data."""
+    part = groups_part(flags)
+    if not part:
+        return
+    if not getattr(flags, "predictive_checks", False):
+        raise ValueError("--predictive_checks_groups is read with --predictive_checks only")
+    if flags.model == "neals_funnel":
+        raise ValueError("--predictive_checks_groups: neals_funnel has no observations, so there is no data to group")
+    spec = models.spec_by_name(flags.model, dataset=getattr(flags, "dataset", None))
+    diagnostics.group_selection(spec.observation_table(), spec, part)
+
+
+def _ppc_all_keys(flags):
+    """The keys a run with these flags writes, in their order: PPC_KEYS, then PPC_MIXED_KEYS (--predictive_checks_redraw),
+    then PPC_GROUP_KEYS (--predictive_checks_groups) and, with both flags, PPC_GROUP_MIXED_KEYS."""
+    mixed, grouped = bool(redraw_parts(flags)), bool(groups_part(flags))
+    return (PPC_KEYS + (PPC_MIXED_KEYS if mixed else ()) + (PPC_GROUP_KEYS if grouped else ())
+            + (PPC_GROUP_MIXED_KEYS if grouped and mixed else ()))
+
+
 def _ppc_null(why, flags=None):
-    """Every key of the predictive checks, and of --predictive_checks_redraw where set, as null; one message says why."""
-    return _null_keys("posterior predictive checks", why, PPC_KEYS + (PPC_MIXED_KEYS if redraw_parts(flags) else ()))
+    """Every key of the predictive checks, and of --predictive_checks_redraw and --predictive_checks_groups where set, as
+    null; one message says why."""
+    return _null_keys("posterior predictive checks", why, _ppc_all_keys(flags))
+
+
+def ppc_group_keys(summary, part, names, n_ungrouped, mixed=False):
+    """The JSON keys of the grouped predictive check (all but the time) from a diagnostics.PpcGroupSummary, the part, its
+    groups' names and the number of observations in no group; pure Python.  mixed: under ppc_group_mixed_ (the groups
+    of the data replicated at the redrawn rows).  Per statistic of PPC_GROUP_STATISTICS the smallest and the largest
+    group p-value with their groups (null where no group defines it: sd of Bernoulli data).  p_threshold = PPC_GROUP_LEVEL
+    / non-empty groups; extreme_groups: the groups whose p-value of the MEAN is <= the threshold or >= 1 - threshold, null
+    when fewer than 1 / threshold draws were used -- a p-value is a multiple of 1 / draws and cannot resolve it then."""
+    prefix = "ppc_group_mixed_" if mixed else "ppc_group_"
+    filled = int(np.sum(summary.sizes > 0))
+    keys = OrderedDict([(prefix + "part", part), (prefix + "groups" if mixed else "ppc_groups", int(summary.sizes.size)),
+                        (prefix + "groups_empty" if mixed else "ppc_groups_empty", int(summary.sizes.size) - filled),
+                        (prefix + "observations_left_out", int(n_ungrouped)), (prefix + "draws", int(summary.draws_used))])
+    for name in PPC_GROUP_STATISTICS:
+        p = summary.p[name]
+        lo, hi = _nan_max(-p), _nan_max(p)
+        keys[prefix + "p_%s_min" % name] = _finite_or_none(-lo[0])
+        keys[prefix + "p_%s_min_group" % name] = names[lo[1]] if lo[1] >= 0 else None
+        keys[prefix + "p_%s_max" % name] = _finite_or_none(hi[0])
+        keys[prefix + "p_%s_max_group" % name] = names[hi[1]] if hi[1] >= 0 else None
+    threshold = PPC_GROUP_LEVEL / filled if filled else None
+    keys[prefix + "p_threshold"] = threshold
+    extreme = None
+    if threshold is not None and summary.draws_used * threshold >= 1.0:
+        with np.errstate(invalid="ignore"):
+            extreme = [names[g] for g in np.flatnonzero((summary.p["mean"] <= threshold) | (summary.p["mean"] >= 1.0 - threshold))]
+    keys[prefix + "extreme_groups"] = extreme
+    return keys
+
+
+def _ppc_group_arrays(summary, prefix=""):
+    """p_<T>, rep_<T>, obs_<T> [G] of <base>_ppc_groups.npz for the five statistics (NaN where not defined)."""
+    return OrderedDict((prefix + "%s_%s" % (what, name), getattr(summary, what)[name])
+                       for what in ("p", "rep", "obs") for name in diagnostics.PPC_STATISTICS)
+
+
+def _ppc_group_report(grouped, spec, y, kind):
+    """The second half of --predictive_checks_groups (_ppc_report): from the all-reduced per-group counts to the keys, the
+    printed line, the warning and the arrays of <base>_ppc_groups.npz.  grouped: (part, group_of, names, posterior counts,
+    mixed counts or None)."""
+    part, group_of, names, counts, mixed_counts = grouped
+    n_ungrouped = int(np.sum(group_of < 0))
+    summary = diagnostics.ppc_group_summary(counts, y, group_of, kind)
+    out = ppc_group_keys(summary, part, names, n_ungrouped)
+    arrays = OrderedDict([("part", np.asarray(part)), ("groups", np.asarray(names)), ("group_of", np.asarray(group_of, np.int32)),
+                          ("n_obs", np.asarray(summary.sizes, np.int64))])
+    arrays.update(_ppc_group_arrays(summary))
+    more = OrderedDict()
+    if mixed_counts is not None:
+        mixed_summary = diagnostics.ppc_group_summary(mixed_counts, y, group_of, kind)
+        more = ppc_group_keys(mixed_summary, part, names, n_ungrouped, mixed=True)
+        arrays.update(_ppc_group_arrays(mixed_summary, "mixed_"))
+    arrays.update([("y", y), ("model", np.asarray(spec.name))])
+    ends = lambda k, pre: "{} ({}) ... {} ({})".format(_fmt(k[pre + "p_mean_min"]), k[pre + "p_mean_min_group"],
+                                                      _fmt(k[pre + "p_mean_max"]), k[pre + "p_mean_max_group"])
+    util.print_("    grouped predictive checks by {}: {} groups ({} empty, {} observations in none), {} draws; p-value of the "
+                "group mean, smallest ... largest: {}{}".format(
+                    part, out["ppc_groups"], out["ppc_groups_empty"], n_ungrouped, out["ppc_group_draws"], ends(out, "ppc_group_"),
+                    "; mixed {}".format(ends(more, "ppc_group_mixed_")) if more else ""))
+    shown = lambda groups: "{} group(s): {}{}".format(len(groups), ", ".join(groups[:PPC_GROUP_SHOWN]),
+                                                       ", ..." if len(groups) > PPC_GROUP_SHOWN else "")
+    extreme = [(label, k[pre + "extreme_groups"]) for label, k, pre in (("posterior", out, "ppc_group_"), ("mixed", more, "ppc_group_mixed_"))
+               if k.get(pre + "extreme_groups")]
+    if extreme:
+        util.print_("    WARNING: predictive p-value of the group mean within {} of 0 or 1 ({} / non-empty groups: Bonferroni at "
+                    "the customary 1 %, a convention, not a derived threshold) for groups of {} -- {} -- groups whose mean the "
+                    "replicated data (almost) never or (almost) always exceed (the p-values: <base>_ppc_groups.npz)".format(
+                        _fmt(out["ppc_group_p_threshold"]), PPC_GROUP_LEVEL, part,
+                        "; ".join("{} {}".format(label, shown(groups)) for label, groups in extreme)))
+    return out, more, arrays
 
 
 def ppc_mixed_keys(summary, chosen, n_elements, kind):
@@ -981,7 +1093,8 @@ def _ppc_report(kernel_results, trace, k, k_total, spec, flags, dev):
     --seed and PPC_SEED; a rank's first global draw number is its chain offset times the number of steps.  Every quantity
     is a sum over draws: the counts behind the p-values and the per-observation sums go through ONE all-reduce, and a
     sharded job reports real numbers (rank 0 writes them; <base>_ppc.npz then holds the draw statistics of rank 0's draws).
-    The posterior PIT (the LOO-PIT: --loo_predictive); no group-level statistics; no user-defined statistic.
+    The posterior PIT (the LOO-PIT: --loo_predictive); group-level statistics: --predictive_checks_groups, below; no
+    user-defined statistic.
     --predictive_checks_redraw=PART[,PART...]: the MIXED predictive check (Gelman, Meng, Stern 1996; Marshall,
     Spiegelhalter 2007) on the same draws, the same tiles and the same global draw numbers.  The posterior check replicates
     y at group effects that were fitted to that very y, so it cannot say whether the effects look like draws from their own
@@ -994,8 +1107,19 @@ def _ppc_report(kernel_results, trace, k, k_total, spec, flags, dev):
     these hyperparameters would have produced it -- leave-group-out cross-validation without a refit.  Every PPC_KEYS value
     and every array of <base>_ppc.npz is the unflagged run's; the keys are null whenever the posterior check's are; the
     arrays of <base>_ppc_mixed.npz wait among the returned ones under PPC_MIXED_ARRAYS, where save_ppc finds them.
-    Selection by part, not by element or group; the data are still replicated at the observed covariates; no per-group
-    statistics.
+    Selection by part, not by element or group; the data are still replicated at the observed covariates.
+    --predictive_checks_groups=PART: the same check per GROUP of observations -- the observations that read one element of
+    the latent part (diagnostics.group_selection: radon's counties for m, election's states for a) -- on the same draws,
+    seed and draw offset, so the replicated values are the posterior check's own, bit for bit: one more kernel pass
+    (replicate_groups over arp_group_predictive_check) folds them per (group, draw), diagnostics.ppc_group_counts turns
+    every group's rows into the counts ppc_counts defines -- no second definition of a statistic -- and the [G, PPC_COUNTS]
+    counts join the SAME all-reduce.  With --predictive_checks_redraw too, a second pass over the redrawn rows the mixed
+    check has on the device already (they are handed to both, not drawn twice) under the mixed check's seeds gives the
+    figure the mixed replication exists for: which county is not a draw from its prior layer (Marshall, Spiegelhalter
+    2007).  PPC_GROUP_KEYS (and PPC_GROUP_MIXED_KEYS), null whenever the posterior check's are; the arrays of
+    <base>_ppc_groups.npz wait under PPC_GROUP_ARRAYS for save_ppc.  One part per run; groups by latent element, not by a
+    covariate; the posterior p-values are conservative (the group effect was fitted to the group's own data), the mixed
+    ones are the sharper check.  Without the flag every output is bit for bit unchanged.
     Returns (JSON keys, arrays of <base>_ppc.npz or None).  (A collective when ws > 1: every rank calls it.)"""
     clock = time.time()
     why, steps, draws = select_draws(trace, k, k_total, flags)
@@ -1007,11 +1131,24 @@ def _ppc_report(kernel_results, trace, k, k_total, spec, flags, dev):
     y = np.asarray(host_table.y, np.float32).reshape(-1)
     draw_offset = int(getattr(getattr(kernel_results, "probe", None), "chain_offset", 0)) * len(steps)
     counts, obs_sums, stats_host = np.zeros(diagnostics.PPC_COUNTS), np.zeros((N, len(diagnostics.PPC_OBS_COLUMNS))), None
+    part, group_time, group_mixed_time = groups_part(flags), 0.0, 0.0
+    if part:
+        group_clock = time.time()
+        group_of, group_names = diagnostics.group_selection(host_table, spec, part)
+        group_counts = np.zeros((len(group_names), diagnostics.PPC_COUNTS))
+        group_mixed_counts = np.zeros_like(group_counts) if names else None
+        group_time = time.time() - group_clock
     if draws is not None:                                                    # (None: an idle rank, zeros into the all-reduce)
         table = diagnostics.upload_table(host_table, int(trace.shape[2]), trace.device)
         stats, sums, mask = replicate_tiles(draws, table, derived_seed(flags.seed, PPC_SEED), draw_offset, budget=LOO_CHUNK_BYTES)
         stats_host, obs_sums = _lib.host64(stats), _lib.host64(sums)
         counts = diagnostics.ppc_counts(stats_host, y, mask)
+        if part:
+            group_clock = time.time()
+            groups = diagnostics.upload_groups(*diagnostics.group_order(group_of, len(group_names)), N, trace.device)
+            group_counts, _ = replicate_groups(draws, table, groups, y, group_of, derived_seed(flags.seed, PPC_SEED), draw_offset,
+                                               budget=LOO_CHUNK_BYTES)
+            group_time += time.time() - group_clock
     mixed, mixed_time = None, 0.0
     if names:
         mixed_clock = time.time()
@@ -1025,12 +1162,23 @@ def _ppc_report(kernel_results, trace, k, k_total, spec, flags, dev):
             left = (mask != 0) | (undrawn != 0)                              # (an undrawn element is NaN: masked too)
             mixed_stats, mixed_sums = _lib.host64(stats), _lib.host64(sums)
             mixed_counts = diagnostics.ppc_counts(mixed_stats, y, left)
+            mixed_time = time.time() - mixed_clock
+            if part:                                                         # (the redrawn rows serve both: not drawn twice)
+                group_clock = time.time()
+                group_mixed_counts, _ = replicate_groups(rows[None], table, groups, y, group_of, next_seed(seed), draw_offset,
+                                                         left_out=undrawn != 0, budget=LOO_CHUNK_BYTES)
+                group_mixed_time = time.time() - group_clock
             del rows
-        mixed_time = time.time() - mixed_clock
-        counts, obs_sums, mixed_counts, mixed_sums = _reduced([counts, obs_sums, mixed_counts, mixed_sums], dev)
-        mixed = (redrawn, mixed_counts, mixed_sums, mixed_stats)
-    else:
-        counts, obs_sums = _reduced([counts, obs_sums], dev)
+        else:
+            mixed_time = time.time() - mixed_clock
+    blocks = [counts, obs_sums] + ([mixed_counts, mixed_sums] if names else []) + ([group_counts] if part else []) \
+        + ([group_mixed_counts] if part and names else [])
+    blocks = _reduced(blocks, dev)                                           # (ONE all-reduce for everything the flags ask)
+    counts, obs_sums = blocks[:2]
+    if names:
+        mixed = (redrawn, blocks[2], blocks[3], mixed_stats)
+    if part:
+        group_counts, group_mixed_counts = blocks[2 + 2 * bool(names)], (blocks[-1] if names else None)
     summary = diagnostics.ppc_from_counts(counts, obs_sums, y, kind)
     keys = ppc_keys(summary, k_total, len(steps))
     p = OrderedDict((name, keys["ppc_p_" + name]) for name in diagnostics.PPC_STATISTICS)
@@ -1055,8 +1203,18 @@ def _ppc_report(kernel_results, trace, k, k_total, spec, flags, dev):
         more, mixed_arrays = _ppc_mixed_report(mixed, names, keys, spec, y, kind)
         arrays[PPC_MIXED_ARRAYS] = mixed_arrays                               # (save_ppc takes them out again: a file of their own)
         more["ppc_mixed_time_sec"] = mixed_time + (time.time() - mixed_clock)
+    if part:
+        group_clock = time.time()
+        group_keys, group_more, group_arrays = _ppc_group_report((part, group_of, group_names, group_counts, group_mixed_counts),
+                                                                 spec, y, kind)
+        arrays[PPC_GROUP_ARRAYS] = group_arrays                               # (save_ppc takes them out again, as the mixed ones)
+        group_keys["ppc_group_time_sec"] = group_time + group_mixed_time + (time.time() - group_clock)
+        if group_more:
+            group_more["ppc_group_mixed_time_sec"] = group_mixed_time         # (the pass over the redrawn rows: a part of the above)
+        more.update(group_keys)
+        more.update(group_more)
     keys["ppc_time_sec"] = time.time() - clock
-    keys.update(more)                                                        # (PPC_KEYS in their order, then PPC_MIXED_KEYS)
+    keys.update(more)                     # (PPC_KEYS in their order, then PPC_MIXED_KEYS, PPC_GROUP_KEYS, PPC_GROUP_MIXED_KEYS)
     return keys, arrays
 
 
@@ -1106,6 +1264,15 @@ def save_ppc_mixed(file_path_base, arrays):
     np.savez(file_path_base + "_ppc_mixed.npz", **arrays)
 
 
+def save_ppc_groups(file_path_base, arrays):
+    """`<base>_ppc_groups.npz` (build-specific, --predictive_checks_groups): `part`, the part whose elements are the groups;
+    `groups` [G], their names; `group_of` [N] int32, every observation's group (-1: none); `n_obs` [G], the groups' sizes;
+    per group `p_<T>`, `rep_<T>`, `obs_<T>` [G] float64 for T in diagnostics.PPC_STATISTICS as the whole-data keys define
+    them, over the group's observations (NaN where not defined: an empty group, sd of a group of one or of Bernoulli data);
+    the same arrays under `mixed_` with --predictive_checks_redraw; `y` [N]; `model`."""
+    np.savez(file_path_base + "_ppc_groups.npz", **arrays)
+
+
 def save_ppc(file_path_base, arrays):
     """`<base>_ppc.npz` (build-specific, --predictive_checks): per observation `predictive_mean`, `predictive_sd` and `pit`
     [N] float64 and `y` [N], the observations themselves; `draw_stats` [R, 8] float64, the per-draw sums of
@@ -1113,10 +1280,12 @@ def save_ppc(file_path_base, arrays):
     the mixed check's arrays wait under PPC_MIXED_ARRAYS and go to a file of their own (save_ppc_mixed): <base>_ppc.npz
     holds what it holds without the flag."""
     arrays = OrderedDict(arrays)
-    mixed = arrays.pop(PPC_MIXED_ARRAYS, None)
+    mixed, grouped = arrays.pop(PPC_MIXED_ARRAYS, None), arrays.pop(PPC_GROUP_ARRAYS, None)
     np.savez(file_path_base + "_ppc.npz", **arrays)
     if mixed is not None:
         save_ppc_mixed(file_path_base, mixed)
+    if grouped is not None:
+        save_ppc_groups(file_path_base, grouped)
 
 
 PSENS_ARRAYS = "psens/"              # where _convergence_report leaves the arrays of <base>_psens.npz
@@ -1991,6 +2160,7 @@ def main(argv=None, flags=FLAGS, out=None):
     check_predictive(flags)
     check_predictive_checks(flags)
     check_predictive_redraw(flags)
+    check_predictive_groups(flags)
     check_sensitivity(flags)
     check_sensitivity_sites(flags)
     check_prior_predictive(flags)

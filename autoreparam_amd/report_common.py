@@ -138,6 +138,31 @@ def replicate_tiles(draws, table, seed, draw_offset=0, y_rep_out=None, budget=No
     return stats, torch.cat(sums, dim=0), mask
 
 
+def group_range_size(G, R, budget=None):
+    """Groups per call of the grouped predictive check: [groups, R, 8] float64 statistics within `budget` bytes
+    (LOO_CHUNK_BYTES); at least one."""
+    budget = LOO_CHUNK_BYTES if budget is None else int(budget)
+    return int(max(1, min(max(int(G), 1), budget // max(1, 64 * int(R)))))
+
+
+def replicate_groups(draws, table, groups, y, group_of, seed, draw_offset=0, left_out=None, budget=None):
+    """(counts [G, PPC_COUNTS] float64 numpy, mask [S C] on the device): the data replicated per draw of `draws` [S, C, D]
+    and folded per group (diagnostics.group_predictive_check), in ascending ranges of groups whose [groups, S C, 8]
+    statistics stay within `budget` (group_range_size); every range is brought to the host and counted by
+    diagnostics.ppc_group_counts before the next is launched -- a group's row does not depend on the range it came in.
+    left_out: further draws to leave out, [S C] bool on the device (the mixed check's undrawn rows), or-ed to the mask."""
+    R = int(draws.shape[0]) * int(draws.shape[1])
+    per = group_range_size(groups.G, R, budget)
+    counts, left = [], None
+    for g0 in range(0, groups.G, per):
+        stats, mask, _ = diagnostics.group_predictive_check(draws, table, groups, g0, min(groups.G, g0 + per), seed=seed,
+                                                            draw_offset=draw_offset)
+        if left is None:
+            left = (mask != 0) if left_out is None else ((mask != 0) | left_out)
+        counts.append(diagnostics.ppc_group_counts(stats, y, group_of, left, g0))
+    return np.concatenate(counts, axis=0), left
+
+
 def joint_loglik(draws, table, out, tile_rows):
     """(total [S C] float64, mask [S C]): the joint log-likelihood of the table's data at every draw of `draws` [S, C, D], in
     ascending tiles (diagnostics.pointwise_loglik into `out`, loglik_total): the float64 sums compose bit for bit."""

@@ -558,6 +558,32 @@ int arp_predictive_check(const float* x, int64_t n_samples, int64_t n_chains, in
                          double* draw_stats, double* obs_sums, float* y_rep, int64_t y_rep_stride, uint8_t* mask,
                          int64_t* n_masked, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* Grouped predictive check (csrc/ppc_group.hip; Marshall, Spiegelhalter 2007): the replicated observations of
+ * arp_predictive_check folded per GROUP of observations and draw.  The trace x and the table are arp_predictive_check's,
+ * the table whole: n_obs is its length.  order [n_grouped] holds the indices (in the whole table) of the grouped
+ * observations sorted by group, ascending within a group; group g of n_groups is order[group_start[g]] ...
+ * order[group_start[g + 1] - 1], group_start [n_groups + 1] ascending from 0 to n_grouped; an observation may belong to no
+ * group.  The call covers the groups [g0, g1).  y_rep of (n, r) is bit for bit arp_predictive_check's under the same seed
+ * and draw_offset: the same Philox counter (n of the whole table, draw_offset + r) and the same float32 operations in the
+ * same order (csrc/ppc_terms.h).  Output (device memory):
+ *   group_stats [g1 - g0][n_samples * n_chains][8] double: draw_stats' eight columns over the observations of one group,
+ *     {sum y_rep, sum y_rep^2, min y_rep, max y_rep, sum dev(y_rep), sum dev(y), sum mu, observations counted}, the sums
+ *     in float64 in order's sequence, min and max of the float32 values.  An empty group: (0, 0, +inf, -inf, 0, 0, 0, 0).
+ *     A draw that is left out: a zero row in every group, by select.
+ *   mask and *n_masked as arp_predictive_check's.
+ * No float atomics and one fixed chain of additions per (group, draw): a row does not depend on the tiling, on [g0, g1)
+ * or on how many draws a call holds; two calls give bitwise equal outputs.  An order entry is clamped into [0, n_obs) and
+ * a group_start entry into [0, n_grouped] before use.  No workspace.  Asynchronous.  Refused before any launch: what
+ * arp_predictive_check refuses of the trace and the table (a NULL pointer, D, the trace shape, row_stride, kind, T), n_obs
+ * outside [1, 2^31), n_grouped outside [0, 2^31), a NULL order with n_grouped > 0, n_groups < 1, 0 <= g0 < g1 <= n_groups
+ * violated, draw_offset < 0. */
+int arp_group_predictive_check(const float* x, int64_t n_samples, int64_t n_chains, int32_t D, int64_t row_stride,
+                               int32_t kind, const int32_t* idx, const float* w, int32_t T, const float* y,
+                               const int32_t* scale_idx, const float* log_scale, int64_t n_obs, const int32_t* order,
+                               int64_t n_grouped, const int32_t* group_start, int64_t n_groups, int64_t g0, int64_t g1,
+                               uint64_t seed, int64_t draw_offset, double* group_stats, uint8_t* mask, int64_t* n_masked,
+                               void* stream);
+
 /* Leave-one-out predictive sums (csrc/loopred.hip; Vehtari, Gelman, Gabry 2017 section 2; loo::E_loo, loo::loo_pit): the
  * per-(observation, draw) predictive quantities of arp_predictive_check folded over the draws with importance weights.
  * The trace x, the table and the observation range [n0, n1) are those of arp_pointwise_loglik (same addressing, same
