@@ -84,6 +84,7 @@ SYMBOLS = ["arp_version", "arp_last_error", "arp_model_create", "arp_model_destr
            "arp_psis_weights_workspace_bytes", "arp_psis_weights",
            "arp_vi_draws", "arp_vi_fold_workspace_bytes", "arp_vi_fold",
            "arp_predictive_workspace_bytes", "arp_predictive_check", "arp_group_predictive_check",
+           "arp_group_loglik",
            "arp_loo_predictive_workspace_bytes", "arp_loo_predictive",
            "arp_loglik_total", "arp_element_order_workspace_bytes", "arp_element_order", "arp_cjs_sums",
            "arp_site_logprior", "arp_site_prior_draws", "arp_site_redraw", "arp_sbc_fold",
@@ -192,6 +193,11 @@ def lib():
                                              C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_uint64, C.c_int64,
                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.arp_group_predictive_check.restype = C.c_int
+    L.arp_group_loglik.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p,
+                                   C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
+                                   C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64] + [C.c_void_p] * 8 + [
+        C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.arp_group_loglik.restype = C.c_int
     L.arp_loo_predictive_workspace_bytes.argtypes = [C.c_int64, C.c_int64]
     L.arp_loo_predictive_workspace_bytes.restype = C.c_int64
     L.arp_loo_predictive.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int64, C.c_int32, C.c_void_p,

@@ -2,6 +2,7 @@
 
     python -m autoreparam_amd.analyze --results_dir=. --model=radon_MN --elbos --ess --rhat --energy --trajectory --geometry --loo --ppc --vi --sbc --reparams
     python -m autoreparam_amd.analyze --loo_compare=radon_MN/CP_tied_loo.npz,radon_stddvs_MN/CP_tied_loo.npz
+    python -m autoreparam_amd.analyze --logo_compare=radon_MN/CP_tied_logo.npz,radon_stddvs_MN/CP_tied_logo.npz
 
 The reference's method list is stale (`cVIP_exp_tied`, analyze.py:19-26) and it expects a
 `num_leapfrog_steps` key that main.py only writes for interleaved runs; here every
@@ -244,7 +245,7 @@ def report_loo(results):
     for m, r in results.items():
         if "loo_observations" not in r:
             continue
-        last = _last(r, ("elpd_", "p_loo", "p_waic", "loo_", "pareto_k_"))
+        last = _last(r, ("elpd_", "p_loo", "p_waic", "loo_", "pareto_k_", "logo_", "p_logo"))
         if last["loo_observations"] is None:
             lines.append("{}: PSIS-LOO / WAIC not computed".format(m))
             continue
@@ -273,6 +274,18 @@ def report_loo(results):
                              last["loo_pred_observations"], last.get("loo_pred_observations_left_out"),
                              _fmt(last.get("loo_is_ess_min")), last.get("loo_is_ess_min_observation"),
                              _secs(last.get("loo_pred_time_sec"))))
+        if last.get("logo_groups") is not None:
+            # leave-one-group-out (--loo_groups): the marginal form next to the conditional one -- that comparison is the report
+            form = lambda pre, e: "{} +/- {}, worst Pareto k-hat {} ({}; {} above {})".format(
+                _fmt(last.get(e)), _fmt(last.get(e + "_se")), _fmt(last.get(pre + "pareto_k_max")), last.get(pre + "pareto_k_max_group"),
+                last.get(pre + "pareto_k_above_threshold"), _fmt(last.get("logo_pareto_k_threshold")))
+            lines.append("      leave-one-group-out by {}: {} groups ({} empty, {} observations in none); marginal elpd_logo {}; "
+                         "conditional elpd {}; {} group(s) not finite; {} draws; {}".format(
+                             last.get("logo_part"), last["logo_groups"], last.get("logo_groups_empty"),
+                             last.get("logo_observations_left_out"),
+                             form("logo_", "elpd_logo") if last.get("logo_marginal") else "n/a (no closed marginal form)",
+                             form("logo_conditional_", "logo_conditional_elpd"), last.get("logo_nonfinite_groups"),
+                             last.get("logo_draws"), _secs(last.get("logo_time_sec"))))
     return lines
 
 
@@ -437,6 +450,26 @@ def report_loo_compare(path_a, path_b):
             str(a["model"]), str(b["model"]), diff, se, int(np.asarray(a["y"]).size))]
 
 
+def report_logo_compare(path_a, path_b):
+    """Build-specific: the paired difference in leave-one-group-out elpd of two models fitted to the same observations
+    and grouped the same way, from their <method>_logo.npz files (diagnostics.loo_compare over the non-empty groups, so the
+    se is over groups): positive favours the first.  The marginal form where both files have it, the conditional one
+    otherwise.  Refused unless y, group_of and part agree."""
+    from . import diagnostics
+    with np.load(path_a) as a, np.load(path_b) as b:
+        for name in ("part", "y", "group_of"):
+            if not np.array_equal(np.asarray(a[name]), np.asarray(b[name])):
+                raise ValueError("logo_compare: the two files differ in %s -- the groups are not the same, and the pairing is "
+                                 "what the se rests on" % name)
+        filled = np.asarray(a["n_obs"]) > 0
+        marginal = all(np.any(np.isfinite(np.asarray(z["elpd_logo_g"], np.float64)[filled])) for z in (a, b))
+        name = "elpd_logo_g" if marginal else "conditional_elpd_logo_g"
+        pair = [{"elpd_loo_i": np.asarray(z[name], np.float64)[filled], "y": np.flatnonzero(filled)} for z in (a, b)]
+        diff, se = diagnostics.loo_compare(*pair)
+        return ["elpd_logo({}) - elpd_logo({}) = {:.4g} +/- {:.4g} over {} groups of {} ({})".format(
+            str(a["model"]), str(b["model"]), diff, se, int(filled.sum()), str(a["part"]), "marginal" if marginal else "conditional")]
+
+
 def report_sbc(results):
     """Build-specific: simulation-based calibration of every method that recorded it (--inference=SBC writes
     <method>_sbc.json next to the method's own file): the worst quantity with its p-value and the two shape figures, then
@@ -469,9 +502,16 @@ def main(argv=None):
               "sbc"):
         ap.add_argument("--" + f, action="store_true")
     ap.add_argument("--loo_compare", default="", help="A_loo.npz,B_loo.npz: the paired elpd_loo difference of two models")
+    ap.add_argument("--logo_compare", default="", help="A_logo.npz,B_logo.npz: the paired leave-one-group-out elpd difference of two models")
     ap.add_argument("--model", default="all")
     ap.add_argument("--results_dir", default="")
     args = ap.parse_args(argv)
+    if args.logo_compare:
+        paths = [p for p in args.logo_compare.split(",") if p]
+        if len(paths) != 2:
+            ap.error("--logo_compare takes two files: A_logo.npz,B_logo.npz")
+        print("\n".join(report_logo_compare(*paths)) + "\n")
+        return
     if args.loo_compare:
         paths = [p for p in args.loo_compare.split(",") if p]
         if len(paths) != 2:

@@ -867,7 +867,7 @@ DeviceGroups = collections.namedtuple("DeviceGroups", ["G", "n_obs", "n_grouped"
 PpcGroupSummary = collections.namedtuple("PpcGroupSummary", ["draws_used", "draws_left_out", "sizes", "p", "rep", "obs"])
 
 
-def group_selection(table, spec, part):
+def group_selection(table, spec, part, flag=GROUPS_FLAG):
     """(group_of [N] int32, names) -- THE grouping rule of the grouped predictive check (--predictive_checks_groups=PART):
     the groups are the elements of the latent part `part` of `spec` (anything with part_names, part_shapes and offsets),
     group_of[n] is the element of it that the linear predictor of observation n of `table` (ModelSpec.observation_table)
@@ -875,26 +875,26 @@ def group_selection(table, spec, part):
     the geometry report names them (`m[17]`).  An element nobody reads is an empty group.  Pure numpy.  Refused, by a
     ValueError that names the flag: a name that is no part; a part of one element (that is the whole-data check); a part
     no observation reads; a part of which some observation reads more than one element (beta of German credit: a
-    regression coefficient groups nothing)."""
+    regression coefficient groups nothing).  flag: the flag the messages name (--loo_groups groups by the same rule)."""
     from .report_common import element_names
     names = list(spec.part_names)
     if part not in names:
-        raise ValueError("%s: %s is no latent part of %s; its parts: %s" % (GROUPS_FLAG, part, spec.name, ", ".join(names)))
+        raise ValueError("%s: %s is no latent part of %s; its parts: %s" % (flag, part, spec.name, ", ".join(names)))
     k = names.index(part)
     lo, hi = int(spec.offsets[k]), int(spec.offsets[k + 1])
     if hi - lo < 2:
-        raise ValueError("%s: %s has one element, so its one group is all the data: that is --predictive_checks itself"
-                         % (GROUPS_FLAG, part))
+        raise ValueError("%s: %s has one element, so its one group is all the data: %s" % (
+            flag, part, "that is --predictive_checks itself" if flag == GROUPS_FLAG else "leaving it out leaves nothing to predict it from"))
     idx, w = np.asarray(table.idx, np.int64), np.asarray(table.w)
     reads = (w != 0) & (idx >= lo) & (idx < hi)
     if not reads.any():
-        raise ValueError("%s: no observation's linear predictor reads %s" % (GROUPS_FLAG, part))
+        raise ValueError("%s: no observation's linear predictor reads %s" % (flag, part))
     first = np.where(reads, idx - lo, hi - lo).min(axis=1)
     last = np.where(reads, idx - lo, -1).max(axis=1)
     several = np.flatnonzero(reads.any(axis=1) & (first != last))
     if several.size:
         raise ValueError("%s: %d observation(s) read more than one element of %s (the first: observation %d), so its elements "
-                         "do not group the data" % (GROUPS_FLAG, several.size, part, int(several[0])))
+                         "do not group the data" % (flag, several.size, part, int(several[0])))
     return last.astype(np.int32), element_names(spec)[lo:hi]
 
 
@@ -1000,6 +1000,118 @@ def ppc_group_summary(counts, y, group_of, kind):
     used = int(round(counts[filled[0], 0])) if filled.size else 0
     left = int(round(counts[filled[0], 1])) if filled.size else 0
     return PpcGroupSummary(used, left, sizes, p, rep, obs)
+
+
+# ---- leave-one-group-out cross-validation: the group log-likelihood, conditional and marginal (csrc/logo.hip) ----
+LOGO_FLAG = "--loo_groups"
+# DeviceGroups' fields and, on the device, slope [n_grouped] float32 parallel to order and elem [G] int32
+# (include/autoreparam.h: arp_group_loglik)
+DeviceLogoGroups = collections.namedtuple("DeviceLogoGroups", DeviceGroups._fields + ("slope", "elem"))
+# total: the LooSummary of the non-empty groups' rows (elpd_loo, its se OVER GROUPS, p_loo, and the marginal or conditional
+# group WAIC); groups, empty: ints
+LogoSummary = collections.namedtuple("LogoSummary", ["total", "groups", "empty"])
+
+
+def marginal_selection(site_table, table, spec, part):
+    """(group_of [N] int32, names, slope [N] float32, elem [G] int32, marginal_ok, why) for leave-one-group-out by the
+    elements of the latent part `part` (--loo_groups=PART): group_of and names are group_selection's (its refusals name
+    --loo_groups), slope[n] is the sum of the weights with which observation n reads its group's element (0 for an
+    observation in no group), elem[g] the index of group g's element in the state.  marginal_ok: whether the MARGINAL
+    group likelihood -- the element integrated against its conditional prior N(loc, exp(s)) of `site_table`
+    (ModelSpec.site_table) -- has the closed form arp_group_loglik computes; `why` says why not (None otherwise): Bernoulli
+    data; an element whose site is not of the form SITE_NORMAL; an element that a later site reads with a non-zero weight
+    (not a leaf: integrating it changes that site's density too); an observation whose scale reads an element of the part
+    (the likelihood is then not Gaussian in it).  The conditional form needs none of these.  Pure numpy."""
+    group_of, names = group_selection(table, spec, part, flag=LOGO_FLAG)
+    k = list(spec.part_names).index(part)
+    lo, hi = int(spec.offsets[k]), int(spec.offsets[k + 1])
+    idx, w = np.asarray(table.idx, np.int64), np.asarray(table.w, np.float32).astype(np.float64)
+    own = (idx == (lo + group_of.astype(np.int64))[:, None]) & (group_of >= 0)[:, None]
+    slope = np.where(own, w, 0.0).sum(axis=1).astype(np.float32)
+    elem = np.arange(lo, hi, dtype=np.int32)
+    form = np.asarray(site_table.form, np.int64).reshape(-1)
+    inside = lambda i: (np.asarray(i, np.int64) >= lo) & (np.asarray(i, np.int64) < hi)
+    reads_loc = (np.asarray(site_table.loc_w) != 0) & inside(site_table.loc_idx) & (form != 2)[:, None]
+    reads_scale = (np.asarray(site_table.scale_w) != 0) & inside(site_table.scale_idx)
+    children = np.flatnonzero(reads_loc.any(axis=1) | reads_scale.any(axis=1))
+    scaled = np.flatnonzero(inside(np.asarray(table.scale_idx).reshape(-1)))
+    why = None
+    if int(table.kind) != 0:
+        why = "the data are Bernoulli: the marginal group likelihood has no closed form (quadrature is not implemented)"
+    elif np.any(form[lo:hi] != 0):
+        why = "the prior of %s is not a Normal with scale exp(s) (site form %d)" % (part, int(form[lo:hi][form[lo:hi] != 0][0]))
+    elif children.size:
+        why = "%s is not a leaf: the site of element %d reads it, so integrating it changes that density too" % (
+            part, int(children[0]))
+    elif scaled.size:
+        why = "the scale of observation %d reads %s: the likelihood is not Gaussian in it" % (int(scaled[0]), part)
+    return group_of, names, slope, elem, why is None, why
+
+
+def upload_logo_groups(order, group_start, slope, elem, n_obs, D, device):
+    """upload_groups(order, group_start, n_obs, device), its checks included, plus `slope` -- [n_obs] float32, one per
+    OBSERVATION (marginal_selection's); it is uploaded in order's sequence, slope[order] -- and `elem` [G] int32, every
+    entry in [0, D): the kernel addresses its tile and the site table with it -> DeviceLogoGroups."""
+    g = upload_groups(order, group_start, n_obs, device)
+    slope = np.ascontiguousarray(slope, np.float32).reshape(-1)
+    elem = np.ascontiguousarray(elem, np.int32).reshape(-1)
+    if slope.size != g.n_obs or not np.all(np.isfinite(slope)):
+        raise ValueError("observation groups: slope must have one finite entry per observation (%d)" % g.n_obs)
+    if elem.size != g.G or elem.min() < 0 or elem.max() >= int(D):
+        raise ValueError("observation groups: elem must have one entry per group (%d) inside the state's %d elements" % (g.G, int(D)))
+    in_order = slope[np.ascontiguousarray(order, np.int64).reshape(-1)] if g.n_grouped else np.zeros(1, np.float32)
+    dev = lambda a: torch.as_tensor(np.ascontiguousarray(a), device=device)
+    return DeviceLogoGroups(*g, dev(in_order), dev(elem))
+
+
+def group_loglik(trace, table, groups, site=None, g0=0, g1=None, out=None):
+    """(lc, lm or None, mask, n_masked) of `arp_group_loglik` for a recorded CENTRED [S, C, D] float32 trace on the GPU, a
+    DeviceTable (whole) and the groups [g0, g1) of a DeviceLogoGroups over it: lc [g1 - g0, S C] float32, the CONDITIONAL
+    log-likelihood of group g at draw r -- float32 of the float64 sum, ascending, of pointwise_loglik's values of the
+    group's observations; lm, with `site` (a DeviceSiteTable) and Normal data, the MARGINAL one: the group's element
+    integrated against its conditional prior in closed form, float64 behind the per-observation float32 values.  An empty
+    group and a draw left out are 0 in both; mask, n_masked as pointwise_loglik's.  A row depends neither on [g0, g1) nor
+    on how the draws are spread over calls; without `site` lc is bitwise the same.  A block of chains of a wider trace is
+    read in place.  out: an optional float32 device matrix with unit column stride whose rows are at least S C apart, of
+    at least g1 - g0 rows (2 (g1 - g0) with `site`: lc is a view of the first g1 - g0, lm of the next)."""
+    who = "group_loglik"
+    view, _, _, R = _table_call(trace, table, 0, None, who)
+    dev = view[0].device
+    g1 = groups.G if g1 is None else int(g1)
+    g0 = int(g0)
+    if not isinstance(groups, DeviceLogoGroups):
+        raise ValueError("%s: a DeviceLogoGroups is required (upload_logo_groups)" % who)
+    if groups.n_obs != table.N:
+        raise ValueError("%s: the groups were uploaded for a table of %d observations, not %d" % (who, groups.n_obs, table.N))
+    if not 0 <= g0 < g1 <= groups.G:
+        raise ValueError("%s: 0 <= g0 < g1 <= %d groups is required" % (who, groups.G))
+    if site is not None and not isinstance(site, DeviceSiteTable):
+        raise ValueError("%s: site must be a DeviceSiteTable (upload_site_table)" % who)
+    if site is not None and site.D != view[3]:
+        raise ValueError("%s: the trace has %d elements, the site table %d" % (who, view[3], site.D))
+    n, rows = g1 - g0, (g1 - g0) * (2 if site is not None else 1)
+    if out is None:
+        out = torch.empty(rows, R, dtype=torch.float32, device=dev)
+    out, stride = _draw_matrix(out, torch.float32, rows, R, who, "out")
+    lc, lm = out[:n], (out[n:2 * n] if site is not None else None)
+    mask = torch.empty(R, dtype=torch.uint8, device=dev)
+    n_masked = torch.zeros((), dtype=torch.int64, device=dev)
+    columns = [getattr(site, name, None) for name in ("loc_idx", "loc_w", "loc0", "scale_idx", "scale_w", "log_scale0")]
+    _lib.call(dev, _lib.lib().arp_group_loglik, *_table_args(view, table, 0, table.N)[:-2], table.N, _lib.ptr(groups.order),
+              _lib.ptr(groups.slope), groups.n_grouped, _lib.ptr(groups.group_start), _lib.ptr(groups.elem), groups.G, g0, g1,
+              *(_lib.ptr(c) for c in columns), _lib.ptr(lc), _lib.ptr(lm), stride, _lib.ptr(mask), _lib.ptr(n_masked))
+    return lc[:, :R], (None if lm is None else lm[:, :R]), mask, n_masked
+
+
+def logo_summary(columns):
+    """The totals of leave-one-group-out from the [G, 8] per-group columns of psis_loo (host float64; an EMPTY group is a
+    row of NaN throughout) -> LogoSummary: loo_summary over the rows of the non-empty groups -- so its standard errors are
+    over groups, sqrt(G' var_g) -- and the counts.  A non-finite entry of a non-empty group carries through, as in
+    loo_summary."""
+    c = np.asarray(_lib.host64(columns), np.float64).reshape(-1, len(PSIS_COLUMNS))
+    empty = np.all(np.isnan(c), axis=1)
+    f = c[~empty]
+    return LogoSummary(loo_summary(f[:, 0], f[:, 2], f[:, 3]), int(c.shape[0]), int(empty.sum()))
 
 
 # ---- leave-one-out predictive report: the predictive quantities folded with the PSIS weights (csrc/loopred.hip) ----

@@ -160,6 +160,21 @@ _DEFS = [
                                     "matching; an observation with a high Pareto k-hat is as unreliable here as its "
                                     "elpd_loo.  Every other output of --predictive_diagnostics is bit for bit unchanged.  "
                                     "One process only: a sharded job writes null."),
+    ("loo_groups", str, "", "With --predictive_diagnostics only: PART, one latent part of the model whose elements group the "
+                            "observations (m for radon: the counties; theta for 8schools; a or b for electric; a for "
+                            "election -- the rule of --predictive_checks_groups).  PSIS leave-one-GROUP-out cross-validation "
+                            "on the draws of the report: how well does the model predict a county it has not seen?  "
+                            "Per group and draw the joint log-likelihood of the group's observations (arp_group_loglik) in "
+                            "two forms: CONDITIONAL, at the recorded group effect, whose importance ratios usually have "
+                            "a high Pareto k-hat; and MARGINAL, the group's own effect integrated against its conditional "
+                            "prior N(loc, exp(s)) in closed form (Normal data; Merkle, Furr, Rabe-Hesketh 2019), whose "
+                            "reciprocal is the exact leave-group-out ratio.  arp_psis_loo reads either in the place of a "
+                            "pointwise log-likelihood (elpd_logo, logo_* JSON keys, <base>_logo.npz; analyze --loo prints a "
+                            "line, analyze --logo_compare pairs two models by group).  Bernoulli data (election) get the "
+                            "conditional form only: no quadrature.  No moment matching or refits for high k-hat, one part "
+                            "per run, the data at the observed covariates, and k-hat is itself an estimate.  Every other "
+                            "output of --predictive_diagnostics is bit for bit unchanged.  Refused: the flag without "
+                            "--predictive_diagnostics, neals_funnel, and what --predictive_checks_groups refuses of a part."),
     ("sensitivity_diagnostics", bool, False, "Sampling runs, with --convergence_diagnostics: how much of each posterior "
                                              "marginal comes from the prior, how much from the data?  Power-scaling "
                                              "sensitivity (Kallioinen, Paananen, Buerkner, Vehtari 2023; priorsense, ArviZ "

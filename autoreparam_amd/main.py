@@ -735,6 +735,36 @@ LOO_PRED_KEYS = ("loo_pred_observations", "loo_pred_observations_left_out", "loo
                  "loo_is_ess_min_observation", "loo_pred_time_sec")
 
 
+LOGO_ARRAYS = "logo/"                # where _loo_report leaves the arrays of <base>_logo.npz among those of _loo.npz (--loo_groups)
+LOGO_SHOWN = 8                       # groups with a high marginal k-hat the warning names
+_LOGO_FORM = ("elpd", "elpd_se", "p", "pareto_k_max", "pareto_k_max_group", "pareto_k_above_threshold")
+LOGO_MARGINAL_KEYS = ("elpd_logo", "elpd_logo_se", "p_logo", "logo_pareto_k_max", "logo_pareto_k_max_group",
+                      "logo_pareto_k_above_threshold")
+LOGO_KEYS = (("logo_part", "logo_groups", "logo_groups_empty", "logo_observations_left_out", "logo_draws") + LOGO_MARGINAL_KEYS
+             + tuple("logo_conditional_" + name for name in _LOGO_FORM)
+             + ("logo_pareto_k_threshold", "logo_nonfinite_groups", "logo_marginal", "logo_time_sec"))
+
+
+def loo_groups_part(flags):
+    """The part --loo_groups names; "" without the flag."""
+    return getattr(flags, "loo_groups", "") or ""
+
+
+def check_loo_groups(flags):
+    """--loo_groups against the job, before anything runs -- raises ValueError, naming the flag, for the flag without
+    --predictive_diagnostics, for neals_funnel (no observations) and for whatever diagnostics.group_selection refuses: a
+    name that is no part, a part of one element, a part no observation reads, a part whose elements do not group the data."""
+    part = loo_groups_part(flags)
+    if not part:
+        return
+    if not getattr(flags, "predictive_diagnostics", False):
+        raise ValueError("--loo_groups is read with --predictive_diagnostics only")
+    if flags.model == "neals_funnel":
+        raise ValueError("--loo_groups: neals_funnel has no observations, so there is no group to leave out")
+    spec = models.spec_by_name(flags.model, dataset=getattr(flags, "dataset", None))
+    diagnostics.group_selection(spec.observation_table(), spec, part, flag=diagnostics.LOGO_FLAG)
+
+
 def check_predictive(flags):
     """--predictive_diagnostics and --loo_predictive against the job, before anything runs: raises ValueError for a model
     without observations (neals_funnel), whose pointwise log-likelihood does not exist, and for --loo_predictive without
@@ -753,8 +783,10 @@ def loo_tile_rows(N, R, budget=None):
 
 
 def _loo_null(why, flags=None):
-    """Every key of the predictive report, and with --loo_predictive of that report too, as null; one message says why."""
-    return _null_keys("PSIS-LOO / WAIC", why, LOO_KEYS + (LOO_PRED_KEYS if getattr(flags, "loo_predictive", False) else ()))
+    """Every key of the predictive report, and with --loo_predictive and --loo_groups of those reports too, as null; one
+    message says why."""
+    return _null_keys("PSIS-LOO / WAIC", why, LOO_KEYS + (LOO_PRED_KEYS if getattr(flags, "loo_predictive", False) else ())
+                      + (LOGO_KEYS if loo_groups_part(flags) else ()))
 
 
 def loo_pred_keys(summary):
@@ -791,6 +823,120 @@ def loo_keys(columns, R, left_out, n_chains, n_steps):
         ("loo_nonfinite_observations", int(np.sum(~np.isfinite(c[:, 0]))))])
 
 
+def _logo_form_keys(columns, names, threshold, prefix):
+    """The six keys of one form (marginal: prefix "", conditional: "logo_conditional_") from its [G, 8] columns, the empty
+    groups' rows NaN; all null without columns (no marginal form)."""
+    keys = LOGO_MARGINAL_KEYS if not prefix else tuple(prefix + name for name in _LOGO_FORM)
+    if columns is None:
+        return OrderedDict((key, None) for key in keys)
+    total = diagnostics.logo_summary(columns).total
+    filled = ~np.all(np.isnan(columns), axis=1)
+    k = np.where(filled, columns[:, 1], np.nan)
+    k_max, at = _nan_max(k)
+    with np.errstate(invalid="ignore"):
+        above = int(np.sum(k > threshold)) if np.isfinite(threshold) else int(np.sum(filled & ~np.isfinite(k)))
+    return OrderedDict(zip(keys, (_finite_or_none(total.elpd_loo), _finite_or_none(total.elpd_loo_se), _finite_or_none(total.p_loo),
+                                  _finite_or_none(k_max), names[at] if at >= 0 else None, above)))
+
+
+def logo_keys(conditional, marginal, part, names, n_ungrouped, R, left_out):
+    """The JSON keys of leave-one-group-out (all but logo_time_sec) from the [G, 8] per-group columns of diagnostics.psis_loo
+    on the conditional and on the marginal group log-likelihood (host float64, an empty group's row NaN; marginal: None when
+    the model has no closed marginal form, its six keys are then null and logo_marginal is false); pure numpy.  elpd, its se
+    over groups and p = sum_g (lppd_g - elpd_g) per form; the worst k-hat is named by its group (`m[17]`);
+    logo_nonfinite_groups counts the non-empty groups whose elpd is not finite in a form that was computed."""
+    c = np.asarray(conditional, np.float64).reshape(-1, 8)
+    m = None if marginal is None else np.asarray(marginal, np.float64).reshape(-1, 8)
+    used = int(R) - int(left_out)
+    threshold = diagnostics.pareto_k_threshold(used)
+    filled = ~np.all(np.isnan(c), axis=1)
+    bad = ~np.isfinite(c[:, 0]) if m is None else (~np.isfinite(c[:, 0]) | ~np.isfinite(m[:, 0]))
+    keys = OrderedDict([("logo_part", part), ("logo_groups", int(c.shape[0])), ("logo_groups_empty", int(np.sum(~filled))),
+                        ("logo_observations_left_out", int(n_ungrouped)), ("logo_draws", used)])
+    keys.update(_logo_form_keys(m, names, threshold, ""))
+    keys.update(_logo_form_keys(c, names, threshold, "logo_conditional_"))
+    keys.update([("logo_pareto_k_threshold", _finite_or_none(threshold)), ("logo_nonfinite_groups", int(np.sum(filled & bad))),
+                 ("logo_marginal", m is not None)])
+    return keys
+
+
+def logo_columns(draws, table, groups, site, sizes, budget=None):
+    """(conditional [G, 8], marginal [G, 8] or None, mask) host float64: diagnostics.psis_loo on the conditional and (with
+    `site`) the marginal group log-likelihood of every group at the draws `draws` [S, C, D] (diagnostics.group_loglik), in
+    ascending ranges of groups whose lc, lm and PSIS workspace stay within `budget` (report_common.logo_range_size) -- a
+    group's row does not depend on the range it came in.  The rows of empty groups (sizes [G] == 0) are NaN throughout."""
+    import torch
+    R = int(draws.shape[0]) * int(draws.shape[1])
+    forms = 2 if site is not None else 1
+    per = report_common.logo_range_size(groups.G, R, forms, diagnostics.psis_workspace_bytes,
+                                        LOO_CHUNK_BYTES if budget is None else budget)
+    buffer = torch.empty(forms * per, R, dtype=torch.float32, device=draws.device)
+    cond, marg, mask = [], [], None
+    for g0 in range(0, groups.G, per):
+        lc, lm, mask, _ = diagnostics.group_loglik(draws, table, groups, site, g0, min(groups.G, g0 + per), out=buffer)
+        cond.append(diagnostics.psis_loo(lc, mask).cpu().numpy())
+        if lm is not None:
+            marg.append(diagnostics.psis_loo(lm, mask).cpu().numpy())
+    del buffer
+    empty = np.asarray(sizes).reshape(-1) == 0
+    out = []
+    for blocks in (cond, marg):
+        c = np.concatenate(blocks, axis=0) if blocks else None
+        if c is not None:
+            c[empty] = np.nan
+        out.append(c)
+    return out[0], out[1], mask
+
+
+def _logo_report(draws, table, spec, part, R, left_out):
+    """--loo_groups=PART, the second half of _loo_report, on its draws: PSIS leave-one-GROUP-out, the groups being the
+    observations that read one element of the latent part (diagnostics.marginal_selection: group_selection's rule).  Per
+    group and draw the joint log-likelihood of the group's observations at the recorded effect (conditional) and, Normal
+    data with a Normal leaf prior, with the group's own effect integrated against its conditional prior in closed form
+    (marginal; diagnostics.group_loglik, one kernel for both) -- the per-(observation, draw) matrix is never materialised;
+    diagnostics.psis_loo reads either in the place of a pointwise log-likelihood (logo_columns), its lppd and p_waic
+    columns becoming the group WAIC.  The conditional ratio's k-hat is usually high -- the other draws' effect of a county
+    says little about the posterior without the county -- and is the contrast the marginal form is read against (Merkle,
+    Furr, Rabe-Hesketh 2019).  Returns (LOGO_KEYS, the arrays of <base>_logo.npz).
+    Without a marginal form (Bernoulli data, ...) its keys are null and one message says why."""
+    clock = time.time()
+    dev, D = draws.device, int(draws.shape[2])
+    site_host = spec.site_table()
+    group_of, names, slope, elem, ok, why = diagnostics.marginal_selection(site_host, spec.observation_table(), spec, part)
+    G = len(names)
+    order, start = diagnostics.group_order(group_of, G)
+    groups = diagnostics.upload_logo_groups(order, start, slope, elem, table.N, D, dev)
+    if not ok:
+        util.print_("    marginal leave-one-group-out by {}: not computed, {}".format(part, why))
+    site = diagnostics.upload_site_table(site_host, D, dev) if ok else None
+    cond, marg, _ = logo_columns(draws, table, groups, site, groups.sizes)
+    keys = logo_keys(cond, marg, part, names, int(np.sum(group_of < 0)), R, left_out)
+    form = lambda pre, e: "{} +/- {}, worst Pareto k-hat {} ({})".format(
+        _fmt(keys[e]), _fmt(keys[e + "_se"]), _fmt(keys[pre + "pareto_k_max"]), keys[pre + "pareto_k_max_group"])
+    util.print_("    PSIS leave-one-group-out by {}: {} groups ({} empty, {} observations in none), {} draws: marginal elpd_logo {}; "
+                "conditional elpd {}".format(part, G, keys["logo_groups_empty"], keys["logo_observations_left_out"], keys["logo_draws"],
+                                             form("logo_", "elpd_logo") if ok else "n/a",
+                                             form("logo_conditional_", "logo_conditional_elpd")))
+    if ok and keys["logo_pareto_k_above_threshold"]:
+        threshold = keys["logo_pareto_k_threshold"]
+        with np.errstate(invalid="ignore"):
+            k = marg[:, 1]
+            high = [names[g] for g in np.flatnonzero((k > threshold) if threshold is not None else (groups.sizes > 0) & ~np.isfinite(k))]
+        util.print_("    WARNING: marginal Pareto k-hat above {} for {} group(s) of {}: {}{} -- their leave-group-out estimates "
+                    "are unreliable (which: <base>_logo.npz)".format(_fmt(threshold), len(high), part, ", ".join(high[:LOGO_SHOWN]),
+                                                                     ", ..." if len(high) > LOGO_SHOWN else ""))
+    nan = np.full(G, np.nan)
+    column = lambda c, j: nan.copy() if c is None else c[:, j]
+    arrays = OrderedDict(
+        [("part", np.asarray(part)), ("groups", np.asarray(names)), ("group_of", np.asarray(group_of, np.int32)),
+         ("n_obs", np.asarray(groups.sizes, np.int64))]
+        + [(pre + name, column(c, j)) for pre, c in (("", marg), ("conditional_", cond))
+           for name, j in (("elpd_logo_g", 0), ("pareto_k", 1), ("lppd_g", 2), ("p_waic_g", 3))]
+        + [("y", np.asarray(table.y_host, np.float32)), ("model", np.asarray(spec.name))])
+    keys["logo_time_sec"] = time.time() - clock
+    return keys, arrays
+
+
 def _loo_report(kernel_results, trace, k, spec, flags, side=None):
     """--predictive_diagnostics: how well does this MODEL predict an observation it has not seen?  Over the leading `k`
     chains of the device trace -- the chains split R-hat covers -- and clamp(--loo_draws // k, 1, S) evenly spaced recorded
@@ -807,6 +953,8 @@ def _loo_report(kernel_results, trace, k, spec, flags, side=None):
     PIT of every (observation, draw) with those weights; the per-observation sums are turned into the report on the host
     (diagnostics.loo_predictive_summary -> LOO_PRED_KEYS; no threshold can be derived for them, so no warning) and the
     arrays of <base>_loopred.npz are left in `side` under LOO_PRED_ARRAYS.  The keys are null whenever the report is.
+    --loo_groups=PART: PSIS leave-one-group-out on the same draws (_logo_report -> LOGO_KEYS; the arrays of <base>_logo.npz
+    wait under LOGO_ARRAYS for save_loo); it runs behind everything above and touches none of it.
     Returns (JSON keys, arrays of <base>_loo.npz or None)."""
     import torch
     pred = bool(getattr(flags, "loo_predictive", False))
@@ -867,6 +1015,9 @@ def _loo_report(kernel_results, trace, k, spec, flags, side=None):
                 ("loo_is_ess", summary.is_ess), ("y", np.asarray(table.y_host, np.float32)), ("model", np.asarray(spec.name))])
         keys.update(more)
         keys["loo_pred_time_sec"] = pred_time + (time.time() - pred_clock)
+    if loo_groups_part(flags):
+        logo, arrays[LOGO_ARRAYS] = _logo_report(draws, table, spec, loo_groups_part(flags), R, left_out)    # (save_loo takes them out again)
+        keys.update(logo)
     keys["loo_time_sec"] = time.time() - clock
     return keys, arrays
 
@@ -874,8 +1025,22 @@ def _loo_report(kernel_results, trace, k, spec, flags, side=None):
 def save_loo(file_path_base, arrays):
     """`<base>_loo.npz` (build-specific, --predictive_diagnostics): per observation `elpd_loo_i`, `pareto_k` (+inf where no
     tail was fitted), `lppd_i` and `p_waic_i` [N] float64; `y` [N], the observations themselves -- what
-    diagnostics.loo_compare pairs two models by -- and `model`, the model's name."""
+    diagnostics.loo_compare pairs two models by -- and `model`, the model's name.  With --loo_groups the arrays of
+    <base>_logo.npz wait among them under LOGO_ARRAYS and are written by save_logo: _loo.npz is the unflagged run's."""
+    arrays = OrderedDict(arrays)
+    grouped = arrays.pop(LOGO_ARRAYS, None)
     np.savez(file_path_base + "_loo.npz", **arrays)
+    if grouped is not None:
+        save_logo(file_path_base, grouped)
+
+
+def save_logo(file_path_base, arrays):
+    """`<base>_logo.npz` (build-specific, --loo_groups): `part`, the part whose elements are the groups; `groups` [G], their
+    names; `group_of` [N] int32, the group of every observation (-1: none); `n_obs` [G], the groups' sizes; per group
+    `elpd_logo_g`, `pareto_k`, `lppd_g`, `p_waic_g` [G] float64 of the MARGINAL form (NaN for an empty group, and
+    throughout when the model has no marginal form) and the same four under `conditional_`; `y` [N] and `model` --
+    what analyze --logo_compare pairs two models by."""
+    np.savez(file_path_base + "_logo.npz", **arrays)
 
 
 def save_loo_pred(file_path_base, arrays):
@@ -2158,6 +2323,7 @@ def main(argv=None, flags=FLAGS, out=None):
         # accepting the flag silently would write a *_reparam_variational*.json that holds ordinary mean-field results
         raise NotImplementedError("--reparameterise_variational is not supported by this build (SURVEY.md section 2)")
     check_predictive(flags)
+    check_loo_groups(flags)
     check_predictive_checks(flags)
     check_predictive_redraw(flags)
     check_predictive_groups(flags)

@@ -145,6 +145,17 @@ def group_range_size(G, R, budget=None):
     return int(max(1, min(max(int(G), 1), budget // max(1, 64 * int(R)))))
 
 
+def logo_range_size(G, R, forms, workspace_bytes, budget=None):
+    """Groups per call of leave-one-group-out: `forms` (1: conditional, 2: and marginal) [groups, R] float32 matrices and
+    the PSIS workspace `workspace_bytes(groups, R)` of one of them within `budget` bytes (LOO_CHUNK_BYTES) -- group_range_size
+    with this report's rows, halved as ppc_tile_rows halves until the workspace fits too; at least one."""
+    budget = LOO_CHUNK_BYTES if budget is None else int(budget)
+    per = int(max(1, min(max(int(G), 1), budget // max(1, 4 * int(forms) * int(R)))))
+    while per > 1 and 4 * int(forms) * int(R) * per + workspace_bytes(per, R) > budget:
+        per = (per + 1) // 2
+    return per
+
+
 def replicate_groups(draws, table, groups, y, group_of, seed, draw_offset=0, left_out=None, budget=None):
     """(counts [G, PPC_COUNTS] float64 numpy, mask [S C] on the device): the data replicated per draw of `draws` [S, C, D]
     and folded per group (diagnostics.group_predictive_check), in ascending ranges of groups whose [groups, S C, 8]

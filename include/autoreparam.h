@@ -584,6 +584,40 @@ int arp_group_predictive_check(const float* x, int64_t n_samples, int64_t n_chai
                                uint64_t seed, int64_t draw_offset, double* group_stats, uint8_t* mask, int64_t* n_masked,
                                void* stream);
 
+/* Group log-likelihood (csrc/logo.hip; PSIS leave-one-group-out: Vehtari, Gelman, Gabry 2017; Merkle, Furr, Rabe-Hesketh
+ * 2019): per group of observations and draw, the joint log-likelihood of the group at the recorded state (CONDITIONAL) and,
+ * Normal data, with the group's own latent element integrated against its conditional prior (MARGINAL).  The trace x, the
+ * table (whole: n_obs its length), order, n_grouped, group_start, n_groups and [g0, g1) are arp_group_predictive_check's.
+ * slope [n_grouped] float runs parallel to order: the sum of the weights with which observation order[j] reads its
+ * group's element; elem [n_groups]: that element's index in the state, clamped into [0, D) before use.  The site table --
+ * site_loc_idx, site_scale_idx [D][ARP_SITE_TERMS] int32, site_loc_w, site_scale_w [D][ARP_SITE_TERMS] and site_loc0,
+ * site_log_scale0 [D] float -- is arp_site_logprior's; only the rows elem names are read, as the float32 chains
+ * loc = loc0 + sum_t loc_w x[loc_idx], sj = log_scale0 + sum_t scale_w x[scale_idx] of that kernel.
+ * Per (n, r) the float32 value ll is arp_pointwise_loglik's, operation for operation; Normal data also b = slope *
+ * exp(-s_n) and the float32 products b * z, b * b (z = (y_n - eta_n) * exp(-s_n)).  Per (group, draw), float64, in order's
+ * sequence: S_ll = sum ll, S_bz = sum b z, S_bb = sum b b.  Outputs (device memory, either may be NULL, not both):
+ *   lc [g1 - g0][out_stride] float, lc[(g - g0) * out_stride + r] = (float)S_ll: the float64 sum, in order's sequence, of
+ *     the values arp_pointwise_loglik writes for the group's observations, rounded once.
+ *   lm, same layout, kind ARP_OBS_NORMAL only.  With t0 = x[elem[g]], tau = exp(-2 sj), m = t0 - loc, P = S_bb + tau,
+ *     q = S_bz - m * tau, all float64:  lm = (float)(S_ll - 0.5 * (m * m * tau - q * q / P) - 0.5 * log1p(S_bb / tau))
+ *     = log of the integral over t of prod_n p(y_n | eta_n + slope_n (t - t0), s_n) * N(t | loc, exp(sj)) -- exact when
+ *     nothing but the group's linear predictors reads the element.  A tau of 0, inf or NaN gives a non-finite lm, written
+ *     as it comes.  lm == NULL: nothing is computed for it and lc is bitwise unchanged.
+ *   An empty group writes 0 in both; a draw that is left out writes 0 in both, by select.
+ *   mask and *n_masked as arp_pointwise_loglik's.
+ * No float atomics and one fixed chain of additions per (group, draw): a row does not depend on the tiling, on [g0, g1) or
+ * on how many draws a call holds; two calls give bitwise equal outputs.  Error bound of lm: the header of csrc/logo.hip.
+ * No workspace.  Asynchronous.  Refused before any launch: what arp_group_predictive_check refuses of the trace, the
+ * table and the groups; a NULL slope or elem; both outputs NULL; a NULL site pointer with lm; lm with kind
+ * ARP_OBS_BERNOULLI; out_stride < n_samples * n_chains. */
+int arp_group_loglik(const float* x, int64_t n_samples, int64_t n_chains, int32_t D, int64_t row_stride, int32_t kind,
+                     const int32_t* idx, const float* w, int32_t T, const float* y, const int32_t* scale_idx,
+                     const float* log_scale, int64_t n_obs, const int32_t* order, const float* slope, int64_t n_grouped,
+                     const int32_t* group_start, const int32_t* elem, int64_t n_groups, int64_t g0, int64_t g1,
+                     const int32_t* site_loc_idx, const float* site_loc_w, const float* site_loc0,
+                     const int32_t* site_scale_idx, const float* site_scale_w, const float* site_log_scale0, float* lc,
+                     float* lm, int64_t out_stride, uint8_t* mask, int64_t* n_masked, void* stream);
+
 /* Leave-one-out predictive sums (csrc/loopred.hip; Vehtari, Gelman, Gabry 2017 section 2; loo::E_loo, loo::loo_pit): the
  * per-(observation, draw) predictive quantities of arp_predictive_check folded over the draws with importance weights.
  * The trace x, the table and the observation range [n0, n1) are those of arp_pointwise_loglik (same addressing, same
