@@ -85,6 +85,7 @@ SYMBOLS = ["arp_version", "arp_last_error", "arp_model_create", "arp_model_destr
            "arp_vi_draws", "arp_vi_fold_workspace_bytes", "arp_vi_fold",
            "arp_predictive_workspace_bytes", "arp_predictive_check", "arp_group_predictive_check",
            "arp_group_loglik",
+           "arp_weighted_moments_workspace_bytes", "arp_weighted_moments", "arp_affine_rows",
            "arp_loo_predictive_workspace_bytes", "arp_loo_predictive",
            "arp_loglik_total", "arp_element_order_workspace_bytes", "arp_element_order", "arp_cjs_sums",
            "arp_site_logprior", "arp_site_prior_draws", "arp_site_redraw", "arp_sbc_fold",
@@ -198,6 +199,14 @@ def lib():
                                    C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64] + [C.c_void_p] * 8 + [
         C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
     L.arp_group_loglik.restype = C.c_int
+    L.arp_weighted_moments_workspace_bytes.argtypes = [C.c_int64, C.c_int32, C.c_int64]
+    L.arp_weighted_moments_workspace_bytes.restype = C.c_int64
+    L.arp_weighted_moments.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p,
+                                       C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+    L.arp_weighted_moments.restype = C.c_int
+    L.arp_affine_rows.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                  C.c_int32, C.c_void_p, C.c_void_p]
+    L.arp_affine_rows.restype = C.c_int
     L.arp_loo_predictive_workspace_bytes.argtypes = [C.c_int64, C.c_int64]
     L.arp_loo_predictive_workspace_bytes.restype = C.c_int64
     L.arp_loo_predictive.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int64, C.c_int32, C.c_void_p,

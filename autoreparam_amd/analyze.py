@@ -240,7 +240,8 @@ def report_loo(results):
     run of each file): elpd_loo and elpd_waic with their standard errors, the effective numbers of parameters, and the
     worst Pareto k-hat against its threshold.  No r_eff correction, no moment matching, no K-fold.  A run with
     --loo_predictive gets a second line: the calibration of the LOO-PIT (with the posterior PIT's of --predictive_checks
-    next to it where recorded), RMSE and R^2 or Brier score and accuracy, and the smallest importance-sampling ESS."""
+    next to it where recorded), RMSE and R^2 or Brier score and accuracy, and the smallest importance-sampling ESS; a run
+    with --loo_moment_match a line per moment-matched report: the matched total and worst k-hat next to the plain ones."""
     lines = []
     for m, r in results.items():
         if "loo_observations" not in r:
@@ -286,6 +287,20 @@ def report_loo(results):
                              form("logo_", "elpd_logo") if last.get("logo_marginal") else "n/a (no closed marginal form)",
                              form("logo_conditional_", "logo_conditional_elpd"), last.get("logo_nonfinite_groups"),
                              last.get("logo_draws"), _secs(last.get("logo_time_sec"))))
+        for pre, e, plain, plain_k, what in (("loo", "elpd_loo_mm", "elpd_loo", "pareto_k_max", "observation(s)"),
+                                             ("logo", "elpd_logo_mm", "logo_conditional_elpd", "logo_conditional_pareto_k_max",
+                                              "group(s), conditional form")):
+            if last.get(pre + "_mm_observations") is None:
+                continue
+            # moment matching (--loo_moment_match): the matched total and worst k-hat next to the plain ones
+            lines.append("      moment matching over {} {} ({} more above the threshold not attempted): k-hat fell for {}, resolved "
+                         "{}, at most {} map(s); {} {} +/- {} (plain {}), worst Pareto k-hat {} (plain {}; {} still above the "
+                         "threshold); full-posterior k-hat up to {}; {}".format(
+                             last[pre + "_mm_observations"], what, last.get(pre + "_mm_not_attempted"), last.get(pre + "_mm_improved"),
+                             last.get(pre + "_mm_resolved"), last.get(pre + "_mm_iterations_max"), e, _fmt(last.get(e)),
+                             _fmt(last.get(e + "_se")), _fmt(last.get(plain)), _fmt(last.get(pre + "_mm_pareto_k_max")),
+                             _fmt(last.get(plain_k)), last.get(pre + "_mm_pareto_k_above_threshold"),
+                             _fmt(last.get(pre + "_mm_full_pareto_k_max")), _secs(last.get(pre + "_mm_time_sec"))))
     return lines
 
 

@@ -1114,6 +1114,256 @@ def logo_summary(columns):
     return LogoSummary(loo_summary(f[:, 0], f[:, 2], f[:, 3]), int(c.shape[0]), int(empty.sum()))
 
 
+# ---- moment matching for a high Pareto k-hat (csrc/mmatch.hip; Paananen, Piironen, Buerkner, Vehtari 2021) ----
+MM_FLAG = "--loo_moment_match"
+MM_MAX_ITERATIONS = 30            # the most maps accepted per target (loo::loo_moment_match's max_iters)
+MM_MAX_D = 255                    # the widest matrix arp_weighted_moments and arp_affine_rows take
+MM_MAX_TARGETS = 4096             # the most targets they take in one call
+MM_HEAD = ("lw_max", "sum_w", "sum_w_sq", "draws_kept")        # in front of the D pairs (sum w e, sum w e^2) of a row
+# What moment_match returns, one entry per target, host numpy: attempted [T] bool (the plain k-hat was above the threshold);
+# elpd [T] (the split's where a map was accepted, the plain one otherwise); pareto_k (the loop's final k-hat; the plain one
+# where nothing was accepted or attempted); pareto_k_full (the k-hat of the full posterior's ratios under the last accepted
+# map; 0 where attempted and nothing was accepted), pareto_k_split, is_ess (of the split's weights) -- NaN where they do not
+# exist; iterations [T] int (maps accepted) and maps [T] str ("112": T1, T1, T2); scale, shift [T, D]: S and U - m0 of
+# theta = (x - m0) S + U, NaN where not attempted; centre [D]: m0.
+MomentMatch = collections.namedtuple("MomentMatch", ["attempted", "elpd", "pareto_k", "pareto_k_full", "pareto_k_split", "is_ess",
+                                                     "iterations", "maps", "scale", "shift", "centre"])
+
+
+def _mm_rows(x, who):
+    """x, a float32 [R, D] device matrix with unit column stride, read in place -> (x, R, D, row stride)."""
+    if not (torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.numel() > 0):
+        raise ValueError("%s: a non-empty float32 [R, D] matrix on the GPU is required (there is no CPU fallback)" % who)
+    R, D = (int(v) for v in x.shape)
+    if not (x.stride(1) == 1 and (R == 1 or x.stride(0) >= D)):
+        x = x.contiguous()
+    if D > MM_MAX_D:
+        raise ValueError("%s: at most %d columns" % (who, MM_MAX_D))
+    return x, R, D, (int(x.stride(0)) if R > 1 else D)
+
+
+def _mm_targets(B, who):
+    if not 1 <= int(B) <= MM_MAX_TARGETS:
+        raise ValueError("%s: 1 ... %d targets per call are required" % (who, MM_MAX_TARGETS))
+    return int(B)
+
+
+def weighted_moments_workspace_bytes(R, D, B):
+    """Bytes of device workspace `weighted_moments` takes for B targets over [R, D]; raises on a shape that is refused."""
+    need = int(_lib.lib().arp_weighted_moments_workspace_bytes(int(R), int(D), int(B)))
+    if need <= 0:
+        raise ValueError("weighted_moments: 1 <= R < 2^31 rows, 1 <= D <= %d and 1 ... %d targets are required" % (MM_MAX_D, MM_MAX_TARGETS))
+    return need
+
+
+def weighted_moments(x, lw, centre):
+    """out [B, 4 + 2 D] float64 device tensor of `arp_weighted_moments`: x [R, D] float32 on the GPU (rows may be further
+    apart than D, read in place), lw [B, R] float64 log weights (-inf: the draw is left out; arp_psis_weights' layout, rows
+    may be further apart than R), centre [D] float32.  Row b: MM_HEAD, then per column the pair sum w e, sum w e^2 with
+    w = exp(lw - lw_max) and e = x - centre, float64.  The workspace is owned here."""
+    who = "weighted_moments"
+    x, R, D, stride = _mm_rows(x, who)
+    lw, lw_stride = _draw_matrix(lw, torch.float64, 1, R, who, "lw")
+    if lw.shape[1] != R:
+        raise ValueError("%s: lw must have one column per row of x" % who)
+    B = _mm_targets(lw.shape[0], who)
+    _lib.device_operand(centre, torch.float32, (D,), who, "centre", "D")
+    if centre is None:
+        raise ValueError("%s: centre is required" % who)
+    out = torch.empty(B, len(MM_HEAD) + 2 * D, dtype=torch.float64, device=x.device)
+    _lib.call(x.device, _lib.lib().arp_weighted_moments, _lib.ptr(x), R, D, stride, _lib.ptr(lw), B, lw_stride, _lib.ptr(centre),
+              _lib.ptr(out), workspace=weighted_moments_workspace_bytes(R, D, B))
+    return out
+
+
+def affine_rows_bytes(R, D, B):
+    """Bytes of the [B, R, D] float32 output of `affine_rows`."""
+    return 4 * int(R) * int(D) * int(B)
+
+
+def affine_rows(x, m, s, u, parity=-1, out=None):
+    """out [B, R, D] float32 device tensor of `arp_affine_rows`: out[b, r] = (x[r] - m[b]) * s[b] + u[b], three float32
+    roundings in that order, for every row (parity < 0) or the rows with (r & 1) == parity; the other rows are copies of
+    x's, bit for bit.  x [R, D] float32 on the GPU, read in place; m, s, u [B, D] float32 contiguous.  out: an optional
+    contiguous float32 tensor of at least B R D elements, written in place (the result is a view of it)."""
+    who = "affine_rows"
+    x, R, D, stride = _mm_rows(x, who)
+    if not (torch.is_tensor(m) and m.dim() == 2 and m.shape[1] == D):
+        raise ValueError("%s: m, s and u must be float32 [B, D] tensors on the GPU" % who)
+    B = _mm_targets(m.shape[0], who)
+    for name, t in (("m", m), ("s", s), ("u", u)):
+        if t is None:
+            raise ValueError("%s: %s is required" % (who, name))
+        _lib.device_operand(t, torch.float32, (B, D), who, name, "B, D")
+    parity = int(parity)
+    if parity > 1:
+        raise ValueError("%s: parity must be negative (every row), 0 or 1" % who)
+    if out is None:
+        out = torch.empty(B, R, D, dtype=torch.float32, device=x.device)
+    elif not (torch.is_tensor(out) and out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() >= B * R * D):
+        raise ValueError("%s: out must be a contiguous float32 tensor of at least B R D elements on the GPU" % who)
+    res = out.reshape(-1)[:B * R * D].view(B, R, D)
+    _lib.call(x.device, _lib.lib().arp_affine_rows, _lib.ptr(x), R, D, stride, _lib.ptr(m), _lib.ptr(s), _lib.ptr(u), B, parity,
+              _lib.ptr(res))
+    return res
+
+
+def _mm_ratio_rows(rho, kept):
+    """Log ratios rho [n, R] float64 as psis_weights reads them: the NEGATED ratio in float32, about each row's mean over
+    the kept draws (it cancels; float32 then resolves the ratios and not their size -- powerscale_lw's rule).  A row with a
+    non-finite kept ratio comes out non-finite and is not fitted."""
+    zero = torch.zeros_like(rho)
+    centre = torch.where(kept[None], rho, zero).sum(dim=1, keepdim=True) / kept.sum().clamp(min=1)
+    return (-torch.where(kept[None], rho - centre, zero)).to(torch.float32).contiguous()
+
+
+def _mm_moments(sums, D):
+    """(mean [n, D], variance [n, D], sum w, sum w^2, lw_max) of e = x - centre from rows of weighted_moments, host float64."""
+    with np.errstate(all="ignore"):
+        sw = sums[:, 1:2]
+        pairs = sums[:, len(MM_HEAD):].reshape(-1, D, 2)
+        mean = pairs[:, :, 0] / sw
+        return mean, pairs[:, :, 1] / sw - mean * mean, sums[:, 1], sums[:, 2], sums[:, 0]
+
+
+def moment_match(x, left, logp_fn, loglik_fn, targets, plain_k, plain_elpd, threshold, batch=1):
+    """Implicitly adaptive importance sampling (Paananen, Piironen, Buerkner, Vehtari 2021; loo::loo_moment_match with
+    its maps T1 and T2 and the split of its section 4) for the targets whose plain Pareto k-hat is above `threshold` ->
+    MomentMatch.  THE definition of the algorithm here; the reports only feed it.
+      x [R, D] float32 on the GPU: the draws, in coordinates where every element is unconstrained (the centred trace);
+      left [R] bool or uint8 on the GPU: draws that are left out of everything;
+      logp_fn(rows [n, D] float32) -> [n]: the log joint density of the full posterior up to a constant;
+      loglik_fn(target, rows [n, D]) -> [n]: the log-likelihood term that leaving `target` out removes;
+      targets: T labels handed to loglik_fn; plain_k, plain_elpd [T]: their plain PSIS figures;
+      batch: targets per call of the kernels (report_common.mm_batch_size).
+    State.  m0 = float32 of the unweighted mean of the kept draws (one weighted_moments call with zero log weights about
+    0); L0 = logp_fn(x); l0 = loglik_fn(t, x).  The draws of a target are always the TOTAL map applied to the original
+    ones, theta = (x - m0) S + U (S = 1, U = m0 at the start; float64 on the host, rounded to float32 once per affine_rows
+    call), so no rounding accumulates.  The weighted (rows lw) and unweighted (a row of zeros) mean and variance of theta
+    come from one weighted_moments call on x about m0, mapped through (S, U) on the host.
+    Loop, per target, from (lw, k) = psis_weights(l0) and k_f = 0, while k > threshold and fewer than MM_MAX_ITERATIONS
+    maps are accepted:  T1: U' = U + (mu_w - mu);  refused -> T2, f = sqrt(v_w / v): S' = S f, U' = (U - mu) f + mu_w.  A
+    candidate's ratios rho = -l' + L' - L0 and rho_f = L' - L0 are smoothed by one psis_weights call; it is accepted iff
+    k' < k (a non-finite kept ratio gives k' = +inf).  Both refused: the loop ends.  The Jacobian is constant and cancels.
+    Split, where a map was accepted: A = x with the total map on its even rows, B = x with the inverse map
+    (x - U) / S + m0 on its odd rows; rho = -l(A) + L(A) - logaddexp(L(A), L(B) - sum_d log S_d), smoothed to lw_s;
+    elpd = log sum exp(lw_s + l(A)) - log sum exp(lw_s) and the ESS (sum w)^2 / sum w^2, the sums from weighted_moments.
+    Every active target of a batch goes through each kernel call together; a target's figures do not depend on `batch`."""
+    who = "moment_match"
+    x, R, D, _ = _mm_rows(x, who)
+    dev = x.device
+    T = len(targets)
+    plain_k, plain_elpd = (np.array(_lib.host64(v), np.float64).reshape(-1) for v in (plain_k, plain_elpd))
+    if plain_k.size != T or plain_elpd.size != T:
+        raise ValueError("%s: plain_k and plain_elpd must have one entry per target" % who)
+    batch = _mm_targets(int(batch) + 1, who) - 1                               # (and one row for the unweighted moments)
+    threshold = float(threshold)
+    with np.errstate(invalid="ignore"):
+        attempted = ~(plain_k <= threshold) if np.isfinite(threshold) else ~np.isfinite(plain_k)
+    nan = lambda *shape: np.full(shape, np.nan)
+    res = MomentMatch(attempted, plain_elpd.copy(), plain_k.copy(), nan(T), nan(T), nan(T), np.zeros(T, np.int64), [""] * T,
+                      nan(T, D), nan(T, D), None)
+    left = torch.as_tensor(left, device=dev).reshape(-1) != 0
+    if left.numel() != R:
+        raise ValueError("%s: left must have one entry per draw" % who)
+    f64 = lambda t: t.to(torch.float64).reshape(-1)
+    L0 = f64(logp_fn(x))
+    left = left | ~torch.isfinite(L0)
+    kept, mask = ~left, left.to(torch.uint8).contiguous()
+    base = torch.where(kept, torch.zeros(R, dtype=torch.float64, device=dev),
+                       torch.full((R,), float("-inf"), dtype=torch.float64, device=dev))
+    zero_centre = torch.zeros(D, dtype=torch.float32, device=dev)
+    m0 = _mm_moments(weighted_moments(x, base[None], zero_centre).cpu().numpy(), D)[0][0].astype(np.float32)
+    res = res._replace(centre=m0.astype(np.float64))
+    m0_d = torch.as_tensor(m0, device=dev)
+    m0 = m0.astype(np.float64)
+    up = lambda a: torch.as_tensor(np.ascontiguousarray(a, np.float32), device=dev)
+    out_buffer = torch.empty(batch * R * D, dtype=torch.float32, device=dev)
+
+    def densities(ids, rows):
+        """(L, l) [n, R] float64 at rows [n, R, D]: one logp_fn call, one loglik_fn call per target."""
+        n = len(ids)
+        L = f64(logp_fn(rows.view(n * R, D))).view(n, R)
+        return L, torch.stack([f64(loglik_fn(targets[t], rows[j])) for j, t in enumerate(ids)])
+
+    def candidates(ids, S, U):
+        """The k-hat, the full posterior's k-hat and the log weights of the maps (S, U) [n, D] of the targets `ids`."""
+        rows = affine_rows(x, m0_d[None].expand(len(ids), D).contiguous(), up(S), up(U), -1, out=out_buffer)
+        L, l = densities(ids, rows)
+        rho_f = L - L0[None]
+        out8, lw = psis_weights(_mm_ratio_rows(torch.cat([rho_f - l, rho_f]), kept), mask)
+        k = out8[:, 1].cpu().numpy()
+        return k[:len(ids)], k[len(ids):], lw[:len(ids)]
+
+    todo = [int(t) for t in np.flatnonzero(attempted)]
+    for b0 in range(0, len(todo), batch):
+        ids = todo[b0:b0 + batch]
+        n = len(ids)
+        l0 = torch.stack([loglik_fn(targets[t], x).to(torch.float32).reshape(-1) for t in ids]).contiguous()
+        out8, lw = psis_weights(l0, mask)
+        k = out8[:, 1].cpu().numpy().copy()
+        k_f = np.zeros(n)
+        S, U = np.ones((n, D)), np.tile(m0, (n, 1))
+        maps = [""] * n
+        active = [j for j in range(n) if k[j] > threshold or not np.isfinite(k[j])]
+        while active:
+            sums = weighted_moments(x, torch.cat([lw[active], base[None]]).contiguous(), m0_d).cpu().numpy()
+            mean_e, var_e, _, _, _ = _mm_moments(sums, D)
+            Sa, Ua = S[active], U[active]
+            with np.errstate(all="ignore"):
+                mu_w, v_w = mean_e[:-1] * Sa + Ua, var_e[:-1] * Sa * Sa
+                mu, v = mean_e[-1:] * Sa + Ua, var_e[-1:] * Sa * Sa
+                f = np.sqrt(v_w / v)
+            trial = [(Sa, Ua + (mu_w - mu), "1"), (Sa * f, (Ua - mu) * f + mu_w, "2")]
+            pending, accepted = list(range(len(active))), []
+            for S_c, U_c, name in trial:
+                if not pending:
+                    break
+                pick = [active[i] for i in pending]
+                k_c, kf_c, lw_c = candidates([ids[j] for j in pick], S_c[pending], U_c[pending])
+                still = []
+                for pos, (i, j) in enumerate(zip(pending, pick)):
+                    if k_c[pos] < k[j]:
+                        S[j], U[j], k[j], k_f[j] = S_c[i], U_c[i], k_c[pos], kf_c[pos]
+                        lw[j] = lw_c[pos]
+                        maps[j] += name
+                        accepted.append(j)
+                    else:
+                        still.append(i)
+                pending = still
+            active = [j for j in sorted(accepted) if k[j] > threshold and len(maps[j]) < MM_MAX_ITERATIONS]
+        for j, t in enumerate(ids):
+            res.pareto_k[t], res.pareto_k_full[t], res.iterations[t], res.maps[t] = k[j], k_f[j], len(maps[j]), maps[j]
+            res.scale[t], res.shift[t] = S[j], U[j] - m0
+        # the split, for the targets that moved: A and B share the buffer, half a batch at a time
+        moved = [j for j in range(n) if maps[j]]
+        half = max(1, batch // 2)
+        for c0 in range(0, len(moved), half):
+            js = moved[c0:c0 + half]
+            nj, sub = len(js), [ids[j] for j in js]
+            A = affine_rows(x, m0_d[None].expand(nj, D).contiguous(), up(S[js]), up(U[js]), 0, out=out_buffer)
+            if batch >= 2:
+                B_out = out_buffer[nj * R * D:]
+            else:
+                B_out = None
+            Bm = affine_rows(x, up(U[js]), up(1.0 / S[js]), m0_d[None].expand(nj, D).contiguous(), 1, out=B_out)
+            LA, lA = densities(sub, A)
+            LB = f64(logp_fn(Bm.view(nj * R, D))).view(nj, R)
+            log_det = torch.as_tensor(np.log(S[js]).sum(axis=1), device=dev)[:, None]
+            rho = -lA + LA - torch.logaddexp(LA, LB - log_det)
+            out8, lw_s = psis_weights(_mm_ratio_rows(rho, kept), mask)
+            k_s = out8[:, 1].cpu().numpy()
+            lA = torch.where(kept[None], lA, torch.zeros_like(lA))            # (lw_s is -inf there)
+            sums = weighted_moments(x, torch.cat([lw_s + lA, lw_s]).contiguous(), m0_d).cpu().numpy()
+            with np.errstate(all="ignore"):
+                log_sum = sums[:, 0] + np.log(sums[:, 1])
+                for pos, t in enumerate(sub):
+                    res.elpd[t] = log_sum[pos] - log_sum[nj + pos]
+                    res.is_ess[t] = sums[nj + pos, 1] ** 2 / sums[nj + pos, 2]
+                    res.pareto_k_split[t] = k_s[pos]
+    return res
+
+
 # ---- leave-one-out predictive report: the predictive quantities folded with the PSIS weights (csrc/loopred.hip) ----
 LOO_PRED_COLUMNS = ("sum_w", "sum_w_sq", "sum_w_mu", "sum_w_second_moment", "sum_w_pit", "draws_counted")
 # The report (loo_predictive_summary).  observations: those whose four figures are finite; left_out: the others.  loo_mean,

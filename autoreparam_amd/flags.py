@@ -175,6 +175,22 @@ _DEFS = [
                             "per run, the data at the observed covariates, and k-hat is itself an estimate.  Every other "
                             "output of --predictive_diagnostics is bit for bit unchanged.  Refused: the flag without "
                             "--predictive_diagnostics, neals_funnel, and what --predictive_checks_groups refuses of a part."),
+    ("loo_moment_match", bool, False, "With --predictive_diagnostics only: moment matching for the observations -- and, with "
+                                      "--loo_groups, the groups in their CONDITIONAL form -- whose Pareto k-hat is above the "
+                                      "threshold (implicitly adaptive importance sampling: Paananen, Piironen, Buerkner, "
+                                      "Vehtari 2021; loo::loo_moment_match).  The draws are moved by an affine map in the "
+                                      "centred coordinates until their weighted mean (T1) and marginal variance (T2) match, the "
+                                      "centred log joint and the left-out term are evaluated there, the tail is fitted again, "
+                                      "and the estimate is taken from the split of the paper's section 4 (arp_weighted_moments, "
+                                      "arp_affine_rows; loo_mm_* and logo_mm_* JSON keys, <base>_loo_mm.npz, <base>_logo_mm.npz; "
+                                      "analyze --loo prints a line).  No refit of the model.  No covariance map (T3), no "
+                                      "moment-matched --loo_predictive figures, no r_eff, not the marginal group form; the log "
+                                      "joint is float32.  Every other output of --predictive_diagnostics is bit for bit "
+                                      "unchanged.  One process only: a sharded job writes null.  Refused: the flag without "
+                                      "--predictive_diagnostics, neals_funnel."),
+    ("loo_moment_match_max", int, 64, "With --loo_moment_match: the most observations (and the most groups) taken, the worst "
+                                      "k-hat first; the others above the threshold are counted (loo_mm_not_attempted).  "
+                                      "1 ... 4096."),
     ("sensitivity_diagnostics", bool, False, "Sampling runs, with --convergence_diagnostics: how much of each posterior "
                                              "marginal comes from the prior, how much from the data?  Power-scaling "
                                              "sensitivity (Kallioinen, Paananen, Buerkner, Vehtari 2023; priorsense, ArviZ "

@@ -783,10 +783,12 @@ def loo_tile_rows(N, R, budget=None):
 
 
 def _loo_null(why, flags=None):
-    """Every key of the predictive report, and with --loo_predictive and --loo_groups of those reports too, as null; one
-    message says why."""
+    """Every key of the predictive report, and with --loo_predictive, --loo_groups and --loo_moment_match of those reports
+    too, as null; one message says why."""
+    mm = loo_moment_match(flags)
     return _null_keys("PSIS-LOO / WAIC", why, LOO_KEYS + (LOO_PRED_KEYS if getattr(flags, "loo_predictive", False) else ())
-                      + (LOGO_KEYS if loo_groups_part(flags) else ()))
+                      + (LOGO_KEYS if loo_groups_part(flags) else ()) + (LOO_MM_KEYS if mm else ())
+                      + (LOGO_MM_KEYS if mm and loo_groups_part(flags) else ()))
 
 
 def loo_pred_keys(summary):
@@ -888,7 +890,7 @@ def logo_columns(draws, table, groups, site, sizes, budget=None):
     return out[0], out[1], mask
 
 
-def _logo_report(draws, table, spec, part, R, left_out):
+def _logo_report(draws, table, spec, part, R, left_out, flags=None):
     """--loo_groups=PART, the second half of _loo_report, on its draws: PSIS leave-one-GROUP-out, the groups being the
     observations that read one element of the latent part (diagnostics.marginal_selection: group_selection's rule).  Per
     group and draw the joint log-likelihood of the group's observations at the recorded effect (conditional) and, Normal
@@ -898,7 +900,9 @@ def _logo_report(draws, table, spec, part, R, left_out):
     columns becoming the group WAIC.  The conditional ratio's k-hat is usually high -- the other draws' effect of a county
     says little about the posterior without the county -- and is the contrast the marginal form is read against (Merkle,
     Furr, Rabe-Hesketh 2019).  Returns (LOGO_KEYS, the arrays of <base>_logo.npz).
-    Without a marginal form (Bernoulli data, ...) its keys are null and one message says why."""
+    Without a marginal form (Bernoulli data, ...) its keys are null and one message says why.
+    With --loo_moment_match (`flags`) the groups whose CONDITIONAL k-hat is above the threshold are moment matched (_mm_run ->
+    LOGO_MM_KEYS; the arrays of <base>_logo_mm.npz wait under LOGO_MM_ARRAYS for save_logo); no key or array above changes."""
     clock = time.time()
     dev, D = draws.device, int(draws.shape[2])
     site_host = spec.site_table()
@@ -909,7 +913,7 @@ def _logo_report(draws, table, spec, part, R, left_out):
     if not ok:
         util.print_("    marginal leave-one-group-out by {}: not computed, {}".format(part, why))
     site = diagnostics.upload_site_table(site_host, D, dev) if ok else None
-    cond, marg, _ = logo_columns(draws, table, groups, site, groups.sizes)
+    cond, marg, mask = logo_columns(draws, table, groups, site, groups.sizes)
     keys = logo_keys(cond, marg, part, names, int(np.sum(group_of < 0)), R, left_out)
     form = lambda pre, e: "{} +/- {}, worst Pareto k-hat {} ({})".format(
         _fmt(keys[e]), _fmt(keys[e + "_se"]), _fmt(keys[pre + "pareto_k_max"]), keys[pre + "pareto_k_max_group"])
@@ -933,8 +937,168 @@ def _logo_report(draws, table, spec, part, R, left_out):
         + [(pre + name, column(c, j)) for pre, c in (("", marg), ("conditional_", cond))
            for name, j in (("elpd_logo_g", 0), ("pareto_k", 1), ("lppd_g", 2), ("p_waic_g", 3))]
         + [("y", np.asarray(table.y_host, np.float32)), ("model", np.asarray(spec.name))])
+    if loo_moment_match(flags):
+        more, merged = _mm_run(draws, mask, left_out, spec, flags, cond, _TableLoglik(table, groups), "logo",
+                               "group(s) of {}, conditional form".format(part), keys["logo_conditional_elpd"], names)
+        merged.update([(name, arrays[name]) for name in ("part", "groups", "group_of", "y", "model")])
+        arrays[LOGO_MM_ARRAYS] = merged                                    # (save_logo takes them out again)
+        keys.update(more)
     keys["logo_time_sec"] = time.time() - clock
     return keys, arrays
+
+
+LOO_MM_ARRAYS = "loo_mm/"            # where _loo_report leaves the arrays of <base>_loo_mm.npz among those of _loo.npz (--loo_moment_match)
+LOGO_MM_ARRAYS = "logo_mm/"          # ... and _logo_report those of <base>_logo_mm.npz among those of _logo.npz
+MM_MAX_RANGE = (1, 4096)             # --loo_moment_match_max
+MM_SHOWN = 8                         # targets still above the threshold the warning names
+_MM_FORM = ("observations", "not_attempted", "improved", "resolved", "iterations_max")
+LOO_MM_KEYS = (tuple("loo_mm_" + name for name in _MM_FORM) + ("elpd_loo_mm", "elpd_loo_mm_se", "p_loo_mm", "loo_mm_pareto_k_max",
+               "loo_mm_pareto_k_max_observation", "loo_mm_pareto_k_above_threshold", "loo_mm_full_pareto_k_max", "loo_mm_time_sec"))
+LOGO_MM_KEYS = (tuple("logo_mm_" + name for name in _MM_FORM) + ("elpd_logo_mm", "elpd_logo_mm_se", "p_logo_mm",
+                "logo_mm_pareto_k_max", "logo_mm_pareto_k_max_group", "logo_mm_pareto_k_above_threshold",
+                "logo_mm_full_pareto_k_max", "logo_mm_time_sec"))
+
+
+def loo_moment_match(flags):
+    """Whether --loo_moment_match is set."""
+    return bool(getattr(flags, "loo_moment_match", False))
+
+
+def check_loo_moment_match(flags):
+    """--loo_moment_match and --loo_moment_match_max against the job, before anything runs -- raises ValueError, naming the
+    flag, for the flag without --predictive_diagnostics, for neals_funnel (no observations) and for a cap outside
+    MM_MAX_RANGE."""
+    if not loo_moment_match(flags):
+        return
+    if not getattr(flags, "predictive_diagnostics", False):
+        raise ValueError("--loo_moment_match is read with --predictive_diagnostics only")
+    if flags.model == "neals_funnel":
+        raise ValueError("--loo_moment_match: neals_funnel has no observations, so there is no leave-one-out ratio to repair")
+    cap = getattr(flags, "loo_moment_match_max", 64)
+    if not (isinstance(cap, int) and MM_MAX_RANGE[0] <= cap <= MM_MAX_RANGE[1]):
+        raise ValueError("--loo_moment_match_max: %r is outside %d ... %d" % (cap, MM_MAX_RANGE[0], MM_MAX_RANGE[1]))
+
+
+def mm_select(pareto_k, threshold, cap):
+    """(chosen, not_attempted): the indices of the targets whose k-hat is above `threshold` -- those without a fitted tail
+    (+inf) included, NaN rows (empty groups) not -- the worst first (ties in ascending index), at most `cap` of them, and
+    how many above the threshold lie past the cap; pure numpy."""
+    k = np.asarray(pareto_k, np.float64).reshape(-1)
+    with np.errstate(invalid="ignore"):
+        above = np.flatnonzero((k > threshold) if np.isfinite(threshold) else np.isposinf(k))
+    ranked = above[np.argsort(-k[above], kind="stable")]
+    return ranked[:int(cap)], int(max(0, ranked.size - int(cap)))
+
+
+def mm_merge(columns, chosen, result):
+    """The per-target arrays of <base>_loo_mm.npz / _logo_mm.npz from the plain [T, 8] columns (host float64), the targets
+    handed to diagnostics.moment_match (`chosen`) and its MomentMatch over THEM: every figure is the plain one where the
+    target was not attempted, the matched `elpd_loo_i` replaces the plain one where a map was accepted; pure numpy."""
+    c = np.asarray(columns, np.float64).reshape(-1, 8)
+    T, chosen = c.shape[0], np.asarray(chosen, np.int64).reshape(-1)
+    D = int(result.scale.shape[1])
+    attempted = np.zeros(T, bool)
+    attempted[chosen] = True
+    full = lambda values, fill, dtype=np.float64: _scatter(np.full(T, fill, dtype), chosen, values)
+    wide = lambda values: _scatter(np.full((T, D), np.nan), chosen, values)
+    return OrderedDict([
+        ("attempted", attempted), ("elpd_loo_i", _scatter(c[:, 0].copy(), chosen, result.elpd)),
+        ("pareto_k", _scatter(c[:, 1].copy(), chosen, result.pareto_k)), ("pareto_k_full", full(result.pareto_k_full, np.nan)),
+        ("pareto_k_split", full(result.pareto_k_split, np.nan)), ("is_ess", full(result.is_ess, np.nan)),
+        ("iterations", full(result.iterations, 0, np.int64)), ("maps", _scatter(np.full(T, "", object), chosen, result.maps).astype(str)),
+        ("shift", wide(result.shift)), ("scale", wide(result.scale))])
+
+
+def _scatter(into, at, values):
+    if len(at):
+        into[at] = np.asarray(values)[:len(at)]
+    return into
+
+
+def mm_keys(prefix, columns, merged, not_attempted, threshold, names=None):
+    """The JSON keys of moment matching (all but the time) from the plain [T, 8] columns and mm_merge's arrays; pure numpy.
+    prefix "loo": LOO_MM_KEYS, the worst k-hat named by its observation's index; "logo": LOGO_MM_KEYS, by its group's name
+    (`names`), totals over the non-empty groups (diagnostics.logo_summary).  The totals go through loo_summary with the
+    merged elpd column in the plain one's place: nothing is restated."""
+    c = np.asarray(columns, np.float64).reshape(-1, 8).copy()
+    tried = merged["attempted"]
+    k_plain, k = c[:, 1].copy(), merged["pareto_k"]
+    c[:, 0], c[:, 1] = merged["elpd_loo_i"], k
+    grouped = prefix == "logo"
+    total = diagnostics.logo_summary(c).total if grouped else diagnostics.loo_summary(c[:, 0], c[:, 2], c[:, 3])
+    filled = ~np.all(np.isnan(c), axis=1)
+    k_max, at = _nan_max(np.where(filled, k, np.nan))
+    with np.errstate(invalid="ignore"):
+        above = (k > threshold) if np.isfinite(threshold) else (filled & ~np.isfinite(k))
+        improved = int(np.sum(tried & (k < k_plain)))
+        resolved = int(np.sum(tried & (k <= threshold)))
+    kf_max, _ = _nan_max(np.where(tried, merged["pareto_k_full"], np.nan))
+    e = "elpd_%s_mm" % prefix
+    named = ("%s_mm_pareto_k_max_group" % prefix, names[at] if at >= 0 else None) if grouped else \
+        ("%s_mm_pareto_k_max_observation" % prefix, at if at >= 0 else None)
+    return OrderedDict([
+        (prefix + "_mm_observations", int(tried.sum())), (prefix + "_mm_not_attempted", int(not_attempted)),
+        (prefix + "_mm_improved", improved), (prefix + "_mm_resolved", resolved),
+        (prefix + "_mm_iterations_max", int(merged["iterations"].max()) if tried.any() else 0),
+        (e, _finite_or_none(total.elpd_loo)), (e + "_se", _finite_or_none(total.elpd_loo_se)),
+        ("p_%s_mm" % prefix, _finite_or_none(total.p_loo)), (prefix + "_mm_pareto_k_max", _finite_or_none(k_max)), named,
+        (prefix + "_mm_pareto_k_above_threshold", int(np.sum(above))), (prefix + "_mm_full_pareto_k_max", _finite_or_none(kf_max))])
+
+
+def _mm_run(draws, mask, left_out, spec, flags, columns, loglik_fn, prefix, what, plain_total, names=None):
+    """--loo_moment_match over the targets of one report (observations: prefix "loo"; groups in their conditional form:
+    "logo") whose plain k-hat in `columns` [T, 8] is above the threshold, the worst --loo_moment_match_max first:
+    diagnostics.moment_match on the report's draws, with the centred log joint of an engine of the report's own set to CP
+    (the run's handles are untouched: _psens_report's way) and `loglik_fn(target, rows [1, n, D])` for the left-out term.
+    mask [R], left_out: the report's left-out draws (moment_match adds those whose log joint is not finite).
+    Prints the line that sets the matched total next to the plain one (`plain_total`), and one warning naming what is still above the
+    threshold.  Returns (keys, mm_merge's arrays)."""
+    import torch
+    clock = time.time()
+    dev, D = draws.device, int(draws.shape[2])
+    R = int(draws.shape[0]) * int(draws.shape[1])
+    x = draws.reshape(R, D)
+    threshold = diagnostics.pareto_k_threshold(R - int(left_out))
+    chosen, past = mm_select(columns[:, 1], threshold, getattr(flags, "loo_moment_match_max", 64))
+    eng = _engine.Engine(spec, dev)                                                  # the report's own handle: the run's stay as they are
+    eng.set_param(0, "CP")
+    result = diagnostics.moment_match(
+        x, mask, lambda rows: eng.logp_grad(rows, which=0)[0], lambda t, rows: loglik_fn(int(t), rows[None]), list(chosen),
+        columns[chosen, 1], columns[chosen, 0], threshold, batch=report_common.mm_batch_size(max(len(chosen), 1), R, D, LOO_CHUNK_BYTES))
+    del eng
+    merged = mm_merge(columns, chosen, result)
+    keys = mm_keys(prefix, columns, merged, past, threshold, names)
+    label = (lambda t: names[t]) if names is not None else str
+    plain_k, _ = _nan_max(columns[:, 1])
+    e = "elpd_%s_mm" % prefix
+    util.print_("    moment matching over {} {} ({} more above the threshold not attempted): k-hat fell for {}, at or below {} "
+                "for {}; {} {} +/- {} (plain {}), worst Pareto k-hat {} (plain {}); full-posterior k-hat up to {}".format(
+                    keys[prefix + "_mm_observations"], what, past, keys[prefix + "_mm_improved"], _fmt(_finite_or_none(threshold)),
+                    keys[prefix + "_mm_resolved"], e, _fmt(keys[e]), _fmt(keys[e + "_se"]), _fmt(plain_total), _fmt(keys[prefix + "_mm_pareto_k_max"]),
+                    _fmt(_finite_or_none(plain_k)), _fmt(keys[prefix + "_mm_full_pareto_k_max"])))
+    with np.errstate(invalid="ignore"):
+        k = merged["pareto_k"]
+        high = np.flatnonzero((k > threshold) if np.isfinite(threshold) else np.isposinf(k))
+    if high.size:
+        util.print_("    WARNING: after moment matching the Pareto k-hat is still above {} for {} of the {}: {}{} -- their "
+                    "estimates remain unreliable (which: <base>_{}_mm.npz)".format(
+                        _fmt(_finite_or_none(threshold)), high.size, what, ", ".join(label(t) for t in high[:MM_SHOWN]),
+                        ", ..." if high.size > MM_SHOWN else "", prefix))
+    keys[prefix + "_mm_time_sec"] = time.time() - clock
+    return keys, merged
+
+
+class _TableLoglik(object):
+    """loglik_fn of _mm_run over a DeviceTable: observation n (pointwise_loglik over [n, n + 1)) or, with `groups`, group g
+    in its conditional form (group_loglik over [g, g + 1) without a site table)."""
+
+    def __init__(self, table, groups=None):
+        self.table, self.groups = table, groups
+
+    def __call__(self, t, rows):
+        if self.groups is None:
+            return diagnostics.pointwise_loglik(rows, self.table, t, t + 1)[0][0]
+        return diagnostics.group_loglik(rows, self.table, self.groups, None, t, t + 1)[0][0]
 
 
 def _loo_report(kernel_results, trace, k, spec, flags, side=None):
@@ -955,6 +1119,9 @@ def _loo_report(kernel_results, trace, k, spec, flags, side=None):
     arrays of <base>_loopred.npz are left in `side` under LOO_PRED_ARRAYS.  The keys are null whenever the report is.
     --loo_groups=PART: PSIS leave-one-group-out on the same draws (_logo_report -> LOGO_KEYS; the arrays of <base>_logo.npz
     wait under LOGO_ARRAYS for save_loo); it runs behind everything above and touches none of it.
+    --loo_moment_match: moment matching for the observations (and, in _logo_report, the groups' conditional form) with a
+    k-hat above the threshold (_mm_run -> LOO_MM_KEYS, LOGO_MM_KEYS; the arrays of <base>_loo_mm.npz and _logo_mm.npz wait
+    under LOO_MM_ARRAYS and LOGO_MM_ARRAYS for save_loo); it runs last, adds keys and files, and changes none that exist.
     Returns (JSON keys, arrays of <base>_loo.npz or None)."""
     import torch
     pred = bool(getattr(flags, "loo_predictive", False))
@@ -1016,8 +1183,13 @@ def _loo_report(kernel_results, trace, k, spec, flags, side=None):
         keys.update(more)
         keys["loo_pred_time_sec"] = pred_time + (time.time() - pred_clock)
     if loo_groups_part(flags):
-        logo, arrays[LOGO_ARRAYS] = _logo_report(draws, table, spec, loo_groups_part(flags), R, left_out)    # (save_loo takes them out again)
+        logo, arrays[LOGO_ARRAYS] = _logo_report(draws, table, spec, loo_groups_part(flags), R, left_out, flags)    # (save_loo takes them out again)
         keys.update(logo)
+    if loo_moment_match(flags):
+        more, merged = _mm_run(draws, mask, left_out, spec, flags, c, _TableLoglik(table), "loo", "observation(s)", keys["elpd_loo"])
+        merged.update([("y", np.asarray(table.y_host, np.float32)), ("model", np.asarray(spec.name))])
+        arrays[LOO_MM_ARRAYS] = merged                                     # (save_loo takes them out again)
+        keys.update(more)
     keys["loo_time_sec"] = time.time() - clock
     return keys, arrays
 
@@ -1026,12 +1198,15 @@ def save_loo(file_path_base, arrays):
     """`<base>_loo.npz` (build-specific, --predictive_diagnostics): per observation `elpd_loo_i`, `pareto_k` (+inf where no
     tail was fitted), `lppd_i` and `p_waic_i` [N] float64; `y` [N], the observations themselves -- what
     diagnostics.loo_compare pairs two models by -- and `model`, the model's name.  With --loo_groups the arrays of
-    <base>_logo.npz wait among them under LOGO_ARRAYS and are written by save_logo: _loo.npz is the unflagged run's."""
+    <base>_logo.npz wait among them under LOGO_ARRAYS and are written by save_logo, with --loo_moment_match those of
+    <base>_loo_mm.npz under LOO_MM_ARRAYS (save_mm): _loo.npz is the unflagged run's."""
     arrays = OrderedDict(arrays)
-    grouped = arrays.pop(LOGO_ARRAYS, None)
+    grouped, matched = arrays.pop(LOGO_ARRAYS, None), arrays.pop(LOO_MM_ARRAYS, None)
     np.savez(file_path_base + "_loo.npz", **arrays)
     if grouped is not None:
         save_logo(file_path_base, grouped)
+    if matched is not None:
+        save_mm(file_path_base + "_loo_mm.npz", matched)
 
 
 def save_logo(file_path_base, arrays):
@@ -1040,7 +1215,20 @@ def save_logo(file_path_base, arrays):
     `elpd_logo_g`, `pareto_k`, `lppd_g`, `p_waic_g` [G] float64 of the MARGINAL form (NaN for an empty group, and
     throughout when the model has no marginal form) and the same four under `conditional_`; `y` [N] and `model` --
     what analyze --logo_compare pairs two models by."""
+    arrays = OrderedDict(arrays)
+    matched = arrays.pop(LOGO_MM_ARRAYS, None)
     np.savez(file_path_base + "_logo.npz", **arrays)
+    if matched is not None:
+        save_mm(file_path_base + "_logo_mm.npz", matched)
+
+
+def save_mm(path, arrays):
+    """`<base>_loo_mm.npz` and `<base>_logo_mm.npz` (build-specific, --loo_moment_match), per observation or group:
+    `attempted` bool; `elpd_loo_i`, `pareto_k` (the matched figures where a map was accepted, the plain ones otherwise);
+    `pareto_k_full`, `pareto_k_split`, `is_ess` (NaN where they do not exist); `iterations` and `maps` (the maps accepted,
+    "112": T1, T1, T2); `shift`, `scale` [., D]: U - m0 and S of the total map theta = (x - m0) S + U in the centred
+    coordinates, NaN where not attempted; `y`, `model`; for groups also `part`, `groups`, `group_of`."""
+    np.savez(path, **arrays)
 
 
 def save_loo_pred(file_path_base, arrays):
@@ -2324,6 +2512,7 @@ def main(argv=None, flags=FLAGS, out=None):
         raise NotImplementedError("--reparameterise_variational is not supported by this build (SURVEY.md section 2)")
     check_predictive(flags)
     check_loo_groups(flags)
+    check_loo_moment_match(flags)
     check_predictive_checks(flags)
     check_predictive_redraw(flags)
     check_predictive_groups(flags)

@@ -156,6 +156,16 @@ def logo_range_size(G, R, forms, workspace_bytes, budget=None):
     return per
 
 
+MM_MAX_BATCH = 4095                 # arp_weighted_moments takes 4096 rows of weights: a batch's and one for the unweighted moments
+
+
+def mm_batch_size(T, R, D, budget=None):
+    """Targets per call of moment matching: the mapped draws [targets, R, D] float32 of diagnostics.affine_rows within
+    `budget` bytes (LOO_CHUNK_BYTES); at least one, at most T and at most MM_MAX_BATCH."""
+    budget = LOO_CHUNK_BYTES if budget is None else int(budget)
+    return int(max(1, min(max(int(T), 1), MM_MAX_BATCH, budget // max(1, 4 * int(R) * int(D)))))
+
+
 def replicate_groups(draws, table, groups, y, group_of, seed, draw_offset=0, left_out=None, budget=None):
     """(counts [G, PPC_COUNTS] float64 numpy, mask [S C] on the device): the data replicated per draw of `draws` [S, C, D]
     and folded per group (diagnostics.group_predictive_check), in ascending ranges of groups whose [groups, S C, 8]

@@ -859,6 +859,49 @@ int arp_vi_fold(const float* z, const float* grad, const float* e, int64_t row_s
                 const float* scale, const float* e0, int64_t n_draws, int32_t D, double* elem, double* tot, void* workspace,
                 int64_t workspace_bytes, void* stream);
 
+/* Moment matching for importance sampling (csrc/mmatch.hip; needs no model handle; Paananen, Piironen, Buerkner, Vehtari
+ * 2021; loo::loo_moment_match): the two device pieces of diagnostics.moment_match besides the densities and
+ * arp_psis_weights.  Device pointers; asynchronous; everything is refused before any launch with 1 (arp_last_error).
+ *
+ * arp_weighted_moments: the first two weighted moments of every column of x for n_targets rows of log weights at once.
+ * x is [n_rows][D] float, rows row_stride floats apart, read in place (1 <= D <= 255; nothing is read past a row's D-th
+ * element); lw[b * lw_stride + r] (double) is the log weight of draw r for target b, as arp_psis_weights writes it: -inf
+ * leaves the draw out; centre is [D] float.  Per target b, with lw_max = max_r lw (NaN entries skipped),
+ * w_r = exp(lw_r - lw_max) and e = (double)x[r][d] - (double)centre[d]:
+ *   out[b][4 + 2 D] double = { lw_max, sum w, sum w^2, draws kept, then for d = 0 ... D - 1 the pair sum w e, sum w e^2 }
+ * The sums are about centre so that nothing cancels (arp_cjs_sums' shift); everything after the float32 load is float64.
+ * A draw with lw = -inf enters nothing, by select (its row of x may be non-finite), and neither does a kept draw whose w
+ * underflows to 0; a target without a kept draw gives lw_max = -inf, zeros and a count of 0; a NaN lw is kept, is counted
+ * and gives NaN in the sums of ITS target and nowhere else; lw_max and the count are exact.  A row of all-zero lw gives the
+ * unweighted sums.  The rows are walked in chunks of 256 and the chunks' partial sums added in ascending order by a
+ * second launch; every order of addition is a function of (n_rows, D) alone and there are no float atomics: two calls give
+ * bitwise equal output, and the row of target b depends neither on n_targets nor on where b stands among the targets.  A
+ * chunk of x is read once for (up to) 8 targets.  First-order bound, u = 2^-53, R' kept draws, for every output sum
+ * s = sum w t (t = 1, w, e, e^2), against the exact sum over the same weights w_r = exp(fl(lw_r - lw_max)):
+ *   |s_dev - s| <= (R' + 32) 2 u sum w |t|
+ * (R' roundings of the summation in any order, the roundings of e and of the products, one unit in the last place of exp;
+ * derivation: csrc/mmatch.hip).  The workspace (arp_weighted_moments_workspace_bytes: the chunks' partial sums,
+ * ceil(n_rows / 256) * n_targets * (2 + 2 D) * 8 bytes and the targets' heads; 0 for a shape that is refused) is the
+ * caller's, 256-byte aligned.  Refused: a NULL x, lw, centre or out, n_rows < 1 or >= 2^31, D < 1 or D > 255, n_targets < 1
+ * or > 4096, row_stride < D, lw_stride < n_rows, a workspace that is missing, too small or misaligned. */
+int64_t arp_weighted_moments_workspace_bytes(int64_t n_rows, int32_t D, int64_t n_targets);
+int arp_weighted_moments(const float* x, int64_t n_rows, int32_t D, int64_t row_stride, const double* lw, int64_t n_targets,
+                         int64_t lw_stride, const float* centre, double* out, void* workspace, int64_t workspace_bytes,
+                         void* stream);
+
+/* arp_affine_rows: one matrix of draws pushed through n_targets elementwise affine maps.  x as above; m, s, u are
+ * [n_targets][D] float, out is [n_targets][n_rows][D] float, contiguous.  For the rows the parity picks -- every row when
+ * parity < 0, the rows with (r & 1) == parity when parity is 0 or 1 --
+ *   out[b][r][d] = (x[r][d] - m[b][d]) * s[b][d] + u[b][d]
+ * in float32 with contraction off: three roundings, in that order.  Every other row is copied bit for bit (NaN payloads
+ * and the sign of zero included).  Non-finite values are results; nothing is clamped.  An element of x is loaded once for
+ * all targets; nothing is read past the D-th element of a row, so a view into a wider matrix is read in place.  No
+ * workspace, no atomics; two calls give bitwise equal output, and out[b] does not depend on n_targets.  Refused: a NULL
+ * pointer, n_rows < 1 or >= 2^31, D < 1 or D > 255, n_targets < 1 or > 4096, row_stride < D, parity > 1, out == x,
+ * more than 2^35 values written. */
+int arp_affine_rows(const float* x, int64_t n_rows, int32_t D, int64_t row_stride, const float* m, const float* s,
+                    const float* u, int64_t n_targets, int32_t parity, float* out, void* stream);
+
 /* Test hook: the step-size adaptation recurrence of the chain kernels on SCRIPTED log acceptance ratios
  * (tfp.mcmc.DualAveragingStepSizeAdaptation / SimpleStepSizeAdaptation as wired at inference.py:224-226, 288-306;
  * SURVEY.md 8c known answer (7)).  For each of `n` independent rows, applies the update after transitions
