@@ -2,12 +2,10 @@
 // joint log-likelihood of the group's observations at the recorded state (lc, the CONDITIONAL form) and, for Normal data,
 // the same with the group's own latent element integrated against its conditional prior (lm, the MARGINAL form) -- what
 // PSIS leave-one-group-out cross-validation is computed from (psis.hip reads either in the place of a pointwise
-// log-likelihood; Merkle, Furr, Rabe-Hesketh 2019 for why the marginal form is the one to trust).  A group is a list of
-// observation indices (diagnostics.group_selection), laid out as ppc_group.hip's: `order` holds the grouped observations
-// sorted by group, ascending within a group, group_start[g] ... group_start[g + 1] is group g's stretch of it.  slope[j]
-// runs parallel to order: the sum of the weights with which observation order[j] reads the group's element, elem[g] that
-// element's index in the state.  Model-independent; the table, the tile of draws, eta_n and s_n: obs_table.h; the site
-// chains: site_table.h.
+// log-likelihood; Merkle, Furr, Rabe-Hesketh 2019 for why the marginal form is the one to trust).  The groups, `order` /
+// `group_start`, their clamps, the walk and which wave owns which group: group_table.h.  slope[j] runs parallel to order:
+// the sum of the weights with which observation order[j] reads the group's element, elem[g] that element's index in the
+// state.  Model-independent; the table, the tile of draws, eta_n and s_n: obs_table.h; the site chains: site_table.h.
 //
 // Build-specific: the reference evaluates joint densities only.
 //
@@ -40,14 +38,10 @@
 // a residual, not a difference of large terms -- expanding about loc instead would subtract two squares of the size of
 // (loc / exp(sj))^2.  Everything behind the three sums is float64: tau = exp(-2 sj), m, P, q and the line above.
 //
-// Shape of the work: ppc_group.hip's.  A workgroup of four waves stages one tile of 64 draws in LDS, a draw per lane; the
-// observation is uniform per wave, so group_start, order, slope, elem, idx, w, y and the site rows are scalar loads (the
-// table pointers are separate __restrict__ arguments; the next entry of order is asked for before the current body).
-// Every wave owns WHOLE groups -- wave v of workgroup (tile, b) takes g0 + 4 b + v, then every (4 gridDim.y)-th -- and
-// carries the three sums in registers: no LDS fold, no workspace, no second launch, no float atomics.  A lane stores one
-// float per output and group, 256 adjacent bytes a wave.  The sums of a (group, draw) are one fixed chain of additions:
-// a row depends neither on [g0, g1), nor on the tiling, nor on how the draws are spread over calls.  Without lm (the
-// kernel's other instantiation) b, b z and b b are not computed and lc is bitwise the same.
+// Shape of the work: group_table.h's; slope, elem and the site rows are scalar loads like order (the table pointers are
+// separate __restrict__ arguments).  A wave carries the three sums in registers; a lane stores one float per output and
+// group, 256 adjacent bytes a wave.  A row depends neither on [g0, g1), nor on the tiling, nor on how the draws are spread
+// over calls.  Without lm (the kernel's other instantiation) b, b z and b b are not computed and lc is bitwise the same.
 //
 // Cost.  Per (n, r) loglik.hip's (one expf, or expf and log1pf) and, with lm, two products more; per (group, r) two site
 // chains, one exp, one log1p and one division in float64.  Against ppc_group.hip: no Philox, logf, sqrtf, cospif, erfcf,
@@ -74,13 +68,12 @@
 //    and PSIS reports the group as not finite.
 //  * An empty group writes lc = lm = 0, by select (the formula would give 0 - 0 only for a finite tau).
 //  * A draw that is left out writes 0 in both, by select (0 * inf is NaN).
-//  * order, group_start: clamped as ppc_group.hip clamps them; elem[g] is clamped into [0, D) before it addresses the
-//    tile or the site table.  A clamped entry gives a wrong number, never a read past the end.
-//  * A wave without a group still takes part in the staging and its barriers, and stores nothing; dead lanes of the last
-//    ragged tile compute on a zero row and store nothing.
+//  * Clamped order and group_start entries, a wave without a group: group_table.h.  elem[g] is clamped into [0, D)
+//    before it addresses the tile or the site table: a wrong number, never a read past the end.
+//  * Dead lanes of the last ragged tile compute on a zero row and store nothing.
 //  * Bernoulli data has no closed form: lm with kind ARP_OBS_BERNOULLI is refused on the host, not approximated.
 #include "arp_device.h"
-#include "obs_table.h"
+#include "group_table.h"
 #include "site_table.h"
 
 #pragma clang fp contract(off)
@@ -114,13 +107,13 @@ __global__ __launch_bounds__(kObsThreads) void logo_kernel(
   const float* row = tile + lane * (D | 1);
   const long long hop = (long long)gridDim.y * kObsWaves;
   for (long long grp = g0 + (long long)blockIdx.y * kObsWaves + wave; grp < g1; grp += hop) {
-    const int jb = min(max(group_start[grp], 0), n_grouped);
-    const int je = min(max(group_start[grp + 1], jb), n_grouped);
+    const int jb = group_begin(group_start, grp, n_grouped);
+    const int je = group_end(group_start, grp, jb, n_grouped);
     double s_ll = 0.0, s_bz = 0.0, s_bb = 0.0;
-    int next = jb < je ? order[jb] : 0;
+    int next = first_member(order, jb, je);
     for (int j = jb; j < je; ++j) {
-      const long long n = min(max(next, 0), n_obs - 1);
-      if (j + 1 < je) next = order[j + 1];
+      const long long n = member_obs(next, n_obs);
+      next = next_member(order, j, je, next);
       const float eta = obs_eta(row, idx, w, n, T, D);
       const float yn = y[n];
       float v;
@@ -180,22 +173,16 @@ extern "C" int arp_group_loglik(const float* x, int64_t n_samples, int64_t n_cha
                     "required with lm");
     return 1;
   }
-  if (n_obs < 1 || n_obs >= (1ll << 31)) { set_error(who + ": 1 <= n_obs < 2^31 is required"); return 1; }
+  if (!group_call_ok(name, n_obs, n_grouped, order, n_groups, g0, g1)) return 1;
   if (!table_call_ok(name, n_samples, n_chains, D, row_stride, kind, T, 0, n_obs)) return 1;
   if (lm && kind != 0) {
     set_error(who + ": lm is for kind ARP_OBS_NORMAL only (the Bernoulli marginal has no closed form)");
     return 1;
   }
-  if (n_grouped < 0 || n_grouped >= (1ll << 31)) { set_error(who + ": 0 <= n_grouped < 2^31 is required"); return 1; }
-  if (n_grouped > 0 && !order) { set_error(who + ": order is required (n_grouped > 0)"); return 1; }
-  if (n_groups < 1 || n_groups >= (1ll << 31)) { set_error(who + ": 1 <= n_groups < 2^31 is required"); return 1; }
-  if (g0 < 0 || g1 <= g0 || g1 > n_groups) { set_error(who + ": 0 <= g0 < g1 <= n_groups is required"); return 1; }
   const long long R = n_samples * n_chains;
   if (out_stride < R) { set_error(who + ": out_stride >= n_samples * n_chains is required"); return 1; }
   const long long ntiles = (R + kObsDraws - 1) / kObsDraws;
-  // enough workgroups to fill the device at few tiles; never more waves than groups (ppc_group.hip's rule)
-  long long shares = std::max<long long>(1, (kObsTargetWorkgroups + ntiles - 1) / ntiles);
-  shares = std::min<long long>(std::min<long long>(shares, (g1 - g0 + kObsWaves - 1) / kObsWaves), 65535);
+  const long long shares = shares_of(ntiles, g1 - g0);
   hipStream_t st = (hipStream_t)stream;
   ARP_HIP_OK(hipMemsetAsync(n_masked, 0, sizeof(int64_t), st));
   auto kernel = lm ? logo_kernel<true> : logo_kernel<false>;

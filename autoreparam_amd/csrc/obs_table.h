@@ -129,13 +129,19 @@ __device__ __forceinline__ PredTerms bernoulli_terms(float eta, float y) {
 }
 
 // ---- host ----
+// The one launch rule, gridDim.y of `ntiles` tiles over `units` (observations, or groups of them: group_table.h): enough
+// workgroups to fill the device at few tiles; never more waves than units
+inline long long shares_of(long long ntiles, long long units) {
+  const long long shares = std::max<long long>(1, (kObsTargetWorkgroups + ntiles - 1) / ntiles);
+  return std::min<long long>(std::min<long long>(shares, (units + kObsWaves - 1) / kObsWaves), 65535);
+}
+
 // how the observations [n0, n1) are shared among blockIdx.y, and the tiles of R draws
 struct Split { long long ntiles, groups, per_group; };
 inline Split split_of(long long nobs, long long R) {
   Split s;
   s.ntiles = (R + kObsDraws - 1) / kObsDraws;
-  long long groups = std::max<long long>(1, (kObsTargetWorkgroups + s.ntiles - 1) / s.ntiles);
-  groups = std::min<long long>(std::min<long long>(groups, (nobs + kObsWaves - 1) / kObsWaves), 65535);
+  const long long groups = shares_of(s.ntiles, nobs);
   s.per_group = (nobs + groups - 1) / groups;
   s.groups = (nobs + s.per_group - 1) / s.per_group;
   return s;

@@ -1,32 +1,23 @@
 // Grouped predictive check (include/autoreparam.h: arp_group_predictive_check): the replicated observations of
 // arp_predictive_check, folded per GROUP of observations and draw into the eight per-draw test statistics -- which county
-// does the model fail to produce?  A group is a list of observation indices (diagnostics.group_selection: the
-// observations that read one element of a latent part), so its members need not be contiguous in the table: `order`
-// holds the grouped observations sorted by group, ascending observation index within a group, and group_start[g] ...
-// group_start[g + 1] is group g's stretch of it.  Model-independent; the table, the tile of draws, eta_n and s_n:
-// obs_table.h; the per-(n, r) body: ppc_terms.h, which ppc.hip calls too, so y_rep of (n, r) is bit for bit
-// arp_predictive_check's under the same seed and draw offset.
+// does the model fail to produce?  The groups, `order` / `group_start`, their clamps, the walk and which wave owns which
+// group: group_table.h.  Model-independent; the table, the tile of draws, eta_n and s_n: obs_table.h; the per-(n, r) body:
+// ppc_terms.h, which ppc.hip calls too, so y_rep of (n, r) is bit for bit arp_predictive_check's under the same seed and
+// draw offset.
 //
 // Build-specific: the reference has no predictive checks.
 //
 // Random numbers.  ppc.hip's: one philox4x32_10(counter (n, lo32 g, hi32 g, 0), key (lo32 seed, hi32 seed)) per (n, r),
 // g = draw_offset + r, n the observation's index in the WHOLE table (what order[j] holds), never its place in the group.
 //
-// Shape of the work: obs_table.h's.  A workgroup of four waves stages one tile of 64 draws in LDS, one draw per lane; the
-// observation is uniform per wave, so group_start, order, idx, w and y are scalar loads (the next entry of order is
-// asked for before the current observation's body, which hides the first of the two dependent scalar loads).  Every
-// wave owns WHOLE groups -- wave v of workgroup (tile, b) takes the groups g0 + 4 b + v, then every (4 gridDim.y)-th -- and
-// carries a group's eight statistics in one set of registers over its observations in order's sequence: sums in float64,
-// min and max in float32, as ppc_kernel's.  Hence no LDS fold, no barrier behind the tile's, no workspace and no second
-// launch; a lane stores its row of eight doubles (64 adjacent bytes, the wave 4 096) once per group.  No float atomics:
-// the sums of a group are one fixed chain of additions, whatever the tiling, the group range [g0, g1) of the call and
-// the way groups are shared among waves and workgroups -- two calls, a call over a sub-range of the groups and two calls
-// over halves of the draws give bitwise equal rows.
+// Shape of the work: group_table.h's.  A wave carries its group's eight statistics in one set of registers: sums in
+// float64, min and max in float32, as ppc_kernel's; a lane stores its row of eight doubles (64 adjacent bytes, the wave
+// 4 096) once per group.  Two calls, a call over a sub-range of the groups and two calls over halves of the draws give
+// bitwise equal rows.
 //
 // Cost.  Per (n, r) ppc.hip's (Philox, logf, sqrtf, cospif, two expf and erfcf, or expf, log1pf and a division) without
 // its per-observation butterfly; the staging of the tile is paid once per workgroup, so a call with few, small groups (8
-// schools: eight groups of one) is all staging.  The longest group bounds a wave's time: groups are dealt out round
-// robin, not by size.  Measured next to arp_predictive_check: DESIGN.md section 6.
+// schools: eight groups of one) is all staging.  Measured next to arp_predictive_check: DESIGN.md section 6.
 //
 // Arithmetic.  ppc.hip's per-(n, r) values and bounds; columns 0 - 3 and 7 are exact functions of the float32 y_rep
 // (float64 sums of at most 2^31 float32 values and of their exact float64 squares, in ascending n).
@@ -34,15 +25,10 @@
 // Things that go wrong quietly here:
 //  * An empty group writes (0, 0, +inf, -inf, 0, 0, 0, 0): the fold's start values, not zeros -- min and max of nothing.
 //  * A draw that is left out writes a zero row in every group, by select (ppc.hip: 0 * inf is NaN).
-//  * order and group_start come from the caller: an order entry is clamped into [0, n_obs) and a group_start entry into
-//    [0, n_grouped], the end of a group not before its start, before they address anything; the uploader
-//    (diagnostics.upload_groups) keeps them there in the first place.  A clamped entry gives a wrong number, never a
-//    read past the end.
-//  * A wave without a group (more waves than groups in the call) still takes part in the staging and its barriers, and
-//    stores nothing.
-//  * Dead lanes of the last ragged tile compute on a zero row and store nothing.
+//  * Clamped order and group_start entries, a wave without a group: group_table.h.  Dead lanes of the last ragged tile
+//    compute on a zero row and store nothing.
 #include "arp_device.h"
-#include "obs_table.h"
+#include "group_table.h"
 #include "ppc_terms.h"
 
 #pragma clang fp contract(off)
@@ -73,14 +59,14 @@ __global__ __launch_bounds__(kObsThreads) void ppc_group_kernel(
   const float* row = tile + lane * (D | 1);
   const long long hop = (long long)gridDim.y * kObsWaves;
   for (long long grp = g0 + (long long)blockIdx.y * kObsWaves + wave; grp < g1; grp += hop) {
-    const int jb = min(max(group_start[grp], 0), n_grouped);
-    const int je = min(max(group_start[grp + 1], jb), n_grouped);
+    const int jb = group_begin(group_start, grp, n_grouped);
+    const int je = group_end(group_start, grp, jb, n_grouped);
     double a_y = 0.0, a_yy = 0.0, a_dr = 0.0, a_do = 0.0, a_mu = 0.0, a_n = 0.0;
     float a_min = __builtin_inff(), a_max = -__builtin_inff();
-    int next = jb < je ? order[jb] : 0;
+    int next = first_member(order, jb, je);
     for (int j = jb; j < je; ++j) {
-      const long long n = min(max(next, 0), n_obs - 1);
-      if (j + 1 < je) next = order[j + 1];
+      const long long n = member_obs(next, n_obs);
+      next = next_member(order, j, je, next);
       const PpcTerms pc = ppc_terms(row, kind, T, D, idx, w, y, scale_idx, log_scale, n, g_lo, g_hi, key0, key1);
       a_y += (double)pc.yr;
       a_yy += (double)pc.yr * (double)pc.yr;
@@ -115,18 +101,12 @@ extern "C" int arp_group_predictive_check(const float* x, int64_t n_samples, int
     set_error(who + ": x, the table (idx, w, y, scale_idx, log_scale), group_start, group_stats, mask and n_masked are required");
     return 1;
   }
-  if (n_obs < 1 || n_obs >= (1ll << 31)) { set_error(who + ": 1 <= n_obs < 2^31 is required"); return 1; }
+  if (!group_call_ok(name, n_obs, n_grouped, order, n_groups, g0, g1)) return 1;
   if (!table_call_ok(name, n_samples, n_chains, D, row_stride, kind, T, 0, n_obs)) return 1;
-  if (n_grouped < 0 || n_grouped >= (1ll << 31)) { set_error(who + ": 0 <= n_grouped < 2^31 is required"); return 1; }
-  if (n_grouped > 0 && !order) { set_error(who + ": order is required (n_grouped > 0)"); return 1; }
-  if (n_groups < 1 || n_groups >= (1ll << 31)) { set_error(who + ": 1 <= n_groups < 2^31 is required"); return 1; }
-  if (g0 < 0 || g1 <= g0 || g1 > n_groups) { set_error(who + ": 0 <= g0 < g1 <= n_groups is required"); return 1; }
   if (draw_offset < 0) { set_error(who + ": draw_offset >= 0 is required"); return 1; }
   const long long R = n_samples * n_chains;
   const long long ntiles = (R + kObsDraws - 1) / kObsDraws;
-  // enough workgroups to fill the device at few tiles; never more waves than groups
-  long long shares = std::max<long long>(1, (kObsTargetWorkgroups + ntiles - 1) / ntiles);
-  shares = std::min<long long>(std::min<long long>(shares, (g1 - g0 + kObsWaves - 1) / kObsWaves), 65535);
+  const long long shares = shares_of(ntiles, g1 - g0);
   hipStream_t st = (hipStream_t)stream;
   ARP_HIP_OK(hipMemsetAsync(n_masked, 0, sizeof(int64_t), st));
   hipLaunchKernelGGL(ppc_group_kernel, dim3((unsigned)ntiles, (unsigned)shares), dim3(kObsThreads), tile_lds_bytes(D), st, x, R,

@@ -577,6 +577,11 @@ def _table_call(trace, table, n0, n1, who):
     return view, n0, n1, R
 
 
+def _mask_pair(R, dev):
+    """(mask [R] uint8, n_masked: an int64 scalar at 0) on `dev`: what every kernel that leaves draws out writes."""
+    return torch.empty(R, dtype=torch.uint8, device=dev), torch.zeros((), dtype=torch.int64, device=dev)
+
+
 def _table_args(view, table, n0, n1):
     """The leading C arguments of those entry points: the trace, the table, the range."""
     x, S, Cn, D, row_stride = view
@@ -613,8 +618,7 @@ def pointwise_loglik(trace, table, n0=0, n1=None, out=None):
     if out is None:
         out = torch.empty(n1 - n0, R, dtype=torch.float32, device=dev)
     out, ll_stride = _draw_matrix(out, torch.float32, n1 - n0, R, "pointwise_loglik", "out")
-    mask = torch.empty(R, dtype=torch.uint8, device=dev)
-    n_masked = torch.zeros((), dtype=torch.int64, device=dev)
+    mask, n_masked = _mask_pair(R, dev)
     _lib.call(dev, _lib.lib().arp_pointwise_loglik, *_table_args(view, table, n0, n1), _lib.ptr(out), ll_stride, _lib.ptr(mask),
               _lib.ptr(n_masked))
     return out[:n1 - n0, :R], mask, n_masked
@@ -731,8 +735,7 @@ def predictive_check(trace, table, n0=0, n1=None, seed=0, draw_offset=0, want_y_
     draw_stats = torch.empty(R, len(PPC_DRAW_COLUMNS), dtype=torch.float64, device=dev)
     obs_sums = torch.empty(n1 - n0, len(PPC_OBS_COLUMNS), dtype=torch.float64, device=dev)
     y_rep = torch.empty(n1 - n0, R, dtype=torch.float32, device=dev) if want_y_rep else None
-    mask = torch.empty(R, dtype=torch.uint8, device=dev)
-    n_masked = torch.zeros((), dtype=torch.int64, device=dev)
+    mask, n_masked = _mask_pair(R, dev)
     _lib.call(dev, _lib.lib().arp_predictive_check, *_table_args(view, table, n0, n1), int(seed) & 0xFFFFFFFFFFFFFFFF,
               int(draw_offset), _lib.ptr(draw_stats), _lib.ptr(obs_sums), _lib.ptr(y_rep), R, _lib.ptr(mask), _lib.ptr(n_masked),
               workspace=predictive_workspace_bytes(n1 - n0, R))
@@ -930,6 +933,19 @@ def upload_groups(order, group_start, n_obs, device):
                         dev(start), np.diff(start.astype(np.int64)))
 
 
+def _group_call(trace, table, groups, g0, g1, who):
+    """How the wrappers over the groups of a whole observation table open -> (view, g0, g1, R): _table_call over the whole
+    table, the resolved group range; groups of another table or an empty range are refused."""
+    view, _, _, R = _table_call(trace, table, 0, None, who)
+    g1 = groups.G if g1 is None else int(g1)
+    g0 = int(g0)
+    if groups.n_obs != table.N:
+        raise ValueError("%s: the groups were uploaded for a table of %d observations, not %d" % (who, groups.n_obs, table.N))
+    if not 0 <= g0 < g1 <= groups.G:
+        raise ValueError("%s: 0 <= g0 < g1 <= %d groups is required" % (who, groups.G))
+    return view, g0, g1, R
+
+
 def group_predictive_check(trace, table, groups, g0=0, g1=None, seed=0, draw_offset=0):
     """(group_stats, mask, n_masked) of `arp_group_predictive_check` for a recorded CENTRED [S, C, D] float32 trace on the
     GPU, a DeviceTable (whole) and the groups [g0, g1) of a DeviceGroups over it, all device tensors: group_stats
@@ -938,19 +954,12 @@ def group_predictive_check(trace, table, groups, g0=0, g1=None, seed=0, draw_off
     draw r) is predictive_check's under the same seed and draw_offset, bit for bit, and a group's row depends neither on
     [g0, g1) nor on how the draws are spread over calls.  A block of chains of a wider trace is read in place."""
     who = "group_predictive_check"
-    view, _, _, R = _table_call(trace, table, 0, None, who)
+    view, g0, g1, R = _group_call(trace, table, groups, g0, g1, who)
     dev = view[0].device
-    g1 = groups.G if g1 is None else int(g1)
-    g0 = int(g0)
-    if groups.n_obs != table.N:
-        raise ValueError("%s: the groups were uploaded for a table of %d observations, not %d" % (who, groups.n_obs, table.N))
-    if not 0 <= g0 < g1 <= groups.G:
-        raise ValueError("%s: 0 <= g0 < g1 <= %d groups is required" % (who, groups.G))
     if int(draw_offset) < 0:
         raise ValueError("%s: draw_offset >= 0 is required" % who)
     stats = torch.empty(g1 - g0, R, len(PPC_DRAW_COLUMNS), dtype=torch.float64, device=dev)
-    mask = torch.empty(R, dtype=torch.uint8, device=dev)
-    n_masked = torch.zeros((), dtype=torch.int64, device=dev)
+    mask, n_masked = _mask_pair(R, dev)
     _lib.call(dev, _lib.lib().arp_group_predictive_check, *_table_args(view, table, 0, table.N)[:-2], table.N,
               _lib.ptr(groups.order), groups.n_grouped, _lib.ptr(groups.group_start), groups.G, g0, g1,
               int(seed) & 0xFFFFFFFFFFFFFFFF, int(draw_offset), _lib.ptr(stats), _lib.ptr(mask), _lib.ptr(n_masked))
@@ -1075,16 +1084,10 @@ def group_loglik(trace, table, groups, site=None, g0=0, g1=None, out=None):
     read in place.  out: an optional float32 device matrix with unit column stride whose rows are at least S C apart, of
     at least g1 - g0 rows (2 (g1 - g0) with `site`: lc is a view of the first g1 - g0, lm of the next)."""
     who = "group_loglik"
-    view, _, _, R = _table_call(trace, table, 0, None, who)
-    dev = view[0].device
-    g1 = groups.G if g1 is None else int(g1)
-    g0 = int(g0)
     if not isinstance(groups, DeviceLogoGroups):
         raise ValueError("%s: a DeviceLogoGroups is required (upload_logo_groups)" % who)
-    if groups.n_obs != table.N:
-        raise ValueError("%s: the groups were uploaded for a table of %d observations, not %d" % (who, groups.n_obs, table.N))
-    if not 0 <= g0 < g1 <= groups.G:
-        raise ValueError("%s: 0 <= g0 < g1 <= %d groups is required" % (who, groups.G))
+    view, g0, g1, R = _group_call(trace, table, groups, g0, g1, who)
+    dev = view[0].device
     if site is not None and not isinstance(site, DeviceSiteTable):
         raise ValueError("%s: site must be a DeviceSiteTable (upload_site_table)" % who)
     if site is not None and site.D != view[3]:
@@ -1094,8 +1097,7 @@ def group_loglik(trace, table, groups, site=None, g0=0, g1=None, out=None):
         out = torch.empty(rows, R, dtype=torch.float32, device=dev)
     out, stride = _draw_matrix(out, torch.float32, rows, R, who, "out")
     lc, lm = out[:n], (out[n:2 * n] if site is not None else None)
-    mask = torch.empty(R, dtype=torch.uint8, device=dev)
-    n_masked = torch.zeros((), dtype=torch.int64, device=dev)
+    mask, n_masked = _mask_pair(R, dev)
     columns = [getattr(site, name, None) for name in ("loc_idx", "loc_w", "loc0", "scale_idx", "scale_w", "log_scale0")]
     _lib.call(dev, _lib.lib().arp_group_loglik, *_table_args(view, table, 0, table.N)[:-2], table.N, _lib.ptr(groups.order),
               _lib.ptr(groups.slope), groups.n_grouped, _lib.ptr(groups.group_start), _lib.ptr(groups.elem), groups.G, g0, g1,
@@ -1753,8 +1755,7 @@ def site_logprior(trace, table, group_of=None, want_elements=False):
         groups, G = torch.as_tensor(np.ascontiguousarray(g, np.int32), device=dev), int(g.max()) + 1
     group_lp = torch.empty(R, G, dtype=torch.float64, device=dev)
     elem_lp = torch.empty(R, D, dtype=torch.float32, device=dev) if want_elements else None
-    mask = torch.empty(R, dtype=torch.uint8, device=dev)
-    n_masked = torch.zeros((), dtype=torch.int64, device=dev)
+    mask, n_masked = _mask_pair(R, dev)
     _lib.call(dev, _lib.lib().arp_site_logprior, _lib.ptr(x), S, Cn, D, row_stride, _lib.ptr(table.form), _lib.ptr(table.loc_idx),
               _lib.ptr(table.loc_w), _lib.ptr(table.loc0), _lib.ptr(table.scale_idx), _lib.ptr(table.scale_w),
               _lib.ptr(table.log_scale0), _lib.ptr(table.norm), _lib.ptr(groups), G, _lib.ptr(group_lp), _lib.ptr(elem_lp),

@@ -23,9 +23,9 @@ from . import _lib, diagnostics, graphs, inference, models, parallel, report_com
 from . import engine as _engine
 from . import sbc as _sbc
 from .flags import FLAGS, check_vi_check_draws
-from .report_common import (LOO_CHUNK_BYTES, _finite_or_none, _fmt, _nan_max, _null_keys, _write_json_atomic, derived_seed,
-                            element_names, joint_loglik, loo_steps, next_seed, ppc_tile_rows, probe_steps, replicate_groups,
-                            replicate_tiles, select_draws)
+from .report_common import (LOO_CHUNK_BYTES, _above, _finite_or_none, _fmt, _nan_max, _null_keys, _shown, _write_json_atomic,
+                            data_tail, derived_seed, element_names, grouped_head, joint_loglik, loo_steps, next_seed,
+                            ppc_tile_rows, probe_steps, replicate_groups, replicate_tiles, select_draws)
 
 
 def _vip_suffix(flags):
@@ -750,17 +750,23 @@ def loo_groups_part(flags):
     return getattr(flags, "loo_groups", "") or ""
 
 
+def _check_extends(flags, name, parent, nothing):
+    """The two refusals every flag that extends a report over the data opens with: --`name` without --`parent`, and
+    neals_funnel, which has no observations and hence no `nothing`."""
+    if not getattr(flags, parent, False):
+        raise ValueError("--%s is read with --%s only" % (name, parent))
+    if flags.model == "neals_funnel":
+        raise ValueError("--%s: neals_funnel has no observations, so there is no %s" % (name, nothing))
+
+
 def check_loo_groups(flags):
-    """--loo_groups against the job, before anything runs -- raises ValueError, naming the flag, for the flag without
-    --predictive_diagnostics, for neals_funnel (no observations) and for whatever diagnostics.group_selection refuses: a
-    name that is no part, a part of one element, a part no observation reads, a part whose elements do not group the data."""
+    """--loo_groups against the job, before anything runs -- raises ValueError, naming the flag: _check_extends' two
+    refusals (--predictive_diagnostics), and whatever diagnostics.group_selection refuses: a name that is no part, a part of
+    one element, a part no observation reads, a part whose elements do not group the data."""
     part = loo_groups_part(flags)
     if not part:
         return
-    if not getattr(flags, "predictive_diagnostics", False):
-        raise ValueError("--loo_groups is read with --predictive_diagnostics only")
-    if flags.model == "neals_funnel":
-        raise ValueError("--loo_groups: neals_funnel has no observations, so there is no group to leave out")
+    _check_extends(flags, "loo_groups", "predictive_diagnostics", "group to leave out")
     spec = models.spec_by_name(flags.model, dataset=getattr(flags, "dataset", None))
     diagnostics.group_selection(spec.observation_table(), spec, part, flag=diagnostics.LOGO_FLAG)
 
@@ -775,6 +781,13 @@ def check_predictive(flags):
     if getattr(flags, "predictive_diagnostics", False) and flags.model == "neals_funnel":
         raise ValueError("--predictive_diagnostics: neals_funnel has no observations, so there is no pointwise "
                          "log-likelihood to cross-validate")
+
+
+def _centred_engine(spec, dev):
+    """An engine of a report's own, set to CP: the centred log joint at recorded draws; the run's handles stay as they are."""
+    eng = _engine.Engine(spec, dev)
+    eng.set_param(0, "CP")
+    return eng
 
 
 def loo_tile_rows(N, R, budget=None):
@@ -812,8 +825,7 @@ def loo_keys(columns, R, left_out, n_chains, n_steps):
     total = diagnostics.loo_summary(c[:, 0], c[:, 2], c[:, 3])
     threshold = diagnostics.pareto_k_threshold(used)
     k_max, at = _nan_max(c[:, 1])
-    with np.errstate(invalid="ignore"):
-        above = int(np.sum(c[:, 1] > threshold)) if np.isfinite(threshold) else int(np.sum(~np.isfinite(c[:, 1])))
+    above = int(np.sum(_above(c[:, 1], threshold)))
     return OrderedDict([
         ("loo_draws", used), ("loo_draws_left_out", int(left_out)), ("loo_chains", int(n_chains)), ("loo_steps", int(n_steps)),
         ("loo_observations", int(c.shape[0])),
@@ -835,8 +847,7 @@ def _logo_form_keys(columns, names, threshold, prefix):
     filled = ~np.all(np.isnan(columns), axis=1)
     k = np.where(filled, columns[:, 1], np.nan)
     k_max, at = _nan_max(k)
-    with np.errstate(invalid="ignore"):
-        above = int(np.sum(k > threshold)) if np.isfinite(threshold) else int(np.sum(filled & ~np.isfinite(k)))
+    above = int(np.sum(_above(k, threshold, filled)))
     return OrderedDict(zip(keys, (_finite_or_none(total.elpd_loo), _finite_or_none(total.elpd_loo_se), _finite_or_none(total.p_loo),
                                   _finite_or_none(k_max), names[at] if at >= 0 else None, above)))
 
@@ -923,20 +934,16 @@ def _logo_report(draws, table, spec, part, R, left_out, flags=None):
                                              form("logo_conditional_", "logo_conditional_elpd")))
     if ok and keys["logo_pareto_k_above_threshold"]:
         threshold = keys["logo_pareto_k_threshold"]
-        with np.errstate(invalid="ignore"):
-            k = marg[:, 1]
-            high = [names[g] for g in np.flatnonzero((k > threshold) if threshold is not None else (groups.sizes > 0) & ~np.isfinite(k))]
-        util.print_("    WARNING: marginal Pareto k-hat above {} for {} group(s) of {}: {}{} -- their leave-group-out estimates "
-                    "are unreliable (which: <base>_logo.npz)".format(_fmt(threshold), len(high), part, ", ".join(high[:LOGO_SHOWN]),
-                                                                     ", ..." if len(high) > LOGO_SHOWN else ""))
+        high = [names[g] for g in np.flatnonzero(_above(marg[:, 1], threshold, groups.sizes > 0))]
+        util.print_("    WARNING: marginal Pareto k-hat above {} for {} group(s) of {}: {} -- their leave-group-out estimates "
+                    "are unreliable (which: <base>_logo.npz)".format(_fmt(threshold), len(high), part, _shown(high, LOGO_SHOWN)))
     nan = np.full(G, np.nan)
     column = lambda c, j: nan.copy() if c is None else c[:, j]
     arrays = OrderedDict(
-        [("part", np.asarray(part)), ("groups", np.asarray(names)), ("group_of", np.asarray(group_of, np.int32)),
-         ("n_obs", np.asarray(groups.sizes, np.int64))]
+        grouped_head(part, names, group_of, groups.sizes)
         + [(pre + name, column(c, j)) for pre, c in (("", marg), ("conditional_", cond))
            for name, j in (("elpd_logo_g", 0), ("pareto_k", 1), ("lppd_g", 2), ("p_waic_g", 3))]
-        + [("y", np.asarray(table.y_host, np.float32)), ("model", np.asarray(spec.name))])
+        + data_tail(table.y_host, spec))
     if loo_moment_match(flags):
         more, merged = _mm_run(draws, mask, left_out, spec, flags, cond, _TableLoglik(table, groups), "logo",
                                "group(s) of {}, conditional form".format(part), keys["logo_conditional_elpd"], names)
@@ -966,14 +973,10 @@ def loo_moment_match(flags):
 
 def check_loo_moment_match(flags):
     """--loo_moment_match and --loo_moment_match_max against the job, before anything runs -- raises ValueError, naming the
-    flag, for the flag without --predictive_diagnostics, for neals_funnel (no observations) and for a cap outside
-    MM_MAX_RANGE."""
+    flag: _check_extends' two refusals (--predictive_diagnostics), and a cap outside MM_MAX_RANGE."""
     if not loo_moment_match(flags):
         return
-    if not getattr(flags, "predictive_diagnostics", False):
-        raise ValueError("--loo_moment_match is read with --predictive_diagnostics only")
-    if flags.model == "neals_funnel":
-        raise ValueError("--loo_moment_match: neals_funnel has no observations, so there is no leave-one-out ratio to repair")
+    _check_extends(flags, "loo_moment_match", "predictive_diagnostics", "leave-one-out ratio to repair")
     cap = getattr(flags, "loo_moment_match_max", 64)
     if not (isinstance(cap, int) and MM_MAX_RANGE[0] <= cap <= MM_MAX_RANGE[1]):
         raise ValueError("--loo_moment_match_max: %r is outside %d ... %d" % (cap, MM_MAX_RANGE[0], MM_MAX_RANGE[1]))
@@ -984,8 +987,7 @@ def mm_select(pareto_k, threshold, cap):
     (+inf) included, NaN rows (empty groups) not -- the worst first (ties in ascending index), at most `cap` of them, and
     how many above the threshold lie past the cap; pure numpy."""
     k = np.asarray(pareto_k, np.float64).reshape(-1)
-    with np.errstate(invalid="ignore"):
-        above = np.flatnonzero((k > threshold) if np.isfinite(threshold) else np.isposinf(k))
+    above = np.flatnonzero(_above(k, threshold, ~np.isnan(k)))          # (a k-hat is finite or +inf, psis.hip; NaN: an empty group)
     ranked = above[np.argsort(-k[above], kind="stable")]
     return ranked[:int(cap)], int(max(0, ranked.size - int(cap)))
 
@@ -1028,8 +1030,8 @@ def mm_keys(prefix, columns, merged, not_attempted, threshold, names=None):
     total = diagnostics.logo_summary(c).total if grouped else diagnostics.loo_summary(c[:, 0], c[:, 2], c[:, 3])
     filled = ~np.all(np.isnan(c), axis=1)
     k_max, at = _nan_max(np.where(filled, k, np.nan))
+    above = _above(k, threshold, filled)
     with np.errstate(invalid="ignore"):
-        above = (k > threshold) if np.isfinite(threshold) else (filled & ~np.isfinite(k))
         improved = int(np.sum(tried & (k < k_plain)))
         resolved = int(np.sum(tried & (k <= threshold)))
     kf_max, _ = _nan_max(np.where(tried, merged["pareto_k_full"], np.nan))
@@ -1048,8 +1050,8 @@ def mm_keys(prefix, columns, merged, not_attempted, threshold, names=None):
 def _mm_run(draws, mask, left_out, spec, flags, columns, loglik_fn, prefix, what, plain_total, names=None):
     """--loo_moment_match over the targets of one report (observations: prefix "loo"; groups in their conditional form:
     "logo") whose plain k-hat in `columns` [T, 8] is above the threshold, the worst --loo_moment_match_max first:
-    diagnostics.moment_match on the report's draws, with the centred log joint of an engine of the report's own set to CP
-    (the run's handles are untouched: _psens_report's way) and `loglik_fn(target, rows [1, n, D])` for the left-out term.
+    diagnostics.moment_match on the report's draws, with the centred log joint of a _centred_engine and
+    `loglik_fn(target, rows [1, n, D])` for the left-out term.
     mask [R], left_out: the report's left-out draws (moment_match adds those whose log joint is not finite).
     Prints the line that sets the matched total next to the plain one (`plain_total`), and one warning naming what is still above the
     threshold.  Returns (keys, mm_merge's arrays)."""
@@ -1060,8 +1062,7 @@ def _mm_run(draws, mask, left_out, spec, flags, columns, loglik_fn, prefix, what
     x = draws.reshape(R, D)
     threshold = diagnostics.pareto_k_threshold(R - int(left_out))
     chosen, past = mm_select(columns[:, 1], threshold, getattr(flags, "loo_moment_match_max", 64))
-    eng = _engine.Engine(spec, dev)                                                  # the report's own handle: the run's stay as they are
-    eng.set_param(0, "CP")
+    eng = _centred_engine(spec, dev)
     result = diagnostics.moment_match(
         x, mask, lambda rows: eng.logp_grad(rows, which=0)[0], lambda t, rows: loglik_fn(int(t), rows[None]), list(chosen),
         columns[chosen, 1], columns[chosen, 0], threshold, batch=report_common.mm_batch_size(max(len(chosen), 1), R, D, LOO_CHUNK_BYTES))
@@ -1076,14 +1077,11 @@ def _mm_run(draws, mask, left_out, spec, flags, columns, loglik_fn, prefix, what
                     keys[prefix + "_mm_observations"], what, past, keys[prefix + "_mm_improved"], _fmt(_finite_or_none(threshold)),
                     keys[prefix + "_mm_resolved"], e, _fmt(keys[e]), _fmt(keys[e + "_se"]), _fmt(plain_total), _fmt(keys[prefix + "_mm_pareto_k_max"]),
                     _fmt(_finite_or_none(plain_k)), _fmt(keys[prefix + "_mm_full_pareto_k_max"])))
-    with np.errstate(invalid="ignore"):
-        k = merged["pareto_k"]
-        high = np.flatnonzero((k > threshold) if np.isfinite(threshold) else np.isposinf(k))
+    high = np.flatnonzero(_above(merged["pareto_k"], threshold, ~np.isnan(merged["pareto_k"])))
     if high.size:
-        util.print_("    WARNING: after moment matching the Pareto k-hat is still above {} for {} of the {}: {}{} -- their "
+        util.print_("    WARNING: after moment matching the Pareto k-hat is still above {} for {} of the {}: {} -- their "
                     "estimates remain unreliable (which: <base>_{}_mm.npz)".format(
-                        _fmt(_finite_or_none(threshold)), high.size, what, ", ".join(label(t) for t in high[:MM_SHOWN]),
-                        ", ..." if high.size > MM_SHOWN else "", prefix))
+                        _fmt(_finite_or_none(threshold)), high.size, what, _shown([label(t) for t in high], MM_SHOWN), prefix))
     keys[prefix + "_mm_time_sec"] = time.time() - clock
     return keys, merged
 
@@ -1162,8 +1160,8 @@ def _loo_report(kernel_results, trace, k, spec, flags, side=None):
         util.print_("    WARNING: Pareto k-hat above {} for {} of {} observations (not fitted ones included): their "
                     "leave-one-out estimates are unreliable, the posterior hangs on them (which: <base>_loo.npz)".format(
                         _fmt(keys["pareto_k_threshold"]), keys["pareto_k_above_threshold"], N))
-    arrays = OrderedDict([("elpd_loo_i", c[:, 0]), ("pareto_k", c[:, 1]), ("lppd_i", c[:, 2]), ("p_waic_i", c[:, 3]),
-                          ("y", np.asarray(table.y_host, np.float32)), ("model", np.asarray(spec.name))])
+    arrays = OrderedDict([("elpd_loo_i", c[:, 0]), ("pareto_k", c[:, 1]), ("lppd_i", c[:, 2]), ("p_waic_i", c[:, 3])]
+                         + data_tail(table.y_host, spec))
     if pred:
         pred_clock = time.time()
         summary = diagnostics.loo_predictive_summary(np.concatenate(sums, axis=0), table.y_host, table.kind)
@@ -1179,7 +1177,7 @@ def _loo_report(kernel_results, trace, k, spec, flags, side=None):
         if side is not None:
             side[LOO_PRED_ARRAYS] = OrderedDict([
                 ("loo_mean", summary.loo_mean), ("loo_sd", summary.loo_sd), ("loo_pit", summary.loo_pit),
-                ("loo_is_ess", summary.is_ess), ("y", np.asarray(table.y_host, np.float32)), ("model", np.asarray(spec.name))])
+                ("loo_is_ess", summary.is_ess)] + data_tail(table.y_host, spec))
         keys.update(more)
         keys["loo_pred_time_sec"] = pred_time + (time.time() - pred_clock)
     if loo_groups_part(flags):
@@ -1187,7 +1185,7 @@ def _loo_report(kernel_results, trace, k, spec, flags, side=None):
         keys.update(logo)
     if loo_moment_match(flags):
         more, merged = _mm_run(draws, mask, left_out, spec, flags, c, _TableLoglik(table), "loo", "observation(s)", keys["elpd_loo"])
-        merged.update([("y", np.asarray(table.y_host, np.float32)), ("model", np.asarray(spec.name))])
+        merged.update(data_tail(table.y_host, spec))
         arrays[LOO_MM_ARRAYS] = merged                                     # (save_loo takes them out again)
         keys.update(more)
     keys["loo_time_sec"] = time.time() - clock
@@ -1270,16 +1268,13 @@ def redraw_parts(flags):
 
 
 def check_predictive_redraw(flags):
-    """--predictive_checks_redraw against the job, before anything runs -- raises ValueError for the flag without
-    --predictive_checks, for neals_funnel (no observations) and for whatever diagnostics.redraw_selection refuses: an empty
-    name, a duplicate, a name that is no latent part, a selection that is not closed under descent."""
+    """--predictive_checks_redraw against the job, before anything runs -- raises ValueError: _check_extends' two refusals
+    (--predictive_checks), and whatever diagnostics.redraw_selection refuses: an empty name, a duplicate, a name that is no
+    latent part, a selection that is not closed under descent."""
     names = redraw_parts(flags)
     if not names:
         return
-    if not getattr(flags, "predictive_checks", False):
-        raise ValueError("--predictive_checks_redraw is read with --predictive_checks only")
-    if flags.model == "neals_funnel":
-        raise ValueError("--predictive_checks_redraw: neals_funnel has no observations, so there is no data to replicate")
+    _check_extends(flags, "predictive_checks_redraw", "predictive_checks", "data to replicate")
     spec = models.spec_by_name(flags.model, dataset=getattr(flags, "dataset", None))
     diagnostics.redraw_selection(spec.site_table(), spec.part_names, names)
 
@@ -1302,16 +1297,13 @@ def groups_part(flags):
 
 
 def check_predictive_groups(flags):
-    """--predictive_checks_groups against the job, before anything runs -- raises ValueError for the flag without
-    --predictive_checks, for neals_funnel (no observations) and for whatever diagnostics.group_selection refuses: a name
-    that is no part, a part of one element, a part no observation reads, a part whose elements do not group the data."""
+    """--predictive_checks_groups against the job, before anything runs -- raises ValueError: _check_extends' two refusals
+    (--predictive_checks), and whatever diagnostics.group_selection refuses: a name that is no part, a part of one element,
+    a part no observation reads, a part whose elements do not group the data."""
     part = groups_part(flags)
     if not part:
         return
-    if not getattr(flags, "predictive_checks", False):
-        raise ValueError("--predictive_checks_groups is read with --predictive_checks only")
-    if flags.model == "neals_funnel":
-        raise ValueError("--predictive_checks_groups: neals_funnel has no observations, so there is no data to group")
+    _check_extends(flags, "predictive_checks_groups", "predictive_checks", "data to group")
     spec = models.spec_by_name(flags.model, dataset=getattr(flags, "dataset", None))
     diagnostics.group_selection(spec.observation_table(), spec, part)
 
@@ -1373,23 +1365,21 @@ def _ppc_group_report(grouped, spec, y, kind):
     n_ungrouped = int(np.sum(group_of < 0))
     summary = diagnostics.ppc_group_summary(counts, y, group_of, kind)
     out = ppc_group_keys(summary, part, names, n_ungrouped)
-    arrays = OrderedDict([("part", np.asarray(part)), ("groups", np.asarray(names)), ("group_of", np.asarray(group_of, np.int32)),
-                          ("n_obs", np.asarray(summary.sizes, np.int64))])
+    arrays = OrderedDict(grouped_head(part, names, group_of, summary.sizes))
     arrays.update(_ppc_group_arrays(summary))
     more = OrderedDict()
     if mixed_counts is not None:
         mixed_summary = diagnostics.ppc_group_summary(mixed_counts, y, group_of, kind)
         more = ppc_group_keys(mixed_summary, part, names, n_ungrouped, mixed=True)
         arrays.update(_ppc_group_arrays(mixed_summary, "mixed_"))
-    arrays.update([("y", y), ("model", np.asarray(spec.name))])
+    arrays.update(data_tail(y, spec))
     ends = lambda k, pre: "{} ({}) ... {} ({})".format(_fmt(k[pre + "p_mean_min"]), k[pre + "p_mean_min_group"],
                                                       _fmt(k[pre + "p_mean_max"]), k[pre + "p_mean_max_group"])
     util.print_("    grouped predictive checks by {}: {} groups ({} empty, {} observations in none), {} draws; p-value of the "
                 "group mean, smallest ... largest: {}{}".format(
                     part, out["ppc_groups"], out["ppc_groups_empty"], n_ungrouped, out["ppc_group_draws"], ends(out, "ppc_group_"),
                     "; mixed {}".format(ends(more, "ppc_group_mixed_")) if more else ""))
-    shown = lambda groups: "{} group(s): {}{}".format(len(groups), ", ".join(groups[:PPC_GROUP_SHOWN]),
-                                                       ", ..." if len(groups) > PPC_GROUP_SHOWN else "")
+    shown = lambda groups: "{} group(s): {}".format(len(groups), _shown(groups, PPC_GROUP_SHOWN))
     extreme = [(label, k[pre + "extreme_groups"]) for label, k, pre in (("posterior", out, "ppc_group_"), ("mixed", more, "ppc_group_mixed_"))
                if k.get(pre + "extreme_groups")]
     if extreme:
@@ -1597,10 +1587,9 @@ def _ppc_mixed_report(mixed, names, posterior_keys, spec, y, kind):
                         PPC_EXTREME[0], PPC_EXTREME[1], ", ".join(extreme), ", ".join(chosen)))
     out = keys["ppc_mixed_pit_extreme_observations"]
     if out:
-        util.print_("    {} of {} observations have a mixed PIT outside [{}, {}] -- outliers against a new draw of {}: {}{} "
+        util.print_("    {} of {} observations have a mixed PIT outside [{}, {}] -- outliers against a new draw of {}: {} "
                     "(the PIT values: <base>_ppc_mixed.npz)".format(
-                        len(out), int(y.size), PPC_EXTREME[0], PPC_EXTREME[1], ", ".join(chosen),
-                        ", ".join(str(n) for n in out[:PPC_MIXED_SHOWN]), ", ..." if len(out) > PPC_MIXED_SHOWN else ""))
+                        len(out), int(y.size), PPC_EXTREME[0], PPC_EXTREME[1], ", ".join(chosen), _shown(out, PPC_MIXED_SHOWN)))
     arrays = OrderedDict([("parts", np.asarray(chosen)), ("redrawn", np.asarray(redrawn, np.uint8)),
                           ("predictive_mean", summary.predictive_mean), ("predictive_sd", summary.predictive_sd),
                           ("pit", summary.pit), ("y", y),
@@ -1814,8 +1803,7 @@ def _psens_report(trace, k, spec, flags, pooled_mean=None, side=None):
     ll_buffer = torch.empty(rows, R, dtype=torch.float32, device=dev)
     log_lik, mask = joint_loglik(draws, table, ll_buffer, rows)
     del ll_buffer
-    eng = _engine.Engine(spec, dev)                                                  # the report's own handle: the run's stay as they are
-    eng.set_param(0, "CP")
+    eng = _centred_engine(spec, dev)
     log_joint = eng.logp_grad(draws.reshape(R, D), which=0)[0].to(torch.float64)
     logp_const = float(eng.logp_const(0))
     del eng
@@ -1853,10 +1841,9 @@ def _psens_report(trace, k, spec, flags, pooled_mean=None, side=None):
     if high:
         util.print_("    WARNING: Pareto k-hat above {} for {} of the 4 power-scaled weight rows (not fitted ones included): "
                     "their sensitivities are unreliable".format(_fmt(threshold), high))
-    arrays = OrderedDict([("elements", np.asarray(names)), ("y", np.asarray(table.y_host, np.float32)),
-                          ("model", np.asarray(spec.name)), ("pareto_k", pareto_k),
-                          ("log_prior", log_prior.cpu().numpy()), ("log_likelihood", log_lik.cpu().numpy()),
-                          ("left_out", left.cpu().numpy())])
+    arrays = OrderedDict([("elements", np.asarray(names))] + data_tail(table.y_host, spec)
+                         + [("pareto_k", pareto_k), ("log_prior", log_prior.cpu().numpy()),
+                            ("log_likelihood", log_lik.cpu().numpy()), ("left_out", left.cpu().numpy())])
     _by_part(spec, arrays, (("prior", summary.prior), ("likelihood", summary.likelihood),
                             ("mean_shift_prior", summary.mean_shift_prior),
                             ("mean_shift_likelihood", summary.mean_shift_likelihood),
@@ -1999,9 +1986,9 @@ def _prior_report(spec, flags, dev, post_mean, post_sd):
                 "-- quantile scale of the prior, moment scale of the posterior".format(
                     D, keys["prior_elements_left_out"], _fmt(keys["prior_contraction_min"]), keys["prior_contraction_min_element"],
                     _fmt(keys["prior_z_score_max_abs"]), keys["prior_z_score_max_element"]))
-    arrays = OrderedDict([("elements", np.asarray(names)), ("y", y), ("model", np.asarray(spec.name)),
-                          ("draw_stats", stats_host), ("left_out", left_host),
-                          ("predictive_mean", summary.predictive_mean), ("predictive_sd", summary.predictive_sd)])
+    arrays = OrderedDict([("elements", np.asarray(names))] + data_tail(y, spec)
+                         + [("draw_stats", stats_host), ("left_out", left_host),
+                            ("predictive_mean", summary.predictive_mean), ("predictive_sd", summary.predictive_sd)])
     _by_part(spec, arrays, (("prior_q05", quantiles[:, 0]), ("prior_median", quantiles[:, 1]), ("prior_q95", quantiles[:, 2]),
                             ("contraction", contraction.contraction), ("z_score", contraction.z_score)))
     keys["prior_time_sec"] = time.time() - clock

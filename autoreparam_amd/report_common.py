@@ -31,6 +31,32 @@ def _fmt(v):
     return "n/a" if v is None else "{:.4g}".format(v)
 
 
+def _shown(items, limit):
+    """The first `limit` of `items`, comma separated, then `, ...` when there are more: how a warning names what it found."""
+    return ", ".join(str(v) for v in items[:limit]) + (", ..." if len(items) > limit else "")
+
+
+def _above(k, threshold, present=None):
+    """[len(k)] bool: Pareto k-hat above `threshold`; where the threshold is not finite (None: written as null), not
+    fitted -- not finite -- among the rows that are `present` (all; an empty group's row is NaN and absent)."""
+    k = np.asarray(k, np.float64)
+    with np.errstate(invalid="ignore"):
+        if threshold is not None and np.isfinite(threshold):
+            return k > threshold
+        return ~np.isfinite(k) if present is None else present & ~np.isfinite(k)
+
+
+def grouped_head(part, names, group_of, sizes):
+    """The arrays a grouped side file opens with: the part, its groups' names, every observation's group, the groups' sizes."""
+    return [("part", np.asarray(part)), ("groups", np.asarray(names)), ("group_of", np.asarray(group_of, np.int32)),
+            ("n_obs", np.asarray(sizes, np.int64))]
+
+
+def data_tail(y, spec):
+    """The pair a side file closes with: the observations themselves and the model's name."""
+    return [("y", np.asarray(y, np.float32)), ("model", np.asarray(spec.name))]
+
+
 def element_names(spec):
     """One name per element of the flat state, in trace order: `tau` for a scalar part, `m[17]`, `z[2,3]` otherwise."""
     names = []
@@ -86,22 +112,29 @@ def loo_steps(S, k, draws):
     return sorted(S - 1 - s for s in probe_steps(S, min(want, diagnostics.PSIS_MAX_DRAWS // k)))
 
 
+def rows_within(count, bytes_per_row, budget=None, workspace_bytes=None, cap=None):
+    """The one budget rule of the reports: clamp(budget // bytes_per_row, 1, count) rows (at most `cap`), then halved,
+    (rows + 1) // 2, while `workspace_bytes(rows)` -- whatever more a call of that many rows takes -- is over `budget`
+    bytes (LOO_CHUNK_BYTES); at least one."""
+    budget = LOO_CHUNK_BYTES if budget is None else int(budget)
+    rows = max(1, min(max(int(count), 1), budget // max(1, int(bytes_per_row))))
+    rows = int(rows if cap is None else min(rows, cap))
+    while workspace_bytes is not None and rows > 1 and workspace_bytes(rows) > budget:
+        rows = (rows + 1) // 2
+    return rows
+
+
 def loo_tile_rows(N, R, budget=None):
     """Observations per tile of the predictive report: rows of R float32 within `budget` bytes (LOO_CHUNK_BYTES); at
     least one."""
-    budget = LOO_CHUNK_BYTES if budget is None else int(budget)
-    return int(max(1, min(max(int(N), 1), budget // max(1, 4 * int(R)))))
+    return rows_within(N, 4 * int(R), budget)
 
 
 def ppc_tile_rows(N, R, workspace_bytes, budget=None):
     """Observations per tile of the predictive checks: loo_tile_rows, halved until `workspace_bytes(rows, R)` -- the
     kernel's partial sums, the only [observations, draws]-sized memory this report takes -- is within the budget too; at
     least one."""
-    budget = LOO_CHUNK_BYTES if budget is None else int(budget)
-    rows = loo_tile_rows(N, R, budget)
-    while rows > 1 and workspace_bytes(rows, R) > budget:
-        rows = (rows + 1) // 2
-    return rows
+    return rows_within(N, 4 * int(R), budget, lambda rows: workspace_bytes(rows, R))
 
 
 def select_draws(trace, k, k_steps, flags):
@@ -141,19 +174,15 @@ def replicate_tiles(draws, table, seed, draw_offset=0, y_rep_out=None, budget=No
 def group_range_size(G, R, budget=None):
     """Groups per call of the grouped predictive check: [groups, R, 8] float64 statistics within `budget` bytes
     (LOO_CHUNK_BYTES); at least one."""
-    budget = LOO_CHUNK_BYTES if budget is None else int(budget)
-    return int(max(1, min(max(int(G), 1), budget // max(1, 64 * int(R)))))
+    return rows_within(G, 64 * int(R), budget)
 
 
 def logo_range_size(G, R, forms, workspace_bytes, budget=None):
     """Groups per call of leave-one-group-out: `forms` (1: conditional, 2: and marginal) [groups, R] float32 matrices and
     the PSIS workspace `workspace_bytes(groups, R)` of one of them within `budget` bytes (LOO_CHUNK_BYTES) -- group_range_size
     with this report's rows, halved as ppc_tile_rows halves until the workspace fits too; at least one."""
-    budget = LOO_CHUNK_BYTES if budget is None else int(budget)
-    per = int(max(1, min(max(int(G), 1), budget // max(1, 4 * int(forms) * int(R)))))
-    while per > 1 and 4 * int(forms) * int(R) * per + workspace_bytes(per, R) > budget:
-        per = (per + 1) // 2
-    return per
+    row = 4 * int(forms) * int(R)
+    return rows_within(G, row, budget, lambda per: row * per + workspace_bytes(per, R))
 
 
 MM_MAX_BATCH = 4095                 # arp_weighted_moments takes 4096 rows of weights: a batch's and one for the unweighted moments
@@ -162,8 +191,7 @@ MM_MAX_BATCH = 4095                 # arp_weighted_moments takes 4096 rows of we
 def mm_batch_size(T, R, D, budget=None):
     """Targets per call of moment matching: the mapped draws [targets, R, D] float32 of diagnostics.affine_rows within
     `budget` bytes (LOO_CHUNK_BYTES); at least one, at most T and at most MM_MAX_BATCH."""
-    budget = LOO_CHUNK_BYTES if budget is None else int(budget)
-    return int(max(1, min(max(int(T), 1), MM_MAX_BATCH, budget // max(1, 4 * int(R) * int(D)))))
+    return rows_within(T, 4 * int(R) * int(D), budget, cap=MM_MAX_BATCH)
 
 
 def replicate_groups(draws, table, groups, y, group_of, seed, draw_offset=0, left_out=None, budget=None):

@@ -1,6 +1,7 @@
 """CPU: what the reports share (autoreparam_amd/report_common.py) and the table of side reports in main.py.  The seed
-rule against the expression it replaces; the draw selection's refusals, their order and its draws; the two tile walks on
-recording stand-ins of the device functions; the no-trace branch of main._convergence_report for every combination of the
+rule, the one budget rule, the k-hat threshold test and the grouped-file builders against the expressions they replace; the
+draw selection's refusals, their order and its draws; the two tile walks on recording stand-ins of the device functions; the
+no-trace branch of main._convergence_report for every combination of the
 flags; _save_diagnostics on one array per tag; and that neither report_common nor sbc drags main in."""
 import itertools
 import os
@@ -30,13 +31,111 @@ def test_seeds_are_the_spelled_out_expression():
 def test_main_names_are_the_shared_objects(monkeypatch):
     from autoreparam_amd import main, report_common as rc
     for name in ("_finite_or_none", "_nan_max", "_fmt", "probe_steps", "loo_steps", "ppc_tile_rows", "LOO_CHUNK_BYTES",
-                 "element_names", "_write_json_atomic"):
+                 "element_names", "_write_json_atomic", "_above", "_shown", "grouped_head", "data_tail"):
         assert getattr(main, name) is getattr(rc, name), name
     # main.loo_tile_rows is the shared rule within main's own budget, which the tile tests shrink there
     for N, R in ((11566, 65536), (8, 65536), (5, 1 << 30), (1000, 256)):
         assert main.loo_tile_rows(N, R) == rc.loo_tile_rows(N, R) and main.loo_tile_rows(N, R, 4096) == rc.loo_tile_rows(N, R, 4096)
     monkeypatch.setattr(main, "LOO_CHUNK_BYTES", 100 * 4 * 256)
     assert main.loo_tile_rows(1000, 256) == 100 and rc.loo_tile_rows(1000, 256) == 1000
+
+
+def test_rows_within_is_each_of_the_five_spelled_out_rules():
+    """The five sizing rules as they stood before rows_within, spelled out, against the names that now call it."""
+    from autoreparam_amd import report_common as rc
+    assert rc.LOO_CHUNK_BYTES == 256 << 20 and rc.MM_MAX_BATCH == 4095
+    halved = 0
+    for count, R, D in itertools.product((0, 1, 7, 4096, 5000), (1, 64, 65536, 1 << 24), (1, 255)):
+        for budget in (1, 4 * R, 256 << 20):
+            loo = int(max(1, min(max(int(count), 1), budget // max(1, 4 * int(R)))))
+            assert rc.loo_tile_rows(count, R, budget) == loo == rc.rows_within(count, 4 * R, budget)
+            assert rc.group_range_size(count, R, budget) == int(max(1, min(max(int(count), 1), budget // max(1, 64 * int(R)))))
+            assert rc.mm_batch_size(count, R, D, budget) == int(
+                max(1, min(max(int(count), 1), rc.MM_MAX_BATCH, budget // max(1, 4 * int(R) * int(D)))))
+            if budget == 256 << 20:                                                            # the default budget
+                assert rc.loo_tile_rows(count, R) == loo and rc.group_range_size(count, R) == rc.group_range_size(count, R, budget)
+                assert rc.mm_batch_size(count, R, D) == rc.mm_batch_size(count, R, D, budget)
+            # a workspace that is nothing, linear in the rows, and over the budget whatever the rows
+            for workspace in (lambda rows, R: 0, lambda rows, R: 8 * rows * R, lambda rows, R: budget + 1):
+                rows = loo
+                while rows > 1 and workspace(rows, R) > budget:
+                    rows = (rows + 1) // 2
+                halved += rows != loo
+                assert rc.ppc_tile_rows(count, R, workspace, budget) == rows
+                for forms in (1, 2):
+                    per = int(max(1, min(max(int(count), 1), budget // max(1, 4 * int(forms) * int(R)))))
+                    while per > 1 and 4 * int(forms) * int(R) * per + workspace(per, R) > budget:
+                        per = (per + 1) // 2
+                    assert rc.logo_range_size(count, R, forms, workspace, budget) == per
+                if workspace(1, R) > budget:
+                    assert rows == per == 1                                                    # at least one
+    assert halved > 0
+
+
+def test_above_is_each_of_the_six_spelled_out_tests():
+    """k-hat above the threshold, or not fitted when there is no threshold: the six expressions _above replaced, on a column
+    with finite values on both sides of the threshold, +inf, a NaN and an empty group's all-NaN row."""
+    import warnings
+    from autoreparam_amd import report_common as rc
+    columns = np.array([[0.0, 0.2], [-1.0, 0.9], [-2.0, np.inf], [-3.0, np.nan], [np.nan, np.nan], [-4.0, 0.7]])
+    sizes = np.array([3, 2, 1, 4, 0, 5])
+    k_all = columns[:, 1]
+    filled = ~np.all(np.isnan(columns), axis=1)
+    k = np.where(filled, k_all, np.nan)
+    same = lambda a, b: a.dtype == bool and b.dtype == bool and np.array_equal(a, b)
+    with warnings.catch_warnings():
+        warnings.simplefilter("error")                                                         # (the guard is _above's)
+        for threshold in (0.7, float("nan")):
+            with np.errstate(invalid="ignore"):
+                loo = int(np.sum(k_all > threshold)) if np.isfinite(threshold) else int(np.sum(~np.isfinite(k_all)))
+                form = int(np.sum(k > threshold)) if np.isfinite(threshold) else int(np.sum(filled & ~np.isfinite(k)))
+                key = rc._finite_or_none(threshold)                                             # what _logo_report reads back
+                warned = (k > key) if key is not None else (sizes > 0) & ~np.isfinite(k)
+                select = (k > threshold) if np.isfinite(threshold) else np.isposinf(k)
+                keys = (k > threshold) if np.isfinite(threshold) else (filled & ~np.isfinite(k))
+            assert int(np.sum(rc._above(k_all, threshold))) == loo == (2 if np.isfinite(threshold) else 3)       # loo_keys
+            assert int(np.sum(rc._above(k, threshold, filled))) == form == (2 if np.isfinite(threshold) else 2)  # _logo_form_keys
+            assert same(rc._above(k, key, sizes > 0), warned)                                   # _logo_report's warning
+            assert same(rc._above(k, threshold, ~np.isnan(k)), select)                          # mm_select, _mm_run's warning
+            assert same(rc._above(k, threshold, filled), keys)                                  # mm_keys
+        assert list(rc._above(k, 0.7)) == [False, True, True, False, False, False]
+        assert list(rc._above(k, None)) == [False, False, True, True, True, False]
+        assert list(rc._above(k, None, ~np.isnan(k))) == [False, False, True, False, False, False]
+
+
+def test_shown_names_the_first_and_says_when_there_are_more():
+    from autoreparam_amd import main, report_common as rc
+    assert main.LOGO_SHOWN == main.MM_SHOWN == main.PPC_GROUP_SHOWN == main.PPC_MIXED_SHOWN == 8
+    for limit in (1, 8):
+        for n in (0, limit - 1, limit, limit + 1):
+            names = ["m[%d]" % i for i in range(n)]
+            assert rc._shown(names, limit) == ", ".join(names[:limit]) + (", ..." if len(names) > limit else "")
+            at = np.arange(n) * 3                                                              # indices, as flatnonzero gives them
+            assert rc._shown(at, limit) == ", ".join(str(i) for i in at[:limit]) + (", ..." if at.size > limit else "")
+            assert rc._shown([int(i) for i in at], limit) == rc._shown(at, limit)
+    assert rc._shown(["a", "b", "c"], 2) == "a, b, ..." and rc._shown(["a", "b"], 2) == "a, b" and rc._shown(["a"], 2) == "a"
+
+
+def test_grouped_file_builders_keep_names_dtypes_and_order(tmp_path):
+    """The arrays a grouped side file opens and closes with, as _logo_report and _ppc_group_report spelled them."""
+    from autoreparam_amd import report_common as rc
+    part, names, group_of, sizes = "m", ["m[0]", "m[1]", "m[2]"], np.array([0, -1, 2, 2]), [1, 0, 2]
+    y, spec = np.array([0.5, 1.5, -2.0, 3.0]), types.SimpleNamespace(name="radon")
+    want = ([("part", np.asarray(part)), ("groups", np.asarray(names)), ("group_of", np.asarray(group_of, np.int32)),
+             ("n_obs", np.asarray(sizes, np.int64))],
+            [("y", np.asarray(y, np.float32)), ("model", np.asarray(spec.name))])
+    for got, expected in zip((rc.grouped_head(part, names, group_of, sizes), rc.data_tail(y, spec)), want):
+        assert [n for n, _ in got] == [n for n, _ in expected]
+        for (_, a), (_, b) in zip(got, expected):
+            assert isinstance(a, np.ndarray) and a.dtype == b.dtype and a.shape == b.shape and np.array_equal(a, b)
+    head, tail = rc.grouped_head(part, names, group_of, sizes), rc.data_tail(y, spec)
+    assert [a.dtype for _, a in head] == [np.dtype("<U1"), np.dtype("<U4"), np.dtype(np.int32), np.dtype(np.int64)]
+    assert tail[0][1].dtype == np.float32 and tail[1][1].shape == () and str(tail[1][1]) == "radon"
+    y32 = np.asarray(y, np.float32)
+    assert rc.data_tail(y32, spec)[0][1] is y32                                                # float32 as uploaded: no copy
+    path = str(tmp_path / "grouped.npz")
+    np.savez(path, **dict(head + [("elpd_logo_g", np.zeros(3))] + tail))
+    assert np.load(path).files == ["part", "groups", "group_of", "n_obs", "elpd_logo_g", "y", "model"]
 
 
 FLAGS = types.SimpleNamespace(loo_draws=6)
